@@ -15,9 +15,12 @@ resident in HBM.  Workloads (BASELINE.json ``configs``):
      data-path collective; the only collective is the one-time RCCL broadcast of the packed weight blob, timed separately
   5  B=8 x T=512 (T_y=1536), bf16 Generator + fp16 flow
 
-At N=1 the line also carries ``secondary``: configs 3, 4 (one GPU's share) and 5 measured in the same process right after the primary,
-each with its own roofline block, so the driver-run line documents every BASELINE configuration.  Nothing is profiled inside a timed
-region: the per-kernel HIP-event pass (roofline) is a separate eager pass after it.  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times K steps (``ms_per_step`` = one of them), writes the last step's outputs if ``--dump-outputs DIR`` is
+given, and prints the line.  Everything else the benchmark measures runs only with ``--full``: the roofline / upsampling / encoder-GEMM /
+PCIe-inclusive passes, repeats of the timed region, the CPU baseline and parity block, the single-GPU anchor of an N>1 line, and at N=1
+``secondary``: configs 3, 4 (one GPU's share) and 5 measured in the same process right after the primary, each with its own roofline
+block, so that line documents every BASELINE configuration.  Nothing is profiled inside a timed region: the per-kernel HIP-event pass
+(roofline) is a separate eager pass after it.  Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
 
@@ -81,10 +84,18 @@ def parse(argv=None):
     ap.add_argument("--variants", default=None, metavar="SPEC,CL,HC",
                     help="bv2_test_set_variants(spec, cl_generic, hc_generic) before the run (tuning A/B only)")
     ap.add_argument("--streams", type=int, default=2, help="requests in flight for the secondary two-stream leg of config 2")
-    ap.add_argument("--full-profile", action="store_true", help="extra untimed pass timing every MFMA kernel launch site")
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the roofline / upsampling / encoder-GEMM / PCIe-inclusive passes, the "
+                         "secondary legs, the CPU baseline and parity at N=1, the single-GPU anchor at N>1, repeats of the timed region "
+                         "and the details file.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (waveform, alignment, masks, latents) as "
+                         "DIR/<name>.npy in float32, at most 64 MB in all (a fixed sample of an array too large for its share)")
+    ap.add_argument("--full-profile", action="store_true",
+                    help="extra untimed pass timing every MFMA kernel launch site (runs the --full passes of the primary config too)")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the primary timed region is run this many times back to back; `value` is the FIRST (the contract's K steps after W "
-                         "warm-ups), the others are reported as its spread")
+                         "warm-ups), the others are reported as its spread (default: 3 with --full, else 1)")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N>1 code path at whatever world size there is — at --gpus 1: a world-size-1 RCCL process group on the "
                          "device, the blob broadcast, both barriers, all_reduce(MAX), all_gather_object and the N>1 line builder — so "
@@ -93,8 +104,9 @@ def parse(argv=None):
     ap.add_argument("--library", default=None, metavar="PATH",
                     help="same-box A/B of two BUILDS (tools/ab_build.py): load this libbv2 (same C ABI) instead of the in-tree build")
     ap.add_argument("--details-out", default=None, metavar="PATH",
-                    help="where the full record (launch tables, PMC families, every secondary leg in full) is written; default "
-                         "gpurun_out/bench_details.json.  stdout carries ONE compact (< 4 KB) strict-JSON line")
+                    help="where the full record (launch tables, PMC families, every secondary leg in full) is written; a --full run "
+                         "writes it to emit()'s default path when this is not given, a plain run only when it is.  stdout carries ONE "
+                         "compact (< 4 KB) strict-JSON line")
     ap.add_argument("--seam", default=None, help=argparse.SUPPRESS)   # tests only: module replacing the GPU-touching seam (see Seam)
     return ap.parse_args(argv)
 
@@ -502,13 +514,15 @@ def encoder_gemms_block(rows, psteps, config):
 
 
 def run_config(num, model, hp, dev, rank, world, steps, warmup, overrides, full_profile=False, solo=False, collective=False,
-               repeats=1, contract=True):
+               repeats=1, contract=True, extras=True, keep_outputs=False):
     """Time `steps` steps of BASELINE config `num` on this rank; returns the result dict (rank-local times; the caller reduces).
     ``collective``: a process group exists and every rank is in this call — the timed region is bracketed by its barriers (always at
     world > 1).  ``solo``: this rank runs alone while the others wait (the N=1 anchor of the N>1 line): no barriers, no extra legs.
     ``repeats``: the timed region (exactly `steps` steps between two syncs) is run this many times back to back.  ``contract`` = True
     (the primary line): `dt` is the FIRST region — the K steps after the W warm-ups the driver's contract names — and the others are
-    reported as its spread; False (secondary legs): `dt` is the median region, so one bad draw cannot set a leg's figure."""
+    reported as its spread; False (secondary legs): `dt` is the median region, so one bad draw cannot set a leg's figure.
+    ``extras`` = False: nothing after the timed region (no PCIe-inclusive, roofline or encoder-GEMM pass).  ``keep_outputs``: host copies
+    of what the last timed step returned, taken right after the clock stops, are in ``res["outputs"]`` (--dump-outputs)."""
     cfg = dict(CONFIGS[num])
     B = overrides.get("batch") or cfg["batch"]
     T = overrides.get("symbols") or cfg["symbols"]
@@ -535,7 +549,8 @@ def run_config(num, model, hp, dev, rank, world, steps, warmup, overrides, full_
     for i in range(warmup):
         out = call()
     torch.cuda.synchronize()
-    assert int(out[2].sum().item()) == frames_per_step, (int(out[2].sum().item()), frames_per_step)
+    if warmup:
+        assert int(out[2].sum().item()) == frames_per_step, (int(out[2].sum().item()), frames_per_step)
     dts = []
     for _rep in range(max(1, repeats)):
         barrier()
@@ -551,13 +566,20 @@ def run_config(num, model, hp, dev, rank, world, steps, warmup, overrides, full_
     Ty = y_mask.shape[2]
     res = dict(config=num, B=B, T=T, Ty=Ty, gen_dtype=gen_dtype, flow_dtype=flow_dtype, graph=use_graph, dt=dt, steps=steps,
                audio_per_step=audio_per_step, lengths=lengths)
+    if keep_outputs:
+        # copied now: with static_io the graph's output buffers are overwritten by any later pass
+        z, z_p, m_p, logs_p = _rest
+        res["outputs"] = {k: v.detach().cpu() for k, v in (("o", o), ("attn", attn), ("y_mask", y_mask), ("z", z), ("z_p", z_p),
+                                                           ("m_p", m_p), ("logs_p", logs_p)) if v is not None}
+    if not warmup:
+        assert int(y_mask.sum().item()) == frames_per_step, (int(y_mask.sum().item()), frames_per_step)
     if len(dts) > 1:
         ms = [d / steps * 1e3 for d in dts]
         spread = (max(ms) - min(ms)) / min(ms)
         res["repeats"] = dict(ms_per_step=[round(m, 4) for m in ms], min=round(min(ms), 4), max=round(max(ms), 4),
                               median=round(sorted(ms)[len(ms) // 2], 4), spread=round(spread, 4), unstable=bool(spread > 0.05),
                               reported="first region (the contract's K steps)" if contract else "median region")
-    if solo:
+    if solo or not extras:
         model.enable_graphs(False)
         return res
     if rank == 0:
@@ -1080,6 +1102,31 @@ def emit(line, details_out=None):
     return txt
 
 
+DUMP_BUDGET_BYTES = 60 << 20       # --dump-outputs: every array together stays below 64 MB, .npy headers included
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(outs, out_dir, prefix="", budget=DUMP_BUDGET_BYTES):
+    """Write each tensor of `outs` as <out_dir>/<prefix><name>.npy (float64 stays float64, anything else becomes float32) so that two builds
+    can be compared output for output.  When everything does not fit in `budget` bytes, the smallest arrays are stored whole and each of
+    the others gets an equal share of what is left: a 1-D sample of the flattened array at sorted positions drawn by a generator with a
+    fixed seed — the same positions for the same shape in every run."""
+    import numpy as np
+    arrs = {k: (v.double() if v.dtype == torch.float64 else v.float()).contiguous() for k, v in outs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    left, todo = budget, sorted(arrs, key=lambda k: arrs[k].numel() * arrs[k].element_size())
+    for i, k in enumerate(todo):
+        a = arrs[k]
+        cap = (left // (len(todo) - i)) // a.element_size()
+        if a.numel() > cap:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            a = a.reshape(-1)[torch.randperm(a.numel(), generator=g)[:cap].sort().values]
+            log(f"dump: {prefix}{k} {tuple(arrs[k].shape)} -> seeded sample of {cap} elements")
+        left -= a.numel() * a.element_size()
+        np.save(os.path.join(out_dir, f"{prefix}{k}.npy"), a.numpy())
+    log(f"dump: {len(todo)} arrays ({budget - left} bytes) -> {out_dir}")
+
+
 class Seam:
     """Everything in the N-rank driver that touches a GPU, so that a CPU test can drive the SAME launcher / reduction code with
     gloo and world size 2 (tests/test_bench_multi_cpu.py passes --seam tests.bench_seam_cpu, whose `seam` object replaces this one)."""
@@ -1188,17 +1235,27 @@ def rank_main(args):
         model.set_option(key, int(val))
         log(f"option {key} = {val}")
 
+    repeats = args.repeats if args.repeats is not None else (3 if args.full else 1)
+    # infer() draws its two noise tensors from torch's generators: seeded, so that the same arguments give the same outputs in every run
+    torch.manual_seed(1234 + rank)
     res = seam.run_config(primary, model, hp, dev, rank, world, args.steps, args.warmup, overrides, args.full_profile,
-                          collective=use_dist, repeats=args.repeats, contract=True)
+                          collective=use_dist, repeats=repeats, contract=True, extras=args.full or args.full_profile,
+                          keep_outputs=bool(args.dump_outputs))
     log(f"rank {rank}: config {primary}: timed region {res['dt']:.3f}s for {args.steps} steps")
+    if args.dump_outputs:
+        if res.get("outputs"):
+            dump_outputs(res.pop("outputs"), args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "",
+                         budget=DUMP_BUDGET_BYTES // world)
+        else:
+            log("dump: this run_config returned no outputs; nothing written")
     dt, audio = res["dt"], res["audio_per_step"] * args.steps
     per_rank = None
     n1_same = None
     if use_dist:
         # the same-workload single-GPU anchor of this line: rank 0 runs ITS shard once more, alone, while every other rank waits at the
         # barrier below (outside the timed region) — so that value / (N x n1) is a scaling efficiency on ONE workload, whatever the
-        # N = 1 line of the driver measured (that one is BASELINE config 2, batch 1)
-        if rank == 0:
+        # N = 1 line of the driver measured (that one is BASELINE config 2, batch 1).  --full only: it is a run of its own
+        if rank == 0 and args.full:
             r1 = seam.run_config(primary, model, hp, dev, 0, 1, args.steps, min(args.warmup, 2), overrides, solo=True)
             n1_same = dict(value=round(r1["audio_per_step"] * args.steps / r1["dt"], 2), ms_per_step=round(r1["dt"] / args.steps * 1e3, 4),
                            utterances=r1["B"], steps=args.steps)
@@ -1222,7 +1279,7 @@ def rank_main(args):
         dt = float(tmax.item())
 
     secondary = {}
-    if world == 1 and not use_dist and rank == 0 and not args.no_secondary and args.config is None and not args.residual_flow:
+    if args.full and world == 1 and not use_dist and rank == 0 and not args.no_secondary and args.config is None and not args.residual_flow:
         for num in (3, 4, 5):
             try:
                 r = run_config(num, model, hp, dev, 0, 1, max(3, min(args.steps, 10)), 3, {}, repeats=3, contract=False)
@@ -1303,7 +1360,7 @@ def rank_main(args):
 
     if rank == 0:
         cpu, parity = None, None
-        if world == 1 and not use_dist and not args.no_cpu_baseline:
+        if args.full and world == 1 and not use_dist and not args.no_cpu_baseline:
             log("timing the CPU baseline (oracle port)")
             cpu, par = cpu_baseline(hp, sd, args.cpu_iters)
             if primary == 2 and not any(v is not None for v in overrides.values()):
@@ -1351,7 +1408,11 @@ def rank_main(args):
             line["secondary"] = secondary
         if res.get("full"):
             line["kernel_families_untimed_pass"] = res["full"]
-        emit(line, args.details_out)
+        if args.full or args.details_out:
+            emit(line, args.details_out)
+        else:                                              # a plain run: the line is the whole record, no details file
+            sys.stdout.write(headline(_finite(line)) + "\n")
+            sys.stdout.flush()
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -138,3 +138,26 @@ def test_headline_sheds_blocks_rather_than_overflow():
     rec["secondary"] = {f"leg{i}": dict(value=1.0, ms_per_step=2.0, roofline=dict(frac=0.5, bound="mfma", kernel="k" * 40)) for i in range(80)}
     txt = bench.headline(rec)
     assert len(txt) < 4096 and _strict(txt)["secondary"] == "see details" and _strict(txt)["roofline"]["frac"] > 0
+
+
+def test_dump_outputs_fit_the_budget_and_sample_the_same_positions(tmp_path):
+    """`--dump-outputs`: float32 (float64 kept) .npy files, small arrays whole, a larger one as a seeded 1-D sample, all within the budget,
+    and the same file contents from the same outputs in every run."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = dict(o=torch.randn(3, 1, 5000, generator=g), y_mask=torch.ones(3, 1, 40, dtype=torch.float16),
+                lat=torch.randn(2, 7, generator=g, dtype=torch.float64))
+    budget = 16 * 1024
+    for d in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / d), budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["lat.npy", "o.npy", "y_mask.npy"]
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert a["lat.npy"].dtype == np.float64 and a["o.npy"].dtype == np.float32 and a["y_mask.npy"].dtype == np.float32
+    assert a["lat.npy"].shape == (2, 7) and a["y_mask.npy"].shape == (3, 1, 40)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget + 128 * len(files)
+    o = a["o.npy"]
+    assert o.ndim == 1 and 1000 < o.size < 15000 and np.isin(o, outs["o"].numpy().reshape(-1)).all()
+    assert all(np.array_equal(a[f], np.load(tmp_path / "b" / f)) for f in files)

@@ -41,22 +41,31 @@ def _check(d, launcher):
 
 
 def test_self_launched_two_ranks_gloo():
-    d = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--seam", "tests.bench_seam_cpu"])
+    d = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--seam", "tests.bench_seam_cpu"])
     _check(d, "self")
 
 
 def test_torchrun_launched_two_ranks_gloo():
     port = 29600 + os.getpid() % 1500
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-              "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--seam", "tests.bench_seam_cpu"])
+              "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--seam", "tests.bench_seam_cpu"])
     _check(d, "torch.distributed.run")
 
 
 def test_forced_dist_at_world_size_one_gloo():
     """--gpus 1 --force-dist: the N>1 code path (process group, blob broadcast, barriers, all_reduce(MAX), all_gather_object, the N>1
     line builder) at world size 1 — what tests/test_dist_w1_gpu.py runs against RCCL on the one GPU of the test box."""
-    d = _run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--steps", "4", "--warmup", "1", "--seam", "tests.bench_seam_cpu"])
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--steps", "4", "--warmup", "1", "--full", "--seam", "tests.bench_seam_cpu"])
     assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and "config 4" in d["config"]["workload"]
     assert "world size 1" in d["forced_dist"] and d["per_rank"][0]["rank"] == 0
     assert abs(d["ms_per_step"] - 10.0) < 1e-6 and abs(d["n1_same_workload"]["ms_per_step"] - 8.0) < 1e-6
     assert abs(d["scaling_efficiency"] - 0.8) < 1e-3
+
+
+def test_plain_run_is_the_timed_region_alone():
+    """Without --full the line carries the headline figure only: no single-GPU anchor, no CPU baseline, no secondary legs, no details file."""
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--steps", "4", "--warmup", "1", "--seam", "tests.bench_seam_cpu"])
+    assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and abs(d["ms_per_step"] - 10.0) < 1e-6
+    assert d["metric"].startswith("audio-seconds/sec") and d["unit"] == "audio-seconds/sec" and d["higher_is_better"] is True
+    assert "n1_same_workload" not in d and "scaling_efficiency" not in d and "secondary" not in d and "details" not in d
+    assert d["cpu_baseline"] is None

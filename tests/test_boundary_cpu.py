@@ -1,12 +1,12 @@
 """CPU: the drop-in boundary —
  * the RNG contract: the shim's two draws reproduce what a seeded run of the REAL reference drew (fixture
    tests/golden/seeded_*.npz, written by oracle/gen_golden.py from an un-injected ``torch.manual_seed(s); net.infer(...)``);
- * the reference's OWN callers run unchanged on the shim: ``utils.save_checkpoint`` -> ``utils.load_checkpoint`` and the body of
-   ``infer.get_net_g`` (infer.py:84-104) — live reference needed, skipped where /root/reference is absent (the GPU box);
  * the reference's ONNX consumer (onnx_modules/V230_OnnxInference/__init__.py) drives ``onnx_api.StageRunner`` objects through its
-   own glue code — the runner protocol / tensor names are what that code expects (runners backed by the oracle here: no GPU);
+   own glue code (stored run, oracle/gen_reference_fixtures.py) — this package's consumer gives the same audio from the same runners, and
+   the runner protocol / tensor names are what that code expects (runners backed by the oracle here: no GPU);
  * handle hygiene: a blob packed under another pack layout is rejected, repack() refuses never-loaded parameters."""
 import ctypes as C
+import json
 import os
 import sys
 import types
@@ -16,11 +16,8 @@ import pytest
 import torch
 
 from bert_vits2_amd import hparams as H, lib as L, models, onnx_api
-from oracle import bv2_oracle as O, cases, ref_import
+from oracle import bv2_oracle as O, cases
 from tests.helpers import GOLDEN, cached_state_dict, load_golden, rms
-
-needs_ref = pytest.mark.skipif(not ref_import.available(), reason="live reference (/root/reference) not present")
-
 
 def _seeded():
     z = np.load(os.path.join(GOLDEN, "seeded_" + cases.SEEDED_CASE + ".npz"), allow_pickle=False)
@@ -55,35 +52,6 @@ def test_seeded_reference_run_is_what_the_oracle_computes_from_those_draws():
     assert rms(out["o"] - g["o"]) <= 2e-5
 
 
-@needs_ref
-def test_reference_utils_load_checkpoint_and_get_net_g_body_run_unchanged_on_the_shim(tmp_path):
-    ref_import.reference_models()                                         # installs the two sys.modules stubs, REF on sys.path
-    import utils as ref_utils                                             # /root/reference/utils.py, unmodified
-    hp = H.default_v23()
-    sd = cached_state_dict(hp, 0)
-    net = ref_import.build_reference_net(hp, sd)
-    opt = torch.optim.AdamW(net.parameters(), lr=2e-4)
-    path = str(tmp_path / "G_1234.pth")
-    ref_utils.save_checkpoint(net, opt, 2e-4, 1234, path)                 # reference utils.py:123-139
-    # --- the body of infer.get_net_g (infer.py:84-104) with models.SynthesizerTrn swapped for the shim
-    hps = ref_utils.get_hparams_from_file(os.path.join(ref_import.REF, "configs", "config.json"))
-    symbols = sys.modules["text"].symbols
-    net_g = models.SynthesizerTrn(len(symbols), hps.data.filter_length // 2 + 1, hps.train.segment_size // hps.data.hop_length,
-                                  n_speakers=hps.data.n_speakers, **hps.model).to("cpu")
-    _ = net_g.eval()
-    out = ref_utils.load_checkpoint(path, net_g, None, skip_optimizer=True)
-    assert out[0] is net_g and out[3] == 1234
-    # every inference tensor arrived; what gets packed is bit-identical to packing the state_dict directly
-    got = net_g.state_dict()
-    for k, v in sd.items():
-        assert torch.equal(got[k], v), k
-    direct = models.from_hparams(hp)
-    direct.load_state_dict(sd, strict=False)
-    assert torch.equal(net_g.pack_host_blob(), direct.pack_host_blob())
-    # the probing the reference does on the returned object
-    assert not hasattr(net_g, "module") and net_g.training is False
-
-
 class _OracleBackedRunner(onnx_api.StageRunner):
     """StageRunner whose ``_call`` is answered by the oracle on the CPU (the product's own ``_call`` needs a GPU): what is under
     test is the run()/name/shape protocol the reference's consumer code relies on."""
@@ -109,30 +77,22 @@ class _OracleBackedRunner(onnx_api.StageRunner):
         return [O.generator(sd, hp, f["z_in"], f["g"])]
 
 
-@needs_ref
 def test_reference_onnx_consumer_drives_the_stage_runners():
-    sys.modules.setdefault("onnxruntime", types.ModuleType("onnxruntime"))   # imported at module level by the consumer; unused here
-    import importlib.util
-    spec = importlib.util.spec_from_file_location(
-        "ref_onnx_infer", os.path.join(ref_import.REF, "onnx_modules", "V230_OnnxInference", "__init__.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    """The waveform the reference's own consumer produced while driving these runners (its glue code run by
+    oracle/gen_reference_fixtures.py, stored in tests/golden/onnx_consumer_reference.npz) is what this package's consumer gives."""
+    from oracle import gen_reference_fixtures as G
     hp = H.default_v23()
     sd = cached_state_dict(hp, 0)
-    sess = object.__new__(mod.OnnxInferenceSession)                            # skip __init__ (it opens .onnx files)
-    for s in onnx_api.STAGES:
-        setattr(sess, s, _OracleBackedRunner(sd, hp, s))
-    T = len(cases.ONNX_INFER_SYMBOLS)
-    rng = np.random.RandomState(5)
-    seq = np.array(cases.ONNX_INFER_SYMBOLS)
-    berts = [rng.randn(T, 1024).astype(np.float32) for _ in range(3)]          # the exported graph's [T, 1024] layout
-    kw = dict(seed=7, seq_noise_scale=0.6, sdp_noise_scale=0.9, sdp_ratio=0.5)
-    wav_ref_glue = sess(seq, np.zeros(T, np.int64), np.zeros(T, np.int64), *berts, np.array([3]), **kw)
+    z = np.load(G.ONNX_PATH, allow_pickle=False)
+    assert cases.weight_checksums(sd) == json.loads(str(z["meta"]))["checksums"]
+    wav_ref_glue = z["wav"]
+    seq, berts, sid, kw = G.onnx_consumer_inputs()
+    T = len(seq)
     # the same runners under THIS package's consumer (own glue: gather-form length regulation) give the same audio
     mine = onnx_api.StageSession.__new__(onnx_api.StageSession)
     for s in onnx_api.STAGES:
         setattr(mine, s, _OracleBackedRunner(sd, hp, s))
-    wav_own_glue = mine(seq, np.zeros(T, np.int64), np.zeros(T, np.int64), *berts, np.array([3]), **kw)
+    wav_own_glue = mine(seq, np.zeros(T, np.int64), np.zeros(T, np.int64), *berts, sid, **kw)
     assert wav_ref_glue.shape == wav_own_glue.shape and wav_ref_glue.shape[1] == 1
     assert rms(torch.from_numpy(wav_ref_glue - wav_own_glue)) <= 1e-6
     assert rms(torch.from_numpy(wav_ref_glue)) > 0.05

@@ -20,7 +20,7 @@ def test_forced_dist_world_size_one_rccl():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = os.path.join(ROOT, "gpurun_out", "dist_w1_details.json")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--steps", "5", "--warmup", "2", "--details-out", out],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--steps", "5", "--warmup", "2", "--full", "--details-out", out],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -21,7 +21,7 @@ def main():
             extra = argv[1].split()
         argv = argv[2:]
     for spec in argv:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--no-secondary", "--no-cpu-baseline"] + extra
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--full", "--no-secondary", "--no-cpu-baseline"] + extra
         for kv in filter(None, spec.split(",")):
             cmd += ["--option", kv]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)

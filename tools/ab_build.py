@@ -42,7 +42,7 @@ def make(rev):
 
 def run(extra, ref):
     det = os.path.join(ROOT, "gpurun_out", f"ab_build_details_{os.getpid()}.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-secondary", "--no-cpu-baseline", "--details-out", det] +
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-secondary", "--no-cpu-baseline", "--details-out", det] +
                        (["--library", REF] if ref else []) + extra,
                        stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]

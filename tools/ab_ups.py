@@ -18,7 +18,7 @@ def main():
         cfg, argv = argv[1], argv[2:]
     for spec in argv:
         with tempfile.NamedTemporaryFile(suffix=".json") as f:
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "12", "--no-secondary", "--no-cpu-baseline", "--details-out", f.name]
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "12", "--full", "--no-secondary", "--no-cpu-baseline", "--details-out", f.name]
             if spec:
                 cmd += ["--variants", spec]
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)

@@ -60,7 +60,7 @@ def one_pass(counter, extra_args):
     d = tempfile.mkdtemp(prefix="bv2pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "-d", d, "--output-format", "csv", "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-secondary"] + extra_args
+           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary"] + extra_args
     subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=False, timeout=600)
     tot, n = collections.Counter(), collections.Counter()
     for cc in glob.glob(d + "/**/*_counter_collection.csv", recursive=True):
