@@ -211,8 +211,25 @@ static int ready(bv2_handle* h, const void* ws) {
   return 0;
 }
 
+// a bv2_item_controls the caller built against another layout is refused (NULL = the scalar call)
+static int check_controls(bv2_handle* h, const bv2_item_controls* ic, const char* what) {
+  if (ic && ic->struct_bytes != (int32_t)sizeof(bv2_item_controls)) {
+    h->err = std::string(what) + ": bv2_item_controls.struct_bytes must be sizeof(bv2_item_controls) (" +
+             std::to_string(sizeof(bv2_item_controls)) + ")";
+    return -1;
+  }
+  return 0;
+}
+
 int bv2_encode_durations(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
                          void* ws, int64_t wsb) {
+  return bv2_encode_durations_ex(h, stream, in, out, nullptr, ws, wsb);
+}
+
+int bv2_encode_durations_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
+                            const bv2_item_controls* ic, void* ws, int64_t wsb) {
+  if (!h) return -1;
+  if (int rc = check_controls(h, ic, "bv2_encode_durations")) return rc;
   if (int rc = ready(h, ws)) return rc;
   BV2_TRY
   if (!in || !out || in->B < 1 || in->T < 1) { h->err = "bv2_encode_durations: bad argument"; return -1; }
@@ -223,18 +240,25 @@ int bv2_encode_durations(bv2_handle* h, bv2_stream stream, const bv2_encode_in* 
     if (in->bert_index[f] && (in->bert_cols[f] < 1 || in->bert_cols[f] > in->T)) {
       h->err = "bv2_encode_durations: bert_cols must be in [1, T] for a word-level feature"; return -1;
     }
-  return run_encode(h, static_cast<hipStream_t>(stream), *in, *out, ws, wsb);
+  return run_encode(h, static_cast<hipStream_t>(stream), *in, *out, ws, wsb, ic);
   BV2_CATCH(h)
 }
 
 int bv2_decode(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out, void* ws, int64_t wsb) {
+  return bv2_decode_ex(h, stream, in, out, nullptr, ws, wsb);
+}
+
+int bv2_decode_ex(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out,
+                  const bv2_item_controls* ic, void* ws, int64_t wsb) {
+  if (!h) return -1;
+  if (int rc = check_controls(h, ic, "bv2_decode")) return rc;
   if (int rc = ready(h, ws)) return rc;
   BV2_TRY
   if (!in || !out || in->B < 1 || in->T < 1 || in->Ty < 1) { h->err = "bv2_decode: bad argument"; return -1; }
   if (!in->m_p || !in->logs_p || !in->x_mask || !in->w_ceil || !in->y_lengths || !in->g || !in->noise_z || !out->o) {
     h->err = "bv2_decode: null tensor pointer"; return -1;
   }
-  return run_decode(h, static_cast<hipStream_t>(stream), *in, *out, ws, wsb);
+  return run_decode(h, static_cast<hipStream_t>(stream), *in, *out, ws, wsb, ic);
   BV2_CATCH(h)
 }
 
@@ -301,7 +325,15 @@ int bv2_stage_generator(bv2_handle* h, bv2_stream stream, int B, int Ty, int L, 
 int bv2_infer(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* enc_out,
               const float* noise_z, int64_t nz_bstride, int64_t nz_cstride, int64_t nz_tstride, float noise_scale, int32_t max_len,
               int32_t Ty_cap, const bv2_decode_out* dec_out, int32_t* Ty_out, void* ws, int64_t wsb) {
-  if (int rc = bv2_encode_durations(h, stream, in, enc_out, ws, wsb)) return rc;
+  return bv2_infer_ex(h, stream, in, enc_out, noise_z, nz_bstride, nz_cstride, nz_tstride, noise_scale, max_len, Ty_cap, dec_out,
+                      Ty_out, nullptr, ws, wsb);
+}
+
+int bv2_infer_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* enc_out,
+                 const float* noise_z, int64_t nz_bstride, int64_t nz_cstride, int64_t nz_tstride, float noise_scale, int32_t max_len,
+                 int32_t Ty_cap, const bv2_decode_out* dec_out, int32_t* Ty_out, const bv2_item_controls* ic, void* ws,
+                 int64_t wsb) {
+  if (int rc = bv2_encode_durations_ex(h, stream, in, enc_out, ic, ws, wsb)) return rc;
   BV2_TRY
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::vector<int64_t> yl((size_t)in->B);
@@ -318,7 +350,7 @@ int bv2_infer(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const b
   d.m_p = enc_out->m_p; d.logs_p = enc_out->logs_p; d.x_mask = enc_out->x_mask; d.w_ceil = enc_out->w_ceil;
   d.y_lengths = enc_out->y_lengths; d.g = enc_out->g;
   d.noise_z = noise_z; d.nz_bstride = nz_bstride; d.nz_cstride = nz_cstride; d.nz_tstride = nz_tstride; d.noise_scale = noise_scale;
-  return bv2_decode(h, stream, &d, dec_out, ws, wsb);
+  return bv2_decode_ex(h, stream, &d, dec_out, ic, ws, wsb);
   BV2_CATCH(h)
 }
 
@@ -367,21 +399,33 @@ static int capture_phase(bv2_handle* h, bv2_stream stream, bv2_graph** graph, co
 
 int bv2_graph_capture_encode(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out, void* ws,
                              int64_t wsb, bv2_graph** graph) {
+  return bv2_graph_capture_encode_ex(h, stream, in, out, nullptr, ws, wsb, graph);
+}
+
+int bv2_graph_capture_encode_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
+                                const bv2_item_controls* ic, void* ws, int64_t wsb, bv2_graph** graph) {
   if (!h) return -1;
+  if (int rc = check_controls(h, ic, "bv2_graph_capture_encode")) return rc;
   BV2_TRY
   if (!in || !out || in->B < 1 || in->T < 1) { h->err = "bv2_graph_capture_encode: bad argument"; return -1; }
   return capture_phase(h, stream, graph, "bv2_graph_capture_encode",
-                       [&](hipStream_t s) { return run_encode(h, s, *in, *out, ws, wsb); });
+                       [&](hipStream_t s) { return run_encode(h, s, *in, *out, ws, wsb, ic); });
   BV2_CATCH(h)
 }
 
 int bv2_graph_capture_decode(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out, void* ws,
                              int64_t wsb, bv2_graph** graph) {
+  return bv2_graph_capture_decode_ex(h, stream, in, out, nullptr, ws, wsb, graph);
+}
+
+int bv2_graph_capture_decode_ex(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out,
+                                const bv2_item_controls* ic, void* ws, int64_t wsb, bv2_graph** graph) {
   if (!h) return -1;
+  if (int rc = check_controls(h, ic, "bv2_graph_capture_decode")) return rc;
   BV2_TRY
   if (!in || !out || in->B < 1 || in->T < 1 || in->Ty < 1 || !out->o) { h->err = "bv2_graph_capture_decode: bad argument"; return -1; }
   return capture_phase(h, stream, graph, "bv2_graph_capture_decode",
-                       [&](hipStream_t s) { return run_decode(h, s, *in, *out, ws, wsb); });
+                       [&](hipStream_t s) { return run_decode(h, s, *in, *out, ws, wsb, ic); });
   BV2_CATCH(h)
 }
 

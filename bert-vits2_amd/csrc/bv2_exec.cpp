@@ -463,7 +463,7 @@ int64_t workspace_bytes(const Model& m, int B, int T, int Ty) {
 // the front launch: emb_g lookup (or a given g), the speaker-conditioning GEMVs, x_mask and the scaled SDP noise
 static void run_front(Ctx& c, const int64_t* sid, const float* g_in, float* g_out, const GemvW* const* gw, float* const* go,
                       int n, int out_stride, const int64_t* x_lengths, float* x_mask, int B, int T, const float* noise,
-                      float* z, float noise_scale) {
+                      float* z, float noise_scale, const float* noise_scale_b = nullptr) {
   const bv2_config& cf = c.m.cfg;
   FrontArgs F;
   std::memset(&F, 0, sizeof(F));
@@ -475,6 +475,7 @@ static void run_front(Ctx& c, const int64_t* sid, const float* g_in, float* g_ou
   if (sid) { F.table = c.W(c.m.emb_g.off); F.sid = sid; F.nrows = cf.n_speakers; F.g_out = g_out; }
   F.lengths = x_lengths; F.mask = x_mask; F.T = T;
   F.noise = noise; F.z = z; F.noise_scale = noise_scale; F.nz = z ? (int64_t)B * 2 * T : 0;
+  F.noise_scale_b = noise_scale_b;
   c.chk(launch_front(c.s, F), "front");
 }
 
@@ -601,12 +602,15 @@ static void sdp_core(Ctx& c, PlanA& P, const float* x, const float* mask, const 
 }
 
 static void run_durations(Ctx& c, const PlanA& P, const float* logw_dp, const float* mask, float sdp_ratio, float length_scale,
-                          float* logw_sdp, float* logw, float* w_ceil, int64_t* y_lengths, int B, int T) {
+                          float* logw_sdp, float* logw, float* w_ceil, int64_t* y_lengths, int B, int T,
+                          const bv2_item_controls* ic = nullptr) {
   const Model& m = c.m;
   DurArgs d;
   d.z = P.z; d.ea_m = c.W(m.ea_m.off); d.ea_logs = c.W(m.ea_logs.off);
   d.logw_dp = logw_dp; d.mask = mask;
   d.sdp_ratio = sdp_ratio; d.one_minus_ratio = (float)(1.0 - (double)sdp_ratio); d.length_scale = length_scale;
+  d.sdp_ratio_b = ic ? ic->sdp_ratio : nullptr;     // per-utterance values (bv2_item_controls); null keeps the scalars
+  d.length_scale_b = ic ? ic->length_scale : nullptr;
   d.logw_sdp = logw_sdp; d.logw = logw; d.w_ceil = w_ceil; d.y_lengths = y_lengths;
   d.B = B; d.T = T;
   c.chk(launch_durations(c.s, d), "durations");
@@ -614,7 +618,8 @@ static void run_durations(Ctx& c, const PlanA& P, const float* logw_dp, const fl
 
 // ===============================================================================================================
 // phase A: emb_g, enc_p, sdp, dp, durations
-int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_encode_out& out, void* ws, int64_t wsb) {
+int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_encode_out& out, void* ws, int64_t wsb,
+               const bv2_item_controls* ic) {
   const Model& m = h->model;
   const bv2_config& cf = m.cfg;
   const int B = in.B, T = in.T, H = cf.hidden_channels;
@@ -629,7 +634,8 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   {
     const GemvW* gw[3] = {&m.enc.spk, &m.sdp_cond, &m.dp_cond};
     float* go[3] = {spk, sdp_c, dp_c};
-    run_front(c, in.sid, nullptr, out.g, gw, go, 3, 3 * H, in.x_lengths, out.x_mask, B, T, in.noise_w, P.z, in.noise_scale_w);
+    run_front(c, in.sid, nullptr, out.g, gw, go, 3, 3 * H, in.x_lengths, out.x_mask, B, T, in.noise_w, P.z, in.noise_scale_w,
+              ic ? ic->noise_scale_w : nullptr);
   }
   const float* berts[3] = {in.bert, in.ja_bert, in.en_bert};
   enc_p_core(c, P, in.x, in.tone, in.language, berts, mask, spk, 3 * H, B, T, out.x, out.m_p, out.logs_p, P.dp0, dp_c,
@@ -661,7 +667,7 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   sdp_core(c, P, out.x, mask, sdp_c, 3 * H, B, T);
   if (forked && hipStreamWaitEvent(s, h->ev_join, 0) != hipSuccess) c.fail("dp join", -6);
   run_durations(c, P, logw_dp, mask, in.sdp_ratio, in.length_scale, out.logw_sdp ? out.logw_sdp : P.logw_sdp, out.logw,
-                out.w_ceil, out.y_lengths, B, T);
+                out.w_ceil, out.y_lengths, B, T, ic);
   return c.rc;
 }
 
@@ -1278,7 +1284,8 @@ static void phase_b_gemv(Ctx& c, const PlanB& P, const float* g, int B) {
   c.chk(launch_gemv(c.s, G), "gemv.B");
 }
 
-int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb) {
+int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
+               const bv2_item_controls* ic) {
   const Model& m = h->model;
   const bv2_config& cf = m.cfg;
   const int B = in.B, T = in.T, Ty = in.Ty, C = cf.inter_channels;
@@ -1294,6 +1301,7 @@ int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_
   e.w_ceil = in.w_ceil; e.x_mask = in.x_mask; e.y_lengths = in.y_lengths; e.m_p = in.m_p; e.logs_p = in.logs_p;
   e.noise = in.noise_z; e.nz_bstride = in.nz_bstride; e.nz_cstride = in.nz_cstride; e.nz_tstride = in.nz_tstride;
   e.noise_scale = in.noise_scale;
+  e.noise_scale_b = ic ? ic->noise_scale : nullptr;
   e.frame_idx = P.fidx; e.attn = out.attn; e.y_mask = ymask; e.z_p = z; e.m_e = out.m_p; e.logs_e = out.logs_p;
   e.z_p2 = out.z_p;                                  // the flow updates z in place: z_p is kept as a second store
   e.B = B; e.C = C; e.T = T; e.Ty = Ty;

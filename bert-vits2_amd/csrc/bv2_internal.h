@@ -181,8 +181,11 @@ bool key_in_schema(const Model& m, const std::string& key);
 
 // bv2_exec.cpp
 int64_t workspace_bytes(const Model& m, int B, int T, int Ty);
-int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_encode_out& out, void* ws, int64_t wsb);
-int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb);
+// ic: per-utterance controls (may be null: the scalars of in); a null member keeps that scalar
+int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_encode_out& out, void* ws, int64_t wsb,
+               const bv2_item_controls* ic = nullptr);
+int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
+               const bv2_item_controls* ic = nullptr);
 int run_flow(bv2_handle* h, hipStream_t s, int B, int Ty, const float* z_p, const int64_t* y_lengths, const float* y_mask,
              const float* g, float* z, void* ws, int64_t wsb);
 int run_stage_emb_g(bv2_handle* h, hipStream_t s, int B, const int64_t* sid, float* g);

@@ -566,6 +566,7 @@ struct FrontArgs {
   const float* table; const int64_t* sid; int nrows; float* g_out; int gin;
   const int64_t* lengths; float* mask; int T;
   const float* noise; float* z; float noise_scale; int64_t nz;
+  const float* noise_scale_b;   // [B] per-utterance noise_scale_w (bv2_item_controls), or null = noise_scale; z is [B][2][T]
 };
 int launch_front(hipStream_t stream, const FrontArgs& a);
 
@@ -607,6 +608,8 @@ struct DurArgs {
   const float* logw_dp;     // [B][T]
   const float* mask;
   float sdp_ratio, one_minus_ratio, length_scale;   // one_minus_ratio = (float)(1.0 - (double)sdp_ratio)
+  const float* sdp_ratio_b;     // [B] per-utterance sdp_ratio (bv2_item_controls), or null = the two scalars above
+  const float* length_scale_b;  // [B] per-utterance length_scale, or null = length_scale
   float* logw_sdp; float* logw; float* w_ceil; int64_t* y_lengths;
   int B, T;
 };
@@ -643,6 +646,7 @@ struct ExpandArgs {
   const float* w_ceil; const float* x_mask; const int64_t* y_lengths;
   const float* m_p; const float* logs_p;             // [B][C][T]
   const float* noise; int64_t nz_bstride, nz_cstride, nz_tstride; float noise_scale;
+  const float* noise_scale_b;                         // [B] per-utterance noise_scale (bv2_item_controls), or null = noise_scale
   int* frame_idx;                                     // [B][Ty] scratch
   float* attn; float* y_mask; float* z_p; float* m_e; float* logs_e;   // outputs (attn/y_mask/m_e/logs_e may be null)
   float* z_p2;                                        // optional second copy of z_p (the flow updates z_p in place)

@@ -241,8 +241,18 @@ __global__ void __launch_bounds__(256) front_kernel(const FrontArgs A) {
       const int b = (int)(i / A.T), t = (int)(i - (int64_t)b * A.T);
       A.mask[i] = (!A.lengths || (int64_t)t < A.lengths[b]) ? 1.f : 0.f;
     }
-  if (A.z)
+  if (A.z && !A.noise_scale_b)
     for (int64_t i = i0; i < A.nz; i += step) A.z[i] = A.noise[i] * A.noise_scale;
+  if (A.z && A.noise_scale_b) {                    // per-utterance scale: loaded once per item this thread visits
+    const int64_t per = (int64_t)2 * A.T;
+    int bc = -1;
+    float sc = 0.f;
+    for (int64_t i = i0; i < A.nz; i += step) {
+      const int b = (int)(i / per);
+      if (b != bc) { bc = b; sc = A.noise_scale_b[b]; }
+      A.z[i] = A.noise[i] * sc;
+    }
+  }
 }
 
 int launch_front(hipStream_t stream, const FrontArgs& a) {
@@ -431,6 +441,9 @@ __global__ void __launch_bounds__(256) durations_kernel(const DurArgs A) {
   __shared__ float part[256];
   const int b = blockIdx.x;
   const float m0 = A.ea_m[0], il0 = expf(-A.ea_logs[0]);
+  float r = A.sdp_ratio, omr = A.one_minus_ratio, lsc = A.length_scale;
+  if (A.sdp_ratio_b) { r = A.sdp_ratio_b[b]; omr = (float)(1.0 - (double)r); }   // the host's rounding of 1 - r (bv2_exec.cpp)
+  if (A.length_scale_b) lsc = A.length_scale_b[b];
   float s = 0.f;
   for (int t = threadIdx.x; t < A.T; t += 256) {
     const int64_t bt = (int64_t)b * A.T + t;
@@ -439,8 +452,8 @@ __global__ void __launch_bounds__(256) durations_kernel(const DurArgs A) {
     if (A.logw_sdp) A.logw_sdp[bt] = ls;
     if (!A.logw_dp) continue;                      // bv2_stage_sdp: only the ElementwiseAffine inverse is wanted
     const float ld = A.logw_dp[bt];
-    const float lw = ls * A.sdp_ratio + ld * A.one_minus_ratio;
-    const float w = expf(lw) * mk * A.length_scale;
+    const float lw = ls * r + ld * omr;
+    const float w = expf(lw) * mk * lsc;
     const float wc = ceilf(w);
     A.logw[bt] = lw;
     A.w_ceil[bt] = wc;
@@ -514,7 +527,8 @@ __global__ void expand_kernel(const ExpandArgs A) {
   }
   const int64_t off = ((int64_t)b * A.C + c) * A.Ty + j;
   const float nz = A.noise[(int64_t)b * A.nz_bstride + (int64_t)c * A.nz_cstride + (int64_t)j * A.nz_tstride];
-  const float zp = m + nz * expf(lg) * A.noise_scale;
+  const float ns = A.noise_scale_b ? A.noise_scale_b[b] : A.noise_scale;   // workgroup-uniform (b = blockIdx.z)
+  const float zp = m + nz * expf(lg) * ns;
   A.z_p[off] = zp;
   if (A.z_p2) A.z_p2[off] = zp;
   if (A.m_e) A.m_e[off] = m;

@@ -76,6 +76,12 @@ class DecodeOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("o", "attn", "y_mask", "z", "z_p", "m_p", "logs_p")]
 
 
+class ItemControls(C.Structure):
+    """include/bv2.h bv2_item_controls: per-utterance [B] fp32 DEVICE arrays (null = the scalar of the plain struct)."""
+    _fields_ = [("struct_bytes", C.c_int32), ("noise_scale_w", C.c_void_p), ("sdp_ratio", C.c_void_p), ("length_scale", C.c_void_p),
+                ("noise_scale", C.c_void_p)]
+
+
 class ProfileRow(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -106,9 +112,19 @@ SYMBOLS = [
     ("bv2_stage_generator", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64]),
     ("bv2_infer", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.c_int64, C.c_int64, C.c_float,
                             C.c_int32, C.c_int32, C.POINTER(DecodeOut), C.POINTER(C.c_int32), _P, C.c_int64]),
+    ("bv2_encode_durations_ex", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P,
+                                          C.c_int64]),
+    ("bv2_decode_ex", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), C.POINTER(ItemControls), _P, C.c_int64]),
+    ("bv2_infer_ex", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.c_int64, C.c_int64, C.c_float,
+                               C.c_int32, C.c_int32, C.POINTER(DecodeOut), C.POINTER(C.c_int32), C.POINTER(ItemControls), _P,
+                               C.c_int64]),
     ("bv2_pcm16", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
     ("bv2_graph_capture_encode", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_decode", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), _P, C.c_int64, C.POINTER(_P)]),
+    ("bv2_graph_capture_encode_ex", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P,
+                                              C.c_int64, C.POINTER(_P)]),
+    ("bv2_graph_capture_decode_ex", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), C.POINTER(ItemControls), _P,
+                                              C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_launch", C.c_int, [_P, _P]),
     ("bv2_graph_num_nodes", C.c_int, [_P]),
     ("bv2_graph_destroy", None, [_P]),

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 from typing import Dict, Optional
 
 import torch
@@ -41,6 +42,45 @@ def draw_noise_z(B: int, C: int, Ty: int, device) -> torch.Tensor:
     with those strides reproduces the reference's values (plain ``torch.randn(B, C, T_y)`` does not); the
     C ABI takes the strides (``bv2_decode_in.nz_*stride``), so the tensor is handed over as it is."""
     return torch.randn_like(torch.empty(B, Ty, C, device=device, dtype=torch.float32).transpose(1, 2))
+
+
+def item_control(name: str, value, B: int, device):
+    """One synthesis control (``sdp_ratio``, ``noise_scale``, ``noise_scale_w``, ``length_scale``) as ``infer`` takes it.  A Python
+    number or a 0-d tensor -> ``(float, None)``: the scalar path.  A tensor of B elements shaped ``[B]``, ``[B,1]`` or ``[B,1,1]``
+    (the shapes the reference's ``infer`` broadcasts) -> ``(None, fp32 [B] on device)``: one value per utterance
+    (``bv2_item_controls``; ``device`` None keeps the tensor where it is).  Any other shape raises ValueError naming the control."""
+    if not isinstance(value, torch.Tensor):
+        if isinstance(value, numbers.Real):
+            return float(value), None
+        try:
+            value = torch.as_tensor(value)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise ValueError(f"{name} must be a number or a tensor of B = {B} values") from e
+    if value.dim() == 0:
+        return float(value), None
+    if tuple(value.shape) not in ((B,), (B, 1), (B, 1, 1)):
+        raise ValueError(f"{name} must be a number or a tensor shaped [B], [B,1] or [B,1,1] with B = {B}, got {tuple(value.shape)}")
+    return None, value.detach().to(device=device or value.device, dtype=torch.float32).reshape(B).contiguous()
+
+
+def _control_buffer(values) -> torch.Tensor:
+    """A zeroed [4, B] fp32 control buffer, on the host when every per-item value is there (then one upload moves it)."""
+    t = [v for v in values if v is not None]
+    host = all(v.device.type == "cpu" for v in t)
+    return torch.zeros(4, t[0].shape[0], dtype=torch.float32, device="cpu" if host else t[0].device)
+
+
+def _controls_ptr(ctl: Optional[torch.Tensor], rows):
+    """bv2_item_controls over the rows of a [4, B] fp32 control buffer (noise_scale_w, sdp_ratio, length_scale, noise_scale);
+    ``rows`` names the members that are set, the others stay null."""
+    if ctl is None:
+        return None
+    ic = L.ItemControls()
+    ic.struct_bytes = C.sizeof(L.ItemControls)
+    for r, name in enumerate(("noise_scale_w", "sdp_ratio", "length_scale", "noise_scale")):
+        if r in rows:
+            setattr(ic, name, ctl[r].data_ptr())
+    return C.byref(ic)
 
 
 class _Node(nn.Module):
@@ -348,6 +388,22 @@ class SynthesizerTrn(nn.Module):
             return ein
         if noise_w.shape != (B, 2, T):
             raise ValueError("noise_w must be [B,2,T]")
+        # per-utterance controls: if any of the three is a [B] tensor, all three go to the library as [B] arrays (rows 0-2 of a
+        # [4, B] buffer, bv2_item_controls); otherwise the scalar call runs exactly as before
+        ctrl = [item_control(n, v, B, None) for n, v in (("noise_scale_w", noise_scale_w), ("sdp_ratio", sdp_ratio),
+                                                          ("length_scale", length_scale))]
+        ctl = None
+        if any(t is not None for _, t in ctrl):
+            ctl = _control_buffer([t for _, t in ctrl])
+            for r, (v, t) in enumerate(ctrl):
+                if t is not None:
+                    ctl[r].copy_(t)
+                else:
+                    ctl[r].fill_(v)
+            ctl = ctl.to(dev)                                     # one upload when the values came from the host
+            noise_scale_w = sdp_ratio = length_scale = 0.0        # ignored by the library: every member of the controls is set
+        else:
+            noise_scale_w, sdp_ratio, length_scale = (v for v, _ in ctrl)
         hp = self.hp
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         okeys = ("g", "x", "m_p", "logs_p", "x_mask", "logw_sdp", "logw_dp", "logw", "w_ceil", "y_lengths")
@@ -361,11 +417,14 @@ class SynthesizerTrn(nn.Module):
             for i in range(3):
                 if bidx[i] is not None:
                     ins[f"bert_index{i}"] = bidx[i]
+            if ctl is not None:
+                ins["ctl"] = ctl                    # the graph owns a [4, B] copy: its values are refilled before every replay
 
             static = self._graphs_static
+            moving = ("noise_w", "ctl")
 
             def build(own_inputs):
-                staged = tuple(ins) if own_inputs else ("noise_w",)     # static_io: everything but the noise is read in place
+                staged = tuple(ins) if own_inputs else tuple(k for k in moving if k in ins)   # static_io: the rest is read in place
                 sin = {k: (torch.empty_like(v) if k in staged else v) for k, v in ins.items()}
                 sout = mk_out()
                 ein = L.EncodeIn(B, T, *[_ptr(sin[k]) for k in ("x", "x_lengths", "sid", "tone", "language", "bert", "ja_bert",
@@ -374,13 +433,18 @@ class SynthesizerTrn(nn.Module):
                 with_index(ein, lambda i: sin[f"bert_index{i}"].data_ptr())
                 eout = L.EncodeOut(*[_ptr(sout[k]) for k in okeys])
                 with torch.cuda.device(dev):
-                    g = self._capture(self._lib.bv2_graph_capture_encode, C.byref(ein), C.byref(eout),
-                                      C.c_void_p(ws.data_ptr()), ws.numel())
+                    if ctl is None:
+                        g = self._capture(self._lib.bv2_graph_capture_encode, C.byref(ein), C.byref(eout),
+                                          C.c_void_p(ws.data_ptr()), ws.numel())
+                    else:
+                        g = self._capture(self._lib.bv2_graph_capture_encode_ex, C.byref(ein), C.byref(eout),
+                                          _controls_ptr(sin["ctl"], (0, 1, 2)), C.c_void_p(ws.data_ptr()), ws.numel())
                 return dict(graph=g, sin=sin, sout=sout, staged=staged)
 
-            ptrs = tuple(ins[k].data_ptr() for k in ins if k != "noise_w") if static else ()
-            ent = self._graph_entry(("A", B, T, float(noise_scale_w), float(sdp_ratio), float(length_scale), tuple(cols),
-                                     tuple(sorted(ins))), build, ptrs)
+            ptrs = tuple(ins[k].data_ptr() for k in ins if k not in moving) if static else ()
+            # per-utterance controls: the key carries the fact ("ctl" in ins), not the values
+            scal = ("item",) if ctl is not None else (float(noise_scale_w), float(sdp_ratio), float(length_scale))
+            ent = self._graph_entry(("A", B, T) + scal + (tuple(cols), tuple(sorted(ins))), build, ptrs)
             for k in ent["staged"]:
                 ent["sin"][k].copy_(ins[k], non_blocking=True)
             with torch.cuda.device(dev):
@@ -397,8 +461,13 @@ class SynthesizerTrn(nn.Module):
         ws = self._workspace(B, T, 1)
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self._check(self._lib.bv2_encode_durations(self._handle, stream, C.byref(ein), C.byref(eout),
-                                                       C.c_void_p(ws.data_ptr()), ws.numel()), "bv2_encode_durations")
+            if ctl is None:
+                self._check(self._lib.bv2_encode_durations(self._handle, stream, C.byref(ein), C.byref(eout),
+                                                           C.c_void_p(ws.data_ptr()), ws.numel()), "bv2_encode_durations")
+            else:
+                self._check(self._lib.bv2_encode_durations_ex(self._handle, stream, C.byref(ein), C.byref(eout),
+                                                              _controls_ptr(ctl, (0, 1, 2)), C.c_void_p(ws.data_ptr()), ws.numel()),
+                            "bv2_encode_durations_ex")
         return out
 
     @torch.no_grad()
@@ -413,6 +482,13 @@ class SynthesizerTrn(nn.Module):
         hp = self.hp
         B, _, T = enc["x"].shape
         Ci = hp.inter_channels
+        noise_scale, ns_item = item_control("noise_scale", noise_scale, B, None)
+        ctl = None
+        if ns_item is not None:                         # per-utterance noise_scale: row 3 of a [4, B] control buffer
+            ctl = _control_buffer([ns_item])
+            ctl[3].copy_(ns_item)
+            ctl = ctl.to(dev)
+            noise_scale = 0.0
         draw_z = noise_z is None                        # infer(): draw #2 straight into the graph's buffer (static_io)
         if not draw_z:
             assert noise_z.is_cuda and noise_z.dtype == torch.float32 and noise_z.shape[2] >= Ty and noise_z.shape[1] == Ci
@@ -468,21 +544,30 @@ class SynthesizerTrn(nn.Module):
                 sin = {k: (torch.empty_like(enc[k]) if own_inputs else enc[k]) for k in ikeys}
                 # the reference's strides for the prior noise (draw_noise_z): an in-place normal_() on it IS randn_like(m_p)
                 sin["noise_z"] = torch.zeros(B, Ty, Ci, dtype=torch.float32, device=dev).transpose(1, 2)   # zeros: a bucket's tail is never drawn
+                if ctl is not None:
+                    sin["ctl"] = torch.zeros_like(ctl)
                 sout = mk_out()
                 din = L.DecodeIn(B, T, int(Ty), int(L_dec), *[_ptr(sin[k]) for k in ikeys], _ptr(sin["noise_z"]),
                                  sin["noise_z"].stride(0), sin["noise_z"].stride(1), sin["noise_z"].stride(2),
                                  float(noise_scale), mode)
                 dout = L.DecodeOut(*[_ptr(sout[k]) for k in okeys])
                 with torch.cuda.device(dev):
-                    g = self._capture(self._lib.bv2_graph_capture_decode, C.byref(din), C.byref(dout),
-                                      C.c_void_p(ws.data_ptr()), ws.numel())
+                    if ctl is None:
+                        g = self._capture(self._lib.bv2_graph_capture_decode, C.byref(din), C.byref(dout),
+                                          C.c_void_p(ws.data_ptr()), ws.numel())
+                    else:
+                        g = self._capture(self._lib.bv2_graph_capture_decode_ex, C.byref(din), C.byref(dout),
+                                          _controls_ptr(sin["ctl"], (3,)), C.c_void_p(ws.data_ptr()), ws.numel())
                 return dict(graph=g, sin=sin, sout=sout)
 
             ptrs = tuple(enc[k].data_ptr() for k in ikeys) if static else ()
-            ent = self._graph_entry(("B", B, T, int(Ty), int(L_dec), bool(want_attn), float(noise_scale), mode), build, ptrs)
+            scal = "item" if ctl is not None else float(noise_scale)   # per-utterance: the fact, not the values
+            ent = self._graph_entry(("B", B, T, int(Ty), int(L_dec), bool(want_attn), scal, mode), build, ptrs)
             if ent["own_inputs"]:
                 for k in ikeys:
                     ent["sin"][k].copy_(enc[k])
+            if ctl is not None:
+                ent["sin"]["ctl"].copy_(ctl)
             if draw_z and not bucketed:
                 ent["sin"]["noise_z"].normal_()
             elif draw_z:                                # the reference draws exactly [B, C, T_y] in its memory order (draw_noise_z): keep the RNG contract
@@ -509,8 +594,12 @@ class SynthesizerTrn(nn.Module):
         ws = self._workspace(B, T, Ty)
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self._check(self._lib.bv2_decode(self._handle, stream, C.byref(din), C.byref(dout), C.c_void_p(ws.data_ptr()),
-                                             ws.numel()), "bv2_decode")
+            if ctl is None:
+                self._check(self._lib.bv2_decode(self._handle, stream, C.byref(din), C.byref(dout), C.c_void_p(ws.data_ptr()),
+                                                 ws.numel()), "bv2_decode")
+            else:
+                self._check(self._lib.bv2_decode_ex(self._handle, stream, C.byref(din), C.byref(dout), _controls_ptr(ctl, (3,)),
+                                                    C.c_void_p(ws.data_ptr()), ws.numel()), "bv2_decode_ex")
         return cut(out)
 
     # ------------------------------------------------------------------ the reference entry point
@@ -524,7 +613,12 @@ class SynthesizerTrn(nn.Module):
         ``exact_lengths=True`` makes every utterance of a ragged batch come out exactly as if it had been run alone (the
         reference's unmasked decoder lets the padding bleed into an utterance's last ~40 ms; bv2.h ``exact_lengths``),
         ``bert_index`` hands BERT features over at word level (see ``encode_durations``), ``ty_bucket`` runs phase B at T_y rounded up to
-        a multiple of it (default: ``enable_graphs``' bucket when graphs are on, exact T_y otherwise; see ``enable_graphs``)."""
+        a multiple of it (default: ``enable_graphs``' bucket when graphs are on, exact T_y otherwise; see ``enable_graphs``).
+
+        ``sdp_ratio``, ``noise_scale``, ``noise_scale_w`` and ``length_scale`` each take a number (or 0-d tensor) or, as in the
+        reference, one value per utterance as a tensor shaped [B], [B,1] or [B,1,1] (``item_control``): utterance b then gets what a
+        batch-1 call with its own values gets (``bv2_item_controls``).  With graphs on, one capture per shape serves every set of
+        per-utterance values; scalar values stay part of the graph key as before."""
         if self.device.type != "cuda":
             raise RuntimeError("bert_vits2_amd.SynthesizerTrn.infer needs a GPU: no CPU fallback exists by design")
         dev = self.device

@@ -23,7 +23,9 @@ from . import hparams as H
 
 @dataclass
 class Utterance:
-    """One piece as reference ``infer.get_text`` (infer.py:107-152) produces it: 1-D ids and ``[1024, T]`` features."""
+    """One piece as reference ``infer.get_text`` (infer.py:107-152) produces it: 1-D ids and ``[1024, T]`` features.  The four
+    synthesis controls are the request's own sliders (hiyoriUI ``/voice``: sdp_ratio, noise, noisew, length); ``None`` takes the value
+    ``synthesize`` was called with."""
     phones: torch.Tensor
     tones: torch.Tensor
     lang_ids: torch.Tensor
@@ -31,6 +33,10 @@ class Utterance:
     ja_bert: torch.Tensor
     en_bert: torch.Tensor
     sid: int = 0
+    sdp_ratio: Optional[float] = None
+    noise_scale: Optional[float] = None
+    noise_scale_w: Optional[float] = None
+    length_scale: Optional[float] = None
 
     def __post_init__(self):
         T = int(self.phones.shape[0])
@@ -45,12 +51,19 @@ class Utterance:
         return int(self.phones.shape[0])
 
 
-def plan_batches(lengths: Sequence[int], max_batch: int = 32, max_pad_ratio: float = 1.25) -> List[List[int]]:
+def plan_batches(lengths: Sequence[int], max_batch: int = 32, max_pad_ratio: float = 1.25,
+                 weights: Optional[Sequence[float]] = None) -> List[List[int]]:
     """Length-bucketed batches: utterances sorted by length, a batch is closed when it is full or when its longest
-    member would exceed ``max_pad_ratio`` x its shortest (padding is wasted work: every kernel runs over B x T_max)."""
+    member would exceed ``max_pad_ratio`` x its shortest (padding is wasted work: every kernel runs over B x T_max).
+    ``weights`` (optional, one per utterance): plan on ``length x weight`` instead — with per-utterance ``length_scale`` that is
+    the expected frame count, which sizes the Generator (most of the work); None keeps the plan on symbols."""
     if max_batch < 1:
         raise ValueError("max_batch must be >= 1")
-    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    if weights is not None:
+        if len(weights) != len(lengths):
+            raise ValueError("weights must have one entry per utterance")
+        lengths = [float(n) * float(w) for n, w in zip(lengths, weights)]
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i] if weights is not None else int(lengths[i]), i))
     batches, cur = [], []
     for i in order:
         if cur and (len(cur) >= max_batch or lengths[i] > max_pad_ratio * lengths[cur[0]]):
@@ -138,7 +151,10 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     infer.py:315-319, or int16 with ``as_pcm16``).  Defaults are the reference web UI's (webui.py:443-454).
     ``noise`` (tests): per utterance a pair ``(noise_w [2,T], noise_z [inter, >= T_y])`` to inject instead of drawing.
     ``requests_in_flight`` > 1: the buckets are dealt round-robin to that many ``replicas`` (own handle + HIP stream, shared
-    weights), so one bucket's small-kernel phases overlap another's Generator; results do not depend on it."""
+    weights), so one bucket's small-kernel phases overlap another's Generator; results do not depend on it.
+    An utterance that carries its own ``sdp_ratio`` / ``noise_scale`` / ``noise_scale_w`` / ``length_scale`` gets it inside the
+    shared batch (per-utterance controls, one value per batch item); the call's values fill in the rest.  Buckets are then planned
+    on expected frames (symbols x length_scale)."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
     dev = model.device
@@ -148,10 +164,20 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     lanes = replicas(model, requests_in_flight) if requests_in_flight > 1 else [(model, None)]
     if requests_in_flight > 1:
         torch.cuda.current_stream(dev).synchronize()       # inputs prepared on the caller's stream are visible to the lanes
-    for bi, idx in enumerate(plan_batches([u.length for u in utts], max_batch, max_pad_ratio)):
+    call = dict(sdp_ratio=sdp_ratio, noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale)
+    per_item = any(getattr(u, k) is not None for u in utts for k in call)
+    weights = None
+    if per_item and any(u.length_scale is not None for u in utts):
+        weights = [float(length_scale if u.length_scale is None else u.length_scale) for u in utts]
+    for bi, idx in enumerate(plan_batches([u.length for u in utts], max_batch, max_pad_ratio, weights)):
         lane, lane_stream = lanes[bi % len(lanes)]
+        if per_item:                                        # one value per batch item: [B] tensors (models.item_control)
+            ctl = {k: torch.tensor([float(v if getattr(utts[i], k) is None else getattr(utts[i], k)) for i in idx],
+                                   dtype=torch.float32) for k, v in call.items()}
+        else:
+            ctl = call
         with torch.cuda.stream(lane_stream) if lane_stream is not None else contextlib.nullcontext():
-            _run_bucket(lane, utts, idx, dev, noise, pending, as_pcm16, sdp_ratio, noise_scale, noise_scale_w, length_scale)
+            _run_bucket(lane, utts, idx, dev, noise, pending, as_pcm16, **ctl)
     for idx, host, y_len, ev in pending:
         ev.synchronize()
         for r, i in enumerate(idx):

@@ -229,6 +229,33 @@ int bv2_infer(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const b
               const float* noise_z, int64_t nz_bstride, int64_t nz_cstride, int64_t nz_tstride, float noise_scale, int32_t max_len,
               int32_t Ty_cap, const bv2_decode_out* dec_out, int32_t* Ty_out, void* workspace, int64_t workspace_bytes);
 
+/* ---- per-utterance synthesis controls --------------------------------------------------------------------------------
+ * The reference's infer() takes sdp_ratio, noise_scale, noise_scale_w and length_scale as values torch broadcasts, so a caller
+ * may pass one value per utterance as a [B,1,1] tensor (models.py:248-251, 1052-1056, 1071); a serving front end gives every
+ * request its own sliders (hiyoriUI /voice: sdp_ratio, noise, noisew, length).  The _ex calls below take such values as DEVICE
+ * fp32 arrays of B elements: utterance b then gets exactly what a batch-1 call with those four values as scalars gets (same
+ * logw / w_ceil / y_lengths / path bit for bit; sdp_ratio's complement is formed per utterance as (float)(1.0 - (double)r), the
+ * rounding of the scalar path).  A NULL member keeps the scalar of bv2_encode_in / bv2_decode_in / bv2_infer; a NULL
+ * bv2_item_controls* is the plain call (the five calls without _ex are exactly that).  A captured graph bakes in the four
+ * ADDRESSES, not the values: refill the arrays in place before a replay, and one capture per shape serves every control set.
+ * struct_bytes must be sizeof(bv2_item_controls), otherwise the call fails (-1, message in bv2_last_error). */
+typedef struct bv2_item_controls {
+  int32_t struct_bytes;            /* = sizeof(bv2_item_controls) */
+  const float* noise_scale_w;      /* [B] DEVICE fp32, or NULL = the scalar in bv2_encode_in */
+  const float* sdp_ratio;          /* [B] or NULL */
+  const float* length_scale;       /* [B] or NULL */
+  const float* noise_scale;        /* [B] or NULL = the scalar in bv2_decode_in / bv2_infer */
+} bv2_item_controls;
+
+int bv2_encode_durations_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
+                            const bv2_item_controls* controls, void* workspace, int64_t workspace_bytes);
+int bv2_decode_ex(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out,
+                  const bv2_item_controls* controls, void* workspace, int64_t workspace_bytes);
+int bv2_infer_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* enc_out,
+                 const float* noise_z, int64_t nz_bstride, int64_t nz_cstride, int64_t nz_tstride, float noise_scale, int32_t max_len,
+                 int32_t Ty_cap, const bv2_decode_out* dec_out, int32_t* Ty_out, const bv2_item_controls* controls, void* workspace,
+                 int64_t workspace_bytes);
+
 /* ---- 16-bit PCM (serving glue; replaces the host-side gradio convert_to_16_bit_wav the reference's callers run after
  * .cpu(): webui.py:86,129, hiyoriUI.py:343) -------------------------------------------------------------------- */
 /* pcm[b][i] = (int16) trunc( wave[b][i] / max_j |wave[b][j]| * 32767 ) over the valid samples i, j < y_lengths[b]*hop
@@ -243,13 +270,18 @@ int bv2_pcm16(bv2_stream stream, const float* wave, int64_t wave_bstride, const 
  * stream) into capture mode, records the phase exactly as bv2_encode_durations / bv2_decode would launch it, and
  * instantiates an executable graph.  The graph bakes in every pointer and scalar of in/out/workspace: the caller keeps
  * those buffers alive and at the same addresses (refill the inputs in place before each replay) and re-captures when a
- * shape (B, T, Ty, max_len), a scalar argument or a dtype switch changes.  bv2_graph_launch replays on any stream.
+ * shape (B, T, Ty, max_len), a scalar argument or a dtype switch changes (per-utterance controls are arrays: _ex below).  bv2_graph_launch replays on any stream.
  * Taps and profiling must be off while capturing. */
 typedef struct bv2_graph bv2_graph;
 int bv2_graph_capture_encode(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
                              void* workspace, int64_t workspace_bytes, bv2_graph** graph);
 int bv2_graph_capture_decode(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out,
                              void* workspace, int64_t workspace_bytes, bv2_graph** graph);
+/* the same with per-utterance controls (see bv2_item_controls): the graph reads the control arrays at replay time */
+int bv2_graph_capture_encode_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
+                                const bv2_item_controls* controls, void* workspace, int64_t workspace_bytes, bv2_graph** graph);
+int bv2_graph_capture_decode_ex(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out,
+                                const bv2_item_controls* controls, void* workspace, int64_t workspace_bytes, bv2_graph** graph);
 int bv2_graph_launch(bv2_graph* graph, bv2_stream stream);
 int bv2_graph_num_nodes(const bv2_graph* graph);
 void bv2_graph_destroy(bv2_graph* graph);
