@@ -31,9 +31,10 @@ int bv2_create(const bv2_config* cfg, bv2_handle** out) {
   try {
     h = new bv2_handle();
     std::memset(&h->model.cfg, 0, sizeof(bv2_config));
-    // the struct grew by one trailing field (resblock_type, round 5): the shorter form is still accepted and means ResBlock1
-    const int32_t old_bytes = (int32_t)offsetof(bv2_config, resblock_type);
-    if (cfg->struct_bytes != (int32_t)sizeof(bv2_config) && cfg->struct_bytes != old_bytes) {
+    // the struct grew by one trailing field twice (resblock_type, round 5; spec_channels with the ReferenceEncoder): the shorter forms are
+    // still accepted — no resblock_type means ResBlock1, no spec_channels is legal for a model with a speaker table
+    const int32_t old_bytes = (int32_t)offsetof(bv2_config, resblock_type), mid_bytes = (int32_t)offsetof(bv2_config, spec_channels);
+    if (cfg->struct_bytes != (int32_t)sizeof(bv2_config) && cfg->struct_bytes != mid_bytes && cfg->struct_bytes != old_bytes) {
       g_create_err = "bv2_create: bv2_config.struct_bytes mismatch (ABI drift)";
       delete h;
       return -1;
@@ -41,6 +42,12 @@ int bv2_create(const bv2_config* cfg, bv2_handle** out) {
     std::memcpy(&h->model.cfg, cfg, (size_t)cfg->struct_bytes);
     h->model.cfg.struct_bytes = (int32_t)sizeof(bv2_config);
     if (h->model.cfg.resblock_type == 0) h->model.cfg.resblock_type = 1;
+    if (h->model.cfg.n_speakers == 0 && cfg->struct_bytes != (int32_t)sizeof(bv2_config)) {
+      g_create_err = "bv2_create: n_speakers == 0 needs bv2_config.spec_channels (this bv2_config is the shorter, older struct)";
+      delete h;
+      return -1;
+    }
+    if (h->model.cfg.n_speakers >= 1) h->model.cfg.spec_channels = 0;     // not read: the layout and the blob do not depend on it
     std::string err;
     if (int rc = build_layout(h->model, err)) {
       g_create_err = "bv2_create: " + err;
@@ -228,19 +235,56 @@ int bv2_encode_durations(bv2_handle* h, bv2_stream stream, const bv2_encode_in* 
 
 int bv2_encode_durations_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
                             const bv2_item_controls* ic, void* ws, int64_t wsb) {
-  if (!h) return -1;
-  if (int rc = check_controls(h, ic, "bv2_encode_durations")) return rc;
-  if (int rc = ready(h, ws)) return rc;
-  BV2_TRY
-  if (!in || !out || in->B < 1 || in->T < 1) { h->err = "bv2_encode_durations: bad argument"; return -1; }
-  if (!in->x || !in->x_lengths || !in->sid || !in->tone || !in->language || !in->bert || !in->ja_bert || !in->en_bert ||
+  return bv2_encode_durations_g(h, stream, in, out, ic, nullptr, ws, wsb);
+}
+
+// a model without a speaker table (n_speakers == 0) cannot look g up: checked before anything else, sid is never read
+static int check_speaker(bv2_handle* h, const float* g, const char* what) {
+  if (g || h->model.cfg.n_speakers >= 1) return 0;
+  h->err = std::string(what) + ": this model has no speaker table (n_speakers == 0): pass g (bv2_ref_encode's result) through the _g call";
+  return -1;
+}
+
+// what every phase-A entry point checks; g: the caller's speaker vectors (null: emb_g(in->sid), which needs a speaker table)
+static int check_encode(bv2_handle* h, const bv2_encode_in* in, const bv2_encode_out* out, const float* g, const char* what) {
+  const std::string w(what);
+  if (!in || !out || in->B < 1 || in->T < 1) { h->err = w + ": bad argument"; return -1; }
+  if (!in->x || !in->x_lengths || (!g && !in->sid) || !in->tone || !in->language || !in->bert || !in->ja_bert || !in->en_bert ||
       !in->noise_w || !out->g || !out->x || !out->m_p || !out->logs_p || !out->x_mask || !out->logw || !out->w_ceil ||
-      !out->y_lengths) { h->err = "bv2_encode_durations: null tensor pointer"; return -1; }
+      !out->y_lengths) { h->err = w + ": null tensor pointer"; return -1; }
   for (int f = 0; f < 3; ++f)
     if (in->bert_index[f] && (in->bert_cols[f] < 1 || in->bert_cols[f] > in->T)) {
-      h->err = "bv2_encode_durations: bert_cols must be in [1, T] for a word-level feature"; return -1;
+      h->err = w + ": bert_cols must be in [1, T] for a word-level feature"; return -1;
     }
-  return run_encode(h, static_cast<hipStream_t>(stream), *in, *out, ws, wsb, ic);
+  return 0;
+}
+
+int bv2_encode_durations_g(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
+                           const bv2_item_controls* ic, const float* g, void* ws, int64_t wsb) {
+  if (!h) return -1;
+  if (int rc = check_controls(h, ic, "bv2_encode_durations")) return rc;
+  if (int rc = check_speaker(h, g, "bv2_encode_durations")) return rc;
+  if (int rc = ready(h, ws)) return rc;
+  BV2_TRY
+  if (int rc = check_encode(h, in, out, g, "bv2_encode_durations")) return rc;
+  return run_encode(h, static_cast<hipStream_t>(stream), *in, *out, ws, wsb, ic, g);
+  BV2_CATCH(h)
+}
+
+int64_t bv2_ref_workspace_bytes(const bv2_handle* h, int B, int L) {
+  if (!h || B < 1 || L < 1 || !h->model.ref_enc.present) return -1;
+  return (int64_t)sizeof(float) * ref_enc_workspace_floats(B, L, h->model.cfg.spec_channels) + 256;
+}
+
+int bv2_ref_encode(bv2_handle* h, bv2_stream stream, const float* y, const int64_t* strides, const int64_t* y_lengths, int B, int L,
+                   float* g_out, void* ws, int64_t wsb) {
+  if (!h) return -1;
+  if (!h->model.ref_enc.present) { h->err = "bv2_ref_encode: this model has a speaker table (n_speakers >= 1) and no ReferenceEncoder"; return -2; }
+  if (int rc = ready(h, ws)) return rc;
+  BV2_TRY
+  if (!y || !g_out || B < 1 || B > 65535 || L < 1 || L > (1 << 20)) { h->err = "bv2_ref_encode: bad argument"; return -1; }
+  if (strides && (strides[0] < 0 || strides[1] < 0 || strides[2] < 0)) { h->err = "bv2_ref_encode: negative stride"; return -1; }
+  return run_ref_encode(h, static_cast<hipStream_t>(stream), y, strides, y_lengths, B, L, g_out, ws, wsb);
   BV2_CATCH(h)
 }
 
@@ -267,6 +311,7 @@ int bv2_stage_emb_g(bv2_handle* h, bv2_stream stream, int B, const int64_t* sid,
   if (!h->blob) { h->err = "no weights attached (call bv2_pack_weights + bv2_attach_weights first)"; return -8; }
   BV2_TRY
   if (B < 1 || !sid || !g) { h->err = "bv2_stage_emb_g: bad argument"; return -1; }
+  if (h->model.cfg.n_speakers == 0) { h->err = "bv2_stage_emb_g: this model has no speaker table (n_speakers == 0); g comes from bv2_ref_encode"; return -2; }
   return run_stage_emb_g(h, static_cast<hipStream_t>(stream), B, sid, g);
   BV2_CATCH(h)
 }
@@ -333,7 +378,15 @@ int bv2_infer_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, cons
                  const float* noise_z, int64_t nz_bstride, int64_t nz_cstride, int64_t nz_tstride, float noise_scale, int32_t max_len,
                  int32_t Ty_cap, const bv2_decode_out* dec_out, int32_t* Ty_out, const bv2_item_controls* ic, void* ws,
                  int64_t wsb) {
-  if (int rc = bv2_encode_durations_ex(h, stream, in, enc_out, ic, ws, wsb)) return rc;
+  return bv2_infer_g(h, stream, in, enc_out, noise_z, nz_bstride, nz_cstride, nz_tstride, noise_scale, max_len, Ty_cap, dec_out,
+                     Ty_out, ic, nullptr, ws, wsb);
+}
+
+int bv2_infer_g(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* enc_out,
+                const float* noise_z, int64_t nz_bstride, int64_t nz_cstride, int64_t nz_tstride, float noise_scale, int32_t max_len,
+                int32_t Ty_cap, const bv2_decode_out* dec_out, int32_t* Ty_out, const bv2_item_controls* ic, const float* g, void* ws,
+                int64_t wsb) {
+  if (int rc = bv2_encode_durations_g(h, stream, in, enc_out, ic, g, ws, wsb)) return rc;
   BV2_TRY
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::vector<int64_t> yl((size_t)in->B);
@@ -404,12 +457,18 @@ int bv2_graph_capture_encode(bv2_handle* h, bv2_stream stream, const bv2_encode_
 
 int bv2_graph_capture_encode_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
                                 const bv2_item_controls* ic, void* ws, int64_t wsb, bv2_graph** graph) {
+  return bv2_graph_capture_encode_g(h, stream, in, out, ic, nullptr, ws, wsb, graph);
+}
+
+int bv2_graph_capture_encode_g(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
+                               const bv2_item_controls* ic, const float* g, void* ws, int64_t wsb, bv2_graph** graph) {
   if (!h) return -1;
   if (int rc = check_controls(h, ic, "bv2_graph_capture_encode")) return rc;
   BV2_TRY
   if (!in || !out || in->B < 1 || in->T < 1) { h->err = "bv2_graph_capture_encode: bad argument"; return -1; }
+  if (int rc = check_speaker(h, g, "bv2_graph_capture_encode")) return rc;
   return capture_phase(h, stream, graph, "bv2_graph_capture_encode",
-                       [&](hipStream_t s) { return run_encode(h, s, *in, *out, ws, wsb, ic); });
+                       [&](hipStream_t s) { return run_encode(h, s, *in, *out, ws, wsb, ic, g); });
   BV2_CATCH(h)
 }
 

@@ -472,7 +472,8 @@ static void run_front(Ctx& c, const int64_t* sid, const float* g_in, float* g_ou
     F.p[i].cout = gw[i]->cout; F.p[i].cin = gw[i]->cin; F.p[i].out_bstride = out_stride;
   }
   F.nprob = n; F.B = B; F.g = g_in; F.g_bstride = cf.gin_channels; F.gin = cf.gin_channels;
-  if (sid) { F.table = c.W(c.m.emb_g.off); F.sid = sid; F.nrows = cf.n_speakers; F.g_out = g_out; }
+  if (sid) { F.table = c.W(c.m.emb_g.off); F.sid = sid; F.nrows = cf.n_speakers; }
+  F.g_out = g_out;                                 // the looked-up row, or a copy of the given g
   F.lengths = x_lengths; F.mask = x_mask; F.T = T;
   F.noise = noise; F.z = z; F.noise_scale = noise_scale; F.nz = z ? (int64_t)B * 2 * T : 0;
   F.noise_scale_b = noise_scale_b;
@@ -619,7 +620,7 @@ static void run_durations(Ctx& c, const PlanA& P, const float* logw_dp, const fl
 // ===============================================================================================================
 // phase A: emb_g, enc_p, sdp, dp, durations
 int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_encode_out& out, void* ws, int64_t wsb,
-               const bv2_item_controls* ic) {
+               const bv2_item_controls* ic, const float* g_in) {
   const Model& m = h->model;
   const bv2_config& cf = m.cfg;
   const int B = in.B, T = in.T, H = cf.hidden_channels;
@@ -634,7 +635,8 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   {
     const GemvW* gw[3] = {&m.enc.spk, &m.sdp_cond, &m.dp_cond};
     float* go[3] = {spk, sdp_c, dp_c};
-    run_front(c, in.sid, nullptr, out.g, gw, go, 3, 3 * H, in.x_lengths, out.x_mask, B, T, in.noise_w, P.z, in.noise_scale_w,
+    // a caller's g (a ReferenceEncoder result, a blend, ...) takes the place of the table row: same GEMV code, sid is not read
+    run_front(c, g_in ? nullptr : in.sid, g_in, out.g, gw, go, 3, 3 * H, in.x_lengths, out.x_mask, B, T, in.noise_w, P.z, in.noise_scale_w,
               ic ? ic->noise_scale_w : nullptr);
   }
   const float* berts[3] = {in.bert, in.ja_bert, in.en_bert};
@@ -668,6 +670,27 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   if (forked && hipStreamWaitEvent(s, h->ev_join, 0) != hipSuccess) c.fail("dp join", -6);
   run_durations(c, P, logw_dp, mask, in.sdp_ratio, in.length_scale, out.logw_sdp ? out.logw_sdp : P.logw_sdp, out.logw,
                 out.w_ceil, out.y_lengths, B, T, ic);
+  return c.rc;
+}
+
+// g = ref_enc(y.transpose(1, 2)) (models.py:1047-1048; kernels/ref_enc.hip)
+int run_ref_encode(bv2_handle* h, hipStream_t s, const float* y, const int64_t* strides, const int64_t* y_lengths, int B, int L,
+                   float* g_out, void* ws, int64_t wsb) {
+  const Model& m = h->model;
+  const int spec = m.cfg.spec_channels;
+  if (wsb < (int64_t)sizeof(float) * ref_enc_workspace_floats(B, L, spec)) { h->err = "workspace too small for bv2_ref_encode"; return -5; }
+  Ctx c{h, s, m, h->blob};
+  const RefEncW& R = m.ref_enc;
+  RefEncArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.y = y;
+  a.sb = strides ? strides[0] : (int64_t)spec * L; a.sf = strides ? strides[1] : (int64_t)L; a.st = strides ? strides[2] : 1;
+  a.y_lengths = y_lengths; a.B = B; a.L = L; a.spec = spec; a.gin = m.cfg.gin_channels;
+  for (int i = 0; i < 6; ++i) { a.cw[i] = c.W(R.cw[i].off); a.cb[i] = c.W(R.cb[i].off); }
+  a.w_ih = c.W(R.w_ih.off); a.b_ih = c.W(R.b_ih.off); a.w_hh = c.W(R.w_hh.off); a.b_hh = c.W(R.b_hh.off);
+  a.pw = c.W(R.pw.off); a.pb = c.W(R.pb.off);
+  a.ws = static_cast<float*>(ws); a.g_out = g_out;
+  c.chk(launch_ref_enc(s, a), "ref_enc");
   return c.rc;
 }
 

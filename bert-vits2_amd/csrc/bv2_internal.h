@@ -71,6 +71,14 @@ struct UpW {
   int cl_pad_left = 0;
 };
 
+// ReferenceEncoder (n_speakers == 0 only; kernels/ref_enc.hip)
+struct RefEncW {
+  bool present = false;
+  VecW cw[6], cb[6];                 // conv 1 [9][32], convs 2-6 [Cout/8][Cin][9][8] (weight-norm folded); biases
+  VecW w_ih, b_ih, w_hh, b_hh;       // GRU(128 * W6 -> 128), PyTorch's layout and gate order (r, z, n)
+  VecW pw, pb;                       // proj [gin][128]
+};
+
 struct Model {
   bv2_config cfg;
   bool flow_flip_first = false;      // odd number of couplings: the reverse pass starts with a real channel Flip of z (bv2_model.cpp)
@@ -88,7 +96,8 @@ struct Model {
   GemvW dp_cond;
   ConvW dp_c1, dp_c2, dp_proj;
   VecW dp_g1, dp_b1, dp_g2, dp_b2;
-  VecW emb_g;
+  VecW emb_g;                        // absent (off -1) when n_speakers == 0
+  RefEncW ref_enc;
   // flow: application order (reverse pass): a = 0 is reference flows.{2(n-1)}
   int n_coupling = 0;
   CouplingW coupling[kMaxFlows];
@@ -182,8 +191,11 @@ bool key_in_schema(const Model& m, const std::string& key);
 // bv2_exec.cpp
 int64_t workspace_bytes(const Model& m, int B, int T, int Ty);
 // ic: per-utterance controls (may be null: the scalars of in); a null member keeps that scalar
+// g_in: a caller's speaker vectors [B][gin] (null: emb_g(in.sid)); copied to out.g
 int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_encode_out& out, void* ws, int64_t wsb,
-               const bv2_item_controls* ic = nullptr);
+               const bv2_item_controls* ic = nullptr, const float* g_in = nullptr);
+int run_ref_encode(bv2_handle* h, hipStream_t s, const float* y, const int64_t* strides, const int64_t* y_lengths, int B, int L,
+                   float* g_out, void* ws, int64_t wsb);
 int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
                const bv2_item_controls* ic = nullptr);
 int run_flow(bv2_handle* h, hipStream_t s, int B, int Ty, const float* z_p, const int64_t* y_lengths, const float* y_mask,

@@ -557,8 +557,8 @@ struct GemvProb { const float* w; const float* bias; float* out; int cout, cin; 
 struct GemvLaunch { GemvProb p[16]; int nprob; int B; const float* g; int g_bstride; };
 int launch_gemv(hipStream_t stream, const GemvLaunch& L);            // out[b][co] = bias[co] + w[co][:]·g[b][:]
 
-// phase-A front (one launch): the speaker-conditioning GEMVs with g either given or looked up (g[b] = table[sid[b]], also
-// written to g_out — emb_g, models.py:1046), x_mask = sequence_mask(x_lengths) (commons.py:119-123; lengths null = all ones)
+// phase-A front (one launch): the speaker-conditioning GEMVs with g either given or looked up (g[b] = table[sid[b]] — emb_g,
+// models.py:1046); either way g is also written to g_out when that is set.  x_mask = sequence_mask(x_lengths) (commons.py:119-123; lengths null = all ones)
 // and z = noise * noise_scale_w (models.py:248-251).  Every part is optional.
 struct FrontArgs {
   GemvProb p[16]; int nprob; int B;
@@ -657,5 +657,19 @@ int launch_expand(hipStream_t stream, const ExpandArgs& a);
 // --- 16-bit PCM of the valid samples, peak-normalised per utterance (gradio convert_to_16_bit_wav, reference webui.py:86) ---
 int launch_pcm16(hipStream_t stream, const float* wave, int64_t bstride, const int64_t* y_lengths, int hop, int B, int64_t S,
                  int16_t* pcm, int64_t pstride, unsigned* peak_scratch);
+
+// --- ReferenceEncoder (reference models.py:752-808; kernels/ref_enc.hip): g [B][gin] from a linear spectrogram, eight launches ---
+struct RefEncArgs {
+  const float* y; int64_t sb, sf, st;               // element (b, f, t) of the spectrogram [B][spec][L] at y[b*sb + f*sf + t*st]
+  const int64_t* y_lengths;                          // [B] valid frames per item, or null = all L
+  int B, L, spec, gin;
+  const float* cw[6]; const float* cb[6];            // conv 1: [9][32]; convs 2-6: [Cout/8][Cin][9][8]; biases [Cout]
+  const float *w_ih, *b_ih, *w_hh, *b_hh, *pw, *pb;  // GRU [384][128*W6], [384], [384][128], [384]; proj [gin][128], [gin]
+  float* ws;                                         // ref_enc_workspace_floats(B, L, spec) floats
+  float* g_out;
+};
+void ref_enc_dims(int L, int spec, int* H, int* W);  // H[0..6], W[0..6]: time / frequency extent after i convs (n -> (n - 1) / 2 + 1)
+int64_t ref_enc_workspace_floats(int B, int L, int spec);
+int launch_ref_enc(hipStream_t stream, const RefEncArgs& a);
 
 }  // namespace bv2

@@ -15,6 +15,7 @@
 //   * enc_p.proj split into its m / logs halves (models.py:397-399).
 // The layout is a pure function of bv2_config, so every rank derives identical offsets and the blob can be broadcast.
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <functional>
 
@@ -319,11 +320,68 @@ DDSW pack_dds(Packer& P, const std::string& p, int c) {
   return d;
 }
 
-uint32_t hash_cfg(const bv2_config& c) {
+uint32_t hash_cfg(const bv2_config& c_in) {
+  // A model with a speaker table hashes the struct as it was before spec_channels was appended (the field is not read there), so its blob —
+  // header included — is byte for byte what the earlier packer wrote; a ReferenceEncoder model hashes the whole struct.
+  bv2_config c = c_in;
+  size_t n = sizeof(c);
+  if (c.n_speakers >= 1) { n = offsetof(bv2_config, spec_channels); c.struct_bytes = (int32_t)n; }
   const unsigned char* p = reinterpret_cast<const unsigned char*>(&c);
   uint32_t h = 2166136261u;
-  for (size_t i = 0; i < sizeof(c); ++i) { h ^= p[i]; h *= 16777619u; }
+  for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 16777619u; }
   return h;
+}
+
+// ReferenceEncoder (reference models.py:752-808), present iff n_speakers == 0.  Conv2d weights [Cout][Cin][3][3], weight-normed over all
+// dims but 0 (both forms accepted, like every other conv); packed for kernels/ref_enc.hip: conv 1 as [tap][32], convs 2-6 as
+// [Cout/8][Cin][tap][8] (the 8 weights a wave needs for one (channel, tap) are consecutive).  GRU and proj keep PyTorch's layout.
+void pack_ref_enc(Model& m, Packer& P) {
+  const bv2_config& c = m.cfg;
+  RefEncW& R = m.ref_enc;
+  R.present = true;
+  const int C[7] = {1, 32, 32, 64, 64, 128, 128};
+  int W[7], Hd[7];
+  ref_enc_dims(1, c.spec_channels, Hd, W);
+  for (int i = 0; i < 6; ++i) {
+    const int cin = C[i], cout = C[i + 1];
+    const std::string p = "ref_enc.convs." + std::to_string(i);
+    R.cw[i].n = (int64_t)cout * cin * 9; R.cw[i].off = P.alloc(R.cw[i].n);
+    R.cb[i] = P.vec(p + ".bias", {cout});
+    if (!P.fill()) continue;
+    std::vector<float> w;
+    if (P.has(p + ".weight_v") || !P.has(p + ".weight")) {
+      const HostTensor* v = P.get(p + ".weight_v", {cout, cin, 3, 3});
+      const HostTensor* g = P.get(p + ".weight_g", {cout, 1, 1, 1});
+      if (!v || !g) continue;
+      w.resize(v->data.size());
+      const int64_t inner = (int64_t)cin * 9;
+      for (int a = 0; a < cout; ++a) {
+        double ss = 0;
+        for (int64_t q = 0; q < inner; ++q) { const double x = v->data[a * inner + q]; ss += x * x; }
+        const float sc = g->data[a] / (float)std::sqrt(ss);      // as Packer::folded
+        for (int64_t q = 0; q < inner; ++q) w[a * inner + q] = v->data[a * inner + q] * sc;
+      }
+    } else {
+      const HostTensor* t = P.get(p + ".weight", {cout, cin, 3, 3});
+      if (!t) continue;
+      w = t->data;
+    }
+    float* dst = P.blob + R.cw[i].off;
+    for (int co = 0; co < cout; ++co)
+      for (int ci = 0; ci < cin; ++ci)
+        for (int t = 0; t < 9; ++t) {
+          const float v = w[((int64_t)co * cin + ci) * 9 + t];
+          if (i == 0) dst[t * 32 + co] = v;
+          else dst[(((int64_t)(co / 8) * cin + ci) * 9 + t) * 8 + co % 8] = v;
+        }
+  }
+  const int K = 128 * W[6];
+  R.w_ih = P.vec("ref_enc.gru.weight_ih_l0", {384, K});
+  R.w_hh = P.vec("ref_enc.gru.weight_hh_l0", {384, 128});
+  R.b_ih = P.vec("ref_enc.gru.bias_ih_l0", {384});
+  R.b_hh = P.vec("ref_enc.gru.bias_hh_l0", {384});
+  R.pw = P.vec("ref_enc.proj.weight", {c.gin_channels, 128});
+  R.pb = P.vec("ref_enc.proj.bias", {c.gin_channels});
 }
 
 int pack_all(Model& m, Packer& P) {
@@ -370,7 +428,8 @@ int pack_all(Model& m, Packer& P) {
   m.dp_b2 = P.vec("dp.norm_2.beta", {kDpFilter});
   m.dp_proj = P.conv1d("dp.proj", 1, kDpFilter, 1);
 
-  m.emb_g = P.vec("emb_g.weight", {c.n_speakers, gin});
+  if (c.n_speakers >= 1) m.emb_g = P.vec("emb_g.weight", {c.n_speakers, gin});
+  else pack_ref_enc(m, P);                         // models.py:1047-1048: g comes from the ReferenceEncoder, there is no table
 
   // ---- flow, in APPLICATION order of the reverse pass (reference models.py:143-144 / 443-444)
   m.n_coupling = c.use_transformer_flow ? c.n_flow_layer : 4;
@@ -564,7 +623,10 @@ int validate(const bv2_config& c, std::string& err) {
   if (!in(c.n_layers, kCondLayer + 1, 8)) return bad("n_layers must be 3..8 (cond_layer_idx = 2 < n_layers, attentions.py:69-75)");
   if (c.use_transformer_flow && !in(c.n_layers_trans_flow, kCondLayer + 1, 8)) return bad("n_layers_trans_flow must be 3..8");
   if (!in(c.n_flow_layer, 1, kMaxFlows)) return bad("n_flow_layer must be 1..8");
-  if (c.n_speakers < 1) return bad("n_speakers must be >= 1 (the ReferenceEncoder path, models.py:1047-1048, is out of scope)");
+  if (c.n_speakers < 0) return bad("n_speakers must be >= 0");
+  // n_speakers == 0: g = ref_enc(y) (models.py:1047-1048).  The spectrogram widths pinned against the reference: two odd chains and an even one
+  if (c.n_speakers == 0 && c.spec_channels != 1025 && c.spec_channels != 513 && c.spec_channels != 80)
+    return bad("spec_channels must be 1025, 513 or 80 when n_speakers == 0 (ReferenceEncoder, models.py:752-808)");
   if (!in(c.gin_channels, 64, 768) || c.gin_channels % 64) return bad("gin_channels must be a multiple of 64 in 64..768");
   if (!in(c.n_upsamples, 2, 5)) return bad("2..5 upsampling stages supported");
   if (!in(c.n_resblock_kernels, 1, 3)) return bad("1..3 resblock kernels supported");

@@ -236,6 +236,11 @@ __global__ void __launch_bounds__(256) front_kernel(const FrontArgs A) {
       r = r < 0 ? 0 : (r >= A.nrows ? A.nrows - 1 : r);
       A.g_out[i] = A.table[r * A.gin + c];
     }
+  if (!A.sid && A.g && A.g_out)                     // a given g: phase B and the caller read it from g_out like a looked-up one
+    for (int64_t i = i0; i < (int64_t)A.B * A.gin; i += step) {
+      const int b = (int)(i / A.gin), c = (int)(i - (int64_t)b * A.gin);
+      A.g_out[i] = A.g[(int64_t)b * A.g_bstride + c];
+    }
   if (A.mask)
     for (int64_t i = i0; i < (int64_t)A.B * A.T; i += step) {
       const int b = (int)(i / A.T), t = (int)(i - (int64_t)b * A.T);

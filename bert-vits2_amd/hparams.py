@@ -50,6 +50,7 @@ ENVELOPE = dict(
     upsample_taps_per_phase=(1, 4),                      # kernel / rate, with (kernel - rate) even
     upsample_initial_channel=(64, 512),                  # 1024 would need a K-chunked bf16 ConvTranspose tile (LDS); the fp32 form has no such limit
     final_generator_width=[16, 32, 64],                  # upsample_initial_channel >> n_upsamples
+    spec_channels=[80, 513, 1025],                       # n_speakers == 0 only (ReferenceEncoder input width; ignored with a speaker table)
 )
 
 
@@ -84,6 +85,15 @@ class HParams:
     hop_length: int = 512
 
     @property
+    def ref_enc_freqs(self) -> List[int]:
+        """Frequency extent after each of the ReferenceEncoder's six stride-2 convs (models.py:805-808): n -> (n - 1) // 2 + 1."""
+        out, n = [], int(self.spec_channels)
+        for _ in range(6):
+            n = (n - 1) // 2 + 1
+            out.append(n)
+        return out
+
+    @property
     def total_upsample(self) -> int:
         r = 1
         for u in self.upsample_rates:
@@ -103,8 +113,12 @@ class HParams:
         if self.flow_share_parameter:
             # the reference itself crashes here: attentions.FFT does not exist (models.py:107)
             raise NotImplementedError("flow_share_parameter=True is broken in the reference (models.py:107)")
-        if self.n_speakers < 1:
-            raise NotImplementedError("n_speakers == 0 needs ReferenceEncoder (models.py:1047-1048); out of scope")
+        if self.n_speakers < 0:
+            raise ValueError("n_speakers must be >= 0")
+        if self.n_speakers == 0 and self.spec_channels not in ENVELOPE["spec_channels"]:
+            # g = ref_enc(y) (models.py:1047-1048): the widths pinned against the reference, as for every other bound of the envelope
+            raise ValueError(f"spec_channels must be one of {ENVELOPE['spec_channels']} when n_speakers == 0 (ReferenceEncoder), "
+                             f"got {self.spec_channels}")
         if self.gin_channels <= 0:
             raise NotImplementedError("gin_channels must be > 0 (reference models.py:871-882)")
         if self.hidden_channels % self.n_heads:

@@ -36,6 +36,7 @@ class Config(C.Structure):
         ("n_resblock_dilations", C.c_int32),
         ("resblock_dilation_sizes", (C.c_int32 * MAX_RBD) * MAX_RBK),
         ("resblock_type", C.c_int32),            # appended in round 5: 1 = ResBlock1, 2 = ResBlock2 (the library still takes the shorter struct)
+        ("spec_channels", C.c_int32),            # appended with the ReferenceEncoder: read when n_speakers == 0 only (a shorter struct is legal otherwise)
     ]
 
 
@@ -118,6 +119,15 @@ SYMBOLS = [
     ("bv2_infer_ex", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.c_int64, C.c_int64, C.c_float,
                                C.c_int32, C.c_int32, C.POINTER(DecodeOut), C.POINTER(C.c_int32), C.POINTER(ItemControls), _P,
                                C.c_int64]),
+    ("bv2_ref_workspace_bytes", C.c_int64, [_P, C.c_int, C.c_int]),
+    ("bv2_ref_encode", C.c_int, [_P, _P, _P, C.POINTER(C.c_int64), _P, C.c_int, C.c_int, _P, _P, C.c_int64]),
+    ("bv2_encode_durations_g", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P, _P,
+                                         C.c_int64]),
+    ("bv2_infer_g", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.c_int64, C.c_int64, C.c_float,
+                              C.c_int32, C.c_int32, C.POINTER(DecodeOut), C.POINTER(C.c_int32), C.POINTER(ItemControls), _P, _P,
+                              C.c_int64]),
+    ("bv2_graph_capture_encode_g", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P, _P,
+                                             C.c_int64, C.POINTER(_P)]),
     ("bv2_pcm16", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
     ("bv2_graph_capture_encode", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_decode", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), _P, C.c_int64, C.POINTER(_P)]),
@@ -208,6 +218,7 @@ def make_config(hp: H.HParams) -> Config:
     c.inter_channels, c.hidden_channels, c.filter_channels = hp.inter_channels, hp.hidden_channels, hp.filter_channels
     c.n_heads, c.n_layers, c.kernel_size = hp.n_heads, hp.n_layers, hp.kernel_size
     c.gin_channels, c.n_speakers = hp.gin_channels, hp.n_speakers
+    c.spec_channels = hp.spec_channels if hp.n_speakers == 0 else 0     # the ReferenceEncoder's input width; not read with a speaker table
     c.use_transformer_flow = int(bool(hp.use_transformer_flow))
     c.n_flow_layer, c.n_layers_trans_flow = hp.n_flow_layer, hp.n_layers_trans_flow
     ups, uks = list(hp.upsample_rates), list(hp.upsample_kernel_sizes)

@@ -8,7 +8,9 @@ Mirrors the surface of reference ``models.SynthesizerTrn`` that its callers use
   schema (SURVEY.md Appendix B), so reference ``utils.load_checkpoint`` works unchanged;
 * ``.infer(x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_scale=.667, length_scale=1,
   noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None)`` → ``(o, attn, y_mask, (z, z_p, m_p, logs_p))``
-  (reference models.py:1026-1074), same shapes/dtypes.
+  (reference models.py:1026-1074), same shapes/dtypes.  Both speaker branches of models.py:1045-1048 run: ``emb_g(sid)`` with a
+  speaker table, ``ref_enc(y)`` (``reference_embedding``) for a model built with ``n_speakers=0``; ``g=`` hands over a speaker
+  vector directly (a cached reference voice, a blend of two speakers).
 
 This module is host plumbing only: PyTorch supplies device memory, the current HIP stream and the RNG; every FLOP of
 ``infer()`` happens inside the C-ABI library.  There is deliberately NO PyTorch/CPU fallback: without a GPU or without
@@ -140,6 +142,7 @@ class SynthesizerTrn(nn.Module):
         self._graphs: Dict[tuple, dict] = {}
         self._cap_stream = None
         self._options: Dict[str, int] = {}
+        self.ref_encode_calls = 0          # bv2_ref_encode calls made through reference_embedding (serving encodes a shared reference once)
 
     # ------------------------------------------------------------------ parameter tree
     def _register(self, key: str, value: torch.Tensor) -> None:
@@ -356,11 +359,58 @@ class SynthesizerTrn(nn.Module):
         self._taps[name] = tensor
         lib.bv2_set_tap(self._handle, name.encode(), C.c_void_p(tensor.data_ptr()), tensor.numel())
 
+    # ------------------------------------------------------------------ speaker vectors
+    def _speaker_vector(self, g, B: int) -> torch.Tensor:
+        """A caller's ``g`` as fp32 [B, gin] on the model's device; accepts [B, gin] and the reference's [B, gin, 1]."""
+        gin = self.hp.gin_channels
+        if not isinstance(g, torch.Tensor) or tuple(g.shape) not in ((B, gin), (B, gin, 1)):
+            raise ValueError(f"g must be a tensor shaped [B, gin] or [B, gin, 1] with B = {B}, gin = {gin}, got "
+                             f"{tuple(g.shape) if isinstance(g, torch.Tensor) else type(g).__name__}")
+        return g.detach().to(self.device, torch.float32).reshape(B, gin).contiguous()
+
+    @torch.no_grad()
+    def reference_embedding(self, y: torch.Tensor, y_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``ref_enc(y.transpose(1, 2))`` of reference models.py:1047-1048 -> g [B, gin]: the voice of a reference recording, for a model
+        built with ``n_speakers=0``.  ``y`` is the linear spectrogram [B, spec_channels, L] as the reference's ``infer`` takes it (any
+        strides: it is read in place).  ``y_lengths`` [B] makes a padded batch exact: every layer treats item b's frames past its own
+        length as zero padding and its GRU stops after its last step, so each row is bit for bit what that reference gives alone
+        (``None``: all L frames of every item count, the reference's own semantics).  Eight launches, outside the graphs (the shape
+        depends on L); compute it once per voice and pass it to ``infer(g=...)``."""
+        if self.hp.n_speakers != 0:
+            raise RuntimeError("reference_embedding needs a model built with n_speakers=0 (this one has a speaker table: emb_g)")
+        if self._blob is None:
+            self.repack()
+        dev = self.device
+        if y.dim() != 3 or y.shape[1] != self.hp.spec_channels or y.shape[2] < 1:
+            raise ValueError(f"y must be [B, spec_channels = {self.hp.spec_channels}, L >= 1], got {tuple(y.shape)}")
+        y = y.detach().to(dev, torch.float32)
+        B, _, Lf = y.shape
+        yl = None
+        if y_lengths is not None:
+            yl = torch.as_tensor(y_lengths).to(dev, torch.int64).reshape(-1).contiguous()
+            if yl.shape != (B,):
+                raise ValueError("y_lengths must be [B]")
+        n = self._lib.bv2_ref_workspace_bytes(self._handle, B, Lf)
+        if n < 0:
+            raise RuntimeError("bv2_ref_workspace_bytes failed")
+        ws = torch.empty(n, dtype=torch.uint8, device=dev)      # sized by L: not the phases' workspace (captured graphs bake that one in)
+        g = torch.empty(B, self.hp.gin_channels, dtype=torch.float32, device=dev)
+        strides = (C.c_int64 * 3)(*y.stride())
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self._check(self._lib.bv2_ref_encode(self._handle, stream, _ptr(y), strides, _ptr(yl), B, Lf, _ptr(g),
+                                                 C.c_void_p(ws.data_ptr()), ws.numel()), "bv2_ref_encode")
+        self.ref_encode_calls = getattr(self, "ref_encode_calls", 0) + 1
+        return g
+
     # ------------------------------------------------------------------ the two phases
     @torch.no_grad()
     def encode_durations(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w, noise_scale_w=0.8,
-                         sdp_ratio=0.0, length_scale=1.0, bert_index=None) -> Dict[str, torch.Tensor]:
+                         sdp_ratio=0.0, length_scale=1.0, bert_index=None, g=None) -> Dict[str, torch.Tensor]:
         """Phase A = reference models.py:1045-1057.  ``noise_w`` [B,2,T] is the draw of models.py:248-251.
+
+        ``g`` (optional, [B, gin] or [B, gin, 1]): the speaker vectors to condition on instead of ``emb_g(sid)`` — ``sid`` is then not
+        read and may be None (``bv2_encode_durations_g``).  A model with ``n_speakers=0`` has no table and needs it.
 
         ``bert_index`` (optional, a 3-tuple aligned with bert / ja_bert / en_bert; entries may be None): a feature with an index is
         WORD-level — [B, 1024, S] as the BERT model emitted it, still on the device — and symbol t reads column index[b, t]; the
@@ -372,7 +422,15 @@ class SynthesizerTrn(nn.Module):
         B, T = x.shape
         i64 = lambda t: t.to(dev, torch.int64).contiguous()
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
-        x, x_lengths, sid, tone, language = i64(x), i64(x_lengths), i64(sid), i64(tone), i64(language)
+        if g is not None:
+            g = self._speaker_vector(g, B)
+            sid = None
+        elif self.hp.n_speakers == 0:
+            raise ValueError("this model has no speaker table (n_speakers=0): pass g (reference_embedding(y)) or, to infer(), y")
+        x, x_lengths, tone, language = i64(x), i64(x_lengths), i64(tone), i64(language)
+        sid = None if sid is None else i64(sid)
+        if g is None and sid is None:
+            raise ValueError("sid must be given (or g)")
         bert, ja_bert, en_bert, noise_w = f32(bert), f32(ja_bert), f32(en_bert), f32(noise_w)
         bidx = [None, None, None] if bert_index is None else [None if t is None else t.to(dev, torch.int32).contiguous() for t in bert_index]
         for feat, ix in zip((bert, ja_bert, en_bert), bidx):
@@ -414,6 +472,9 @@ class SynthesizerTrn(nn.Module):
             ws = self._workspace(B, T, 1)
             ins = dict(x=x, x_lengths=x_lengths, sid=sid, tone=tone, language=language, bert=bert, ja_bert=ja_bert,
                        en_bert=en_bert, noise_w=noise_w)
+            if g is not None:
+                del ins["sid"]                      # not read
+                ins["g"] = g                        # the graph owns a [B, gin] copy, refilled before every replay like the controls
             for i in range(3):
                 if bidx[i] is not None:
                     ins[f"bert_index{i}"] = bidx[i]
@@ -421,28 +482,32 @@ class SynthesizerTrn(nn.Module):
                 ins["ctl"] = ctl                    # the graph owns a [4, B] copy: its values are refilled before every replay
 
             static = self._graphs_static
-            moving = ("noise_w", "ctl")
+            moving = ("noise_w", "ctl", "g")
 
             def build(own_inputs):
                 staged = tuple(ins) if own_inputs else tuple(k for k in moving if k in ins)   # static_io: the rest is read in place
                 sin = {k: (torch.empty_like(v) if k in staged else v) for k, v in ins.items()}
                 sout = mk_out()
-                ein = L.EncodeIn(B, T, *[_ptr(sin[k]) for k in ("x", "x_lengths", "sid", "tone", "language", "bert", "ja_bert",
-                                                                "en_bert", "noise_w")],
+                ein = L.EncodeIn(B, T, *[_ptr(sin.get(k)) for k in ("x", "x_lengths", "sid", "tone", "language", "bert", "ja_bert",
+                                                                    "en_bert", "noise_w")],
                                  float(noise_scale_w), float(sdp_ratio), float(length_scale))
                 with_index(ein, lambda i: sin[f"bert_index{i}"].data_ptr())
                 eout = L.EncodeOut(*[_ptr(sout[k]) for k in okeys])
+                icp = None if ctl is None else _controls_ptr(sin["ctl"], (0, 1, 2))
                 with torch.cuda.device(dev):
-                    if ctl is None:
-                        g = self._capture(self._lib.bv2_graph_capture_encode, C.byref(ein), C.byref(eout),
-                                          C.c_void_p(ws.data_ptr()), ws.numel())
+                    if g is not None:
+                        gr = self._capture(self._lib.bv2_graph_capture_encode_g, C.byref(ein), C.byref(eout), icp, _ptr(sin["g"]),
+                                           C.c_void_p(ws.data_ptr()), ws.numel())
+                    elif ctl is None:
+                        gr = self._capture(self._lib.bv2_graph_capture_encode, C.byref(ein), C.byref(eout),
+                                           C.c_void_p(ws.data_ptr()), ws.numel())
                     else:
-                        g = self._capture(self._lib.bv2_graph_capture_encode_ex, C.byref(ein), C.byref(eout),
-                                          _controls_ptr(sin["ctl"], (0, 1, 2)), C.c_void_p(ws.data_ptr()), ws.numel())
-                return dict(graph=g, sin=sin, sout=sout, staged=staged)
+                        gr = self._capture(self._lib.bv2_graph_capture_encode_ex, C.byref(ein), C.byref(eout), icp,
+                                           C.c_void_p(ws.data_ptr()), ws.numel())
+                return dict(graph=gr, sin=sin, sout=sout, staged=staged)
 
             ptrs = tuple(ins[k].data_ptr() for k in ins if k not in moving) if static else ()
-            # per-utterance controls: the key carries the fact ("ctl" in ins), not the values
+            # per-utterance controls and a given g: the key carries the fact ("ctl" / "g" in ins), not the values
             scal = ("item",) if ctl is not None else (float(noise_scale_w), float(sdp_ratio), float(length_scale))
             ent = self._graph_entry(("A", B, T) + scal + (tuple(cols), tuple(sorted(ins))), build, ptrs)
             for k in ent["staged"]:
@@ -461,7 +526,11 @@ class SynthesizerTrn(nn.Module):
         ws = self._workspace(B, T, 1)
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            if ctl is None:
+            if g is not None:
+                self._check(self._lib.bv2_encode_durations_g(self._handle, stream, C.byref(ein), C.byref(eout),
+                                                             None if ctl is None else _controls_ptr(ctl, (0, 1, 2)), _ptr(g),
+                                                             C.c_void_p(ws.data_ptr()), ws.numel()), "bv2_encode_durations_g")
+            elif ctl is None:
                 self._check(self._lib.bv2_encode_durations(self._handle, stream, C.byref(ein), C.byref(eout),
                                                            C.c_void_p(ws.data_ptr()), ws.numel()), "bv2_encode_durations")
             else:
@@ -605,8 +674,8 @@ class SynthesizerTrn(nn.Module):
     # ------------------------------------------------------------------ the reference entry point
     @torch.no_grad()
     def infer(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_scale=0.667, length_scale=1,
-              noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None, *, noise_w=None, noise_z=None, w_ceil=None,
-              want_attn=True, exact_lengths=False, bert_index=None, ty_bucket=None):
+              noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None, *, g=None, y_lengths=None, noise_w=None, noise_z=None,
+              w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, ty_bucket=None):
         """reference models.py:1026-1074.  Keyword-only extras (not in the reference): ``noise_w`` [B,2,T] and
         ``noise_z`` [B,inter,>=T_y] inject the two N(0,1) draws (parity tests; the reference's ONNX export externalises
         them the same way), ``w_ceil`` substitutes the durations, ``want_attn=False`` skips materialising the path,
@@ -618,16 +687,26 @@ class SynthesizerTrn(nn.Module):
         ``sdp_ratio``, ``noise_scale``, ``noise_scale_w`` and ``length_scale`` each take a number (or 0-d tensor) or, as in the
         reference, one value per utterance as a tensor shaped [B], [B,1] or [B,1,1] (``item_control``): utterance b then gets what a
         batch-1 call with its own values gets (``bv2_item_controls``).  With graphs on, one capture per shape serves every set of
-        per-utterance values; scalar values stay part of the graph key as before."""
+        per-utterance values; scalar values stay part of the graph key as before.
+
+        The speaker (models.py:1045-1048): ``g`` ([B, gin] or [B, gin, 1]) wins if given — phase A conditions on it instead of a table
+        row, through the same kernel code (``g = stage_emb_g(s)`` is bit-identical to ``sid = s``), and ``sid`` may be None.  Otherwise a
+        model with ``n_speakers=0`` encodes ``y`` [B, spec_channels, L] first (``reference_embedding(y, y_lengths)``; ``y_lengths`` [B] is
+        this library's addition for padded reference batches), and a model with a speaker table looks ``sid`` up and ignores ``y``, as the
+        reference does.  With graphs on, ``g`` lives in a buffer the graph owns: one capture per shape serves every voice."""
         if self.device.type != "cuda":
             raise RuntimeError("bert_vits2_amd.SynthesizerTrn.infer needs a GPU: no CPU fallback exists by design")
         dev = self.device
         B, T = x.shape
+        if g is None and self.hp.n_speakers == 0:
+            if y is None:
+                raise ValueError("this model has no speaker table (n_speakers=0): infer() needs y (the reference spectrogram) or g")
+            g = self.reference_embedding(y, y_lengths)
         if noise_w is None:
             noise_w = draw_noise_w(B, T, dev)
         enc = self.encode_durations(x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w,
                                     noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, length_scale=length_scale,
-                                    bert_index=bert_index)
+                                    bert_index=bert_index, g=g)
         if w_ceil is not None:
             wc = w_ceil.to(dev, torch.float32).reshape(B, T).contiguous()
             enc["w_ceil"] = wc

@@ -148,8 +148,36 @@ def param_shapes(hp: H.HParams) -> "OrderedDict[str, Tuple[int, ...]]":
     _conv(d, "dp.proj", 1, H.DP_FILTER, 1)
     _conv(d, "dp.cond", hid, gin, 1)
 
-    d["emb_g.weight"] = (hp.n_speakers, gin)
+    if hp.n_speakers >= 1:
+        d["emb_g.weight"] = (hp.n_speakers, gin)
+    else:
+        _ref_enc(d, hp)                  # models.py:932-935: `self.ref_enc = ReferenceEncoder(spec_channels, gin_channels)` instead of emb_g
     return d
+
+
+REF_ENC_FILTERS = (32, 32, 64, 64, 128, 128)     # reference models.py:761
+REF_ENC_GRU = 128                                # 256 // 2, models.py:782
+
+
+def _ref_enc(d, hp: H.HParams, folded: bool = False):
+    """ReferenceEncoder (reference models.py:752-808): six weight-normed Conv2d(3x3, stride 2, pad 1), GRU, Linear."""
+    cin = 1
+    for i, cout in enumerate(REF_ENC_FILTERS):
+        p = f"ref_enc.convs.{i}"
+        d[p + ".bias"] = (cout,)
+        if folded:
+            d[p + ".weight"] = (cout, cin, 3, 3)
+        else:
+            d[p + ".weight_g"] = (cout, 1, 1, 1)
+            d[p + ".weight_v"] = (cout, cin, 3, 3)
+        cin = cout
+    k = REF_ENC_FILTERS[-1] * hp.ref_enc_freqs[-1]
+    d["ref_enc.gru.weight_ih_l0"] = (3 * REF_ENC_GRU, k)
+    d["ref_enc.gru.weight_hh_l0"] = (3 * REF_ENC_GRU, REF_ENC_GRU)
+    d["ref_enc.gru.bias_ih_l0"] = (3 * REF_ENC_GRU,)
+    d["ref_enc.gru.bias_hh_l0"] = (3 * REF_ENC_GRU,)
+    d["ref_enc.proj.weight"] = (hp.gin_channels, REF_ENC_GRU)
+    d["ref_enc.proj.bias"] = (hp.gin_channels,)
 
 
 def n_params(hp: H.HParams) -> int:

@@ -25,7 +25,9 @@ from . import hparams as H
 class Utterance:
     """One piece as reference ``infer.get_text`` (infer.py:107-152) produces it: 1-D ids and ``[1024, T]`` features.  The four
     synthesis controls are the request's own sliders (hiyoriUI ``/voice``: sdp_ratio, noise, noisew, length); ``None`` takes the value
-    ``synthesize`` was called with."""
+    ``synthesize`` was called with.  The voice is ``sid`` (a row of the speaker table) unless the utterance carries ``g`` (a speaker vector
+    ``[gin]``: a cached ``reference_embedding``, a blend of table rows) or ``ref_spec`` (a reference spectrogram ``[spec_channels, L]`` for a
+    model built with ``n_speakers=0``; utterances that share one tensor object share one encoding)."""
     phones: torch.Tensor
     tones: torch.Tensor
     lang_ids: torch.Tensor
@@ -37,8 +39,17 @@ class Utterance:
     noise_scale: Optional[float] = None
     noise_scale_w: Optional[float] = None
     length_scale: Optional[float] = None
+    g: Optional[torch.Tensor] = None
+    ref_spec: Optional[torch.Tensor] = None
 
     def __post_init__(self):
+        if self.g is not None and (not isinstance(self.g, torch.Tensor) or self.g.dim() != 1 or self.g.shape[0] < 1):
+            raise ValueError("g must be a 1-D tensor [gin]")
+        if self.ref_spec is not None and (not isinstance(self.ref_spec, torch.Tensor) or self.ref_spec.dim() != 2
+                                          or min(self.ref_spec.shape) < 1):
+            raise ValueError("ref_spec must be a 2-D tensor [spec_channels, L]")
+        if self.g is not None and self.ref_spec is not None:
+            raise ValueError("an utterance carries g or ref_spec, not both")
         T = int(self.phones.shape[0])
         if self.tones.shape != (T,) or self.lang_ids.shape != (T,):
             raise ValueError("phones / tones / lang_ids must be 1-D with the same length")
@@ -87,6 +98,38 @@ def collate(utts: Sequence[Utterance], device) -> dict:
         out["x"][i, :n], out["tone"][i, :n], out["language"][i, :n] = u.phones, u.tones, u.lang_ids
         out["bert"][i, :, :n], out["ja_bert"][i, :, :n], out["en_bert"][i, :, :n] = u.bert, u.ja_bert, u.en_bert
     return {k: v.to(device, non_blocking=True) for k, v in out.items()}
+
+
+def speaker_vectors(model, utts: Sequence[Utterance]) -> List[Optional[torch.Tensor]]:
+    """Per utterance its speaker vector ``[gin]`` on the model's device, or None where the utterance keeps ``sid``.  The DISTINCT
+    ``ref_spec`` objects of the call are encoded once, as one ragged batch (``reference_embedding`` with ``y_lengths``: each reference
+    gets exactly the g it gets alone)."""
+    gin, spec, dev = model.hp.gin_channels, model.hp.spec_channels, model.device
+    out: List[Optional[torch.Tensor]] = [None] * len(utts)
+    refs, slot = [], {}
+    for i, u in enumerate(utts):
+        if u.g is not None:
+            if tuple(u.g.shape) != (gin,):
+                raise ValueError(f"utterance {i}: g must be [{gin}], got {tuple(u.g.shape)}")
+            out[i] = u.g.detach().to(dev, torch.float32)
+        elif u.ref_spec is not None:
+            if u.ref_spec.shape[0] != spec:
+                raise ValueError(f"utterance {i}: ref_spec must be [{spec}, L], got {tuple(u.ref_spec.shape)}")
+            if id(u.ref_spec) not in slot:
+                slot[id(u.ref_spec)] = len(refs)
+                refs.append(u.ref_spec)
+        elif model.hp.n_speakers == 0:
+            raise ValueError(f"utterance {i}: this model has no speaker table (n_speakers=0), the utterance needs g or ref_spec")
+    if refs:
+        lens = [int(r.shape[1]) for r in refs]
+        y = torch.zeros(len(refs), spec, max(lens), dtype=torch.float32, device=dev)
+        for k, r in enumerate(refs):
+            y[k, :, :lens[k]] = r.to(dev, torch.float32)
+        gs = model.reference_embedding(y, torch.tensor(lens, dtype=torch.int64))
+        for i, u in enumerate(utts):
+            if u.g is None and u.ref_spec is not None:
+                out[i] = gs[slot[id(u.ref_spec)]]
+    return out
 
 
 def pcm16(model, wave: torch.Tensor, y_lengths: torch.Tensor) -> torch.Tensor:
@@ -154,7 +197,8 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     weights), so one bucket's small-kernel phases overlap another's Generator; results do not depend on it.
     An utterance that carries its own ``sdp_ratio`` / ``noise_scale`` / ``noise_scale_w`` / ``length_scale`` gets it inside the
     shared batch (per-utterance controls, one value per batch item); the call's values fill in the rest.  Buckets are then planned
-    on expected frames (symbols x length_scale)."""
+    on expected frames (symbols x length_scale).  Voices: utterances with ``g`` or ``ref_spec`` are conditioned on that vector, the
+    others on their ``sid`` row, all in the same buckets (``speaker_vectors``)."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
     dev = model.device
@@ -162,10 +206,11 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     results: List[Optional[np.ndarray]] = [None] * len(utts)
     pending = []
     lanes = replicas(model, requests_in_flight) if requests_in_flight > 1 else [(model, None)]
-    if requests_in_flight > 1:
-        torch.cuda.current_stream(dev).synchronize()       # inputs prepared on the caller's stream are visible to the lanes
     call = dict(sdp_ratio=sdp_ratio, noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale)
     per_item = any(getattr(u, k) is not None for u in utts for k in call)
+    gvec = speaker_vectors(model, utts)                    # reference spectrograms are encoded here, once per distinct object
+    if requests_in_flight > 1:
+        torch.cuda.current_stream(dev).synchronize()       # inputs prepared on the caller's stream are visible to the lanes
     weights = None
     if per_item and any(u.length_scale is not None for u in utts):
         weights = [float(length_scale if u.length_scale is None else u.length_scale) for u in utts]
@@ -177,7 +222,7 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
         else:
             ctl = call
         with torch.cuda.stream(lane_stream) if lane_stream is not None else contextlib.nullcontext():
-            _run_bucket(lane, utts, idx, dev, noise, pending, as_pcm16, **ctl)
+            _run_bucket(lane, utts, idx, dev, noise, pending, as_pcm16, gvec, **ctl)
     for idx, host, y_len, ev in pending:
         ev.synchronize()
         for r, i in enumerate(idx):
@@ -185,11 +230,16 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     return results
 
 
-def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, sdp_ratio, noise_scale, noise_scale_w, length_scale):
+def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio, noise_scale, noise_scale_w, length_scale):
     """One bucket on the CURRENT stream: collate, infer (exact lengths), optional PCM16, async D2H into pinned memory."""
     group = [utts[i] for i in idx]
     batch = collate(group, dev)
     kw = {}
+    if any(gvec[i] is not None for i in idx):
+        # a bucket that mixes voices by vector and by index runs on ONE [B, gin]: the table rows of the sid utterances are fetched on
+        # the device (bit-identical to the lookup inside phase A, which reads the same row through the same code)
+        rows = model.stage_emb_g(batch["sid"]) if any(gvec[i] is None for i in idx) else None
+        kw["g"] = torch.stack([rows[r] if gvec[i] is None else gvec[i] for r, i in enumerate(idx)])
     if noise is not None:
         T = batch["x"].shape[1]
         Tz = max(int(noise[i][1].shape[1]) for i in idx)
@@ -198,7 +248,7 @@ def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, sdp_ratio, nois
         for r, i in enumerate(idx):
             nw[r, :, :noise[i][0].shape[1]] = noise[i][0]
             nz[r, :, :noise[i][1].shape[1]] = noise[i][1]
-        kw = dict(noise_w=nw.to(dev), noise_z=nz.to(dev))
+        kw.update(noise_w=nw.to(dev), noise_z=nz.to(dev))
     o, _attn, y_mask, _ = model.infer(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"],
                                       batch["bert"], batch["ja_bert"], batch["en_bert"], sdp_ratio=sdp_ratio,
                                       noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale,

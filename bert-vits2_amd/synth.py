@@ -42,6 +42,9 @@ def synthetic_state_dict(hp: H.HParams, seed: int = 0, pin_durations: Optional[f
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     for key, shape in param_shapes(hp).items():
         leaf = key.rsplit(".", 1)[-1]
+        if key.startswith("ref_enc."):
+            sd[key] = _ref_enc_tensor(key, leaf, shape, seed).contiguous()
+            continue
         if leaf in ("gamma",):
             t = _normal(key, seed, shape, 0.1, 1.0)
         elif leaf in ("beta",):
@@ -97,6 +100,47 @@ def synthetic_state_dict(hp: H.HParams, seed: int = 0, pin_durations: Optional[f
         sd["dp.proj.weight"] = torch.zeros_like(sd["dp.proj.weight"])
         sd["dp.proj.bias"] = torch.full((1,), math.log(pin_durations))
     return sd
+
+
+def _ref_enc_tensor(key, leaf, shape, seed):
+    """ReferenceEncoder weights (n_speakers == 0 models): scaled so that the six conv + ReLU layers keep O(1) activations (a unit-norm
+    row times g = 1.4 offsets the halving of the mean square by each ReLU), the GRU gates see O(1) pre-activations and g comes out at the
+    scale of an ``emb_g`` row."""
+    if leaf == "weight_g":
+        return torch.full(shape, 1.4) * (1.0 + 0.05 * torch.randn(shape, generator=_gen(key, seed)))
+    if leaf == "weight_v":
+        return _normal(key, seed, shape, 1.0)
+    if leaf == "weight" and len(shape) == 4:                      # folded Conv2d weight: rows of norm ~1.4
+        return _normal(key, seed, shape, 1.4 / math.sqrt(shape[1] * shape[2] * shape[3]))
+    if leaf in ("weight_ih_l0", "weight_hh_l0"):
+        return _normal(key, seed, shape, 1.0 / math.sqrt(shape[1]))
+    if leaf in ("bias_ih_l0", "bias_hh_l0"):
+        return _normal(key, seed, shape, 0.1)
+    if key == "ref_enc.proj.weight":
+        return _normal(key, seed, shape, 2.0 / math.sqrt(shape[1]))
+    if leaf == "bias":
+        return _normal(key, seed, shape, 0.02)
+    raise KeyError(key)
+
+
+def synthetic_reference_spec(spec_channels: int, L: int, index: int = 0, base_seed: int = 977) -> torch.Tensor:
+    """A seeded linear magnitude spectrogram ``[spec_channels, L]`` (fp32) for the ReferenceEncoder: non-negative, falling off with
+    frequency, with a slowly moving harmonic comb on top of a noise floor — the shape of a voiced recording, not its content.  Frame t of
+    a given (spec_channels, index) does not depend on L, so a shorter reference is a prefix of a longer one."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(base_seed + 7919 * index + spec_channels)
+    Lmax = 512
+    assert 1 <= L <= Lmax, L
+    f = torch.arange(spec_channels, dtype=torch.float32)[:, None] / spec_channels          # [spec, 1] in [0, 1)
+    t = torch.arange(Lmax, dtype=torch.float32)[None, :]
+    noise = torch.randn(spec_channels, Lmax, generator=g).abs()
+    f0 = 0.02 + 0.01 * torch.rand(1, generator=g)
+    pitch = f0 * (1.0 + 0.2 * torch.sin(2 * math.pi * t / (37.0 + 5 * index)))              # [1, Lmax]
+    comb = torch.cos(math.pi * f / pitch).pow(2)                                           # peaks at multiples of the pitch
+    env = torch.exp(-4.0 * f)                                                              # spectral tilt
+    loud = 0.6 + 0.4 * torch.sin(2 * math.pi * t / 23.0 + index).abs()
+    y = env * loud * (1.5 * comb + 0.3 * noise) + 0.01 * noise
+    return y[:, :L].to(torch.float32).contiguous()
 
 
 # ---------------------------------------------------------------------------------------------

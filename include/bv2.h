@@ -59,6 +59,11 @@ typedef struct bv2_config {
    * 0 / 1 = modules.ResBlock1 (convs1 / convs2 pairs, reference modules.py:239-315), 2 = modules.ResBlock2 (ONE conv per dilation,
    * n_resblock_dilations = 2: `resblock: "2"` of models.py:508, modules.py:318-363) */
   int32_t resblock_type;
+  /* appended with the ReferenceEncoder: width of the linear spectrogram the encoder reads (filter_length / 2 + 1; 1025, 513 or 80).  Only
+   * read when n_speakers == 0 — the speaker vector g then comes from ref_enc (models.py:1047-1048, bv2_ref_encode below) and the blob holds
+   * ref_enc.* instead of emb_g.weight.  A caller built against the shorter struct passes its own struct_bytes: legal with n_speakers >= 1
+   * only (the field is ignored there and changes nothing in the blob). */
+  int32_t spec_channels;
 } bv2_config;
 
 enum { BV2_F32 = 0, BV2_F16 = 1, BV2_BF16 = 2 };
@@ -116,7 +121,7 @@ typedef struct bv2_encode_in {
   int32_t B, T;
   const int64_t* x;          /* [B,T] symbol ids */
   const int64_t* x_lengths;  /* [B] */
-  const int64_t* sid;        /* [B] */
+  const int64_t* sid;        /* [B]  (not read by the _g calls when they are given a g) */
   const int64_t* tone;       /* [B,T] */
   const int64_t* language;   /* [B,T] */
   const float* bert;         /* [B,bert_dim,T] */
@@ -135,7 +140,7 @@ typedef struct bv2_encode_in {
 } bv2_encode_in;
 
 typedef struct bv2_encode_out {   /* all DEVICE, caller-allocated */
-  float* g;          /* [B,gin]            emb_g(sid)                       models.py:1046 */
+  float* g;          /* [B,gin]            emb_g(sid), or a copy of the given g     models.py:1046-1048 */
   float* x;          /* [B,hidden,T]       encoder output                   models.py:1049 */
   float* m_p;        /* [B,inter,T] */
   float* logs_p;     /* [B,inter,T] */
@@ -256,6 +261,34 @@ int bv2_infer_ex(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, cons
                  int32_t Ty_cap, const bv2_decode_out* dec_out, int32_t* Ty_out, const bv2_item_controls* controls, void* workspace,
                  int64_t workspace_bytes);
 
+/* ---- speaker conditioning from a reference spectrogram or a given vector ----------------------------------------------
+ * The reference forms the speaker vector g in one of two ways (models.py:1045-1048): emb_g(sid) when the model has a speaker table,
+ * ref_enc(y.transpose(1, 2)) when it was trained with n_speakers = 0 (the voice is taken from a reference recording).
+ *
+ * bv2_ref_encode is that second branch (ReferenceEncoder, models.py:752-808; n_speakers == 0 models only, -2 otherwise): y is the linear
+ * spectrogram [B, spec_channels, L] as the reference's infer() takes it, element (b, f, t) at y[b*strides[0] + f*strides[1] + t*strides[2]]
+ * (strides NULL = contiguous), g_out [B, gin].  Exact fp32 throughout, eight launches, graph-capturable.  y_lengths [B] (int64, DEVICE; NULL =
+ * every item is L frames long, the reference's semantics) makes a padded batch exact: item b's frames >= y_lengths[b] are zero padding in
+ * EVERY layer (the length shrinks as n -> (n - 1) / 2 + 1 per conv) and its GRU stops after its own last step, so each item gets bit for
+ * bit the g it gets alone.  Values outside [1, L] are clamped.  The workspace is sized by bv2_ref_workspace_bytes (it depends on L, which
+ * bv2_workspace_bytes does not know); g is meant to be computed once per voice and cached by the caller.
+ *
+ * The _g calls are bv2_encode_durations_ex / bv2_infer_ex / bv2_graph_capture_encode_ex with one more argument, g [B, gin] (DEVICE fp32):
+ * phase A then conditions on that vector instead of emb_g(sid) — a ref_enc result, a blend of table rows, any vector — through the same
+ * kernel code that reads the table row (g = emb_g row s gives bit-identical results to sid = s), and copies it to bv2_encode_out.g, where
+ * phase B reads it.  in->sid is not read and may be NULL.  g == NULL is the plain _ex call.  A model with n_speakers == 0 has no table:
+ * every phase-A call without g fails (-1, message) and does not read sid.  A captured graph bakes in the ADDRESS of g: refill it in place
+ * before a replay, one capture per shape serves every voice. */
+int64_t bv2_ref_workspace_bytes(const bv2_handle* h, int B, int L);
+int bv2_ref_encode(bv2_handle* h, bv2_stream stream, const float* y, const int64_t* strides, const int64_t* y_lengths, int B, int L,
+                   float* g_out, void* workspace, int64_t workspace_bytes);
+int bv2_encode_durations_g(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
+                           const bv2_item_controls* controls, const float* g, void* workspace, int64_t workspace_bytes);
+int bv2_infer_g(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* enc_out,
+                const float* noise_z, int64_t nz_bstride, int64_t nz_cstride, int64_t nz_tstride, float noise_scale, int32_t max_len,
+                int32_t Ty_cap, const bv2_decode_out* dec_out, int32_t* Ty_out, const bv2_item_controls* controls, const float* g,
+                void* workspace, int64_t workspace_bytes);
+
 /* ---- 16-bit PCM (serving glue; replaces the host-side gradio convert_to_16_bit_wav the reference's callers run after
  * .cpu(): webui.py:86,129, hiyoriUI.py:343) -------------------------------------------------------------------- */
 /* pcm[b][i] = (int16) trunc( wave[b][i] / max_j |wave[b][j]| * 32767 ) over the valid samples i, j < y_lengths[b]*hop
@@ -282,6 +315,10 @@ int bv2_graph_capture_encode_ex(bv2_handle* h, bv2_stream stream, const bv2_enco
                                 const bv2_item_controls* controls, void* workspace, int64_t workspace_bytes, bv2_graph** graph);
 int bv2_graph_capture_decode_ex(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out,
                                 const bv2_item_controls* controls, void* workspace, int64_t workspace_bytes, bv2_graph** graph);
+/* phase A on a caller's g (see bv2_encode_durations_g): the graph reads g at replay time */
+int bv2_graph_capture_encode_g(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const bv2_encode_out* out,
+                               const bv2_item_controls* controls, const float* g, void* workspace, int64_t workspace_bytes,
+                               bv2_graph** graph);
 int bv2_graph_launch(bv2_graph* graph, bv2_stream stream);
 int bv2_graph_num_nodes(const bv2_graph* graph);
 void bv2_graph_destroy(bv2_graph* graph);
