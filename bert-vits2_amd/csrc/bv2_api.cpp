@@ -416,6 +416,126 @@ int bv2_pcm16(bv2_stream stream, const float* wave, int64_t wave_bstride, const 
   } catch (...) { return -100; }
 }
 
+// ---- spectrogram of a waveform (kernels/stft.hip) ---------------------------------------------------------------
+static int stft_check(const bv2_stft_config* c, const char* what) {
+  auto fail = [&](const std::string& m) { g_create_err = std::string(what) + ": " + m; return -1; };
+  if (!c) return fail("cfg is null");
+  if (c->struct_bytes != (int32_t)sizeof(bv2_stft_config)) return fail("bv2_stft_config.struct_bytes mismatch (ABI drift)");
+  if (c->n_fft != 1024 && c->n_fft != 2048) return fail("n_fft must be 1024 or 2048, got " + std::to_string(c->n_fft));
+  if (c->hop < 1 || c->hop > c->n_fft) return fail("hop must be in [1, n_fft], got " + std::to_string(c->hop));
+  if (c->win < 1 || c->win > c->n_fft) return fail("win must be in [1, n_fft], got " + std::to_string(c->win));
+  if (c->n_mels < 0 || c->n_mels > 1024) return fail("n_mels must be in [0, 1024], got " + std::to_string(c->n_mels));
+  if (c->input_format != BV2_WAV_F32 && c->input_format != BV2_WAV_I16) return fail("input_format must be BV2_WAV_F32 or BV2_WAV_I16");
+  return 0;
+}
+
+int64_t bv2_stft_frames(const bv2_stft_config* cfg, int64_t n_samples) {
+  if (stft_check(cfg, "bv2_stft_frames")) return -1;
+  const int64_t pad = (cfg->n_fft - cfg->hop) / 2;
+  if (n_samples <= pad) {
+    g_create_err = "bv2_stft_frames: n_samples must be at least pad + 1 = " + std::to_string(pad + 1) + " (reflect padding), got " + std::to_string(n_samples);
+    return -1;
+  }
+  const int64_t n = n_samples + 2 * pad - cfg->n_fft;
+  if (n < 0) {
+    g_create_err = "bv2_stft_frames: n_samples must be at least n_fft - 2 pad = " + std::to_string(cfg->n_fft - 2 * pad) + " (one whole frame), got " + std::to_string(n_samples);
+    return -1;
+  }
+  return 1 + n / cfg->hop;
+}
+
+// librosa.filters.mel (htk = False, norm = "slaney"): the Slaney scale is linear below 1 kHz (200 / 3 Hz per mel) and logarithmic above
+static double hz_to_mel(double f) {
+  const double f_sp = 200.0 / 3, min_log_hz = 1000.0, logstep = std::log(6.4) / 27.0;
+  return f >= min_log_hz ? min_log_hz / f_sp + std::log(f / min_log_hz) / logstep : f / f_sp;
+}
+static double mel_to_hz(double m) {
+  const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
+  return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
+}
+
+int bv2_mel_basis_f64(const bv2_stft_config* cfg, int32_t sampling_rate, double fmin, double fmax, double* out) {
+  if (int rc = stft_check(cfg, "bv2_mel_basis")) return rc;
+  if (!out || cfg->n_mels < 1 || sampling_rate < 1) { g_create_err = "bv2_mel_basis: needs out, n_mels >= 1 and sampling_rate >= 1"; return -1; }
+  if (fmax <= 0) fmax = sampling_rate / 2.0;
+  if (fmin < 0 || fmin >= fmax) { g_create_err = "bv2_mel_basis: fmin must be in [0, fmax)"; return -1; }
+  try {
+    const int M = cfg->n_mels, C = cfg->n_fft / 2 + 1;
+    std::vector<double> mel_f(M + 2);
+    const double m0 = hz_to_mel(fmin), m1 = hz_to_mel(fmax), step = (m1 - m0) / (M + 1);
+    for (int i = 0; i < M + 2; ++i) mel_f[i] = mel_to_hz(i == M + 1 ? m1 : m0 + step * i);
+    const double fstep = (sampling_rate / 2.0) / (C - 1);
+    for (int m = 0; m < M; ++m) {
+      const double d0 = mel_f[m + 1] - mel_f[m], d1 = mel_f[m + 2] - mel_f[m + 1], norm = 2.0 / (mel_f[m + 2] - mel_f[m]);
+      for (int f = 0; f < C; ++f) {
+        const double fr = f == C - 1 ? sampling_rate / 2.0 : fstep * f;
+        const double lower = -(mel_f[m] - fr) / d0, upper = (mel_f[m + 2] - fr) / d1;
+        out[(size_t)m * C + f] = std::max(0.0, std::min(lower, upper)) * norm;
+      }
+    }
+    return 0;
+  } catch (...) { g_create_err = "bv2_mel_basis: out of memory"; return -100; }
+}
+
+int bv2_mel_basis(const bv2_stft_config* cfg, int32_t sampling_rate, double fmin, double fmax, float* out) {
+  if (int rc = stft_check(cfg, "bv2_mel_basis")) return rc;
+  if (!out || cfg->n_mels < 1) { g_create_err = "bv2_mel_basis: needs out and n_mels >= 1"; return -1; }
+  try {
+    const size_t n = (size_t)cfg->n_mels * (cfg->n_fft / 2 + 1);
+    std::vector<double> d(n);
+    if (int rc = bv2_mel_basis_f64(cfg, sampling_rate, fmin, fmax, d.data())) return rc;
+    for (size_t i = 0; i < n; ++i) out[i] = (float)d[i];
+    return 0;
+  } catch (...) { g_create_err = "bv2_mel_basis: out of memory"; return -100; }
+}
+
+int64_t bv2_stft_workspace_bytes(const bv2_stft_config* cfg, int32_t B, int64_t S) {
+  if (stft_check(cfg, "bv2_stft_workspace_bytes")) return -1;
+  if (B < 1 || S < 1) { g_create_err = "bv2_stft_workspace_bytes: B and S must be at least 1"; return -1; }
+  return stft_workspace_bytes(cfg->n_fft, cfg->n_mels) + 256;
+}
+
+int bv2_spectrogram(bv2_stream stream, const bv2_stft_config* cfg, const void* wav, int64_t wav_bstride, const int64_t* wav_lengths,
+                    int32_t B, int64_t S, const float* mel_basis, float* spec, const int64_t* spec_strides, int64_t* spec_lengths_out,
+                    void* workspace, int64_t workspace_bytes) {
+  const char* what = "bv2_spectrogram";
+  if (int rc = stft_check(cfg, what)) return rc;
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (!wav || !spec) return fail("wav and spec must not be null", -1);
+  if (B < 1 || B > 65535) return fail("B must be in [1, 65535]", -1);
+  if (S < 1 || S > ((int64_t)1 << 31) - 4096) return fail("S must be in [1, 2^31 - 4096]", -1);
+  if (wav_bstride < 0) return fail("wav_bstride must not be negative", -1);
+  if (cfg->n_mels > 0 && !mel_basis) return fail("mel_basis must not be null when n_mels > 0", -1);
+  const int64_t L = bv2_stft_frames(cfg, S);
+  if (L < 1) return -1;                                      // message set by bv2_stft_frames
+  if (L > ((int64_t)1 << 30)) return fail("too many frames", -1);
+  const int64_t C = cfg->n_mels ? cfg->n_mels : cfg->n_fft / 2 + 1;
+  int64_t st[3] = {C * L, L, 1};
+  if (spec_strides) {
+    for (int i = 0; i < 3; ++i) {
+      if (spec_strides[i] < 0) return fail("spec_strides must not be negative", -1);
+      st[i] = spec_strides[i];
+    }
+  }
+  const int64_t need = stft_workspace_bytes(cfg->n_fft, cfg->n_mels);
+  if (!workspace || workspace_bytes < need) return fail("workspace too small (bv2_stft_workspace_bytes)", -5);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const uintptr_t mis = reinterpret_cast<uintptr_t>(ws) & 7u;
+  if (mis) {
+    if (workspace_bytes < need + 8) return fail("workspace too small (bv2_stft_workspace_bytes)", -5);
+    ws += 8 - mis;
+  }
+  try {
+    StftArgs a;
+    a.wav = wav; a.wav_bstride = wav_bstride; a.wav_lengths = wav_lengths; a.B = B; a.S = S;
+    a.n_fft = cfg->n_fft; a.hop = cfg->hop; a.win = cfg->win; a.n_mels = cfg->n_mels; a.input_format = cfg->input_format;
+    a.L = (int)L; a.mel = cfg->n_mels ? mel_basis : nullptr;
+    a.spec = spec; a.sb = st[0]; a.sf = st[1]; a.st = st[2]; a.lengths_out = spec_lengths_out; a.ws = ws;
+    if (launch_stft(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
 // ---- hipGraph capture -----------------------------------------------------------------------------------------
 struct bv2_graph {
   hipGraphExec_t exec = nullptr;

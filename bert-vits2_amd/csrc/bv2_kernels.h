@@ -672,4 +672,19 @@ void ref_enc_dims(int L, int spec, int* H, int* W);  // H[0..6], W[0..6]: time /
 int64_t ref_enc_workspace_floats(int B, int L, int spec);
 int launch_ref_enc(hipStream_t stream, const RefEncArgs& a);
 
+// --- spectrogram of a waveform (reference mel_processing.py:43-78, 95-142; kernels/stft.hip): two launches ---
+struct StftArgs {
+  const void* wav; int64_t wav_bstride;              // [B][>= S] fp32 (input_format 0) or int16 (1)
+  const int64_t* wav_lengths;                        // [B] valid samples per item, or null = all S
+  int B; int64_t S;
+  int n_fft, hop, win, n_mels, input_format;         // n_fft 1024 / 2048; n_mels 0 = the linear spectrogram
+  int L;                                             // frame capacity of the output = frames of S
+  const float* mel;                                  // [n_mels][n_fft / 2 + 1], or null when n_mels == 0
+  float* spec; int64_t sb, sf, st;                   // element (b, f, t) at spec[b*sb + f*sf + t*st]
+  int64_t* lengths_out;                              // [B] frames per item (may be null)
+  void* ws;                                          // stft_workspace_bytes(n_fft, n_mels), 8-byte aligned
+};
+int64_t stft_workspace_bytes(int n_fft, int n_mels);
+int launch_stft(hipStream_t stream, const StftArgs& a);
+
 }  // namespace bv2

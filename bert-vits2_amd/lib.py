@@ -83,6 +83,15 @@ class ItemControls(C.Structure):
                 ("noise_scale", C.c_void_p)]
 
 
+class StftConfig(C.Structure):
+    """include/bv2.h bv2_stft_config"""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("win", C.c_int32), ("n_mels", C.c_int32),
+                ("input_format", C.c_int32)]
+
+
+WAV_F32, WAV_I16 = 0, 1
+
+
 class ProfileRow(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -129,6 +138,12 @@ SYMBOLS = [
     ("bv2_graph_capture_encode_g", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P, _P,
                                              C.c_int64, C.POINTER(_P)]),
     ("bv2_pcm16", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
+    ("bv2_stft_frames", C.c_int64, [C.POINTER(StftConfig), C.c_int64]),
+    ("bv2_mel_basis", C.c_int, [C.POINTER(StftConfig), C.c_int32, C.c_double, C.c_double, _P]),
+    ("bv2_mel_basis_f64", C.c_int, [C.POINTER(StftConfig), C.c_int32, C.c_double, C.c_double, _P]),
+    ("bv2_stft_workspace_bytes", C.c_int64, [C.POINTER(StftConfig), C.c_int32, C.c_int64]),
+    ("bv2_spectrogram", C.c_int, [_P, C.POINTER(StftConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, _P, C.POINTER(C.c_int64), _P, _P,
+                                  C.c_int64]),
     ("bv2_graph_capture_encode", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_decode", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_encode_ex", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P,

@@ -142,6 +142,7 @@ class SynthesizerTrn(nn.Module):
         self._graphs: Dict[tuple, dict] = {}
         self._cap_stream = None
         self._options: Dict[str, int] = {}
+        self._stft_params = None           # audio.StftParams of reference_embedding_from_wav (None: what the hyper-parameters imply)
         self.ref_encode_calls = 0          # bv2_ref_encode calls made through reference_embedding (serving encodes a shared reference once)
 
     # ------------------------------------------------------------------ parameter tree
@@ -402,6 +403,36 @@ class SynthesizerTrn(nn.Module):
                                                  C.c_void_p(ws.data_ptr()), ws.numel()), "bv2_ref_encode")
         self.ref_encode_calls = getattr(self, "ref_encode_calls", 0) + 1
         return g
+
+    @property
+    def stft_params(self):
+        """How a recording becomes this model's spectrogram (``audio.StftParams``).  Defaults to what ``spec_channels``, ``hop_length`` and
+        ``sampling_rate`` imply (``StftParams.from_hparams``); assign ``StftParams.from_config(cfg)`` for a checkpoint whose ``config.json``
+        says otherwise (another ``win_length``, mel limits)."""
+        from . import audio
+        if getattr(self, "_stft_params", None) is None:
+            self._stft_params = audio.StftParams.from_hparams(self.hp)
+        return self._stft_params
+
+    @stft_params.setter
+    def stft_params(self, params) -> None:
+        from . import audio
+        if not isinstance(params, audio.StftParams):
+            raise ValueError("stft_params must be an audio.StftParams")
+        if params.channels != self.hp.spec_channels:
+            raise ValueError(f"these parameters give {params.channels} rows, the model reads spec_channels = {self.hp.spec_channels}")
+        self._stft_params = params
+
+    @torch.no_grad()
+    def reference_embedding_from_wav(self, wav: torch.Tensor, wav_lengths=None) -> torch.Tensor:
+        """The voice of a recording -> g [B, gin]: ``audio.spectrogram(wav, wav_lengths, self.stft_params)`` on the model's device, then
+        ``reference_embedding`` with the frame counts it produced (a ragged batch is exact in both steps).  ``wav`` [B, S] or [S], fp32 in
+        [-1, 1] or int16 PCM at the model's sampling rate."""
+        from . import audio
+        if self.hp.n_speakers != 0:
+            raise RuntimeError("reference_embedding_from_wav needs a model built with n_speakers=0 (this one has a speaker table: emb_g)")
+        spec, lengths = audio.spectrogram(wav, wav_lengths, self.stft_params, device=self.device)
+        return self.reference_embedding(spec, lengths)
 
     # ------------------------------------------------------------------ the two phases
     @torch.no_grad()

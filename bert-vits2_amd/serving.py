@@ -132,6 +132,20 @@ def speaker_vectors(model, utts: Sequence[Utterance]) -> List[Optional[torch.Ten
     return out
 
 
+def reference_spectrogram(model, wav: torch.Tensor) -> torch.Tensor:
+    """One recording (``[S]`` or ``[1, S]``, fp32 in [-1, 1] or int16 PCM at the model's sampling rate) -> its spectrogram ``[spec_channels,
+    L]`` on the model's device (``audio.spectrogram`` with ``model.stft_params``), to be put into ``Utterance(ref_spec=...)``: utterances
+    that share the returned tensor object share one encoding."""
+    from . import audio
+    wav = torch.as_tensor(wav)
+    if wav.dim() == 2 and wav.shape[0] == 1:
+        wav = wav[0]
+    if wav.dim() != 1:
+        raise ValueError(f"reference_spectrogram takes one recording [S], got {tuple(wav.shape)}")
+    spec, _ = audio.spectrogram(wav, None, model.stft_params, device=model.device)
+    return spec[0]
+
+
 def pcm16(model, wave: torch.Tensor, y_lengths: torch.Tensor) -> torch.Tensor:
     """Device-side 16-bit conversion of ``wave`` [B,1,S] (peak-normalised per utterance over its valid samples, the
     semantics of gradio ``convert_to_16_bit_wav`` used by reference webui.py:86) -> int16 [B,S]."""

@@ -212,3 +212,22 @@ def synthetic_noise(B: int, T: int, T_y_cap: int, channels: int = 192, seed: int
     noise_w = torch.randn(B, 2, T, generator=g)
     noise_z = torch.randn(B, channels, T_y_cap, generator=g)
     return noise_w, noise_z
+
+
+def synthetic_reference_wav(n_samples: int, index: int = 0, sampling_rate: int = 44100, base_seed: int = 2718) -> torch.Tensor:
+    """A seeded voice-like recording, int16 PCM [n_samples]: twelve harmonics (amplitude 1 / h) of a fundamental of 110-220 Hz with a slow
+    vibrato, under a syllable-rate amplitude envelope, plus a little white noise; peak 0.8 of full scale.  For benchmarks and for tests that
+    compare the device with itself — fixtures store their waveforms (another libm's ``sin`` may differ in the last bit)."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(base_seed + index)
+    r = torch.rand(4, generator=g, dtype=torch.float64)
+    t = torch.arange(n_samples, dtype=torch.float64) / sampling_rate
+    f0 = 110.0 + 110.0 * float(r[0])
+    phase = 2 * math.pi * f0 * t + 3.0 * torch.sin(2 * math.pi * (4.0 + 2.0 * float(r[1])) * t)          # vibrato of 4-6 Hz
+    x = torch.zeros(n_samples, dtype=torch.float64)
+    for h in range(1, 13):
+        x += torch.sin(h * phase + h * float(r[2])) / h
+    x *= 0.55 + 0.45 * torch.sin(2 * math.pi * (2.0 + 2.0 * float(r[3])) * t)                              # syllables at 2-4 Hz
+    x += 0.01 * torch.randn(n_samples, generator=g, dtype=torch.float64)
+    x *= 0.8 / x.abs().max().clamp_min(1e-9)
+    return torch.round(x * 32767.0).to(torch.int16)

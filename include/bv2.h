@@ -297,6 +297,45 @@ int bv2_infer_g(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const
 int bv2_pcm16(bv2_stream stream, const float* wave, int64_t wave_bstride, const int64_t* y_lengths, int32_t hop, int32_t B,
               int64_t S, int16_t* pcm, int64_t pcm_bstride, uint32_t* peak_scratch);
 
+/* ---- from a waveform to the spectrogram bv2_ref_encode reads (handle-free, like bv2_pcm16) -----------------------------
+ * The reference turns a recording into y with mel_processing.spectrogram_torch (mel_processing.py:43-78, called from data_utils.py:99-138
+ * after audio / max_wav_value): reflect padding by pad = (n_fft - hop) / 2 at both ends, periodic Hann window of `win` samples centred in
+ * n_fft, torch.stft(center = False), sqrt(re^2 + im^2 + 1e-6); a model whose spec_channels is a mel width takes mel_spectrogram_torch
+ * (:95-142): log(max(M . spec, 1e-5)) with M the Slaney-scale, Slaney-normalised filterbank of librosa.filters.mel.  bv2_spectrogram is that
+ * step on the device, as an fp32 FFT (kernels/stft.hip), two launches, asynchronous on `stream`, graph-capturable.
+ *
+ * Accepted: n_fft 1024 or 2048, 1 <= hop <= n_fft, 1 <= win <= n_fft, n_mels >= 0 (0 = the linear spectrogram, n_fft / 2 + 1 rows).  A
+ * failed call returns non-zero (the frame / size queries a negative value) and leaves its message in bv2_last_error(NULL); every argument is
+ * checked before anything touches the device.  No resampling and no file decoding: samples at the model's sampling rate go in. */
+enum { BV2_WAV_F32 = 0, BV2_WAV_I16 = 1 };     /* fp32 in [-1, 1], or 16-bit PCM read as x / 32768 (exact) */
+typedef struct bv2_stft_config {
+  int32_t struct_bytes;            /* = sizeof(bv2_stft_config) */
+  int32_t n_fft, hop, win;
+  int32_t n_mels;                  /* 0 = linear */
+  int32_t input_format;            /* BV2_WAV_F32 / BV2_WAV_I16 */
+} bv2_stft_config;
+/* Frames of a waveform of n_samples: 1 + (n_samples + 2 pad - n_fft) / hop.  Negative for n_samples <= pad (reflect padding needs
+ * pad < n_samples; the reference refuses such an input too), for n_samples + 2 pad < n_fft (no whole frame: only with hop > n_fft / 3) and
+ * for a bad config. */
+int64_t bv2_stft_frames(const bv2_stft_config* cfg, int64_t n_samples);
+/* HOST: the filterbank [n_mels][n_fft / 2 + 1] of librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) (htk = False, norm = "slaney"), built
+ * in fp64; bv2_mel_basis rounds it to fp32 as the reference does, bv2_mel_basis_f64 hands out the fp64 values.  fmax <= 0 means
+ * sampling_rate / 2. */
+int bv2_mel_basis(const bv2_stft_config* cfg, int32_t sampling_rate, double fmin, double fmax, float* out);
+int bv2_mel_basis_f64(const bv2_stft_config* cfg, int32_t sampling_rate, double fmin, double fmax, double* out);
+/* Bytes of DEVICE workspace of a call (twiddles, window and the filterbank's row ranges: it does not grow with B or S). */
+int64_t bv2_stft_workspace_bytes(const bv2_stft_config* cfg, int32_t B, int64_t S);
+/* wav [B][wav_bstride >= S] (fp32 or int16, DEVICE); wav_lengths [B] (int64, DEVICE) or NULL = every item is S samples long.  Item b's
+ * frames are cut from ITS samples [0, wav_lengths[b]) reflect-padded at its own two ends — nothing outside that range is read, so the
+ * padding of a batch may hold anything.  spec: element (b, f, t) at spec[b*spec_strides[0] + f*spec_strides[1] + t*spec_strides[2]]
+ * (NULL = contiguous [B, C, L]), C = n_mels or n_fft / 2 + 1, L = bv2_stft_frames(cfg, S); a frequency stride of 1 ([B, L, C] memory handed
+ * to bv2_ref_encode as the transposed view) is the fast store.  Frames t >= L_b of item b are written as zeros; spec_lengths_out [B] (int64,
+ * DEVICE, may be NULL) receives L_b in the form bv2_ref_encode takes as y_lengths (0 for an item of wav_lengths[b] <= pad).  mel_basis
+ * [n_mels][n_fft / 2 + 1] (fp32, DEVICE) is read when n_mels > 0. */
+int bv2_spectrogram(bv2_stream stream, const bv2_stft_config* cfg, const void* wav, int64_t wav_bstride, const int64_t* wav_lengths,
+                    int32_t B, int64_t S, const float* mel_basis, float* spec, const int64_t* spec_strides, int64_t* spec_lengths_out,
+                    void* workspace, int64_t workspace_bytes);
+
 /* ---- hipGraph capture (BASELINE config 3: "hipGraph-captured decode") ----------------------------------------- */
 /* Both phases are fixed launch sequences on the caller's stream with no allocation, host sync or device->host copy,
  * so they can be recorded once and replayed: bv2_graph_capture_* puts `stream` (which must NOT be the legacy default
