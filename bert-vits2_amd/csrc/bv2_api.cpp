@@ -416,6 +416,73 @@ int bv2_pcm16(bv2_stream stream, const float* wave, int64_t wave_bstride, const 
   } catch (...) { return -100; }
 }
 
+// ---- streamed synthesis (bv2_exec.cpp run_stream_*, kernels/stream.hip) ------------------------------------------
+int bv2_generator_halo(const bv2_handle* h) { return h ? generator_halo(h->model) : -1; }
+
+int64_t bv2_stream_workspace_bytes(const bv2_handle* h, int B, int T, int Ty, int window_frames) {
+  if (!h || B < 1 || T < 1 || Ty < 1 || window_frames < 1) return -1;
+  return stream_workspace_bytes(h->model, B, T, Ty, window_frames);
+}
+
+int bv2_stream_begin(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out,
+                     const bv2_item_controls* ic, void* ws, int64_t wsb) {
+  if (!h) return -1;
+  BV2_TRY
+  if (int rc = check_controls(h, ic, "bv2_stream_begin")) return rc;
+  if (!in || !out || in->B < 1 || in->T < 1 || in->Ty < 1) { h->err = "bv2_stream_begin: bad argument"; return -1; }
+  if (!in->m_p || !in->logs_p || !in->x_mask || !in->w_ceil || !in->y_lengths || !in->g || !in->noise_z) {
+    h->err = "bv2_stream_begin: null tensor pointer"; return -1;
+  }
+  if (!h->taps.empty()) { h->err = "bv2_stream_begin: taps are not supported during a stream (bv2_set_tap(h, NULL, ...) clears them)"; return -1; }
+  if (int rc = ready(h, ws)) return rc;
+  return run_stream_begin(h, static_cast<hipStream_t>(stream), *in, *out, ws, wsb, ic);
+  BV2_CATCH(h)
+}
+
+int bv2_stream_chunk(bv2_handle* h, bv2_stream stream, const bv2_stream_chunk_args* a, void* ws, int64_t wsb) {
+  if (!h) return -1;
+  BV2_TRY
+  auto bad = [&](const std::string& m) { h->err = "bv2_stream_chunk: " + m; return -1; };
+  if (!a) return bad("args is null");
+  if (a->struct_bytes != (int32_t)sizeof(bv2_stream_chunk_args))
+    return bad("bv2_stream_chunk_args.struct_bytes must be sizeof(bv2_stream_chunk_args) (" + std::to_string(sizeof(bv2_stream_chunk_args)) + ")");
+  if (a->B < 1 || a->B > 65535 || a->Ty < 1) return bad("need 1 <= B <= 65535 and Ty >= 1");
+  const int L = (a->max_len > 0 && a->max_len < a->Ty) ? a->max_len : a->Ty;
+  if (a->t0 < 0 || a->t0 >= a->t1) return bad("need 0 <= t0 < t1, got t0 = " + std::to_string(a->t0) + ", t1 = " + std::to_string(a->t1));
+  if (a->t1 > L) return bad("t1 = " + std::to_string(a->t1) + " is past the last frame (" + std::to_string(L) + ")");
+  if (a->window_frames < 1 || a->t1 - a->t0 > a->window_frames)
+    return bad("the chunk keeps " + std::to_string(a->t1 - a->t0) + " frames, the workspace was planned for window_frames = " +
+               std::to_string(a->window_frames));
+  if (!a->y_lengths) return bad("y_lengths is null");
+  if (a->exact_lengths != 0 && a->exact_lengths != 1) return bad("exact_lengths must be 0 or 1");
+  if ((a->dst != nullptr) == (a->dst16 != nullptr)) return bad("exactly one of dst / dst16 must be given");
+  const int64_t n = (int64_t)(a->t1 - a->t0) * h->model.total_up;
+  if ((a->dst ? a->dst_bstride : a->dst16_bstride) < n) return bad("the destination's batch stride is shorter than the chunk (" + std::to_string(n) + " samples)");
+  if (!h->taps.empty()) return bad("taps are not supported during a stream (bv2_set_tap(h, NULL, ...) clears them)");
+  if (!ws || wsb < stream_plan_bytes(h->model, a->B, a->Ty, a->window_frames)) {
+    h->err = "bv2_stream_chunk: workspace is null or smaller than bv2_stream_workspace_bytes(h, B, T, Ty, window_frames)"; return -5;
+  }
+  if (int rc = ready(h, ws)) return rc;
+  bv2_stream_chunk_args c = *a;
+  if (!(c.pcm_gain > 0.f)) c.pcm_gain = 32767.f;
+  return run_stream_chunk(h, static_cast<hipStream_t>(stream), c, ws, wsb);
+  BV2_CATCH(h)
+}
+
+int bv2_emit(bv2_stream stream, const float* src, int64_t src_bstride, int64_t src_off, const int64_t* y_lengths, int32_t hop,
+             int64_t start_sample, int32_t B, int64_t n, float* dst, int16_t* dst16, int64_t dst_bstride, float gain) {
+  auto bad = [&](const char* m) { g_create_err = std::string("bv2_emit: ") + m; return -1; };
+  try {
+    if (!src) return bad("src is null");
+    if ((dst != nullptr) == (dst16 != nullptr)) return bad("exactly one of dst / dst16 must be given");
+    if (B < 1 || B > 65535 || n < 1 || hop < 1 || src_off < 0 || src_bstride < 0) return bad("need 1 <= B <= 65535, n >= 1, hop >= 1, src_off >= 0, src_bstride >= 0");
+    if (dst_bstride < n) return bad("dst_bstride is shorter than n");
+    if (launch_stream_emit(static_cast<hipStream_t>(stream), src, src_bstride, src_off, y_lengths, hop, start_sample, B, n, dst, dst16,
+                           dst_bstride, gain > 0.f ? gain : 32767.f)) return bad("kernel launch failed");
+    return 0;
+  } catch (...) { return -100; }
+}
+
 // ---- spectrogram of a waveform (kernels/stft.hip) ---------------------------------------------------------------
 static int stft_check(const bv2_stft_config* c, const char* what) {
   auto fail = [&](const std::string& m) { g_create_err = std::string(what) + ": " + m; return -1; };

@@ -412,11 +412,11 @@ int64_t gen_unit(const Model& m) {      // max over stages of C_i * (samples per
   }
   return best;
 }
-PlanB plan_b(Arena& A, const Model& m, int B, int Ty) {
+// plan_b in three parts, in this order: what a decode keeps from expand to the last Generator launch (frames = Ty), the flow's scratch
+// (frames = Ty) and the Generator's buffers (frames = what the Generator runs on: Ty for a whole decode, a window for a streamed one)
+void plan_b_keep(PlanB& p, Arena& A, const Model& m, int B, int Ty) {
   const bv2_config& c = m.cfg;
   const int64_t H = c.hidden_channels, BT = (int64_t)B * Ty;
-  PlanB p;
-  std::memset(&p, 0, sizeof(p));
   p.gv_stride = c.upsample_initial_channel +
                 (c.use_transformer_flow ? m.n_coupling * (int)H : m.n_coupling * 2 * (int)H * c.n_flow_layer);
   p.gv = A.get<float>((int64_t)B * p.gv_stride);
@@ -426,6 +426,10 @@ PlanB plan_b(Arena& A, const Model& m, int B, int Ty) {
   p.len_cap = A.get<int64_t>(B);
   p.zp = A.get<float>(BT * c.inter_channels);
   p.z = A.get<float>(BT * c.inter_channels);
+}
+void plan_b_flow(PlanB& p, Arena& A, const Model& m, int B, int Ty) {
+  const bv2_config& c = m.cfg;
+  const int64_t H = c.hidden_channels, BT = (int64_t)B * Ty;
   p.h = A.get<float>(BT * H);
   if (c.use_transformer_flow) {
     p.enc.x = p.h;
@@ -441,10 +445,47 @@ PlanB plan_b(Arena& A, const Model& m, int B, int Ty) {
     p.acts = A.get<float>(BT * H);
     p.outacc = A.get<float>(BT * H);
   }
-  p.pre = A.get<float>(BT * c.upsample_initial_channel);
+}
+void plan_b_gen(PlanB& p, Arena& A, const Model& m, int B, int frames) {
+  const int64_t BT = (int64_t)B * frames;
+  p.pre = A.get<float>(BT * m.cfg.upsample_initial_channel);
   const int64_t unit = gen_unit(m) * BT;
   for (int s = 0; s < 2; ++s)
     for (int i = 0; i < 7; ++i) p.set[s][i] = A.get<float>(unit);
+}
+PlanB plan_b(Arena& A, const Model& m, int B, int Ty) {
+  PlanB p;
+  std::memset(&p, 0, sizeof(p));
+  plan_b_keep(p, A, m, B, Ty);
+  plan_b_flow(p, A, m, B, Ty);
+  plan_b_gen(p, A, m, B, Ty);
+  return p;
+}
+
+// Streamed decode (bv2_stream_begin / bv2_stream_chunk): plan_b's kept part and a [B] window-length array stay for the whole stream; behind
+// them ONE region serves the flow's scratch at Ty (bv2_stream_begin) and then, window after window, the Generator's buffers at the window's
+// frames plus the window's output [B][frames * U] — the flow has finished before the first window.  part: 0 = sizes only (the region is the
+// larger of the two uses), 1 = the flow's pointers, 2 = the Generator's.
+struct PlanS {
+  PlanB b;
+  int64_t* wlens;
+  float* wout;
+};
+PlanS plan_stream(Arena& A, const Model& m, int B, int Ty, int gen_frames, int part) {
+  PlanS p;
+  std::memset(&p, 0, sizeof(p));
+  plan_b_keep(p.b, A, m, B, Ty);
+  p.wlens = A.get<int64_t>(B);
+  const int64_t region = A.off;
+  int64_t end_flow = region, end_gen = region;
+  if (part != 2) { plan_b_flow(p.b, A, m, B, Ty); end_flow = A.off; }
+  if (part != 1) {
+    A.off = region;
+    plan_b_gen(p.b, A, m, B, gen_frames);
+    p.wout = A.get<float>((int64_t)B * gen_frames * m.total_up);
+    end_gen = A.off;
+  }
+  A.off = end_flow > end_gen ? end_flow : end_gen;
   return p;
 }
 
@@ -1377,6 +1418,114 @@ int run_generator(bv2_handle* h, hipStream_t s, int B, int Ty, int L, const floa
   phase_b_gemv(c, P, g, B);
   if (h->gen_dtype == BV2_BF16) gen_core_bf16(c, P, z, Ty, ymask, B, L, o, nullptr);
   else gen_core(c, P, z, Ty, ymask, B, L, o, nullptr);
+  return c.rc;
+}
+
+// ===============================================================================================================
+// streamed decode (include/bv2.h "streamed synthesis"): the flow once, then the Generator window by window
+
+// Frames of z a window must carry on each side for its kept samples to equal the whole decode's: the input interval of output samples
+// [a*U, b*U) walked backwards through conv_post, every stage's widest ResBlock branch and ConvTranspose1d, and conv_pre
+// (hparams.generator_halo is the same walk; tests/test_stream_cpu.py holds both to the same table)
+int generator_halo(const Model& m) {
+  const bv2_config& c = m.cfg;
+  auto floordiv = [](int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+  int64_t reach = 0;
+  for (int j = 0; j < m.n_rbk; ++j) {
+    const int64_t half = (c.resblock_kernel_sizes[j] - 1) / 2;
+    int64_t r = 0;
+    for (int d = 0; d < m.n_rbd; ++d)
+      r += m.rb_type == 2 ? half * c.resblock_dilation_sizes[j][d] : half * (c.resblock_dilation_sizes[j][d] + 1);
+    reach = r > reach ? r : reach;
+  }
+  const int64_t U = m.total_up, a = 0, b = 1;
+  const int64_t post = (m.post_k - 1) / 2;
+  int64_t lo = a * U - post, hi = b * U - 1 + post;
+  for (int i = m.n_ups - 1; i >= 0; --i) {
+    lo -= reach; hi += reach;
+    const int64_t u = m.ups[i].u, k = m.ups[i].k, p = (k - u) / 2;
+    lo = -floordiv(-(lo + p - k + 1), u);            // ceil
+    hi = floordiv(hi + p, u);
+  }
+  const int64_t pre = (m.conv_pre.k - 1) / 2;
+  lo -= pre; hi += pre;
+  const int64_t left = a - lo, right = hi - (b - 1);
+  return (int)(left > right ? left : right);
+}
+
+static int stream_gen_frames(const Model& m, int Ty, int window_frames) {
+  const int64_t w = (int64_t)window_frames + 2 * (int64_t)generator_halo(m);
+  return (int)(w < Ty ? w : Ty);
+}
+
+int64_t stream_plan_bytes(const Model& m, int B, int Ty, int window_frames) {
+  Arena s(nullptr, 0);
+  plan_stream(s, m, B, Ty, stream_gen_frames(m, Ty, window_frames), 0);
+  return s.off;
+}
+
+int64_t stream_workspace_bytes(const Model& m, int B, int T, int Ty, int window_frames) {
+  Arena a(nullptr, 0);
+  plan_a(a, m, B, T);                                // the same workspace serves phase A before the stream begins
+  const int64_t s = stream_plan_bytes(m, B, Ty, window_frames);
+  return (a.off > s ? a.off : s) + 256;
+}
+
+// run_decode up to and including the flow; z, y_mask and the speaker GEMVs stay in the workspace's kept part
+int run_stream_begin(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
+                     const bv2_item_controls* ic) {
+  const Model& m = h->model;
+  const bv2_config& cf = m.cfg;
+  const int B = in.B, T = in.T, Ty = in.Ty, C = cf.inter_channels;
+  Arena A(ws, wsb);
+  PlanS S = plan_stream(A, m, B, Ty, 1, 1);
+  if (!A.ok()) { h->err = "workspace too small for bv2_stream_begin"; return -5; }
+  const PlanB& P = S.b;
+  Ctx c{h, s, m, h->blob};
+
+  ExpandArgs e;
+  std::memset(&e, 0, sizeof(e));
+  e.w_ceil = in.w_ceil; e.x_mask = in.x_mask; e.y_lengths = in.y_lengths; e.m_p = in.m_p; e.logs_p = in.logs_p;
+  e.noise = in.noise_z; e.nz_bstride = in.nz_bstride; e.nz_cstride = in.nz_cstride; e.nz_tstride = in.nz_tstride;
+  e.noise_scale = in.noise_scale;
+  e.noise_scale_b = ic ? ic->noise_scale : nullptr;
+  e.frame_idx = P.fidx; e.attn = out.attn; e.y_mask = P.ymask; e.z_p = P.z; e.m_e = out.m_p; e.logs_e = out.logs_p;
+  e.z_p2 = out.z_p;
+  e.B = B; e.C = C; e.T = T; e.Ty = Ty;
+  c.chk(launch_expand(s, e), "expand");
+  phase_b_gemv(c, P, in.g, B);
+  flow_core(c, P, P.z, P.ymask, in.g, B, Ty);
+  if (c.rc) return c.rc;
+  // the caller's copies (bv2_decode writes them in place; here the workspace's are the ones the windows read)
+  if (out.z && hipMemcpyAsync(out.z, P.z, sizeof(float) * (size_t)B * C * Ty, hipMemcpyDeviceToDevice, s) != hipSuccess) c.fail("stream.z", -1);
+  if (out.y_mask && hipMemcpyAsync(out.y_mask, P.ymask, sizeof(float) * (size_t)B * Ty, hipMemcpyDeviceToDevice, s) != hipSuccess) c.fail("stream.y_mask", -1);
+  return c.rc;
+}
+
+// the Generator on frames [max(0, t0 - H), min(L, t1 + H)) of the kept z, then samples [t0*U, t1*U) to the caller (arguments checked by the caller)
+int run_stream_chunk(bv2_handle* h, hipStream_t s, const bv2_stream_chunk_args& a, void* ws, int64_t wsb) {
+  const Model& m = h->model;
+  const int B = a.B, Ty = a.Ty, H = generator_halo(m), U = m.total_up;
+  const int L = (a.max_len > 0 && a.max_len < Ty) ? a.max_len : Ty;
+  const int w0 = a.t0 - H > 0 ? a.t0 - H : 0;
+  const int w1 = a.t1 + H < L ? a.t1 + H : L;
+  const int W = w1 - w0;
+  Arena A(ws, wsb);
+  PlanS S = plan_stream(A, m, B, Ty, W, 2);
+  if (!A.ok()) { h->err = "workspace too small for bv2_stream_chunk"; return -5; }
+  const PlanB& P = S.b;
+  Ctx c{h, s, m, h->blob};
+  const int64_t* lens = nullptr;
+  if (a.exact_lengths) {
+    c.chk(launch_stream_window_lens(s, a.y_lengths, S.wlens, w0, W, B), "stream.window_lens");
+    lens = S.wlens;
+  }
+  if (h->gen_dtype == BV2_BF16) gen_core_bf16(c, P, P.z + w0, Ty, P.ymask + w0, B, W, S.wout, lens);
+  else gen_core(c, P, P.z + w0, Ty, P.ymask + w0, B, W, S.wout, lens);
+  if (c.rc) return c.rc;
+  c.chk(launch_stream_emit(s, S.wout, (int64_t)W * U, (int64_t)(a.t0 - w0) * U, a.y_lengths, U, (int64_t)a.t0 * U, B,
+                           (int64_t)(a.t1 - a.t0) * U, a.dst, a.dst16, a.dst ? a.dst_bstride : a.dst16_bstride,
+                           a.pcm_gain), "stream.emit");
   return c.rc;
 }
 

@@ -210,5 +210,12 @@ int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, con
                  void* ws, int64_t wsb);
 int run_generator(bv2_handle* h, hipStream_t s, int B, int Ty, int L, const float* z, const int64_t* y_lengths,
                   const float* g, float* o, void* ws, int64_t wsb);
+// streamed decode: the flow once (run_stream_begin), the Generator window by window (run_stream_chunk)
+int generator_halo(const Model& m);
+int64_t stream_plan_bytes(const Model& m, int B, int Ty, int window_frames);            // what a stream itself needs (without phase A)
+int64_t stream_workspace_bytes(const Model& m, int B, int T, int Ty, int window_frames);
+int run_stream_begin(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
+                     const bv2_item_controls* ic = nullptr);
+int run_stream_chunk(bv2_handle* h, hipStream_t s, const bv2_stream_chunk_args& a, void* ws, int64_t wsb);
 
 }  // namespace bv2

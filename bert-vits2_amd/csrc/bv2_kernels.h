@@ -658,6 +658,13 @@ int launch_expand(hipStream_t stream, const ExpandArgs& a);
 int launch_pcm16(hipStream_t stream, const float* wave, int64_t bstride, const int64_t* y_lengths, int hop, int B, int64_t S,
                  int16_t* pcm, int64_t pstride, unsigned* peak_scratch);
 
+// --- streamed synthesis (kernels/stream.hip): a window's per-item lengths, and its kept samples as fp32 or fixed-gain 16-bit PCM ---
+int launch_stream_window_lens(hipStream_t stream, const int64_t* y_lengths, int64_t* wlens, int w0, int W, int B);   // clamp(y_lengths[b] - w0, 1, W)
+// dst[b][i] = i < y_lengths[b] * hop - start_sample ? src[b * src_bstride + src_off + i] : 0, i in [0, n); exactly one of dst / dst16
+// (dst16: (int16) trunc(clamp(x * gain, -32768, 32767))); y_lengths null = nothing masked
+int launch_stream_emit(hipStream_t stream, const float* src, int64_t src_bstride, int64_t src_off, const int64_t* y_lengths, int hop,
+                       int64_t start_sample, int B, int64_t n, float* dst, int16_t* dst16, int64_t dst_bstride, float gain);
+
 // --- ReferenceEncoder (reference models.py:752-808; kernels/ref_enc.hip): g [B][gin] from a linear spectrogram, eight launches ---
 struct RefEncArgs {
   const float* y; int64_t sb, sf, st;               // element (b, f, t) of the spectrogram [B][spec][L] at y[b*sb + f*sf + t*st]

@@ -128,6 +128,36 @@ class HParams:
                 raise ValueError("resblock kernels must be odd")
 
 
+def generator_halo(hp: HParams) -> int:
+    """Latent frames a window of z must carry on EACH side so that the Generator's samples of the window's kept frames equal the whole
+    decode's (streamed synthesis: include/bv2.h bv2_stream_chunk; the same walk in C is bv2_generator_halo).
+
+    The Generator (reference models.py:538-557) is a stack of convolutions, so output samples [a*U, b*U) (U = product of the upsample rates)
+    depend on a finite interval of frames.  Walk that interval [lo, hi] backwards: conv_post (k = 7) reaches 3 samples each way; per stage,
+    last to first, the widest ResBlock branch reaches sum_d (k-1)/2 * (d+1) (ResBlock1: a dilated conv and a plain one per dilation,
+    modules.py:239-315) or sum_{d in dil[:2]} (k-1)/2 * d (ResBlock2, modules.py:318-363), and through ConvTranspose1d(k, stride u,
+    padding p = (k-u)/2) input i reaches output n iff 0 <= n + p - i*u < k, so lo -> ceil((lo + p - k + 1) / u), hi -> floor((hi + p) / u);
+    conv_pre (k = 7) reaches 3 frames.  H = max(a - lo, hi - (b - 1)); it does not depend on a or b."""
+    rb1 = str(hp.resblock) == "1"
+    rates, kernels = [int(u) for u in hp.upsample_rates], [int(k) for k in hp.upsample_kernel_sizes]
+    reach = 0
+    for k, dil in zip(hp.resblock_kernel_sizes, hp.resblock_dilation_sizes):
+        half = (int(k) - 1) // 2
+        r = sum(half * (int(d) + 1) for d in dil[:3]) if rb1 else sum(half * int(d) for d in dil[:2])
+        reach = max(reach, r)
+    U = 1
+    for u in rates:
+        U *= u
+    a, b = 4, 5                                        # any window: the walk is translation-invariant in whole frames
+    lo, hi = a * U - 3, b * U - 1 + 3                  # conv_post
+    for u, k in zip(reversed(rates), reversed(kernels)):
+        lo, hi = lo - reach, hi + reach
+        p = (k - u) // 2
+        lo, hi = -((-(lo + p - k + 1)) // u), (hi + p) // u
+    lo, hi = lo - 3, hi + 3                            # conv_pre
+    return max(a - lo, hi - (b - 1))
+
+
 _CTOR_FIELDS = {f.name for f in dataclasses.fields(HParams)}
 
 

@@ -83,6 +83,14 @@ class ItemControls(C.Structure):
                 ("noise_scale", C.c_void_p)]
 
 
+class StreamChunkArgs(C.Structure):
+    """include/bv2.h bv2_stream_chunk_args"""
+    _fields_ = [("struct_bytes", C.c_int32), ("B", C.c_int32), ("Ty", C.c_int32), ("t0", C.c_int32), ("t1", C.c_int32),
+                ("y_lengths", C.c_void_p), ("exact_lengths", C.c_int32), ("dst", C.c_void_p), ("dst_bstride", C.c_int64),
+                ("dst16", C.c_void_p), ("dst16_bstride", C.c_int64), ("pcm_gain", C.c_float), ("window_frames", C.c_int32),
+                ("max_len", C.c_int32)]
+
+
 class StftConfig(C.Structure):
     """include/bv2.h bv2_stft_config"""
     _fields_ = [("struct_bytes", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("win", C.c_int32), ("n_mels", C.c_int32),
@@ -138,6 +146,11 @@ SYMBOLS = [
     ("bv2_graph_capture_encode_g", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P, _P,
                                              C.c_int64, C.POINTER(_P)]),
     ("bv2_pcm16", C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
+    ("bv2_generator_halo", C.c_int, [_P]),
+    ("bv2_stream_workspace_bytes", C.c_int64, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("bv2_stream_begin", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), C.POINTER(ItemControls), _P, C.c_int64]),
+    ("bv2_stream_chunk", C.c_int, [_P, _P, C.POINTER(StreamChunkArgs), _P, C.c_int64]),
+    ("bv2_emit", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _P, _P, C.c_int64, C.c_float]),
     ("bv2_stft_frames", C.c_int64, [C.POINTER(StftConfig), C.c_int64]),
     ("bv2_mel_basis", C.c_int, [C.POINTER(StftConfig), C.c_int32, C.c_double, C.c_double, _P]),
     ("bv2_mel_basis_f64", C.c_int, [C.POINTER(StftConfig), C.c_int32, C.c_double, C.c_double, _P]),

@@ -96,6 +96,53 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+class SynthesisStream:
+    """What ``SynthesizerTrn.infer_stream`` returns: an iterator of ``(start_sample, audio[B, n])``.  Phase A, the one host sync and the
+    flow have run when it exists; every ``next()`` enqueues one windowed Generator decode (``bv2_stream_chunk``) on the current stream and
+    hands back a fresh tensor.  The chunks tile ``[0, total_samples)`` exactly and in order; rows are zero past an item's end.
+
+    ``y_lengths`` [B] (device, frames; ``y_lengths_host`` is the list read at the host sync), ``Ty``, ``total_samples`` (= frames fed to the Generator x product of the upsample rates), ``halo``
+    (frames a window carries on each side, ``hparams.generator_halo``) and ``aux`` (``attn``, ``y_mask``, ``z``, ``z_p``, ``m_p``,
+    ``logs_p`` as ``infer`` returns them) are there from the start.  The stream owns its workspace, so other ``infer`` calls of the same
+    model may run between two chunks; call ``next()`` on the stream ``infer_stream`` ran on (or one ordered behind it)."""
+
+    def __init__(self, model, enc, ws, Ty, frames, bounds, window_frames, exact_lengths, as_pcm16, pcm_gain, aux):
+        self._model, self._enc, self._ws = model, enc, ws
+        self.y_lengths, self.Ty, self.aux = enc["y_lengths"], int(Ty), aux
+        self.halo = H.generator_halo(model.hp)
+        self._U = model.hp.total_upsample
+        self.total_samples = int(frames) * self._U
+        self._frames, self._bounds, self._next = int(frames), list(bounds), 0
+        self._window, self._exact, self._pcm, self._gain = int(window_frames), int(bool(exact_lengths)), bool(as_pcm16), float(pcm_gain)
+
+    def __iter__(self):
+        return self
+
+    def __len__(self):
+        return len(self._bounds)
+
+    def __next__(self):
+        if self._next >= len(self._bounds):
+            raise StopIteration
+        t0, t1 = self._bounds[self._next]
+        m, B, n = self._model, self.y_lengths.shape[0], (t1 - t0) * self._U
+        out = torch.empty(B, n, dtype=torch.int16 if self._pcm else torch.float32, device=self._ws.device)
+        a = L.StreamChunkArgs()
+        a.struct_bytes = C.sizeof(L.StreamChunkArgs)
+        a.B, a.Ty, a.t0, a.t1 = B, self.Ty, t0, t1
+        a.y_lengths, a.exact_lengths = self.y_lengths.data_ptr(), self._exact
+        if self._pcm:
+            a.dst16, a.dst16_bstride, a.pcm_gain = out.data_ptr(), n, self._gain
+        else:
+            a.dst, a.dst_bstride = out.data_ptr(), n
+        a.window_frames, a.max_len = self._window, self._frames
+        with torch.cuda.device(self._ws.device):
+            m._check(m._lib.bv2_stream_chunk(m._handle, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(a),
+                                             C.c_void_p(self._ws.data_ptr()), self._ws.numel()), "bv2_stream_chunk")
+        self._next += 1
+        return t0 * self._U, out
+
+
 class SynthesizerTrn(nn.Module):
     """Synthesizer (inference path) — see module docstring."""
 
@@ -750,6 +797,82 @@ class SynthesizerTrn(nn.Module):
                           exact_lengths=exact_lengths, ty_bucket=ty_bucket)
         self.last_encode = enc
         return dec["o"], dec["attn"], dec["y_mask"], (dec["z"], dec["z_p"], dec["m_p"], dec["logs_p"])
+
+    @torch.no_grad()
+    def infer_stream(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_scale=0.667, length_scale=1,
+                     noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None, *, g=None, y_lengths=None, noise_w=None, noise_z=None,
+                     w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, chunk_frames=64, first_chunk_frames=None,
+                     as_pcm16=False, pcm_gain=32767.0) -> SynthesisStream:
+        """``infer`` with the audio handed out chunk by chunk (``SynthesisStream``): phase A, the host sync and the flow run here
+        (``bv2_stream_begin``), the Generator runs window by window as the caller iterates — ``chunk_frames`` kept frames per chunk
+        (``first_chunk_frames`` for the first one: a short first chunk is on the host sooner), each window carrying ``generator_halo``
+        frames on both sides so that its kept samples are the whole decode's.  The arguments of ``infer`` mean what they mean there.
+        ``as_pcm16``: chunks are int16, ``trunc(clamp(x * pcm_gain, -32768, 32767))`` — a fixed gain, not the per-utterance peak of
+        ``serving.to_pcm16`` (a stream cannot know the peak).  The workspace is planned for a window, not for T_y
+        (``bv2_stream_workspace_bytes``).  Graph replay and taps do not combine with a stream: it raises if either is on."""
+        if self.device.type != "cuda":
+            raise RuntimeError("bert_vits2_amd.SynthesizerTrn.infer_stream needs a GPU: no CPU fallback exists by design")
+        if self._graphs_on:
+            raise RuntimeError("infer_stream: graph replay is on (enable_graphs(False) first): a chunk's window pointer changes per call")
+        if self._taps:
+            raise RuntimeError("infer_stream: taps are set (set_tap(None) first)")
+        chunk_frames = int(chunk_frames)
+        first = chunk_frames if first_chunk_frames is None else int(first_chunk_frames)
+        if chunk_frames < 1 or first < 1:
+            raise ValueError("chunk_frames and first_chunk_frames must be >= 1")
+        dev, hp = self.device, self.hp
+        B, T = x.shape
+        if g is None and hp.n_speakers == 0:
+            if y is None:
+                raise ValueError("this model has no speaker table (n_speakers=0): infer_stream() needs y (the reference spectrogram) or g")
+            g = self.reference_embedding(y, y_lengths)
+        if noise_w is None:
+            noise_w = draw_noise_w(B, T, dev)
+        enc = self.encode_durations(x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w,
+                                    noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, length_scale=length_scale,
+                                    bert_index=bert_index, g=g)
+        if w_ceil is not None:
+            wc = w_ceil.to(dev, torch.float32).reshape(B, T).contiguous()
+            enc["w_ceil"] = wc
+            enc["y_lengths"] = torch.clamp_min(wc.sum(1), 1).long()
+        yl_host = [int(v) for v in enc["y_lengths"].cpu()]           # the reference's one host sync; every length, for the consumer
+        Ty = max(yl_host)
+        Ci = hp.inter_channels
+        noise_z = draw_noise_z(B, Ci, Ty, dev) if noise_z is None else noise_z.to(dev, torch.float32)
+        assert noise_z.shape[2] >= Ty and noise_z.shape[1] == Ci
+        noise_scale, ns_item = item_control("noise_scale", noise_scale, B, None)
+        ctl = None
+        if ns_item is not None:
+            ctl = _control_buffer([ns_item])
+            ctl[3].copy_(ns_item)
+            ctl = ctl.to(dev)
+            noise_scale = 0.0
+        frames = Ty if (max_len is None or max_len <= 0 or max_len >= Ty) else int(max_len)
+        window = max(chunk_frames, first)
+        e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+        aux = dict(attn=e(B, 1, Ty, T) if want_attn else None, y_mask=e(B, 1, Ty), z=e(B, Ci, Ty), z_p=e(B, Ci, Ty), m_p=e(B, Ci, Ty),
+                   logs_p=e(B, Ci, Ty))
+        nbytes = self._lib.bv2_stream_workspace_bytes(self._handle, B, T, Ty, window)
+        if nbytes < 0:
+            raise RuntimeError("bv2_stream_workspace_bytes failed")
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)        # the stream's own: it must stay untouched until the last chunk
+        din = L.DecodeIn(B, T, int(Ty), int(frames), _ptr(enc["m_p"]), _ptr(enc["logs_p"]), _ptr(enc["x_mask"]), _ptr(enc["w_ceil"]),
+                         _ptr(enc["y_lengths"]), _ptr(enc["g"]), _ptr(noise_z), noise_z.stride(0), noise_z.stride(1), noise_z.stride(2),
+                         float(noise_scale), int(bool(exact_lengths)))
+        dout = L.DecodeOut(None, *[_ptr(aux[k]) for k in ("attn", "y_mask", "z", "z_p", "m_p", "logs_p")])
+        with torch.cuda.device(dev):
+            self._check(self._lib.bv2_stream_begin(self._handle, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(din),
+                                                   C.byref(dout), _controls_ptr(ctl, (3,)), C.c_void_p(ws.data_ptr()), ws.numel()),
+                        "bv2_stream_begin")
+        bounds, t = [], 0
+        while t < frames:
+            t1 = min(frames, t + (first if t == 0 else chunk_frames))
+            bounds.append((t, t1))
+            t = t1
+        self.last_encode = enc
+        st = SynthesisStream(self, enc, ws, Ty, frames, bounds, window, exact_lengths, as_pcm16, pcm_gain, aux)
+        st.y_lengths_host = yl_host
+        return st
 
     # ------------------------------------------------------------------ single stages (reference ONNX seams)
     # onnx_modules/V230/models_onnx.py:896-1063 cuts infer() into emb_g / enc_p / sdp / dp / flow / dec; the six methods below

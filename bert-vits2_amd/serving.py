@@ -246,6 +246,26 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
 
 def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio, noise_scale, noise_scale_w, length_scale):
     """One bucket on the CURRENT stream: collate, infer (exact lengths), optional PCM16, async D2H into pinned memory."""
+    batch, kw = _bucket_inputs(model, utts, idx, dev, noise, gvec)
+    o, _attn, y_mask, _ = model.infer(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"],
+                                      batch["bert"], batch["ja_bert"], batch["en_bert"], sdp_ratio=sdp_ratio,
+                                      noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale,
+                                      want_attn=False, exact_lengths=True, **kw)
+    y_len = model.last_encode["y_lengths"]             # int64 [B], already on the device (phase A output)
+    audio = pcm16(model, o, y_len) if as_pcm16 else o[:, 0]
+    # one async D2H per bucket into pinned memory (audio AND lengths): nothing here blocks the host, so the next bucket's
+    # kernels are enqueued while this copy runs; the drain loop below waits on the bucket's event
+    host = torch.empty(audio.shape, dtype=audio.dtype, pin_memory=True)
+    host.copy_(audio, non_blocking=True)
+    host_len = torch.empty(y_len.shape, dtype=torch.int64, pin_memory=True)
+    host_len.copy_(y_len, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    pending.append((idx, host, host_len, ev))
+
+
+def _bucket_inputs(model, utts, idx, dev, noise, gvec):
+    """The collated batch of one bucket and the keyword extras of its ``infer`` call (speaker vectors, injected noise)."""
     group = [utts[i] for i in idx]
     batch = collate(group, dev)
     kw = {}
@@ -263,18 +283,59 @@ def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio
             nw[r, :, :noise[i][0].shape[1]] = noise[i][0]
             nz[r, :, :noise[i][1].shape[1]] = noise[i][1]
         kw.update(noise_w=nw.to(dev), noise_z=nz.to(dev))
-    o, _attn, y_mask, _ = model.infer(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"],
-                                      batch["bert"], batch["ja_bert"], batch["en_bert"], sdp_ratio=sdp_ratio,
-                                      noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale,
-                                      want_attn=False, exact_lengths=True, **kw)
-    y_len = model.last_encode["y_lengths"]             # int64 [B], already on the device (phase A output)
-    audio = pcm16(model, o, y_len) if as_pcm16 else o[:, 0]
-    # one async D2H per bucket into pinned memory (audio AND lengths): nothing here blocks the host, so the next bucket's
-    # kernels are enqueued while this copy runs; the drain loop below waits on the bucket's event
-    host = torch.empty(audio.shape, dtype=audio.dtype, pin_memory=True)
-    host.copy_(audio, non_blocking=True)
-    host_len = torch.empty(y_len.shape, dtype=torch.int64, pin_memory=True)
-    host_len.copy_(y_len, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record()
-    pending.append((idx, host, host_len, ev))
+    return batch, kw
+
+
+def synthesize_stream(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0.6, noise_scale_w=0.9, length_scale=1.0,
+                      max_batch: int = 32, max_pad_ratio: float = 1.25, chunk_frames: int = 64,
+                      first_chunk_frames: Optional[int] = None, as_pcm16: bool = False, noise: Optional[Sequence] = None):
+    """``synthesize`` with the audio handed out as it is produced: a generator of ``(utterance_index, start_sample, np.ndarray)``.  Same
+    buckets, per-utterance controls, voices and ``exact_lengths=True`` as ``synthesize``; each bucket runs ``infer_stream`` and its
+    Generator chunk by chunk (``chunk_frames`` kept frames, ``first_chunk_frames`` for the first).  A bucket has two pinned host buffers:
+    chunk n + 1 is enqueued before the host waits on chunk n's copy event, so the device-to-host copy of a chunk runs under the next
+    chunk's Generator.  An utterance's pieces arrive in order with contiguous offsets, and nothing is yielded past its own length.
+    ``as_pcm16``: int16 pieces, ``trunc(x * 32767)`` — a FIXED gain, unlike ``synthesize``'s per-utterance peak normalisation (a stream
+    cannot know the peak; the two differ by exactly the factor 1 / max|x| of the utterance)."""
+    if model.device.type != "cuda":
+        raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
+    dev = model.device
+    hop = model.hp.total_upsample
+    call = dict(sdp_ratio=sdp_ratio, noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale)
+    per_item = any(getattr(u, k) is not None for u in utts for k in call)
+    gvec = speaker_vectors(model, utts)
+    weights = None
+    if per_item and any(u.length_scale is not None for u in utts):
+        weights = [float(length_scale if u.length_scale is None else u.length_scale) for u in utts]
+    for idx in plan_batches([u.length for u in utts], max_batch, max_pad_ratio, weights):
+        if per_item:
+            ctl = {k: torch.tensor([float(v if getattr(utts[i], k) is None else getattr(utts[i], k)) for i in idx],
+                                   dtype=torch.float32) for k, v in call.items()}
+        else:
+            ctl = call
+        batch, kw = _bucket_inputs(model, utts, idx, dev, noise, gvec)
+        st = model.infer_stream(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"], batch["bert"],
+                                batch["ja_bert"], batch["en_bert"], want_attn=False, exact_lengths=True, chunk_frames=chunk_frames,
+                                first_chunk_frames=first_chunk_frames, as_pcm16=as_pcm16, **ctl, **kw)
+        ends = [n * hop for n in st.y_lengths_host]
+        width = max(int(chunk_frames), int(first_chunk_frames or chunk_frames)) * hop
+        hosts = [torch.empty(len(idx), width, dtype=torch.int16 if as_pcm16 else torch.float32, pin_memory=True) for _ in range(2)]
+
+        def pieces(start, n, host, ev):
+            ev.synchronize()
+            for r, i in enumerate(idx):
+                keep = min(n, ends[r] - start)
+                if keep > 0:
+                    yield i, start, host[r, :keep].numpy().copy()
+
+        waiting = None
+        for k, (start, audio) in enumerate(st):
+            host = hosts[k & 1]                                 # chunk k - 2 used it and was drained before chunk k - 1 was enqueued
+            n = audio.shape[1]
+            host[:, :n].copy_(audio, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            if waiting is not None:
+                yield from pieces(*waiting)
+            waiting = (start, n, host, ev)
+        if waiting is not None:
+            yield from pieces(*waiting)

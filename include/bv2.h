@@ -293,9 +293,67 @@ int bv2_infer_g(bv2_handle* h, bv2_stream stream, const bv2_encode_in* in, const
  * .cpu(): webui.py:86,129, hiyoriUI.py:343) -------------------------------------------------------------------- */
 /* pcm[b][i] = (int16) trunc( wave[b][i] / max_j |wave[b][j]| * 32767 ) over the valid samples i, j < y_lengths[b]*hop
  * (capped at S); samples past the utterance are 0; an all-zero utterance stays 0.  wave [B][wave_bstride >= S] fp32,
- * pcm [B][pcm_bstride >= S] int16, peak_scratch [B] uint32 — all DEVICE.  Asynchronous on `stream`, graph-capturable. */
+ * pcm [B][pcm_bstride >= S] int16, peak_scratch [B] uint32 — all DEVICE.  Asynchronous on `stream`, graph-capturable.
+ * (Streamed PCM — bv2_stream_chunk / bv2_emit below — has no peak to divide by: it is trunc(clamp(x * gain)) with a fixed gain and differs
+ * from this conversion by exactly the factor 1 / max_j |wave[b][j]|.) */
 int bv2_pcm16(bv2_stream stream, const float* wave, int64_t wave_bstride, const int64_t* y_lengths, int32_t hop, int32_t B,
               int64_t S, int16_t* pcm, int64_t pcm_bstride, uint32_t* peak_scratch);
+
+/* ---- streamed synthesis: the flow once, the Generator window by window, audio chunk by chunk ---------------------------
+ * bv2_decode returns an utterance after the whole Generator has run over all Ty frames, and its workspace holds fourteen
+ * [B, C_i * samples-per-frame * Ty] Generator buffers.  The flow needs all of Ty (its attention spans it); the Generator (models.py:538-557)
+ * is a stack of convolutions with a finite receptive field, so a window of frames decodes to the same samples as the whole — given a halo.
+ *
+ * The halo H = bv2_generator_halo(h): latent frames a window carries on each side.  It is the input interval of output samples [a*U, b*U)
+ * (U = product of the upsample rates) walked backwards: conv_post (k = 7) +-3 samples; per stage, last to first, the widest ResBlock branch
+ * (ResBlock1: sum_d (k-1)/2 * (d+1); ResBlock2: sum_d (k-1)/2 * d) and ConvTranspose1d(k, stride u, p = (k-u)/2): lo -> ceil((lo + p - k + 1) / u),
+ * hi -> floor((hi + p) / u); conv_pre (k = 7) +-3 frames.  13 for the v2.3 shapes.  The Generator work of a stream grows by (N + 2H) / N for chunks
+ * of N frames.
+ *
+ * bv2_stream_begin is bv2_decode_ex up to and including the flow (expand, the speaker GEMVs, the flow): z, y_mask and the GEMV results stay in
+ * the workspace; out->o is not written (may be NULL), the other outputs are written as bv2_decode writes them; in->max_len and
+ * in->exact_lengths are not read (the chunks carry them).  The caller leaves the workspace untouched until the last chunk.
+ * bv2_stream_chunk runs the Generator of the handle's dtype on frames [max(0, t0 - H), min(L, t1 + H)) of that z (L = Ty, or max_len) and
+ * writes samples [t0*U, t1*U) of every item to dst + b * dst_bstride (fp32) or dst16 + b * dst16_bstride (16-bit PCM): sample 0 of the
+ * destination is sample t0*U of the utterance — the caller offsets the pointer.  Samples at or past y_lengths[b]*U are written as zeros in
+ * both exact_lengths modes (bv2_decode's mode 0 leaves the padded batch's bleed there).  Chunks may come in any order and any size up to
+ * window_frames, on the stream bv2_stream_begin ran on (or one ordered behind it).
+ * Numerics: a window is another tiling of the same convolutions, and with "conv_x3" = 1 the layer-wise two-plane fp16 convs take their
+ * activation scale from the max |x| of the window's tensor instead of the utterance's — the agreement with bv2_decode is that of two batch
+ * shapes of the same audio (fp32 round-off in fp32 mode, bf16 round-off with the bf16 Generator), not bit identity.
+ * Streamed PCM is (int16) trunc(clamp(x * pcm_gain, -32768, 32767)) with a FIXED gain (32767 unless the caller wants headroom): a stream cannot
+ * know the utterance's peak, and tanh bounds |x| <= 1.  It differs from bv2_pcm16's peak-normalised conversion by exactly the factor
+ * 1 / max|x| of the utterance.
+ * Every argument is checked before anything touches the device (-1 and a message in bv2_last_error; -5 for a short workspace).
+ * Out of scope: capturing chunks in a hipGraph (the window pointer changes per call), taps during a stream (both calls fail while a tap is set)
+ * and exact_lengths == 2. */
+int bv2_generator_halo(const bv2_handle* h);
+/* window_frames: the largest number of kept frames (t1 - t0) of a chunk.  The kept buffers (speaker GEMV results, y_mask, z, z_p, frame
+ * indices, x3 slots, length caps, a [B] window-length array) come first; behind them ONE region is shared by the flow's scratch at Ty and the
+ * Generator's buffers at min(Ty, window_frames + 2H) frames plus the window's [B, frames * U] output.  Covers phase A at (B, T) as well. */
+int64_t bv2_stream_workspace_bytes(const bv2_handle* h, int B, int T, int Ty, int window_frames);
+int bv2_stream_begin(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, const bv2_decode_out* out,
+                     const bv2_item_controls* controls, void* workspace, int64_t workspace_bytes);
+typedef struct bv2_stream_chunk_args {
+  int32_t struct_bytes;            /* = sizeof(bv2_stream_chunk_args) */
+  int32_t B, Ty;                   /* as given to bv2_stream_begin */
+  int32_t t0, t1;                  /* kept frames: 0 <= t0 < t1 <= L, t1 - t0 <= window_frames */
+  const int64_t* y_lengths;        /* [B] DEVICE */
+  int32_t exact_lengths;           /* 0 / 1 as in bv2_decode_in: 1 = item b's window is clamp(y_lengths[b] - w0, 1, W) frames long
+                                      (w0 = max(0, t0 - H); an item that ended before w0 runs as one masked frame and comes out as zeros) */
+  float* dst; int64_t dst_bstride;           /* EITHER fp32 [B][dst_bstride >= (t1 - t0) * U] ... */
+  int16_t* dst16; int64_t dst16_bstride;     /* ... OR 16-bit PCM; exactly one of dst / dst16 is non-NULL */
+  float pcm_gain;                  /* dst16 only; <= 0 means 32767 */
+  int32_t window_frames;           /* as given to bv2_stream_workspace_bytes */
+  int32_t max_len;                 /* frames fed to the Generator, L = min(Ty, max_len) (models.py:1073); <= 0 means all */
+} bv2_stream_chunk_args;
+int bv2_stream_chunk(bv2_handle* h, bv2_stream stream, const bv2_stream_chunk_args* args, void* workspace, int64_t workspace_bytes);
+/* The copy at the end of a chunk on its own (handle-free, like bv2_pcm16; kernels/stream.hip): n samples per item from
+ * src + b * src_bstride + src_off to dst + b * dst_bstride (fp32, a copy) or dst16 + b * dst_bstride (PCM as above, gain <= 0 means 32767) —
+ * exactly one of the two non-NULL; samples i >= y_lengths[b] * hop - start_sample become zero and their source is not used (y_lengths NULL:
+ * none).  One pass, 16 bytes per thread on the aligned body of the destination, any alignment of source offset, destination and n. */
+int bv2_emit(bv2_stream stream, const float* src, int64_t src_bstride, int64_t src_off, const int64_t* y_lengths, int32_t hop,
+             int64_t start_sample, int32_t B, int64_t n, float* dst, int16_t* dst16, int64_t dst_bstride, float gain);
 
 /* ---- from a waveform to the spectrogram bv2_ref_encode reads (handle-free, like bv2_pcm16) -----------------------------
  * The reference turns a recording into y with mel_processing.spectrogram_torch (mel_processing.py:43-78, called from data_utils.py:99-138
