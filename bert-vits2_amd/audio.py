@@ -4,10 +4,12 @@ The reference turns a wav file into ``y`` with ``mel_processing.spectrogram_torc
 Hann window, ``torch.stft(center=False)``, ``sqrt(re^2 + im^2 + 1e-6)``; mel_processing.py:43-78, called from data_utils.py:99-138 after
 ``audio / max_wav_value``), or with ``mel_spectrogram_torch`` (:95-142) for a model whose ``spec_channels`` is a mel width.  ``spectrogram``
 below is that step: samples at the model's sampling rate go in (fp32 in [-1, 1], or 16-bit PCM read as ``x / 32768``), ``[B, C, L]`` comes
-out.  Not done here: resampling (the reference resamples offline, resample.py) and decoding of audio files.
+out.  A recording at another rate goes through ``resample`` first (the reference resamples offline with librosa, resample.py): a polyphase
+Kaiser-windowed sinc on the device (``bv2_resample``, kernels/resample.hip), the same call that brings synthesised audio to the rate a
+consumer wants.  Not done here: decoding of audio files.
 
-Nothing in here computes: the filterbank comes from ``bv2_mel_basis`` (fp64 on the host, rounded to fp32 as the reference rounds
-librosa's), everything else runs in the two launches of ``bv2_spectrogram`` on the current stream.
+Nothing in here computes: the filterbank comes from ``bv2_mel_basis`` and the resampler's table from ``bv2_resample_taps`` (fp64 on the
+host, rounded to fp32), everything else runs in the two launches of ``bv2_spectrogram`` / the one of ``bv2_resample`` on the current stream.
 """
 from __future__ import annotations
 
@@ -186,3 +188,143 @@ def spectrogram(wav: torch.Tensor, wav_lengths=None, params: Optional[StftParams
     if rc != 0:
         raise RuntimeError(f"bv2_spectrogram failed ({rc}): {lib.bv2_last_error(None).decode()}")
     return spec, lengths
+
+
+# ---- resampling (include/bv2.h bv2_resample) ---------------------------------------------------------------------------------------------
+def resample_config(rate_in: int, rate_out: int, input_format: int = L.WAV_F32) -> L.ResampleConfig:
+    c = L.ResampleConfig()
+    c.struct_bytes = C.sizeof(L.ResampleConfig)
+    c.rate_in, c.rate_out, c.input_format = int(rate_in), int(rate_out), int(input_format)
+    return c
+
+
+def resample_plan(rate_in: int, rate_out: int) -> Tuple[int, int, int]:
+    """``(L, M, K)`` of a rate pair (``bv2_resample_plan``): ``rate_out / gcd``, ``rate_in / gcd`` and the zero crossings' reach in input
+    samples (``2K + 1`` taps per phase).  ``ValueError`` outside the envelope (equal rates, a rate <= 0, ``L > 1024``, a table of more than
+    2^20 entries), with the library's message."""
+    lib = L.load()
+    v = [C.c_int32() for _ in range(3)]
+    if lib.bv2_resample_plan(C.byref(resample_config(rate_in, rate_out)), *[C.byref(x) for x in v]) != 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return tuple(int(x.value) for x in v)
+
+
+def resample_length(rate_in: int, rate_out: int, n_in: int) -> int:
+    """``ceil(n_in L / M)``: the samples ``n_in`` samples become."""
+    Lr, M, _ = resample_plan(rate_in, rate_out)
+    return -((-int(n_in) * Lr) // M)
+
+
+def resample_taps(rate_in: int, rate_out: int, dtype=np.float32) -> np.ndarray:
+    """The filter table ``[L, 2K + 1]`` from ``bv2_resample_taps`` — fp32 (what the device reads) or fp64 (what it was rounded from)."""
+    Lr, _, K = resample_plan(rate_in, rate_out)
+    lib = L.load()
+    f64 = np.dtype(dtype) == np.float64
+    out = np.empty((Lr, 2 * K + 1), np.float64 if f64 else np.float32)
+    rc = (lib.bv2_resample_taps_f64 if f64 else lib.bv2_resample_taps)(C.byref(resample_config(rate_in, rate_out)), C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise RuntimeError(f"bv2_resample_taps failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return out
+
+
+_TAPS: Dict[tuple, torch.Tensor] = {}
+
+
+def device_taps(rate_in: int, rate_out: int, dev) -> torch.Tensor:
+    """The fp32 table on ``dev``, built once per ``(rate_in, rate_out, device)`` (about 1 ms of host time)."""
+    key = (int(rate_in), int(rate_out), str(torch.device(dev)))
+    if key not in _TAPS:
+        _TAPS[key] = torch.from_numpy(resample_taps(rate_in, rate_out)).to(dev)
+    return _TAPS[key]
+
+
+def resample_range(src: torch.Tensor, src_start: int, src_lengths: Optional[torch.Tensor], rate_in: int, rate_out: int, n0: int, n1: int,
+                   dst: Optional[torch.Tensor] = None, dst_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The range form of ``bv2_resample`` on the current stream: ``src`` [B, n] (device, fp32 or int16, unit sample stride) holds samples
+    ``[src_start, src_start + n)`` of every item, ``src_lengths`` [B] (device int64, absolute; ``None``: ``src_start + n``); outputs
+    ``[n0, n1)`` go to ``dst`` [B, >= n1 - n0] (a new tensor if ``None``), ``dst_lengths`` [B] receives ``ceil(len_b L / M)``.  The caller
+    keeps the two edge rules of include/bv2.h."""
+    if not src.is_cuda or src.dim() != 2 or src.stride(1) != 1 or src.dtype not in (torch.float32, torch.int16):
+        raise ValueError("src must be a device tensor [B, n], float32 or int16, with unit sample stride")
+    B, n = src.shape
+    cfg = resample_config(rate_in, rate_out, L.WAV_I16 if src.dtype == torch.int16 else L.WAV_F32)
+    taps = device_taps(rate_in, rate_out, src.device)
+    if dst is None:
+        dst = torch.empty(B, max(int(n1) - int(n0), 0), dtype=torch.float32, device=src.device)
+    lib = L.load()
+    with torch.cuda.device(src.device):
+        rc = lib.bv2_resample(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), C.c_void_p(taps.data_ptr()),
+                              C.c_void_p(src.data_ptr()), src.stride(0) if B > 1 else n, int(src_start), n,
+                              C.c_void_p(src_lengths.data_ptr()) if src_lengths is not None else None, B, int(n0), int(n1),
+                              C.c_void_p(dst.data_ptr()), dst.stride(0) if B > 1 else dst.shape[1],
+                              C.c_void_p(dst_lengths.data_ptr()) if dst_lengths is not None else None)
+    if rc != 0:
+        raise RuntimeError(f"bv2_resample failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return dst
+
+
+@torch.no_grad()
+def resample(wav: torch.Tensor, wav_lengths=None, rate_in: Optional[int] = None, rate_out: Optional[int] = None, device=None
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``wav`` [B, S] or [S] at ``rate_in`` (fp32, or int16 PCM read as ``x / 32768``; host or device, any batch stride) -> ``(out [B,
+    N_max] fp32, out_lengths [B] int64)`` at ``rate_out``, both on the device; ``N_max = ceil(S L / M)``.  ``wav_lengths`` [B] (samples,
+    host or device; ``None``: all S) makes a padded batch exact: item b is its own samples and zero elsewhere — the batch's padding is never
+    read — it gets ``out_lengths[b] = ceil(wav_lengths[b] L / M)`` samples and zeros behind them.  Lengths given on the host are checked
+    there; lengths on the device are not read back.  Equal rates: the input comes back as fp32 on the device, without a launch."""
+    if rate_in is None or rate_out is None:
+        raise ValueError("resample needs rate_in and rate_out")
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    if not isinstance(wav, torch.Tensor):
+        wav = torch.as_tensor(wav)
+    if wav.dim() == 1:
+        wav = wav[None]
+    if wav.dim() != 2 or wav.shape[1] < 1 or wav.shape[0] < 1:
+        raise ValueError(f"wav must be [B, S] or [S], got {tuple(wav.shape)}")
+    if wav.dtype not in (torch.int16, torch.float32):
+        raise ValueError(f"wav must be float32 in [-1, 1] or int16 PCM, got {wav.dtype}")
+    B, S = wav.shape
+    if rate_in != rate_out:
+        resample_plan(rate_in, rate_out)                            # ValueError naming the limit, before anything moves
+    elif rate_in < 1:
+        raise ValueError(f"rates must be positive, got {rate_in}")
+    if wav_lengths is not None and (not isinstance(wav_lengths, torch.Tensor) or not wav_lengths.is_cuda):
+        host = [int(v) for v in torch.as_tensor(wav_lengths).reshape(-1).tolist()]
+        if len(host) != B:
+            raise ValueError("wav_lengths must be [B]")
+        for b, n in enumerate(host):
+            if not 1 <= n <= S:
+                raise ValueError(f"wav_lengths[{b}] = {n} is outside [1, {S}], the samples of the batch")
+    if device is None:
+        device = wav.device if wav.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device(device)
+    wav = wav.detach().to(dev)
+    if wav.stride(1) != 1:
+        wav = wav.contiguous()
+    wl = None
+    if wav_lengths is not None:
+        wl = torch.as_tensor(wav_lengths).to(dev, torch.int64).reshape(-1).contiguous()
+        if wl.shape != (B,):
+            raise ValueError("wav_lengths must be [B]")
+    if rate_in == rate_out:
+        out = wav.to(torch.float32) / 32768.0 if wav.dtype == torch.int16 else wav
+        return out, (wl if wl is not None else torch.full((B,), S, dtype=torch.int64, device=dev))
+    N = resample_length(rate_in, rate_out, S)
+    lengths = torch.empty(B, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        out = resample_range(wav, 0, wl, rate_in, rate_out, 0, N, None, lengths)
+    return out, lengths
+
+
+def to_rate(wav, wav_lengths, sampling_rate: Optional[int], model_rate: int, params: StftParams, device):
+    """A recording at ``sampling_rate`` as ``(wav, wav_lengths)`` at ``model_rate`` for ``spectrogram``: untouched when the rates agree
+    (or ``sampling_rate`` is ``None``), else ``resample``d on the device.  The resampled lengths stay on the device; where the caller's
+    lengths were on the host (or absent) the checks ``spectrogram`` would make there are made here, on the resampled lengths."""
+    if sampling_rate is None or int(sampling_rate) == int(model_rate):
+        return wav, wav_lengths
+    on_host = wav_lengths is None or not isinstance(wav_lengths, torch.Tensor) or not wav_lengths.is_cuda
+    out, lengths = resample(wav, wav_lengths, int(sampling_rate), int(model_rate), device=device)
+    if on_host:
+        given = [torch.as_tensor(wav).shape[-1]] if wav_lengths is None else torch.as_tensor(wav_lengths).reshape(-1).tolist()
+        for n in given:
+            params.frames(resample_length(sampling_rate, model_rate, int(n)))      # ValueError naming the minimum, pad + 1
+    return out, (lengths if wav_lengths is not None else None)

@@ -603,6 +603,143 @@ int bv2_spectrogram(bv2_stream stream, const bv2_stft_config* cfg, const void* w
   } catch (...) { return fail("exception", -100); }
 }
 
+// ---- polyphase resampler (kernels/resample.hip) -------------------------------------------------------------------
+struct ResamplePlan { int L, M, K; };
+static const int RS_ZEROS = 32, RS_MAX_L = 1024;
+static const int64_t RS_MAX_TABLE = (int64_t)1 << 20, RS_MAX_INDEX = (int64_t)1 << 40;
+static const double RS_BETA = 10.0, RS_ROLLOFF = 0.91;
+
+static int resample_plan(const bv2_resample_config* c, const char* what, ResamplePlan* out) {
+  auto fail = [&](const std::string& m) { g_create_err = std::string(what) + ": " + m; return -1; };
+  if (!c) return fail("cfg is null");
+  if (c->struct_bytes != (int32_t)sizeof(bv2_resample_config)) return fail("bv2_resample_config.struct_bytes mismatch (ABI drift)");
+  if (c->rate_in <= 0 || c->rate_out <= 0)
+    return fail("rates must be positive, got " + std::to_string(c->rate_in) + " -> " + std::to_string(c->rate_out));
+  if (c->rate_in == c->rate_out) return fail("rate_in equals rate_out (" + std::to_string(c->rate_in) + "): nothing to resample");
+  if (c->input_format != BV2_WAV_F32 && c->input_format != BV2_WAV_I16) return fail("input_format must be BV2_WAV_F32 or BV2_WAV_I16");
+  int64_t a = c->rate_in, b = c->rate_out;
+  while (b) { const int64_t t = a % b; a = b; b = t; }
+  const int64_t L = c->rate_out / a, M = c->rate_in / a;
+  if (L > RS_MAX_L)
+    return fail("L = rate_out / gcd = " + std::to_string(L) + " exceeds the limit of " + std::to_string(RS_MAX_L) + " phases (" +
+                std::to_string(c->rate_in) + " -> " + std::to_string(c->rate_out) + ")");
+  const double cut = RS_ROLLOFF * std::min(1.0, (double)L / (double)M);
+  const double W = RS_ZEROS / cut;
+  const double Kd = std::ceil(W);
+  if (Kd * 2 + 1 > (double)RS_MAX_TABLE || L * ((int64_t)Kd * 2 + 1) > RS_MAX_TABLE)
+    return fail("L * taps = " + std::to_string(L) + " * " + std::to_string((int64_t)Kd * 2 + 1) + " exceeds the limit of 2^20 = " +
+                std::to_string(RS_MAX_TABLE) + " table entries (" + std::to_string(c->rate_in) + " -> " + std::to_string(c->rate_out) + ")");
+  out->L = (int)L; out->M = (int)M; out->K = (int)Kd;
+  return 0;
+}
+
+static double bessel_i0(double x) {                  // sum_k ((x / 2)^k / k!)^2: positive terms, converged to the last bit for x <= beta
+  const double q = x * x / 4;
+  double term = 1, sum = 1;
+  for (int k = 1; k < 500; ++k) {
+    term *= q / ((double)k * k);
+    sum += term;
+    if (term < sum * 1e-18) break;
+  }
+  return sum;
+}
+
+int bv2_resample_plan(const bv2_resample_config* cfg, int32_t* L, int32_t* M, int32_t* K) {
+  ResamplePlan p;
+  if (int rc = resample_plan(cfg, "bv2_resample_plan", &p)) return rc;
+  if (L) *L = p.L;
+  if (M) *M = p.M;
+  if (K) *K = p.K;
+  return 0;
+}
+
+int64_t bv2_resample_length(const bv2_resample_config* cfg, int64_t n_in) {
+  ResamplePlan p;
+  if (resample_plan(cfg, "bv2_resample_length", &p)) return -1;
+  if (n_in < 0 || n_in >= RS_MAX_INDEX) { g_create_err = "bv2_resample_length: n_in must be in [0, 2^40)"; return -1; }
+  return (n_in * p.L + p.M - 1) / p.M;
+}
+
+int64_t bv2_resample_ready(const bv2_resample_config* cfg, int64_t available_in) {
+  ResamplePlan p;
+  if (resample_plan(cfg, "bv2_resample_ready", &p)) return -1;
+  if (available_in < 0 || available_in >= RS_MAX_INDEX) { g_create_err = "bv2_resample_ready: available_in must be in [0, 2^40)"; return -1; }
+  const int64_t a = available_in - p.K;
+  return a <= 0 ? 0 : (a * p.L + p.M - 1) / p.M;
+}
+
+int bv2_resample_taps_f64(const bv2_resample_config* cfg, double* out) {
+  ResamplePlan p;
+  if (int rc = resample_plan(cfg, "bv2_resample_taps", &p)) return rc;
+  if (!out) { g_create_err = "bv2_resample_taps: out is null"; return -1; }
+  const double pi = 3.14159265358979323846;
+  const double cut = RS_ROLLOFF * std::min(1.0, (double)p.L / (double)p.M), W = RS_ZEROS / cut, i0b = bessel_i0(RS_BETA);
+  const int taps = 2 * p.K + 1;
+  for (int ph = 0; ph < p.L; ++ph) {
+    double* row = out + (size_t)ph * taps;
+    double sum = 0;
+    for (int jj = 0; jj < taps; ++jj) {
+      const double t = (double)ph / (double)p.L - (double)(jj - p.K);
+      double v = 0;
+      if (std::fabs(t) < W) {
+        const double x = cut * t, r = t / W;
+        const double sinc = x == 0 ? 1.0 : std::sin(pi * x) / (pi * x);
+        v = cut * sinc * bessel_i0(RS_BETA * std::sqrt(1 - r * r)) / i0b;
+      }
+      row[jj] = v;
+      sum += v;
+    }
+    for (int jj = 0; jj < taps; ++jj) row[jj] /= sum;          // DC gain exactly 1 in every phase
+  }
+  return 0;
+}
+
+int bv2_resample_taps(const bv2_resample_config* cfg, float* out) {
+  ResamplePlan p;
+  if (int rc = resample_plan(cfg, "bv2_resample_taps", &p)) return rc;
+  if (!out) { g_create_err = "bv2_resample_taps: out is null"; return -1; }
+  try {
+    const size_t n = (size_t)p.L * (2 * p.K + 1);
+    std::vector<double> d(n);
+    if (int rc = bv2_resample_taps_f64(cfg, d.data())) return rc;
+    for (size_t i = 0; i < n; ++i) out[i] = (float)d[i];
+    return 0;
+  } catch (...) { g_create_err = "bv2_resample_taps: out of memory"; return -100; }
+}
+
+int bv2_resample(bv2_stream stream, const bv2_resample_config* cfg, const float* taps, const void* src, int64_t src_bstride,
+                 int64_t src_start, int64_t src_n, const int64_t* src_lengths, int32_t B, int64_t n0, int64_t n1, float* dst,
+                 int64_t dst_bstride, int64_t* dst_lengths_out) {
+  const char* what = "bv2_resample";
+  ResamplePlan p;
+  if (int rc = resample_plan(cfg, what, &p)) return rc;
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (!taps) return fail("taps is null (the DEVICE copy of bv2_resample_taps)", -1);
+  if (!src) return fail("src is null", -1);
+  if (!dst) return fail("dst is null", -1);
+  if (B < 1 || B > 65535) return fail("B must be in [1, 65535]", -1);
+  if (n0 < 0) return fail("n0 must not be negative", -1);
+  if (n1 < n0) return fail("n1 = " + std::to_string(n1) + " is below n0 = " + std::to_string(n0), -1);
+  if (n1 >= RS_MAX_INDEX) return fail("n1 must be below 2^40", -1);
+  if (src_start < 0 || src_n < 0 || src_start + src_n >= RS_MAX_INDEX || src_n >= RS_MAX_INDEX)
+    return fail("src_start and src_n must not be negative and src_start + src_n must be below 2^40", -1);
+  if (src_bstride < 0) return fail("src_bstride must not be negative", -1);
+  if (dst_bstride < n1 - n0) return fail("dst_bstride is shorter than n1 - n0", -1);
+  const int64_t first = (n0 * p.M) / p.L - p.K, lower = first > 0 ? first : 0;
+  if (src_start > lower)
+    return fail("src_start = " + std::to_string(src_start) + " is above the lower edge max(0, i0(n0) - K) = " + std::to_string(lower) +
+                " that output n0 = " + std::to_string(n0) + " reads", -1);
+  if (n1 == n0) return 0;
+  try {
+    ResampleArgs a;
+    a.src = src; a.src_bstride = src_bstride; a.src_start = src_start; a.src_n = src_n; a.src_lengths = src_lengths; a.taps = taps;
+    a.B = B; a.L = p.L; a.M = p.M; a.K = p.K; a.input_format = cfg->input_format; a.n0 = n0; a.n1 = n1;
+    a.dst = dst; a.dst_bstride = dst_bstride; a.dst_lengths_out = dst_lengths_out;
+    if (launch_resample(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
 // ---- hipGraph capture -----------------------------------------------------------------------------------------
 struct bv2_graph {
   hipGraphExec_t exec = nullptr;

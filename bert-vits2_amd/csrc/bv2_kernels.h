@@ -694,4 +694,16 @@ struct StftArgs {
 int64_t stft_workspace_bytes(int n_fft, int n_mels);
 int launch_stft(hipStream_t stream, const StftArgs& a);
 
+// --- polyphase resampler (kernels/resample.hip): outputs [n0, n1) of every item from a buffer that holds its samples [src_start, src_start + src_n) ---
+struct ResampleArgs {
+  const void* src; int64_t src_bstride, src_start, src_n;   // fp32 or int16 (input_format 1), DEVICE
+  const int64_t* src_lengths;                        // [B] absolute len_b, or null = src_start + src_n
+  const float* taps;                                 // [L][2K + 1], DEVICE
+  int B, L, M, K, input_format;
+  int64_t n0, n1;
+  float* dst; int64_t dst_bstride;
+  int64_t* dst_lengths_out;                          // [B] ceil(len_b L / M), or null
+};
+int launch_resample(hipStream_t stream, const ResampleArgs& a);
+
 }  // namespace bv2

@@ -100,6 +100,11 @@ class StftConfig(C.Structure):
 WAV_F32, WAV_I16 = 0, 1
 
 
+class ResampleConfig(C.Structure):
+    """include/bv2.h bv2_resample_config"""
+    _fields_ = [("struct_bytes", C.c_int32), ("rate_in", C.c_int32), ("rate_out", C.c_int32), ("input_format", C.c_int32)]
+
+
 class ProfileRow(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -157,6 +162,13 @@ SYMBOLS = [
     ("bv2_stft_workspace_bytes", C.c_int64, [C.POINTER(StftConfig), C.c_int32, C.c_int64]),
     ("bv2_spectrogram", C.c_int, [_P, C.POINTER(StftConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, _P, C.POINTER(C.c_int64), _P, _P,
                                   C.c_int64]),
+    ("bv2_resample_plan", C.c_int, [C.POINTER(ResampleConfig), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("bv2_resample_length", C.c_int64, [C.POINTER(ResampleConfig), C.c_int64]),
+    ("bv2_resample_ready", C.c_int64, [C.POINTER(ResampleConfig), C.c_int64]),
+    ("bv2_resample_taps", C.c_int, [C.POINTER(ResampleConfig), _P]),
+    ("bv2_resample_taps_f64", C.c_int, [C.POINTER(ResampleConfig), _P]),
+    ("bv2_resample", C.c_int, [_P, C.POINTER(ResampleConfig), _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int64, C.c_int64,
+                               _P, C.c_int64, _P]),
     ("bv2_graph_capture_encode", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_decode", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_encode_ex", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P,

@@ -106,7 +106,7 @@ class SynthesisStream:
     ``logs_p`` as ``infer`` returns them) are there from the start.  The stream owns its workspace, so other ``infer`` calls of the same
     model may run between two chunks; call ``next()`` on the stream ``infer_stream`` ran on (or one ordered behind it)."""
 
-    def __init__(self, model, enc, ws, Ty, frames, bounds, window_frames, exact_lengths, as_pcm16, pcm_gain, aux):
+    def __init__(self, model, enc, ws, Ty, frames, bounds, window_frames, exact_lengths, as_pcm16, pcm_gain, aux, output_rate=None):
         self._model, self._enc, self._ws = model, enc, ws
         self.y_lengths, self.Ty, self.aux = enc["y_lengths"], int(Ty), aux
         self.halo = H.generator_halo(model.hp)
@@ -114,6 +114,26 @@ class SynthesisStream:
         self.total_samples = int(frames) * self._U
         self._frames, self._bounds, self._next = int(frames), list(bounds), 0
         self._window, self._exact, self._pcm, self._gain = int(window_frames), int(bool(exact_lengths)), bool(as_pcm16), float(pcm_gain)
+        self.max_chunk_samples = self._window * self._U
+        self._rs = None
+        if output_rate is not None and int(output_rate) != int(model.hp.sampling_rate):
+            self._init_resampler(int(model.hp.sampling_rate), int(output_rate))
+
+    def _init_resampler(self, rate_in, rate_out):
+        """With ``output_rate`` the chunks leave at that rate: a rolling fp32 device buffer holds the tail of the model-rate audio that
+        later outputs still read (at most ``2K + M / L + 2`` samples) in front of the new chunk; after the chunk that ends at model-rate
+        sample E the outputs ``[done, min(bv2_resample_ready(E), N_total))`` are emitted (everything up to ``N_total`` at the last one).
+        An output's sum does not depend on the range it is emitted in (include/bv2.h), so the pieces are the one-shot result's."""
+        from . import audio
+        Lr, M, K = audio.resample_plan(rate_in, rate_out)
+        dev, B = self._ws.device, self.y_lengths.shape[0]
+        total_in = self.total_samples
+        # item b is its own y_lengths[b] * U samples with exact_lengths, else everything the Generator wrote for it
+        lens = self.y_lengths.to(torch.int64) * self._U if self._exact else torch.full((B,), total_in, dtype=torch.int64, device=dev)
+        self._rs = dict(rate_in=rate_in, rate_out=rate_out, L=Lr, M=M, K=K, cfg=audio.resample_config(rate_in, rate_out), lens=lens,
+                        out_lens=torch.empty(B, dtype=torch.int64, device=dev), total_in=total_in, tail=None, start=0, done=0)
+        self.total_samples = audio.resample_length(rate_in, rate_out, total_in)
+        self.max_chunk_samples = -((-(self._window * self._U + 2 * K + 1) * Lr) // M) + 1
 
     def __iter__(self):
         return self
@@ -121,26 +141,68 @@ class SynthesisStream:
     def __len__(self):
         return len(self._bounds)
 
-    def __next__(self):
-        if self._next >= len(self._bounds):
-            raise StopIteration
-        t0, t1 = self._bounds[self._next]
-        m, B, n = self._model, self.y_lengths.shape[0], (t1 - t0) * self._U
-        out = torch.empty(B, n, dtype=torch.int16 if self._pcm else torch.float32, device=self._ws.device)
+    def _chunk(self, t0, t1, out, bstride, pcm):
+        """One ``bv2_stream_chunk`` on the current stream: samples [t0 * U, t1 * U) to ``out`` (a tensor whose first element is sample
+        t0 * U of item 0, rows ``bstride`` apart)."""
+        m, B = self._model, self.y_lengths.shape[0]
         a = L.StreamChunkArgs()
         a.struct_bytes = C.sizeof(L.StreamChunkArgs)
         a.B, a.Ty, a.t0, a.t1 = B, self.Ty, t0, t1
         a.y_lengths, a.exact_lengths = self.y_lengths.data_ptr(), self._exact
-        if self._pcm:
-            a.dst16, a.dst16_bstride, a.pcm_gain = out.data_ptr(), n, self._gain
+        if pcm:
+            a.dst16, a.dst16_bstride, a.pcm_gain = out.data_ptr(), bstride, self._gain
         else:
-            a.dst, a.dst_bstride = out.data_ptr(), n
+            a.dst, a.dst_bstride = out.data_ptr(), bstride
         a.window_frames, a.max_len = self._window, self._frames
         with torch.cuda.device(self._ws.device):
             m._check(m._lib.bv2_stream_chunk(m._handle, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(a),
                                              C.c_void_p(self._ws.data_ptr()), self._ws.numel()), "bv2_stream_chunk")
+
+    def __next__(self):
+        if self._rs is not None:
+            return self._next_resampled()
+        if self._next >= len(self._bounds):
+            raise StopIteration
+        t0, t1 = self._bounds[self._next]
+        B, n = self.y_lengths.shape[0], (t1 - t0) * self._U
+        out = torch.empty(B, n, dtype=torch.int16 if self._pcm else torch.float32, device=self._ws.device)
+        self._chunk(t0, t1, out, n, self._pcm)
         self._next += 1
         return t0 * self._U, out
+
+    def _next_resampled(self):
+        from . import audio
+        rs, m, dev, B = self._rs, self._model, self._ws.device, self.y_lengths.shape[0]
+        while self._next < len(self._bounds):
+            t0, t1 = self._bounds[self._next]
+            last = self._next == len(self._bounds) - 1
+            self._next += 1
+            n, E = (t1 - t0) * self._U, t1 * self._U
+            keep = 0 if rs["tail"] is None else rs["tail"].shape[1]
+            buf = torch.empty(B, keep + n, dtype=torch.float32, device=dev)       # samples [rs["start"], E) of every item
+            if keep:
+                buf[:, :keep].copy_(rs["tail"])
+            self._chunk(t0, t1, buf[:, keep:], keep + n, False)
+            lib = m._lib
+            ready = self.total_samples if last else min(int(lib.bv2_resample_ready(C.byref(rs["cfg"]), E)), self.total_samples)
+            done = rs["done"]
+            if ready <= done:                                                      # nothing has its whole support yet: keep everything
+                rs["tail"] = buf
+                continue
+            out = audio.resample_range(buf, rs["start"], rs["lens"], rs["rate_in"], rs["rate_out"], done, ready, None, rs["out_lens"])
+            first = max(rs["start"], (ready * rs["M"]) // rs["L"] - rs["K"], 0)     # the next range's lower edge
+            rs["tail"], rs["start"], rs["done"] = (buf[:, first - rs["start"]:] if first < E else None), min(first, E), ready
+            if self._pcm:                                                          # fixed gain on the resampled samples; the clamp takes the filter's overshoot
+                pcm = torch.empty(B, ready - done, dtype=torch.int16, device=dev)
+                with torch.cuda.device(dev):
+                    rc = lib.bv2_emit(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(out.data_ptr()), ready - done, 0,
+                                      C.c_void_p(rs["out_lens"].data_ptr()), 1, done, B, ready - done, None, C.c_void_p(pcm.data_ptr()),
+                                      ready - done, self._gain)
+                if rc:
+                    raise RuntimeError(f"bv2_emit failed ({rc}): {lib.bv2_last_error(None).decode()}")
+                out = pcm
+            return done, out
+        raise StopIteration
 
 
 class SynthesizerTrn(nn.Module):
@@ -471,13 +533,15 @@ class SynthesizerTrn(nn.Module):
         self._stft_params = params
 
     @torch.no_grad()
-    def reference_embedding_from_wav(self, wav: torch.Tensor, wav_lengths=None) -> torch.Tensor:
+    def reference_embedding_from_wav(self, wav: torch.Tensor, wav_lengths=None, sampling_rate: Optional[int] = None) -> torch.Tensor:
         """The voice of a recording -> g [B, gin]: ``audio.spectrogram(wav, wav_lengths, self.stft_params)`` on the model's device, then
         ``reference_embedding`` with the frame counts it produced (a ragged batch is exact in both steps).  ``wav`` [B, S] or [S], fp32 in
-        [-1, 1] or int16 PCM at the model's sampling rate."""
+        [-1, 1] or int16 PCM at ``sampling_rate`` (``None``: the model's).  A recording at another rate is resampled on the device first
+        (``audio.resample``); its resampled lengths stay there, and lengths given on the host are checked as resampled."""
         from . import audio
         if self.hp.n_speakers != 0:
             raise RuntimeError("reference_embedding_from_wav needs a model built with n_speakers=0 (this one has a speaker table: emb_g)")
+        wav, wav_lengths = audio.to_rate(wav, wav_lengths, sampling_rate, self.hp.sampling_rate, self.stft_params, self.device)
         spec, lengths = audio.spectrogram(wav, wav_lengths, self.stft_params, device=self.device)
         return self.reference_embedding(spec, lengths)
 
@@ -802,14 +866,20 @@ class SynthesizerTrn(nn.Module):
     def infer_stream(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_scale=0.667, length_scale=1,
                      noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None, *, g=None, y_lengths=None, noise_w=None, noise_z=None,
                      w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, chunk_frames=64, first_chunk_frames=None,
-                     as_pcm16=False, pcm_gain=32767.0) -> SynthesisStream:
+                     as_pcm16=False, pcm_gain=32767.0, output_rate=None) -> SynthesisStream:
         """``infer`` with the audio handed out chunk by chunk (``SynthesisStream``): phase A, the host sync and the flow run here
         (``bv2_stream_begin``), the Generator runs window by window as the caller iterates — ``chunk_frames`` kept frames per chunk
         (``first_chunk_frames`` for the first one: a short first chunk is on the host sooner), each window carrying ``generator_halo``
         frames on both sides so that its kept samples are the whole decode's.  The arguments of ``infer`` mean what they mean there.
         ``as_pcm16``: chunks are int16, ``trunc(clamp(x * pcm_gain, -32768, 32767))`` — a fixed gain, not the per-utterance peak of
         ``serving.to_pcm16`` (a stream cannot know the peak).  The workspace is planned for a window, not for T_y
-        (``bv2_stream_workspace_bytes``).  Graph replay and taps do not combine with a stream: it raises if either is on."""
+        (``bv2_stream_workspace_bytes``).  Graph replay and taps do not combine with a stream: it raises if either is on.
+        ``output_rate``: the chunks leave at that sampling rate instead of the model's (``bv2_resample`` on a rolling device buffer, see
+        ``SynthesisStream``): offsets and ``total_samples`` then count output-rate samples, a chunk that completes no output yields
+        nothing, and item b is resampled as its own ``y_lengths[b] * U`` samples with ``exact_lengths``, as all ``total`` samples without."""
+        if output_rate is not None and int(output_rate) != int(self.hp.sampling_rate):
+            from . import audio
+            audio.resample_plan(int(self.hp.sampling_rate), int(output_rate))      # ValueError naming the limit, before any work
         if self.device.type != "cuda":
             raise RuntimeError("bert_vits2_amd.SynthesizerTrn.infer_stream needs a GPU: no CPU fallback exists by design")
         if self._graphs_on:
@@ -870,7 +940,7 @@ class SynthesizerTrn(nn.Module):
             bounds.append((t, t1))
             t = t1
         self.last_encode = enc
-        st = SynthesisStream(self, enc, ws, Ty, frames, bounds, window, exact_lengths, as_pcm16, pcm_gain, aux)
+        st = SynthesisStream(self, enc, ws, Ty, frames, bounds, window, exact_lengths, as_pcm16, pcm_gain, aux, output_rate)
         st.y_lengths_host = yl_host
         return st
 

@@ -132,23 +132,25 @@ def speaker_vectors(model, utts: Sequence[Utterance]) -> List[Optional[torch.Ten
     return out
 
 
-def reference_spectrogram(model, wav: torch.Tensor) -> torch.Tensor:
-    """One recording (``[S]`` or ``[1, S]``, fp32 in [-1, 1] or int16 PCM at the model's sampling rate) -> its spectrogram ``[spec_channels,
-    L]`` on the model's device (``audio.spectrogram`` with ``model.stft_params``), to be put into ``Utterance(ref_spec=...)``: utterances
-    that share the returned tensor object share one encoding."""
+def reference_spectrogram(model, wav: torch.Tensor, sampling_rate: Optional[int] = None) -> torch.Tensor:
+    """One recording (``[S]`` or ``[1, S]``, fp32 in [-1, 1] or int16 PCM at ``sampling_rate``; ``None``: the model's) -> its spectrogram
+    ``[spec_channels, L]`` on the model's device (``audio.spectrogram`` with ``model.stft_params``, after ``audio.resample`` where the
+    rates differ), to be put into ``Utterance(ref_spec=...)``: utterances that share the returned tensor object share one encoding."""
     from . import audio
     wav = torch.as_tensor(wav)
     if wav.dim() == 2 and wav.shape[0] == 1:
         wav = wav[0]
     if wav.dim() != 1:
         raise ValueError(f"reference_spectrogram takes one recording [S], got {tuple(wav.shape)}")
+    wav, _ = audio.to_rate(wav, None, sampling_rate, model.hp.sampling_rate, model.stft_params, model.device)
     spec, _ = audio.spectrogram(wav, None, model.stft_params, device=model.device)
     return spec[0]
 
 
-def pcm16(model, wave: torch.Tensor, y_lengths: torch.Tensor) -> torch.Tensor:
+def pcm16(model, wave: torch.Tensor, y_lengths: torch.Tensor, hop: Optional[int] = None) -> torch.Tensor:
     """Device-side 16-bit conversion of ``wave`` [B,1,S] (peak-normalised per utterance over its valid samples, the
-    semantics of gradio ``convert_to_16_bit_wav`` used by reference webui.py:86) -> int16 [B,S]."""
+    semantics of gradio ``convert_to_16_bit_wav`` used by reference webui.py:86) -> int16 [B,S].  Item b's valid samples are the first
+    ``y_lengths[b] * hop``; ``hop`` defaults to the model's samples per frame (``hop = 1``: lengths in samples, as after a resampling)."""
     lib = model._ensure_handle()
     B, _, S = wave.shape
     wave = wave.contiguous()
@@ -157,7 +159,8 @@ def pcm16(model, wave: torch.Tensor, y_lengths: torch.Tensor) -> torch.Tensor:
     yl = y_lengths.to(wave.device, torch.int64).contiguous()
     with torch.cuda.device(wave.device):
         rc = lib.bv2_pcm16(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(wave.data_ptr()), S,
-                           C.c_void_p(yl.data_ptr()), model.hp.total_upsample, B, S, C.c_void_p(out.data_ptr()), S,
+                           C.c_void_p(yl.data_ptr()), model.hp.total_upsample if hop is None else int(hop), B, S,
+                           C.c_void_p(out.data_ptr()), S,
                            C.c_void_p(peak.data_ptr()))
     if rc:
         raise RuntimeError(f"bv2_pcm16 failed ({rc})")
@@ -203,7 +206,7 @@ def replicas(model, n: int) -> list:
 @torch.no_grad()
 def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0.6, noise_scale_w=0.9, length_scale=1.0,
                max_batch: int = 32, max_pad_ratio: float = 1.25, as_pcm16: bool = False,
-               noise: Optional[Sequence] = None, requests_in_flight: int = 1) -> List[np.ndarray]:
+               noise: Optional[Sequence] = None, requests_in_flight: int = 1, output_rate: Optional[int] = None) -> List[np.ndarray]:
     """Synthesise every utterance; returns one 1-D array per utterance in input order (float32 like reference
     infer.py:315-319, or int16 with ``as_pcm16``).  Defaults are the reference web UI's (webui.py:443-454).
     ``noise`` (tests): per utterance a pair ``(noise_w [2,T], noise_z [inter, >= T_y])`` to inject instead of drawing.
@@ -212,11 +215,17 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     An utterance that carries its own ``sdp_ratio`` / ``noise_scale`` / ``noise_scale_w`` / ``length_scale`` gets it inside the
     shared batch (per-utterance controls, one value per batch item); the call's values fill in the rest.  Buckets are then planned
     on expected frames (symbols x length_scale).  Voices: utterances with ``g`` or ``ref_spec`` are conditioned on that vector, the
-    others on their ``sid`` row, all in the same buckets (``speaker_vectors``)."""
+    others on their ``sid`` row, all in the same buckets (``speaker_vectors``).
+    ``output_rate``: audio at that sampling rate instead of the model's — every bucket is resampled on the device (``audio.resample`` over
+    each utterance's own ``y_lengths * hop`` samples) before its one device-to-host copy; an utterance of n model-rate samples comes back
+    with ``ceil(n L / M)``, and ``as_pcm16`` normalises by the peak of the resampled samples."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
     dev = model.device
     hop = model.hp.total_upsample
+    output_rate = _output_rate(model, output_rate)
+    if output_rate is not None:
+        hop = 1                                            # the buckets' lengths then count output-rate samples
     results: List[Optional[np.ndarray]] = [None] * len(utts)
     pending = []
     lanes = replicas(model, requests_in_flight) if requests_in_flight > 1 else [(model, None)]
@@ -236,7 +245,7 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
         else:
             ctl = call
         with torch.cuda.stream(lane_stream) if lane_stream is not None else contextlib.nullcontext():
-            _run_bucket(lane, utts, idx, dev, noise, pending, as_pcm16, gvec, **ctl)
+            _run_bucket(lane, utts, idx, dev, noise, pending, as_pcm16, gvec, output_rate=output_rate, **ctl)
     for idx, host, y_len, ev in pending:
         ev.synchronize()
         for r, i in enumerate(idx):
@@ -244,15 +253,31 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     return results
 
 
-def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio, noise_scale, noise_scale_w, length_scale):
-    """One bucket on the CURRENT stream: collate, infer (exact lengths), optional PCM16, async D2H into pinned memory."""
+def _output_rate(model, output_rate) -> Optional[int]:
+    """``None`` where the audio stays at the model's rate; else the rate, checked against the resampler's envelope before any work."""
+    if output_rate is None or int(output_rate) == int(model.hp.sampling_rate):
+        return None
+    from . import audio
+    audio.resample_plan(int(model.hp.sampling_rate), int(output_rate))
+    return int(output_rate)
+
+
+def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio, noise_scale, noise_scale_w, length_scale,
+                output_rate=None):
+    """One bucket on the CURRENT stream: collate, infer (exact lengths), optional resampling, optional PCM16, async D2H into pinned
+    memory.  The lengths that travel with it count frames, or samples after a resampling."""
     batch, kw = _bucket_inputs(model, utts, idx, dev, noise, gvec)
     o, _attn, y_mask, _ = model.infer(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"],
                                       batch["bert"], batch["ja_bert"], batch["en_bert"], sdp_ratio=sdp_ratio,
                                       noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale,
                                       want_attn=False, exact_lengths=True, **kw)
     y_len = model.last_encode["y_lengths"]             # int64 [B], already on the device (phase A output)
-    audio = pcm16(model, o, y_len) if as_pcm16 else o[:, 0]
+    if output_rate is None:
+        audio = pcm16(model, o, y_len) if as_pcm16 else o[:, 0]
+    else:
+        from . import audio as _audio
+        res, y_len = _audio.resample(o[:, 0], y_len * model.hp.total_upsample, model.hp.sampling_rate, output_rate)
+        audio = pcm16(model, res[:, None], y_len, hop=1) if as_pcm16 else res
     # one async D2H per bucket into pinned memory (audio AND lengths): nothing here blocks the host, so the next bucket's
     # kernels are enqueued while this copy runs; the drain loop below waits on the bucket's event
     host = torch.empty(audio.shape, dtype=audio.dtype, pin_memory=True)
@@ -288,18 +313,22 @@ def _bucket_inputs(model, utts, idx, dev, noise, gvec):
 
 def synthesize_stream(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0.6, noise_scale_w=0.9, length_scale=1.0,
                       max_batch: int = 32, max_pad_ratio: float = 1.25, chunk_frames: int = 64,
-                      first_chunk_frames: Optional[int] = None, as_pcm16: bool = False, noise: Optional[Sequence] = None):
+                      first_chunk_frames: Optional[int] = None, as_pcm16: bool = False, noise: Optional[Sequence] = None,
+                      output_rate: Optional[int] = None):
     """``synthesize`` with the audio handed out as it is produced: a generator of ``(utterance_index, start_sample, np.ndarray)``.  Same
     buckets, per-utterance controls, voices and ``exact_lengths=True`` as ``synthesize``; each bucket runs ``infer_stream`` and its
     Generator chunk by chunk (``chunk_frames`` kept frames, ``first_chunk_frames`` for the first).  A bucket has two pinned host buffers:
     chunk n + 1 is enqueued before the host waits on chunk n's copy event, so the device-to-host copy of a chunk runs under the next
     chunk's Generator.  An utterance's pieces arrive in order with contiguous offsets, and nothing is yielded past its own length.
     ``as_pcm16``: int16 pieces, ``trunc(x * 32767)`` — a FIXED gain, unlike ``synthesize``'s per-utterance peak normalisation (a stream
-    cannot know the peak; the two differ by exactly the factor 1 / max|x| of the utterance)."""
+    cannot know the peak; the two differ by exactly the factor 1 / max|x| of the utterance).
+    ``output_rate``: the pieces leave at that sampling rate (``infer_stream(output_rate=...)``: resampled on the device chunk by chunk,
+    PCM after the resampling); offsets and lengths then count output-rate samples."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
     dev = model.device
     hop = model.hp.total_upsample
+    output_rate = _output_rate(model, output_rate)
     call = dict(sdp_ratio=sdp_ratio, noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale)
     per_item = any(getattr(u, k) is not None for u in utts for k in call)
     gvec = speaker_vectors(model, utts)
@@ -315,9 +344,12 @@ def synthesize_stream(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_
         batch, kw = _bucket_inputs(model, utts, idx, dev, noise, gvec)
         st = model.infer_stream(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"], batch["bert"],
                                 batch["ja_bert"], batch["en_bert"], want_attn=False, exact_lengths=True, chunk_frames=chunk_frames,
-                                first_chunk_frames=first_chunk_frames, as_pcm16=as_pcm16, **ctl, **kw)
+                                first_chunk_frames=first_chunk_frames, as_pcm16=as_pcm16, output_rate=output_rate, **ctl, **kw)
         ends = [n * hop for n in st.y_lengths_host]
-        width = max(int(chunk_frames), int(first_chunk_frames or chunk_frames)) * hop
+        if output_rate is not None:
+            from . import audio
+            ends = [audio.resample_length(model.hp.sampling_rate, output_rate, e) for e in ends]
+        width = st.max_chunk_samples
         hosts = [torch.empty(len(idx), width, dtype=torch.int16 if as_pcm16 else torch.float32, pin_memory=True) for _ in range(2)]
 
         def pieces(start, n, host, ev):

@@ -364,7 +364,8 @@ int bv2_emit(bv2_stream stream, const float* src, int64_t src_bstride, int64_t s
  *
  * Accepted: n_fft 1024 or 2048, 1 <= hop <= n_fft, 1 <= win <= n_fft, n_mels >= 0 (0 = the linear spectrogram, n_fft / 2 + 1 rows).  A
  * failed call returns non-zero (the frame / size queries a negative value) and leaves its message in bv2_last_error(NULL); every argument is
- * checked before anything touches the device.  No resampling and no file decoding: samples at the model's sampling rate go in. */
+ * checked before anything touches the device.  No file decoding: samples go in, at the model's sampling rate (bv2_resample below brings a
+ * recording at another rate there). */
 enum { BV2_WAV_F32 = 0, BV2_WAV_I16 = 1 };     /* fp32 in [-1, 1], or 16-bit PCM read as x / 32768 (exact) */
 typedef struct bv2_stft_config {
   int32_t struct_bytes;            /* = sizeof(bv2_stft_config) */
@@ -393,6 +394,54 @@ int64_t bv2_stft_workspace_bytes(const bv2_stft_config* cfg, int32_t B, int64_t 
 int bv2_spectrogram(bv2_stream stream, const bv2_stft_config* cfg, const void* wav, int64_t wav_bstride, const int64_t* wav_lengths,
                     int32_t B, int64_t S, const float* mel_basis, float* spec, const int64_t* spec_strides, int64_t* spec_lengths_out,
                     void* workspace, int64_t workspace_bytes);
+
+/* ---- polyphase resampler: a voice recorded at any rate in, audio at any rate out (handle-free; kernels/resample.hip) ----
+ * rate_in -> rate_out are positive integers, rate_in != rate_out; g = gcd, L = rate_out / g, M = rate_in / g.  The filter is a Kaiser-windowed
+ * sinc with Z = 32 zero crossings per side, beta = 10.0 and rolloff = 0.91: c = rolloff * min(1, L / M), W = Z / c, K = ceil(W), 2K + 1 taps
+ * per phase.  Table T[p][jj], p in [0, L), jj in [0, 2K]: t = p / L - (jj - K), T = c sinc(c t) I0(beta sqrt(1 - (t / W)^2)) / I0(beta) for
+ * |t| < W, else 0 (sinc(x) = sin(pi x) / (pi x)); every row is then divided by its own sum, so the DC gain is exactly 1 in every phase.  It
+ * is built on the host in fp64 (bv2_resample_taps_f64); the device reads its fp32 rounding (bv2_resample_taps).
+ * Item b's signal is x_b[k] for 0 <= k < len_b and ZERO elsewhere; it has N_out(b) = ceil(len_b L / M) outputs
+ *   y[n] = sum_{jj = 0..2K} x_b[i0 + jj - K] * T[p][jj],   i0 = floor(n M / L),  p = (n M) mod L   (n M in 64 bits),
+ * accumulated in fp32 with fp32 coefficients; int16 input is read as x / 32768 (exact).  Two rules are part of the contract:
+ *   1. a sample outside [0, len_b) is SELECTED to zero before it is used, never multiplied in from memory: the padding of a batch may hold
+ *      anything (NaN included);
+ *   2. the order in which an output's 2K + 1 products are summed depends on nothing but the build of the kernel — not on the tile position,
+ *      the batch row, the batch size, n0 or how a stream was cut into ranges: a range of outputs is bit-identical to the same outputs of
+ *      the whole.
+ * Envelope: L <= 1024 and L * (2K + 1) <= 2^20 table entries (4 MB); 44100 -> 48000 is L = 160 with 73 taps, 44100 -> 8000 L = 80 with 389.
+ * Outside it (44100 -> 48001: L = 48001), for equal rates, a rate <= 0 or a wrong struct_bytes every call below fails (non-zero, the
+ * length queries negative) with a message in bv2_last_error(NULL) that names the limit; every argument is checked before anything touches
+ * the device. */
+typedef struct bv2_resample_config {
+  int32_t struct_bytes;            /* = sizeof(bv2_resample_config) */
+  int32_t rate_in, rate_out;
+  int32_t input_format;            /* BV2_WAV_F32 / BV2_WAV_I16 */
+} bv2_resample_config;
+/* HOST: L, M and K of a rate pair (each pointer may be NULL). */
+int bv2_resample_plan(const bv2_resample_config* cfg, int32_t* L, int32_t* M, int32_t* K);
+/* ceil(n_in L / M): the outputs of an item of n_in samples. */
+int64_t bv2_resample_length(const bv2_resample_config* cfg, int64_t n_in);
+/* max(0, ceil((available_in - K) L / M)): the number of outputs whose whole support lies in [0, available_in) — what a stream that has
+ * produced available_in samples so far may emit. */
+int64_t bv2_resample_ready(const bv2_resample_config* cfg, int64_t available_in);
+/* HOST: the table [L][2K + 1]; bv2_resample_taps is exactly the fp32 rounding of bv2_resample_taps_f64. */
+int bv2_resample_taps(const bv2_resample_config* cfg, float* out);
+int bv2_resample_taps_f64(const bv2_resample_config* cfg, double* out);
+/* One launch on `stream`, no allocation, no host sync, graph-capturable.  src + b * src_bstride (fp32 or int16, DEVICE) holds samples
+ * [src_start, src_start + src_n) of item b; src_lengths [B] (int64, DEVICE) are the ABSOLUTE lengths len_b, NULL = src_start + src_n for
+ * every item.  The call writes outputs [n0, n1) of every item to dst + b * dst_bstride — output n0 lands at offset 0 — and zeros for
+ * n >= N_out(b); dst_lengths_out [B] (int64, DEVICE, may be NULL; not written by an empty range n0 == n1) receives N_out(b).  taps is the
+ * DEVICE copy of bv2_resample_taps.  The caller guarantees two things about the buffer:
+ *   lower edge  src_start <= max(0, i0(n0) - K): checked on the host, -1;
+ *   upper edge  every index below len_b that [n0, n1) needs is below src_start + src_n.  With src_lengths == NULL that holds by
+ *               construction; otherwise the caller limits n1 with bv2_resample_ready.  (An index outside the buffer is never loaded: it
+ *               reads as zero.)
+ * This range form is the whole streaming primitive: keep the last samples from max(0, i0(n1) - K) on, append the next chunk, call again
+ * with n0 = the previous n1. */
+int bv2_resample(bv2_stream stream, const bv2_resample_config* cfg, const float* taps, const void* src, int64_t src_bstride,
+                 int64_t src_start, int64_t src_n, const int64_t* src_lengths, int32_t B, int64_t n0, int64_t n1, float* dst,
+                 int64_t dst_bstride, int64_t* dst_lengths_out);
 
 /* ---- hipGraph capture (BASELINE config 3: "hipGraph-captured decode") ----------------------------------------- */
 /* Both phases are fixed launch sequences on the caller's stream with no allocation, host sync or device->host copy,
