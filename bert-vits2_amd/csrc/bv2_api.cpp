@@ -74,24 +74,6 @@ void bv2_destroy(bv2_handle* h) {
 
 const char* bv2_last_error(const bv2_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
-static float half_to_float(uint16_t v) {
-  const uint32_t sign = (uint32_t)(v & 0x8000) << 16;
-  uint32_t exp = (v >> 10) & 0x1f, man = v & 0x3ff, bits;
-  if (exp == 0) {
-    if (man == 0) bits = sign;
-    else {
-      exp = 127 - 15 + 1;
-      while (!(man & 0x400)) { man <<= 1; --exp; }
-      man &= 0x3ff;
-      bits = sign | (exp << 23) | (man << 13);
-    }
-  } else if (exp == 31) bits = sign | 0x7f800000u | (man << 13);
-  else bits = sign | ((exp + 127 - 15) << 23) | (man << 13);
-  float f;
-  std::memcpy(&f, &bits, 4);
-  return f;
-}
-
 int bv2_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
   if (!h) return -1;
   BV2_TRY
@@ -104,7 +86,7 @@ int bv2_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const 
   if (dtype == BV2_F32) std::memcpy(t.data.data(), host_ptr, sizeof(float) * (size_t)n);
   else if (dtype == BV2_F16) {             // compress_model.py:49-53 "release" checkpoints are .half()
     const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
-    for (int64_t i = 0; i < n; ++i) t.data[(size_t)i] = half_to_float(s[i]);
+    for (int64_t i = 0; i < n; ++i) t.data[(size_t)i] = h2f(s[i]);
   } else if (dtype == BV2_BF16) {
     const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
     for (int64_t i = 0; i < n; ++i) { uint32_t b = (uint32_t)s[i] << 16; std::memcpy(&t.data[(size_t)i], &b, 4); }
@@ -918,616 +900,6 @@ int bv2_profile_report(bv2_handle* h, bv2_profile_row* rows, int max_rows) {
     if (acc[i].launches) rows[n++] = acc[i];
   return n;
   BV2_CATCH(h)
-}
-
-}  // extern "C"
-
-// ================================================================================================================
-// test-only kernel entry points (include/bv2_testing.h)
-#include "../../include/bv2_testing.h"
-
-extern "C" {
-
-static inline int t_round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-int64_t bv2_test_conv_pack_floats(int cin, int cout, int k) {
-  // + 2048 floats: the register-ring conv kernel prefetches up to 4 units (4 KB) past the last weight unit
-  // + the three split-bf16 planes of conv_x6.hip (tile >= TILE_X6), 6 bytes per weight of the 32-row padded matrix
-  const int64_t base = (int64_t)k * t_round_up(cin, 16) * t_round_up(cout, 128) + t_round_up(cout, 32) + 2048;
-  // + the x3 form's region (tile == TILE_X3): two 64-float slots (max |x| in, max |out| back), 1 / S_w, the two fp16 planes
-  return base + (cin % 32 == 0 ? (x6_w_elems(cin, t_round_up(cout, 32), k) + 1) / 2 + 64 +
-                                 2 * X3_SLOT_WORDS + X3_HDR_FLOATS + (x3_w_elems(cin, t_round_up(cout, 32), k) + 1) / 2 + 64 : 0);
-}
-void bv2_test_x6_split(float v, uint16_t* h3) { x6_split(v, h3); }
-int bv2_test_x6_regions(const bv2_handle* h, int64_t* off_floats, int64_t* n_floats, int max_regions) {
-  if (!h || !off_floats || !n_floats) return -1;
-  const Model& m = h->model;
-  int n = 0;
-  auto add = [&](const ConvW& w) {
-    if (w.wx_off < 0) return;
-    if (n < max_regions) { off_floats[n] = w.wx_off; n_floats[n] = (x6_w_elems(w.cin, w.cout_pad, w.k) + 1) / 2; }
-    ++n;
-  };
-  for (int i = 0; i < m.n_ups; ++i)
-    for (int j = 0; j < m.n_rbk; ++j)
-      for (int d = 0; d < m.n_rbd; ++d)
-        for (int e = 0; e < 2; ++e) add(m.rb[i][j][d][e]);
-  return n;
-}
-int bv2_test_x3_regions(const bv2_handle* h, int64_t* off_floats, int64_t* n_floats, int max_regions) {
-  if (!h || !off_floats || !n_floats) return -1;
-  const Model& m = h->model;
-  int n = 0;
-  for (int i = 0; i < m.n_ups; ++i)
-    for (int j = 0; j < m.n_rbk; ++j)
-      for (int d = 0; d < m.n_rbd; ++d)
-        for (int e = 0; e < 2; ++e) {
-          const ConvW& w = m.rb[i][j][d][e];
-          if (w.wy_off < 0 || w.wx_off < 0) continue;
-          if (n < max_regions) { off_floats[n] = w.wy_off; n_floats[n] = X3_HDR_FLOATS + (x3_w_elems(w.cin, w.cout_pad, w.k) + 1) / 2; }
-          ++n;
-        }
-  return n;
-}
-static int64_t t_x6_off(int cin, int cout, int k) {
-  return ((int64_t)k * t_round_up(cin, 16) * t_round_up(cout, 128) + t_round_up(cout, 32) + 2048 + 63) / 64 * 64;
-}
-
-static int64_t t_x3_off(int cin, int cout, int k) {                 // the x3 region: [slot in] [slot out] (X3_SLOT_WORDS each) [1 / S_w (64)] [planes]
-  return (t_x6_off(cin, cout, k) + (x6_w_elems(cin, t_round_up(cout, 32), k) + 1) / 2 + 64 + 63) / 64 * 64;
-}
-int64_t bv2_test_x3_omax_off(int cin, int cout, int k) { return t_x3_off(cin, cout, k) + X3_SLOT_WORDS; }
-
-int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const float* bias_host, float* out, float* wpack_dev,
-                    int B, int cin, int cout, int k, int dil, int pad_left, int L, int tile, float lrelu_slope, int relu,
-                    const float* res, int res_mode, const float* in_mask, const float* out_mask, int mask_pre,
-                    int mask_post, const float* bias2, int nsrc, const float* x1, const float* x2, float in_scale, int ksplit,
-                    int64_t slab_stride) {
-  try {
-    const int cin_pad = t_round_up(cin, 16), ld = t_round_up(cout, 128), cout_pad = t_round_up(cout, 32);
-    std::vector<float> pk;
-    if (w_host) pk.assign((size_t)bv2_test_conv_pack_floats(cin, cout, k), 0.f);
-    if (w_host)                                   // w_host == NULL: wpack_dev already holds the packed weight (timing loops)
-    for (int j = 0; j < k; ++j)
-      for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < cout; ++co)
-          pk[(size_t)conv_w_index(j, ci, co, cin_pad, k)] = w_host[((size_t)co * cin + ci) * k + j];
-    const size_t boff = (size_t)k * cin_pad * ld;
-    if (w_host && bias_host) for (int co = 0; co < cout; ++co) pk[boff + co] = bias_host[co];
-    const bool x6 = tile >= TILE_X6 && cin % 32 == 0;
-    if (w_host && x6) {
-      uint16_t* wx = reinterpret_cast<uint16_t*>(pk.data() + t_x6_off(cin, cout, k));
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co) {
-            uint16_t hh[3];
-            x6_split(w_host[((size_t)co * cin + ci) * k + j], hh);
-            for (int pl = 0; pl < 3; ++pl) wx[x6_w_index(j, ci, co, cin, k, pl)] = hh[pl];
-          }
-    }
-    const bool x3 = tile == TILE_X3 && x6;
-    if (w_host && x3) {
-      float wmax = 0.f;
-      for (size_t i = 0; i < (size_t)cout * cin * k; ++i) wmax = std::max(wmax, std::fabs(w_host[i]));
-      uint32_t mb;
-      std::memcpy(&mb, &wmax, 4);
-      const unsigned e = x3_scale_exp(mb);
-      float* reg = pk.data() + t_x3_off(cin, cout, k);
-      reg[2 * X3_SLOT_WORDS] = x3_scale_inv(e);
-      uint16_t* wy = reinterpret_cast<uint16_t*>(reg + 2 * X3_SLOT_WORDS + X3_HDR_FLOATS);
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co) {
-            const float v = w_host[((size_t)co * cin + ci) * k + j] * x3_scale(e);
-            const _Float16 g0 = (_Float16)v;
-            const _Float16 g1 = (_Float16)(v - (float)g0);
-            std::memcpy(&wy[x3_w_index(j, ci, co, cin, k, 0)], &g0, 2);
-            std::memcpy(&wy[x3_w_index(j, ci, co, cin, k, 1)], &g1, 2);
-          }
-    }
-    if (w_host && hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
-    ConvLaunch cl;
-    std::memset(&cl, 0, sizeof(cl));
-    ConvProb& p = cl.p[0];
-    if (cin % 32 == 0 && ksplit <= 1) {
-      // every kernel's max |out| lands in the region's second slot (bv2_test_x3_omax_off); the x3 form reads max |x| from the first: the
-      // product's producers publish it from their epilogues, here a reduction launch fills the (zeroed) slot
-      float* reg = wpack_dev + t_x3_off(cin, cout, k);
-      if (launch_x3_zero_slots(static_cast<hipStream_t>(stream), reinterpret_cast<unsigned*>(reg), 2)) return -6;
-      p.omax = reinterpret_cast<unsigned*>(reg + X3_SLOT_WORDS);
-      if (x3) {
-        if (nsrc != 1 || launch_absmax(static_cast<hipStream_t>(stream), x, (int64_t)B * cin * L, reinterpret_cast<unsigned*>(reg))) return -2;
-        p.xmax = reinterpret_cast<const unsigned*>(reg);
-        p.w3inv = reg + 2 * X3_SLOT_WORDS; p.w3 = reinterpret_cast<const uint16_t*>(reg + 2 * X3_SLOT_WORDS + X3_HDR_FLOATS);
-      }
-    }
-    p.x[0] = x; p.x[1] = x1; p.x[2] = x2; p.nsrc = nsrc; p.in_scale = in_scale;
-    p.x_bstride = (int64_t)cin * L; p.x_rstride = L; p.Lin = L;
-    p.in_mask = in_mask; p.in_mask_bstride = L; p.out_mask = out_mask; p.out_mask_bstride = L;
-    p.w = wpack_dev; p.bias = bias_host ? wpack_dev + boff : nullptr;
-    if (x6) p.w6 = reinterpret_cast<const uint16_t*>(wpack_dev + t_x6_off(cin, cout, k));
-    p.bias2 = bias2; p.bias2_bstride = cout;
-    p.out = out; p.out_bstride = (int64_t)cout * L; p.out_rstride = L; p.out_tstride = 1; p.out_toff = 0;
-    p.res = res; p.res_bstride = p.out_bstride; p.res_mode = res_mode;
-    p.cin = cin; p.cin_pad = cin_pad; p.cout = cout; p.cout_pad = cout_pad; p.w_ld = ld; p.k = k; p.dil = dil;
-    p.pad_left = pad_left < 0 ? ((k - 1) / 2) * dil : pad_left;
-    p.pre_act = lrelu_slope != 0.f ? PRE_LRELU : PRE_NONE; p.slope = lrelu_slope;
-    p.act = relu ? ACT_RELU : ACT_NONE; p.mask_pre = mask_pre; p.mask_post = mask_post;
-    cl.nprob = 1; cl.B = B; cl.L = L; cl.ksplit = ksplit < 1 ? 1 : ksplit; cl.slab_stride = slab_stride;
-    const char* vn = nullptr;
-    return launch_conv1d(static_cast<hipStream_t>(stream), cl, tile, &vn);
-  } catch (...) { return -100; }
-}
-
-int bv2_test_resblock_fused(void* stream, const float* x, float* out, const float* w1_host, const float* b1_host,
-                            const float* w2_host, const float* b2_host, float* wpack_dev, int B, int C, int k, int dil, int L,
-                            float slope) {
-  try {
-    const int cin_pad = t_round_up(C, 16);
-    const size_t one = (size_t)bv2_test_conv_pack_floats(C, C, k), boff = (size_t)k * cin_pad * t_round_up(C, 128);
-    std::vector<float> pk(2 * one, 0.f);
-    const float* ws[2] = {w1_host, w2_host};
-    const float* bs[2] = {b1_host, b2_host};
-    for (int h = 0; h < 2; ++h) {
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < C; ++ci)
-          for (int co = 0; co < C; ++co)
-            pk[h * one + (size_t)conv_w_index(j, ci, co, cin_pad, k)] = ws[h][((size_t)co * C + ci) * k + j];
-      for (int co = 0; co < C; ++co) pk[h * one + boff + co] = bs[h][co];
-    }
-    if (hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
-    FusedLaunch F;
-    std::memset(&F, 0, sizeof(F));
-    F.nprob = 1; F.B = B; F.C = C; F.L = L; F.slope = slope;
-    F.p[0].x = x; F.p[0].out = out; F.p[0].w1 = wpack_dev; F.p[0].b1 = wpack_dev + boff;
-    F.p[0].w2 = wpack_dev + one; F.p[0].b2 = wpack_dev + one + boff; F.p[0].k = k; F.p[0].dil = dil;
-    return launch_resblock_fused(static_cast<hipStream_t>(stream), F);
-  } catch (...) { return -100; }
-}
-
-static inline uint16_t t_f2bf(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-int64_t bv2_test_resblock_cl_pack_bytes(int C, int k, int nd) {
-  int64_t units = (int64_t)2 * nd * ((C / 16) * k + RBCL_PD) + RBCL_PD;                 // the largest of the stream formats
-  return units * 1024 + (int64_t)2 * nd * (C > 32 ? C : 32) * 4 + 256;
-}
-
-int bv2_test_resblock_cl(void* stream, const void* x, void* out, const float* w_host, const float* bias_host, void* wpack_dev, int B,
-                         int C, int k, const int* dil, int nd, int L, float slope, int variant, const int64_t* lens) {
-  try {
-    if (nd < 1 || nd > BV2_RBCL_MAX_D) return -2;
-    if (variant != 0 && variant != 1) return -2;
-    if (variant == 1 ? !resblock_c16_bf16_supported(C, k, dil, nd) : !resblock_cl_bf16_supported(C, k, dil, nd)) return -2;
-    const int Upad = resblock_cl_bf16_units(C, k), KU = rb16_units(k), G = C / 16;
-    const int64_t wunits = variant == 1 ? (int64_t)2 * nd * KU : (int64_t)2 * nd * Upad + RBCL_PD;
-    const int brow = variant == 1 ? 16 : 32;
-    std::vector<uint16_t> pk((size_t)wunits * 512, 0);
-    std::vector<float> pb((size_t)2 * nd * brow, 0.f);
-    for (int d = 0; d < nd; ++d)
-      for (int e = 0; e < 2; ++e) {
-        const float* w = w_host + (size_t)(2 * d + e) * C * C * k;
-        for (int co = 0; co < C; ++co) {
-          pb[(size_t)(2 * d + e) * brow + co] = bias_host[(size_t)(2 * d + e) * C + co];
-          for (int ci = 0; ci < C; ++ci)
-            for (int j = 0; j < k; ++j) {
-              const uint16_t v = t_f2bf(w[((size_t)co * C + ci) * k + j]);
-              if (variant == 1) {
-                pk[(size_t)(2 * d + e) * KU * 512 + (size_t)rb16_w_index(j, ci, co)] = v;
-              } else {                                  // tap-major units of m-tile 0 (bv2_model.cpp): unit = tap * G + group
-                const int64_t in_unit = cl_w_index(j, ci, co, C, k) % 512;
-                pk[((size_t)(2 * d + e) * Upad + (size_t)j * G + ci / 16) * 512 + (size_t)in_unit] = v;
-              }
-            }
-        }
-      }
-    char* base = static_cast<char*>(wpack_dev);
-    const size_t wbytes = pk.size() * 2, boff = (wbytes + 255) / 256 * 256;
-    if (hipMemcpy(base, pk.data(), wbytes, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    if (hipMemcpy(base + boff, pb.data(), pb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    RbClLaunch F;
-    std::memset(&F, 0, sizeof(F));
-    F.nprob = 1; F.B = B; F.C = C; F.L = L; F.nd = nd; F.slope = slope; F.lens = lens; F.len_mul = 1;
-    F.p[0].x = static_cast<const uint16_t*>(x); F.p[0].out = static_cast<uint16_t*>(out);
-    F.p[0].w = reinterpret_cast<const uint16_t*>(base); F.p[0].bias = reinterpret_cast<const float*>(base + boff);
-    F.p[0].k = k;
-    for (int d = 0; d < nd; ++d) F.p[0].dil[d] = dil[d];
-    return variant == 1 ? launch_resblock_c16_bf16(static_cast<hipStream_t>(stream), F)
-                        : launch_resblock_cl_bf16(static_cast<hipStream_t>(stream), F);
-  } catch (...) { return -100; }
-}
-
-// ---- direct kernel-level entries for the round-4 fused kernels (they were only held to the layer-wise kernels)
-int bv2_test_respair_cl(void* stream, const void* x, void* out, const float* w_host, const float* bias_host, void* wpack_dev, int B,
-                        int C, int k, int dil, int L, float slope, int form, const int64_t* lens) {
-  try {
-    if (!respair_cl_bf16_supported(C, k, dil)) return -2;
-    const int64_t ne = cl_w_elems(C, C, k);
-    std::vector<uint16_t> pk((size_t)2 * ne, 0);
-    for (int e = 0; e < 2; ++e)
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C; ++ci)
-          for (int j = 0; j < k; ++j)
-            pk[(size_t)e * ne + (size_t)cl_w_index(j, ci, co, C, k)] = t_f2bf(w_host[(((size_t)e * C + co) * C + ci) * k + j]);
-    char* base = static_cast<char*>(wpack_dev);
-    const size_t wbytes = pk.size() * 2 + 8192, boff = (wbytes + 255) / 256 * 256;     // + slack: the rings run a few units past a stream's end
-    if (hipMemset(base, 0, boff + (size_t)2 * C * 4) != hipSuccess) return -6;
-    if (hipMemcpy(base, pk.data(), pk.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    if (hipMemcpy(base + boff, bias_host, (size_t)2 * C * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    RpClLaunch F;
-    std::memset(&F, 0, sizeof(F));
-    F.nprob = 1; F.B = B; F.C = C; F.L = L; F.slope = slope; F.lens = lens; F.len_mul = 1; F.form = form; F.mix = 1;
-    RpClProb& q = F.p[0];
-    q.x = static_cast<const uint16_t*>(x); q.out = static_cast<uint16_t*>(out);
-    q.w1 = reinterpret_cast<const uint16_t*>(base); q.w2 = q.w1 + ne;
-    q.b1 = reinterpret_cast<const float*>(base + boff); q.b2 = q.b1 + C;
-    q.k = k; q.dil = dil;
-    return launch_respair_cl_bf16(static_cast<hipStream_t>(stream), F, nullptr);
-  } catch (...) { return -100; }
-}
-int64_t bv2_test_respair_cl_pack_bytes(int C, int k) { return cl_w_elems(C, C, k) * 4 + 8192 + 256 + (int64_t)2 * C * 4; }
-
-int64_t bv2_test_respair_x6_pack_bytes(int C, int k) { return x6_w_elems(C, (C + 31) / 32 * 32, k) * 4 + 16384 + 256 + (int64_t)2 * 32 * 4 + (int64_t)2 * C * 4 + 1024; }
-static int t_respair_x3(void* stream, const float* x, float* out, const float* w_host, const float* bias_host, void* wpack_dev, int B,
-                        int C, int k, int dil, int L, float slope, const int64_t* lens) {
-  try {
-    if (!respair_x6_supported(C, k, dil)) return -2;
-    const int cout_pad = t_round_up(C, 32);
-    const int64_t ne = x3_w_elems(C, cout_pad, k);
-    std::vector<uint16_t> pk((size_t)2 * ne, 0);
-    float inv[2];
-    for (int e = 0; e < 2; ++e) {
-      float wmax = 0.f;
-      for (size_t i = 0; i < (size_t)C * C * k; ++i) wmax = std::max(wmax, std::fabs(w_host[(size_t)e * C * C * k + i]));
-      uint32_t mb;
-      std::memcpy(&mb, &wmax, 4);
-      const unsigned ex = x3_scale_exp(mb);
-      inv[e] = x3_scale_inv(ex);
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C; ++ci)
-          for (int j = 0; j < k; ++j) {
-            const float v = w_host[(((size_t)e * C + co) * C + ci) * k + j] * x3_scale(ex);
-            const _Float16 g0 = (_Float16)v;
-            const _Float16 g1 = (_Float16)(v - (float)g0);
-            std::memcpy(&pk[(size_t)e * ne + (size_t)x3_w_index(j, ci, co, C, k, 0)], &g0, 2);
-            std::memcpy(&pk[(size_t)e * ne + (size_t)x3_w_index(j, ci, co, C, k, 1)], &g1, 2);
-          }
-    }
-    std::vector<float> pb((size_t)2 * cout_pad + 128, 0.f);
-    for (int e = 0; e < 2; ++e)
-      for (int co = 0; co < C; ++co) pb[(size_t)e * cout_pad + co] = bias_host[(size_t)e * C + co];
-    pb[(size_t)2 * cout_pad] = inv[0]; pb[(size_t)2 * cout_pad + 64] = inv[1];
-    char* base = static_cast<char*>(wpack_dev);
-    const size_t wbytes = pk.size() * 2 + 16384, boff = (wbytes + 255) / 256 * 256;
-    if (hipMemset(base, 0, boff + pb.size() * 4) != hipSuccess) return -6;
-    if (hipMemcpy(base, pk.data(), pk.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    if (hipMemcpy(base + boff, pb.data(), pb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    FusedLaunch F;
-    std::memset(&F, 0, sizeof(F));
-    F.nprob = 1; F.B = B; F.C = C; F.L = L; F.slope = slope; F.lens = lens; F.len_mul = 1;
-    FusedProb& q = F.p[0];
-    q.x = x; q.out = out; q.k = k; q.dil = dil;
-    q.w31 = reinterpret_cast<const uint16_t*>(base); q.w32 = q.w31 + ne;
-    q.w61 = q.w31; q.w62 = q.w32;                    // (the launcher insists on them; not read by the x3 form)
-    q.b1 = reinterpret_cast<const float*>(base + boff); q.b2 = q.b1 + cout_pad;
-    q.w3inv1 = q.b1 + 2 * cout_pad; q.w3inv2 = q.w3inv1 + 64;
-    q.w1 = q.b1; q.w2 = q.b1;
-    return launch_respair_x6(static_cast<hipStream_t>(stream), F);
-  } catch (...) { return -100; }
-}
-int bv2_test_respair_x3(void* stream, const float* x, float* out, const float* w_host, const float* bias_host, void* wpack_dev, int B,
-                        int C, int k, int dil, int L, float slope, const int64_t* lens) {
-  return t_respair_x3(stream, x, out, w_host, bias_host, wpack_dev, B, C, k, dil, L, slope, lens);
-}
-int bv2_test_respair_x6(void* stream, const float* x, float* out, const float* w_host, const float* bias_host, void* wpack_dev, int B,
-                        int C, int k, int dil, int L, float slope, const int64_t* lens) {
-  try {
-    if (!respair_x6_supported(C, k, dil)) return -2;
-    const int cout_pad = t_round_up(C, 32);
-    const int64_t ne = x6_w_elems(C, cout_pad, k);
-    std::vector<uint16_t> pk((size_t)2 * ne, 0);
-    for (int e = 0; e < 2; ++e)
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C; ++ci)
-          for (int j = 0; j < k; ++j) {
-            uint16_t h3[3];
-            x6_split(w_host[(((size_t)e * C + co) * C + ci) * k + j], h3);
-            for (int pl = 0; pl < 3; ++pl) pk[(size_t)e * ne + (size_t)x6_w_index(j, ci, co, C, k, pl)] = h3[pl];
-          }
-    std::vector<float> pb((size_t)2 * cout_pad, 0.f);
-    for (int e = 0; e < 2; ++e)
-      for (int co = 0; co < C; ++co) pb[(size_t)e * cout_pad + co] = bias_host[(size_t)e * C + co];
-    char* base = static_cast<char*>(wpack_dev);
-    const size_t wbytes = pk.size() * 2 + 16384, boff = (wbytes + 255) / 256 * 256;
-    if (hipMemset(base, 0, boff + pb.size() * 4) != hipSuccess) return -6;
-    if (hipMemcpy(base, pk.data(), pk.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    if (hipMemcpy(base + boff, pb.data(), pb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    FusedLaunch F;
-    std::memset(&F, 0, sizeof(F));
-    F.nprob = 1; F.B = B; F.C = C; F.L = L; F.slope = slope; F.lens = lens; F.len_mul = 1;
-    FusedProb& q = F.p[0];
-    q.x = x; q.out = out; q.k = k; q.dil = dil;
-    q.w61 = reinterpret_cast<const uint16_t*>(base); q.w62 = q.w61 + ne;
-    q.b1 = reinterpret_cast<const float*>(base + boff); q.b2 = q.b1 + cout_pad;
-    q.w1 = q.b1; q.w2 = q.b1;                        // the fp32 streams are not read by this kernel
-    return launch_respair_x6(static_cast<hipStream_t>(stream), F);
-  } catch (...) { return -100; }
-}
-
-int bv2_test_flow_boundary(void* stream, const float* a, int nslab, int64_t slab_stride, const float* gamma, const float* beta,
-                           const float* mask, float* x1, int64_t z_bstride, const float* post_w_host, const float* post_b_host,
-                           const float* pre_w_host, const float* pre_b_host, float* pre_out, float* wpack_dev, int B, int C, int T) {
-  try {
-    const int C1 = C / 2;
-    // two 1x1 convs in the packed conv layout (conv_w_index, k = 1): post C -> C1, pre C1 -> C
-    const size_t npost = (size_t)t_round_up(C, 16) * t_round_up(C1, 128), npre = (size_t)t_round_up(C1, 16) * t_round_up(C, 128);
-    std::vector<float> pk(npost + npre + (size_t)C1 + (size_t)C + 64, 0.f);
-    for (int co = 0; co < C1; ++co)
-      for (int ci = 0; ci < C; ++ci) pk[(size_t)conv_w_index(0, ci, co, t_round_up(C, 16), 1)] = post_w_host[(size_t)co * C + ci];
-    if (pre_w_host)
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C1; ++ci) pk[npost + (size_t)conv_w_index(0, ci, co, t_round_up(C1, 16), 1)] = pre_w_host[(size_t)co * C1 + ci];
-    for (int co = 0; co < C1; ++co) pk[npost + npre + co] = post_b_host[co];
-    if (pre_b_host)
-      for (int co = 0; co < C; ++co) pk[npost + npre + C1 + co] = pre_b_host[co];
-    if (hipMemcpy(wpack_dev, pk.data(), pk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    FbArgs F;
-    std::memset(&F, 0, sizeof(F));
-    F.a = a; F.nslab = nslab; F.slab_stride = slab_stride; F.gamma = gamma; F.beta = beta; F.eps = 1e-5f; F.mask = mask;
-    F.x1 = x1; F.x1_out = x1; F.z_bstride = z_bstride; F.post_w = wpack_dev; F.post_b = wpack_dev + npost + npre;
-    if (pre_w_host) { F.pre_w = wpack_dev + npost; F.pre_b = wpack_dev + npost + npre + C1; F.pre_out = pre_out; }
-    F.B = B; F.C = C; F.T = T; F.C1 = C1;
-    if (!flow_boundary_supported(F)) return -2;
-    return launch_flow_boundary(static_cast<hipStream_t>(stream), F);
-  } catch (...) { return -100; }
-}
-int64_t bv2_test_flow_boundary_pack_floats(int C) {
-  const int C1 = C / 2;
-  return (int64_t)t_round_up(C, 16) * t_round_up(C1, 128) + (int64_t)t_round_up(C1, 16) * t_round_up(C, 128) + C1 + C + 64;
-}
-
-int64_t bv2_test_conv_cl_pack_bytes(int cin, int cout, int k) {
-  return cl_w_elems(cin, t_round_up(cout, 32), k) * 2 + (int64_t)t_round_up(cout, 32) * 4;
-}
-
-int bv2_test_conv_cl_bf16(void* stream, const void* x0, const void* x1, const void* x2, int nsrc, const float* w_host,
-                          const float* bias_host, void* wpack_dev, void* out, const void* res, const float* bias2, int B, int cin,
-                          int cout, int k, int dil, int pad_left, int L, int pre_lrelu, float slope) {
-  try {
-    if (!conv_cl_bf16_supported(cin, cout, k, dil)) return -2;
-    const int cout_pad = t_round_up(cout, 32);
-    const int64_t ne = cl_w_elems(cin, cout_pad, k);
-    if (w_host) {
-      std::vector<uint16_t> pk((size_t)ne, 0);
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co)
-            pk[(size_t)cl_w_index(j, ci, co, cin, k)] = t_f2bf(w_host[((size_t)co * cin + ci) * k + j]);
-      std::vector<float> bb((size_t)cout_pad, 0.f);
-      if (bias_host) for (int co = 0; co < cout; ++co) bb[(size_t)co] = bias_host[co];
-      if (hipMemcpy(wpack_dev, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-      if (hipMemcpy(static_cast<char*>(wpack_dev) + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    }
-    ClLaunch cl;
-    std::memset(&cl, 0, sizeof(cl));
-    ClProb& p = cl.p[0];
-    p.x[0] = static_cast<const uint16_t*>(x0); p.x[1] = static_cast<const uint16_t*>(x1); p.x[2] = static_cast<const uint16_t*>(x2);
-    p.nsrc = nsrc; p.in_scale = 1.f / (float)nsrc; p.x_bstride = (int64_t)cin * L; p.Lin = L;
-    p.w = static_cast<const uint16_t*>(wpack_dev);
-    p.bias = bias_host ? reinterpret_cast<const float*>(static_cast<char*>(wpack_dev) + ne * 2) : nullptr;
-    p.bias2 = bias2; p.bias2_bstride = cout;
-    p.out = static_cast<uint16_t*>(out); p.out_bstride = (int64_t)cout * L;
-    p.res = static_cast<const uint16_t*>(res); p.res_bstride = p.out_bstride;
-    p.cin = cin; p.cout = cout; p.cout_pad = cout_pad; p.k = k; p.dil = dil;
-    p.pad_left = pad_left < 0 ? ((k - 1) / 2) * dil : pad_left;
-    p.pre_lrelu = pre_lrelu; p.slope = slope;
-    cl.nprob = 1; cl.B = B; cl.L = L;
-    return launch_conv_cl_bf16(static_cast<hipStream_t>(stream), cl, nullptr);
-  } catch (...) { return -100; }
-}
-
-int bv2_test_conv_f16(void* stream, const void* x, int in_ct, const float* in_mask, const float* w_host, const float* bias_host,
-                      void* wpack_dev, void* out, int out_ct, const float* res, int res_mode, const float* out_mask, int mask_pre,
-                      int mask_post, int act, int B, int cin, int cout, int k, int dil, int L, int out_rstride) {
-  try {
-    if (!conv_f16_supported(cin, cout, k, dil, !out_ct)) return -2;
-    const int cout_pad = t_round_up(cout, 32);
-    const int64_t ne = cl_w_elems(cin, cout_pad, k);
-    if (w_host) {
-      std::vector<uint16_t> pk((size_t)ne, 0);
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co) {
-            const _Float16 hv = (_Float16)w_host[((size_t)co * cin + ci) * k + j];
-            std::memcpy(&pk[(size_t)cl_w_index(j, ci, co, cin, k)], &hv, 2);
-          }
-      std::vector<float> bb((size_t)cout_pad, 0.f);
-      if (bias_host) for (int co = 0; co < cout; ++co) bb[(size_t)co] = bias_host[co];
-      if (hipMemcpy(wpack_dev, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-      if (hipMemcpy(static_cast<char*>(wpack_dev) + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    }
-    HcLaunch hl;
-    std::memset(&hl, 0, sizeof(hl));
-    hl.nprob = 1;
-    HcProb& p = hl.p[0];
-    p.x = x; p.in_ct = in_ct; p.x_bstride = (int64_t)cin * L; p.x_rstride = L; p.Lin = L;
-    p.in_mask = in_mask; p.in_mask_bstride = L;
-    p.w = static_cast<const uint16_t*>(wpack_dev);
-    p.bias = bias_host ? reinterpret_cast<const float*>(static_cast<char*>(wpack_dev) + ne * 2) : nullptr;
-    p.out = out; p.out_ct = out_ct;
-    p.out_rstride = out_ct ? (out_rstride > 0 ? out_rstride : L) : 0;
-    p.out_bstride = out_ct ? (int64_t)cout * p.out_rstride : (int64_t)cout * L;
-    p.res = res; p.res_bstride = p.out_bstride; p.res_mode = res_mode;
-    p.out_mask = out_mask; p.out_mask_bstride = L; p.mask_pre = mask_pre; p.mask_post = mask_post; p.act = act;
-    p.cin = cin; p.cout = cout; p.cout_pad = cout_pad; p.k = k; p.dil = dil; p.pad_left = ((k - 1) / 2) * dil;
-    hl.B = B; hl.L = L;
-    return launch_conv_f16(static_cast<hipStream_t>(stream), hl, nullptr);
-  } catch (...) { return -100; }
-}
-
-int bv2_test_dump_cl_conv(bv2_handle* h, const void* host_blob, int kind, int i, int j, int d, int e, int32_t* dims,
-                          float* w_out, float* bias_out) {
-  if (!h || !host_blob || !dims) return -1;
-  try {
-    const Model& m = h->model;
-    const ConvW* w = nullptr;
-    int pad_left = 0;
-    if (kind == 0) { w = &m.conv_pre; pad_left = (w->k - 1) / 2; }
-    else if (kind == 1 && i >= 0 && i < m.n_ups) { w = &m.ups[i].cl; pad_left = m.ups[i].cl_pad_left; }
-    else if (kind == 2 && i >= 0 && i < m.n_ups && j >= 0 && j < m.n_rbk && d >= 0 && d < m.n_rbd && (e == 0 || e == 1)) {
-      w = &m.rb[i][j][d][e];
-      pad_left = ((w->k - 1) / 2) * (e == 0 ? m.cfg.resblock_dilation_sizes[j][d] : 1);
-    }
-    // kind 3: fp16 stream of a transformer-flow Encoder conv — coupling i (application order), layer j, d = 0 qkv / 1 o /
-    //         2 ffn conv_1 / 3 ffn conv_2.   kind 4: resblock conv rb[i][j][d][e] read back from the TAP-MAJOR whole-ResBlock
-    //         stream (must equal kind 2).
-    bool half = false, tapmajor = false, tappair = false;
-    if (kind == 3 && i >= 0 && i < m.n_coupling && m.cfg.use_transformer_flow && j >= 0 && j < m.coupling[i].enc.n_layers &&
-        d >= 0 && d < 4) {
-      const EncLayerW& L = m.coupling[i].enc.layer[j];
-      w = d == 0 ? &L.qkv : (d == 1 ? &L.o : (d == 2 ? &L.ffn1 : &L.ffn2));
-      pad_left = (w->k - 1) / 2;
-      half = true;
-      if (w->wh_off < 0) return -2;
-    } else if (kind == 4 && i >= 0 && i < m.n_ups && j >= 0 && j < m.n_rbk && d >= 0 && d < m.n_rbd && (e == 0 || e == 1)) {
-      w = &m.rb[i][j][d][e];
-      pad_left = ((w->k - 1) / 2) * (e == 0 ? m.cfg.resblock_dilation_sizes[j][d] : 1);
-      tapmajor = true;
-      if (m.rbcl_w_off[i][j] < 0) return -2;
-    }
-    else if (kind == 5 && i >= 0 && i < m.n_ups && j >= 0 && j < m.n_rbk && d >= 0 && d < m.n_rbd && (e == 0 || e == 1)) {
-      // kind 5: rb[i][j][d][e] read back from the tap-PAIR stream of kernels/resblock_c16_bf16.hip (must equal kind 2)
-      w = &m.rb[i][j][d][e];
-      pad_left = ((w->k - 1) / 2) * (e == 0 ? m.cfg.resblock_dilation_sizes[j][d] : 1);
-      tappair = true;
-      if (m.rb16_w_off[i][j] < 0) return -2;
-    }
-    if (!w || (!half && w->wb_off < 0)) return -2;
-    dims[0] = w->cin; dims[1] = w->cout; dims[2] = w->k; dims[3] = pad_left;
-    const float* blob = static_cast<const float*>(host_blob);
-    const uint16_t* wb = reinterpret_cast<const uint16_t*>(blob + (half ? w->wh_off : w->wb_off));
-    if (tapmajor) wb = reinterpret_cast<const uint16_t*>(blob + m.rbcl_w_off[i][j]) +
-                       (int64_t)(2 * d + e) * resblock_cl_bf16_units(w->cin, w->k) * 512;
-    if (tappair) wb = reinterpret_cast<const uint16_t*>(blob + m.rb16_w_off[i][j]) + (int64_t)(2 * d + e) * rb16_units(w->k) * 512;
-    if (w_out)
-      for (int co = 0; co < w->cout; ++co)
-        for (int ci = 0; ci < w->cin; ++ci)
-          for (int jj = 0; jj < w->k; ++jj) {
-            int64_t idx = cl_w_index(jj, ci, co, w->cin, w->k);
-            if (tappair) idx = rb16_w_index(jj, ci, co);
-            if (tapmajor) {                           // unit (group s, tap jj) sits at jj*G + s instead of s*k + jj
-              const int G = w->cin / 16, sg = ci / 16;
-              idx = ((int64_t)jj * G + sg) * 512 + idx % 512;
-            }
-            float f;
-            if (half) {
-              _Float16 hv;
-              std::memcpy(&hv, &wb[idx], 2);
-              f = (float)hv;
-            } else {
-              const uint32_t u = (uint32_t)wb[idx] << 16;
-              std::memcpy(&f, &u, 4);
-            }
-            w_out[((size_t)co * w->cin + ci) * w->k + jj] = f;
-          }
-    if (bias_out)
-      for (int co = 0; co < w->cout; ++co)
-        bias_out[co] = tappair ? blob[m.rb16_b_off[i][j] + (2 * d + e) * 16 + co] : (w->b_off >= 0 ? blob[w->b_off + co] : 0.f);
-    return 0;
-  } catch (...) { return -100; }
-}
-
-int bv2_test_attention(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out,
-                       int B, int H, int D, int T, int W) {
-  AttnArgs a;
-  a.qkv = qkv; a.ld = ld; a.mask = mask; a.erv = erv; a.out = out; a.B = B; a.H = H; a.D = D; a.T = T; a.W = W; a.f16 = 0;
-  return launch_attention(static_cast<hipStream_t>(stream), a);
-}
-
-int bv2_test_attention_f16(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out,
-                           int B, int H, int D, int T, int W) {
-  AttnArgs a;
-  a.qkv = qkv; a.ld = ld; a.mask = mask; a.erv = erv; a.out = out; a.B = B; a.H = H; a.D = D; a.T = T; a.W = W; a.f16 = 1;
-  return launch_attention(static_cast<hipStream_t>(stream), a);
-}
-
-int bv2_test_layernorm(void* stream, const float* a, const float* add, int mode, const float* dww, const float* dwb, int dil,
-                       const float* in_mask, const float* gamma, const float* beta, int post_gelu, const float* res,
-                       const float* vec, const float* mask, float* out, int B, int C, int T, int nslab, int64_t slab_stride) {
-  LnArgs l;
-  std::memset(&l, 0, sizeof(l));
-  l.a = a; l.add = add; l.nslab = nslab; l.slab_stride = slab_stride; l.mode = mode; l.dww = dww; l.dwb = dwb; l.dil = dil; l.in_mask = in_mask;
-  l.gamma = gamma; l.beta = beta; l.eps = 1e-5f; l.post_gelu = post_gelu; l.res = res; l.vec = vec; l.vec_bstride = C;
-  l.mask = mask; l.out = out; l.B = B; l.C = C; l.T = T;
-  return launch_layernorm(static_cast<hipStream_t>(stream), l);
-}
-
-void bv2_test_conv_timeline(void* dev_buf, long long capacity_u64) {
-  conv_set_timeline(static_cast<unsigned long long*>(dev_buf), capacity_u64);
-}
-int bv2_test_conv_timeline_report(long long* meta, int max_launches) { return conv_timeline_report(meta, max_launches); }
-
-void bv2_test_set_tuning(int splitk_waves, int force_ck, long tile_target) { conv_set_tuning(splitk_waves, force_ck, tile_target); }
-void bv2_test_set_x6_tuning(int t256, int t128, int t64, int ck) { conv_x6_set_tuning(t256, t128, t64, ck); }
-void bv2_test_x6_occupancy(int* out4) { conv_x6_occupancy(out4); }
-void bv2_test_set_variants(const char* cl_spec, int cl_generic, int hc_generic) {
-  conv_cl_set_tuning(cl_spec, cl_generic);
-  conv_f16_set_tuning(hc_generic);
-}
-
-int64_t bv2_test_dds_pack_floats(int C) {
-  // [dww 3C][dwb C][g1 C][b1 C][g2 C][b2 C][pre_w C][pre_b C] + conv pack (1x1 C->C) + post conv pack (1x1 C->C rows max)
-  return 10 * (int64_t)C + 2 * bv2_test_conv_pack_floats(C, C, 1);
-}
-
-int bv2_test_dds_layer(void* stream, const float* x, const float* pre_w_host, const float* pre_b_host, const float* z, int z_src,
-                       const float* g, const float* mask, const float* dww_host, const float* dwb_host, const float* g1_host,
-                       const float* b1_host, const float* g2_host, const float* b2_host, const float* w_host,
-                       const float* bias_host, float* out, int dil, int last_mask, const float* post_w_host,
-                       const float* post_b_host, int post_cout, float* post_out, float* zio, int z_dst, float* wpack_dev,
-                       int B, int C, int T) {
-  try {
-    const int64_t one = bv2_test_conv_pack_floats(C, C, 1);
-    std::vector<float> pk((size_t)bv2_test_dds_pack_floats(C), 0.f);
-    size_t o = 0;
-    auto put = [&](const float* src, size_t n) { size_t at = o; if (src) std::memcpy(&pk[o], src, n * sizeof(float)); o += n; return at; };
-    const size_t o_dww = put(dww_host, 3 * (size_t)C), o_dwb = put(dwb_host, C), o_g1 = put(g1_host, C), o_b1 = put(b1_host, C),
-                 o_g2 = put(g2_host, C), o_b2 = put(b2_host, C), o_pw = put(pre_w_host, C), o_pb = put(pre_b_host, C);
-    const int cin_pad = t_round_up(C, 16), ld = t_round_up(C, 128);
-    const size_t o_w = o, boff = (size_t)cin_pad * ld;
-    for (int ci = 0; ci < C; ++ci)
-      for (int co = 0; co < C; ++co) pk[o_w + (size_t)conv_w_index(0, ci, co, cin_pad, 1)] = w_host[(size_t)co * C + ci];
-    for (int co = 0; co < C; ++co) pk[o_w + boff + co] = bias_host[co];
-    const size_t o_p = o_w + (size_t)one;
-    if (post_w_host) {
-      for (int ci = 0; ci < C; ++ci)
-        for (int co = 0; co < post_cout; ++co) pk[o_p + (size_t)conv_w_index(0, ci, co, cin_pad, 1)] = post_w_host[(size_t)co * C + ci];
-      if (post_b_host) for (int co = 0; co < post_cout; ++co) pk[o_p + boff + co] = post_b_host[co];
-    }
-    if (hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
-    DdsArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.x = x;
-    if (pre_w_host) { a.pre_w = wpack_dev + o_pw; a.pre_b = wpack_dev + o_pb; a.z = z; a.z_src = z_src; a.g = g; a.x = nullptr; }
-    a.mask = mask; a.dww = wpack_dev + o_dww; a.dwb = wpack_dev + o_dwb; a.g1 = wpack_dev + o_g1; a.b1 = wpack_dev + o_b1;
-    a.g2 = wpack_dev + o_g2; a.b2 = wpack_dev + o_b2; a.w = wpack_dev + o_w; a.bias = wpack_dev + o_w + boff;
-    a.out = out; a.dil = dil; a.last_mask = last_mask; a.eps = 1e-5f;
-    if (post_w_host) {
-      a.post_w = wpack_dev + o_p; a.post_b = wpack_dev + o_p + boff; a.post_cout = post_cout; a.post_cout_pad = t_round_up(post_cout, 32);
-      a.post_out = post_out; a.zio = zio; a.z_src = z_src; a.z_dst = z_dst; a.sqrt_fc = std::sqrt((float)C); a.tail = 5.0f;
-    }
-    a.B = B; a.C = C; a.T = T;
-    return launch_dds_layer(static_cast<hipStream_t>(stream), a);
-  } catch (...) { return -100; }
-}
-
-int bv2_test_spline(void* stream, float* z, int src, int dst, const float* params, int prow, const float* mask,
-                    float sqrt_fc, float tail, int B, int T) {
-  return launch_spline(static_cast<hipStream_t>(stream), z, src, dst, params, prow, mask, sqrt_fc, tail, B, T);
 }
 
 }  // extern "C"

@@ -165,6 +165,28 @@ inline int64_t x6_w_index(int j, int ci, int co, int cin, int k, int plane) {
   return ((((int64_t)(co >> 5) * U + u) * 3 + plane) * 64 + lane) * 8 + (ci % 8);
 }
 inline int64_t x6_w_elems(int cin, int cout_pad, int k) { return (int64_t)(cout_pad / 32) * (cin / 16) * k * 3 * 512; }
+// Host number formats, one definition each (tests/test_formats_cpu.py holds them to torch bit for bit).
+// fp32 -> bf16, round to nearest even (what torch's .to(torch.bfloat16) and v_cvt_pk_bf16_f32 do); a NaN stays a (quiet) NaN
+inline uint16_t f2bf(float f) {
+  uint32_t u;
+  __builtin_memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+// fp32 -> fp16, round to nearest even (what torch's .to(torch.float16) and v_cvt_f16_f32 do)
+inline uint16_t f2h(float f) {
+  const _Float16 h = (_Float16)f;
+  uint16_t u;
+  __builtin_memcpy(&u, &h, 2);
+  return u;
+}
+// fp16 -> fp32, exact (a signalling NaN comes back quiet)
+inline float h2f(uint16_t u) {
+  _Float16 h;
+  __builtin_memcpy(&h, &u, 2);
+  return (float)h;
+}
 // v = h[0] + h[1] + h[2] exactly (round-to-nearest-even at every step), as bf16 bit patterns.  The FIRST plane saturates: a finite
 // |v| above the largest bf16 (0x7f7f = 3.3895e38; RNE would round the top 0.2 % of the fp32 range to +-inf and the remainder v - inf
 // to NaN) takes +-0x7f7f and the remainder v - h[0] < 2^120 is still exact in the two planes that follow — so every FINITE fp32
@@ -185,7 +207,7 @@ inline void x6_split(float v, uint16_t h[3]) {
   }
 }
 // The two-plane fp16 form of the same kernel ("x3": three products instead of six).  v * S = g0 + g1 with g0 = fp16(v * S) and
-// g1 = fp16(v * S - g0), S a power of two that puts the tensor's largest magnitude just below 2^15: |v * S - g0 - g1| <= 2^-24 |v * S|
+// g1 = fp16(v * S - g0), S a power of two that puts the tensor's largest magnitude just below 2^15: |v * S - g0 - g1| <= 2^-23 |v * S|
 // for every element within 2^15 of the largest (fp16 has 11 significand bits and subnormals down to 2^-24; smaller elements keep an
 // ABSOLUTE error <= 2^-25, i.e. 2^-40 of the largest), and of the four cross terms the three largest, w0x0 + (w0x1 + w1x0), leave out
 // |w1x1| <= 2^-24 |wx| — the same order as the six-product bf16 form, at half the matrix work.  fp16 has no exponent range to spare,

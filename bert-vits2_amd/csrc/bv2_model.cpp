@@ -25,29 +25,6 @@ namespace bv2 {
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-// fp32 -> bf16, round to nearest even (what torch's .to(torch.bfloat16) and v_cvt_pk_bf16_f32 do)
-static inline uint16_t f2bf(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-// fp32 -> fp16, round to nearest even (what torch's .to(torch.float16) and v_cvt_f16_f32 do)
-static inline uint16_t f2h(float f) {
-  const _Float16 h = (_Float16)f;
-  uint16_t u;
-  std::memcpy(&u, &h, 2);
-  return u;
-}
-
-static inline float h2f(uint16_t u) {
-  _Float16 h;
-  std::memcpy(&h, &u, 2);
-  return (float)h;
-}
-
 namespace {
 
 struct Packer {

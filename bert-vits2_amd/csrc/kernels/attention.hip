@@ -29,23 +29,9 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <math.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// wave-uniform base (SGPR pair) + 32-bit per-lane BYTE offset: one VGPR per address instead of a 64-bit pair
-__device__ __forceinline__ float ld_off(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ f32x4 ld_off4(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 
 constexpr int AQ = 32;          // queries per workgroup
 constexpr int AK = 32;          // keys per tile
@@ -249,7 +235,7 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
         for (int e = 0; e < 8; ++e) ka[e] = (_Float16)kreg[8 * t + e];
         }
         const f16x8 qf = *reinterpret_cast<const f16x8*>(Qh + l31 * QP + t * 16 + lh * 8);
-        S = __builtin_amdgcn_mfma_f32_32x32x16_f16(ka, qf, S, 0, 0, 0);
+        S = mfma_32x32x16(ka, qf, S);
       }
     } else {
     // the Q operand streams from LDS a few K-steps ahead of the MFMAs (pinned: hoisting all D/2 reads costs registers)
@@ -329,7 +315,7 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
               for (int e = 0; e < 8; ++e)
                 if ((e < 4 ? ja + e : jb2 + e - 4) >= T) vf[e] = (_Float16)0.f;
             }
-            O[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[s2], O[m], 0, 0, 0);
+            O[m] = mfma_32x32x16(vf, pf[s2], O[m]);
             continue;
           }
           f32x4 va = vreg[m][2 * s2], vb = vreg[m][2 * s2 + 1];
@@ -340,7 +326,7 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
           f16x8 vf;
           vf[0] = (_Float16)va.x; vf[1] = (_Float16)va.y; vf[2] = (_Float16)va.z; vf[3] = (_Float16)va.w;
           vf[4] = (_Float16)vb.x; vf[5] = (_Float16)vb.y; vf[6] = (_Float16)vb.z; vf[7] = (_Float16)vb.w;
-          O[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[s2], O[m], 0, 0, 0);
+          O[m] = mfma_32x32x16(vf, pf[s2], O[m]);
         }
       }
     } else {
@@ -538,6 +524,7 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   if (A.dbg && tid == 0) {
     __builtin_amdgcn_s_waitcnt(0);
     unsigned long long* d = A.dbg + 8ull * (((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+    // not timeline_record: five stamps, words 5 and 6 carry the two extra ones
     d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = __builtin_amdgcn_s_memtime();
     d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
     d[5] = ts3; d[6] = ts4; d[7] = 1;

@@ -3,26 +3,9 @@
 // LDS (B operand) x global weight-fragment stream (A operand) on v_mfma_f32_32x32x16_bf16.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ unsigned bf_pack(float a, float b) {     // round-to-nearest-even (v_cvt_pk_bf16_f32)
-  bf16x2 r;
-  r[0] = (__bf16)a; r[1] = (__bf16)b;
-  return __builtin_bit_cast(unsigned, r);
-}
-
-__device__ __forceinline__ float bf_round(float v) { return (float)(__bf16)v; }     // round-to-nearest-even to a bf16 value
 
 // The stage hand-over's rounding points (oracle generator_bf16; reference models.py:545-552 `xs / self.num_kernels`): a stage's n <= 3 branch
 // outputs r_j (each already bf16) are summed widest kernel first — branch n-1, n-2, ... 0 — with the running sum rounded to bf16 wherever the
@@ -53,11 +36,11 @@ constexpr int CL_PD = 8;          // weight prefetch ring depth (units of 4 MFMA
 // the staging at three SERIAL global round trips of ~4.6k cycles each with batches of 4 — as long as the k = 11 GEMM it feeds.
 template <int NT, int QB, bool MULTI>
 __device__ __forceinline__ void cl_stage_impl(unsigned short* xs, int pitch, const uint16_t* s0, const uint16_t* s1,
-                                              const uint16_t* s2, int nsrc, float in_scale, bool lrelu, float slope, int tb,
+                                              const uint16_t* s2, int nsrc, float in_scale, bool pre_lrelu, float slope, int tb,
                                               int rows, int cin, int Lin, int tid) {
   const int ppr = cin >> 3;                       // 16-byte pieces per row
   const int total = rows * ppr;
-  const bool raw = nsrc == 1 && !lrelu;
+  const bool raw = nsrc == 1 && !pre_lrelu;
   for (int base = 0; base < total; base += QB * NT) {
     u32x4 v[QB][MULTI ? 3 : 1];
     int dst[QB];
@@ -93,7 +76,7 @@ __device__ __forceinline__ void cl_stage_impl(unsigned short* xs, int pitch, con
             a = stage_mean(a, nsrc > 1 ? bf_lo(v[q][1][w]) : 0.f, nsrc > 2 ? bf_lo(v[q][2][w]) : 0.f, nsrc, in_scale);
             b = stage_mean(b, nsrc > 1 ? bf_hi(v[q][1][w]) : 0.f, nsrc > 2 ? bf_hi(v[q][2][w]) : 0.f, nsrc, in_scale);
           }
-          if (lrelu) { a = a < 0.f ? a * slope : a; b = b < 0.f ? b * slope : b; }
+          if (pre_lrelu) { a = a < 0.f ? a * slope : a; b = b < 0.f ? b * slope : b; }
           o[w] = bf_pack(a, b);
         }
       }
@@ -107,10 +90,10 @@ __device__ __forceinline__ void cl_stage_impl(unsigned short* xs, int pitch, con
 // pre(v) = bf16(lrelu(in_scale * sum)).  Rows outside [0, Lin) are zero (the conv's padding).
 template <int NT>
 __device__ __forceinline__ void cl_stage(unsigned short* xs, int pitch, const uint16_t* s0, const uint16_t* s1,
-                                         const uint16_t* s2, int nsrc, float in_scale, bool lrelu, float slope, int tb,
+                                         const uint16_t* s2, int nsrc, float in_scale, bool pre_lrelu, float slope, int tb,
                                          int rows, int cin, int Lin, int tid) {
-  if (nsrc == 1) cl_stage_impl<NT, 12, false>(xs, pitch, s0, s1, s2, nsrc, in_scale, lrelu, slope, tb, rows, cin, Lin, tid);
-  else cl_stage_impl<NT, 6, true>(xs, pitch, s0, s1, s2, nsrc, in_scale, lrelu, slope, tb, rows, cin, Lin, tid);
+  if (nsrc == 1) cl_stage_impl<NT, 12, false>(xs, pitch, s0, s1, s2, nsrc, in_scale, pre_lrelu, slope, tb, rows, cin, Lin, tid);
+  else cl_stage_impl<NT, 6, true>(xs, pitch, s0, s1, s2, nsrc, in_scale, pre_lrelu, slope, tb, rows, cin, Lin, tid);
 }
 
 // acc[mi][ni] += sum over units u = (s, j) of Wfrag(mi, u) x B(u, ni);  B(u, ni) = 8 channels [16s + 8lh, +8) of LDS row
@@ -154,7 +137,7 @@ __device__ __forceinline__ void cl_gemm(f32x16 (&acc)[MI][NI], const uint16_t* w
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[i][mi], bb[i & 1][ni], acc[mi][ni], 0, 0, 0);
+            acc[mi][ni] = mfma_32x32x16(ar[i][mi], bb[i & 1][ni], acc[mi][ni]);
         j = jn; s = sn;
       }
       load_unit(i);
@@ -213,7 +196,7 @@ __device__ __forceinline__ void cl_gemm_tm(f32x16 (&acc)[MI][NI], const uint16_t
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[s][mi], bb[s & 1][ni], acc[mi][ni], 0, 0, 0);
+          acc[mi][ni] = mfma_32x32x16(ar[s][mi], bb[s & 1][ni], acc[mi][ni]);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
         ar[s][mi] = *(const GlobalFrag*)(reinterpret_cast<const char*>(wq[s][mi]) + wlane_bytes);
@@ -261,7 +244,7 @@ __device__ __forceinline__ void cl_tm_run(f32x16 (&acc)[NI], bf16x8 (&ar)[G], co
       for (int ni = 0; ni < NI; ++ni) bb[(s & 1) ^ 1][ni] = *reinterpret_cast<const bf16x8*>(xn + ni * 32 * PITCH);
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[s], bb[s & 1][ni], acc[ni], 0, 0, 0);
+        acc[ni] = mfma_32x32x16(ar[s], bb[s & 1][ni], acc[ni]);
       ar[s] = *(const GlobalFrag*)(reinterpret_cast<const char*>(wq[s]) + wlane_bytes);
       wq[s] += step;
       __builtin_amdgcn_sched_group_barrier(0x100, NI, 0);

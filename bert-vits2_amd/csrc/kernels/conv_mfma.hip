@@ -23,33 +23,9 @@
 // (models.py:539-545), attentions.FFN (attentions.py:438-446), q/k/v/o and all 1x1 projections, DurationPredictor
 // convs (models.py:285-299), WN in/res_skip layers (modules.py:192-210).
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: HIP's float4 struct defeats SROA here
-
-// ConvProb::omax: the wave's max |v| into its XCD's line of the slot (bv2_kernels.h).  |v| >= 0, so fp32 bit patterns order like the
-// values.  `seen`: the word as read at the start of the kernel (stale is fine: it only filters redundant atomics).
-__device__ __forceinline__ unsigned* x3_slot_word(unsigned* slot) {
-  return slot + X3_LINE_WORDS * (__builtin_amdgcn_s_getreg((31 << 11) | 20) & 7u);      // XCC_ID
-}
-__device__ __forceinline__ void x3_publish(unsigned* word, unsigned seen, float vmx, int lane) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) vmx = fmaxf(vmx, __shfl_xor(vmx, d));
-  const unsigned bits = __float_as_uint(vmx);
-  if (lane == 0 && bits > seen) __hip_atomic_fetch_max(word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// load base[byte_off]: wave-uniform base (SGPR pair) + 32-bit per-lane BYTE offset -> the `global_load v, v_off, s[base]`
-// addressing form (one VGPR per address instead of a 64-bit pair)
-__device__ __forceinline__ float ld_off(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ f32x4 ld_off4(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // conv1d_mfma_kernel — LDS-tiled implicit-GEMM conv for problems with enough columns to fill the chip (the Generator, and
@@ -121,7 +97,7 @@ __global__ void __launch_bounds__(256) conv1d_mfma_kernel(const ConvLaunch L, co
     if (t0 >= Lin) return;
   }
   const float in_scale = P.in_scale, slope = P.slope;
-  const bool lrelu = P.pre_act == PRE_LRELU;
+  const bool pre_lrelu = P.pre_act == PRE_LRELU;
   const float* const x0p = P.x[0] + (int64_t)b * P.x_bstride;
   const float* const x1p = P.x[1] ? P.x[1] + (int64_t)b * P.x_bstride : nullptr;
   const float* const x2p = P.x[2] ? P.x[2] + (int64_t)b * P.x_bstride : nullptr;
@@ -218,7 +194,7 @@ __global__ void __launch_bounds__(256) conv1d_mfma_kernel(const ConvLaunch L, co
       for (int r = 0; r < RPW; ++r) {
         float v = xr[r][s];
         const float vn = v * slope;
-        v = (lrelu && v < 0.f) ? vn : v;
+        v = (pre_lrelu && v < 0.f) ? vn : v;
         v *= sc;
         dst[r * XP + 64 * s] = r < rows_ok ? v : 0.f;
       }
@@ -390,10 +366,7 @@ __global__ void __launch_bounds__(256) conv1d_mfma_kernel(const ConvLaunch L, co
     __builtin_amdgcn_s_waitcnt(0);                                  // the epilogue's stores have been issued and acknowledged
     unsigned long long* d = L.dbg + 8ull * (snake_n > 0 ? (unsigned long long)blockIdx.x
                                                         : ((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
-    d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = __builtin_amdgcn_s_memtime();
-    d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);               // HW_ID
-    d[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);              // XCC_ID
-    d[6] = (unsigned long long)k; d[7] = 1;
+    timeline_record(d, ts0, ts1, ts2, k);
   }
 }
 
@@ -448,7 +421,7 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
   }
   const int groups = P.cin_pad / 8;
   const float in_scale = P.in_scale, slope = P.slope;
-  const bool lrelu = P.pre_act == PRE_LRELU;
+  const bool pre_lrelu = P.pre_act == PRE_LRELU;
   const float* const xp = P.x[0] + (int64_t)b * P.x_bstride;       // wave-uniform bases, 32-bit byte offsets per lane
   const float* const mp = MASK ? P.in_mask + (int64_t)b * P.in_mask_bstride : nullptr;
   const float* const wp = P.w;
@@ -561,7 +534,7 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
       const int rr = wid + NWV * i;
       float x = xv[i];
       const float xn = x * slope;
-      x = (lrelu && x < 0.f) ? xn : x;
+      x = (pre_lrelu && x < 0.f) ? xn : x;
       // unconditional: the tile is allocated for SK_RPW rows per wave, rows >= nrows are never read.  Behind `if (rr < nrows)` every
       // store was a basic block of its own and the compiler SANK the row's global load into it (load -> s_waitcnt vmcnt(0) -> store)
       Xs[rr * SK_XP + lane] = (rr < nrows && 8 * G0 + rr < cin) ? x * cs : 0.f;
@@ -612,7 +585,7 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
         for (int q = 0; q < 4; ++q) {
           float x = br[i][q];
           const float xn = x * slope;
-          x = (lrelu && x < 0.f) ? xn : x;
+          x = (pre_lrelu && x < 0.f) ? xn : x;
           bq[q] = x * cs;
         }
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[i].x, bq[0], acc, 0, 0, 0);
@@ -682,10 +655,7 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
   if (L.dbg && tid == 0) {
     __builtin_amdgcn_s_waitcnt(0);
     unsigned long long* d = L.dbg + 8ull * blockIdx.x;
-    d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = __builtin_amdgcn_s_memtime();
-    d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-    d[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    d[6] = (unsigned long long)U; d[7] = 1;
+    timeline_record(d, ts0, ts1, ts2, U);
   }
 }
 

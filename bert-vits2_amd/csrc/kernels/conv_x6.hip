@@ -39,56 +39,9 @@
 // > 512 workgroups, 128x64 with FOUR loader waves and a four-tap ring (RD = 4) for the one-workgroup-per-CU launches.
 // Tiles and what was measured around them: launch_conv1d_x6 at the end of the file; DESIGN.md 3 / 5.
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
-
-namespace {
-
-typedef __bf16 xbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 xbf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 xf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 xf16x2 __attribute__((ext_vector_type(2)));
-typedef float xf32x2 __attribute__((ext_vector_type(2)));
-typedef float xf32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned xu32x4 __attribute__((ext_vector_type(4)));
-// explicit global address space for the ring (see gen_bf16.hip: a FLAT load would also count on lgkmcnt)
-typedef __attribute__((address_space(1))) xbf16x8 XGlobalFrag;
-
-__device__ __forceinline__ float x6_ld(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ unsigned x6_pack(float a, float b) {     // round-to-nearest-even (v_cvt_pk_bf16_f32)
-  xbf16x2 r;
-  r[0] = (__bf16)a; r[1] = (__bf16)b;
-  return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ float x6_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float x6_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-
-constexpr float X6_BF16_MAX = 3.38953139e38f;   // 0x7f7f0000
-// ConvProb::omax: the wave's max |v| into its XCD's line of the slot (bv2_kernels.h).  |v| >= 0, so fp32 bit patterns order like the
-// values.  `seen`: the word as read at the start of the kernel (stale is fine: it only filters redundant atomics).
-__device__ __forceinline__ unsigned* x3_slot_word(unsigned* slot) {
-  return slot + X3_LINE_WORDS * (__builtin_amdgcn_s_getreg((31 << 11) | 20) & 7u);      // XCC_ID
-}
-__device__ __forceinline__ void x3_publish(unsigned* word, unsigned seen, float vmx, int lane) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) vmx = fmaxf(vmx, __shfl_xor(vmx, d));
-  const unsigned bits = __float_as_uint(vmx);
-  if (lane == 0 && bits > seen) __hip_atomic_fetch_max(word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ xf32x16 x6_mfma(xbf16x8 a, xbf16x8 b, xf32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ xf32x16 x6_mfma(xf16x8 a, xf16x8 b, xf32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-// NP = 2 (the x3 form, bv2_kernels.h): fp16 halves of the SCALED value, round-to-nearest-even (v_cvt_f16_f32 x 2 + pack)
-__device__ __forceinline__ unsigned x3_pack(float a, float b) {
-  xf32x2 v = {a, b};
-  const xf16x2 r = __builtin_convertvector(v, xf16x2);
-  return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ xf32x2 x3_unpack(unsigned u) { return __builtin_convertvector(__builtin_bit_cast(xf16x2, u), xf32x2); }
-
-}  // namespace
 
 // NLD = 2: "loader waves".  Two extra waves per workgroup do nothing but the X staging — global loads of chunk c+2, split of chunk
 // c+1 into the OTHER of two LDS buffers — while the four MFMA waves run chunk c; one barrier per chunk.  In the NLD = 0 form the MFMA
@@ -174,7 +127,7 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
   unsigned* const omax_w = P.omax ? x3_slot_word(P.omax) : nullptr;
   unsigned omax_seen = 0xffffffffu;
   if (omax_w) omax_seen = *reinterpret_cast<volatile unsigned*>(omax_w);
-  const bool lrelu = P.pre_act == PRE_LRELU;
+  const bool pre_lrelu = P.pre_act == PRE_LRELU;
   const float* const x0p = P.x[0] + (int64_t)b * P.x_bstride;
   const float* const maskp = P.in_mask ? P.in_mask + (int64_t)b * P.in_mask_bstride : nullptr;
   const unsigned x_rs4 = 4u * (unsigned)P.x_rstride;
@@ -182,7 +135,7 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
   const int nchunks = P.cin / CK;
   const int groups = P.cin / 16;
 
-  xf32x16 acc[MI][NI];
+  f32x16 acc[MI][NI];
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -195,7 +148,7 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
   // The ring holds TWO taps per group — slot [g][(j + par) & 1] for tap j, par = parity of the taps consumed before this chunk — so a
   // unit is requested 2*GR - 1 units (>= 1150 MFMA cycles) before its first MFMA: with one slot per group (the fp32 kernel's ring, one
   // unit = 384 cycles ahead here) a workgroup alone on its CU (C = 256 at batch 1: 288 workgroups) spent 980 cycles per 384-cycle unit.
-  typedef typename std::conditional<NP == 2, xf16x8, xbf16x8>::type frag_t;
+  typedef typename std::conditional<NP == 2, f16x8, bf16x8>::type frag_t;
   typedef __attribute__((address_space(1))) frag_t GlobalFragT;
   frag_t ar[GR][RD][MI][NP];
   const uint16_t* wq[GR][MI];
@@ -241,7 +194,7 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
   auto issue_x = [&](int c) __attribute__((always_inline)) {
     if (maskp) {
 #pragma unroll
-      for (int rg = 0; rg < NRG; ++rg) xm[rg] = x6_ld(maskp, tc[rg]);
+      for (int rg = 0; rg < NRG; ++rg) xm[rg] = ld_off(maskp, tc[rg]);
     } else {
 #pragma unroll
       for (int rg = 0; rg < NRG; ++rg) xm[rg] = 1.f;
@@ -252,7 +205,7 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
 #pragma unroll
       for (int rg = 0; rg < NRG; ++rg)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) xr[rg][o][e] = x6_ld(x0p, row0 + (unsigned)e * x_rs4 + tc[rg]);
+        for (int e = 0; e < 8; ++e) xr[rg][o][e] = ld_off(x0p, row0 + (unsigned)e * x_rs4 + tc[rg]);
     }
   };
   auto store_x = [&](int buf) __attribute__((always_inline)) {
@@ -261,33 +214,31 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
       const float sc = colsc[rg] * xm[rg];
 #pragma unroll
       for (int o = 0; o < OPW; ++o) {
-        xu32x4 p1, p2, p3;
+        u32x4 p1, p2, p3;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
           float a = xr[rg][o][2 * w], bq = xr[rg][o][2 * w + 1];
           const float an = a * slope, bn = bq * slope;
-          a = (lrelu && a < 0.f) ? an : a;
-          bq = (lrelu && bq < 0.f) ? bn : bq;
+          a = (pre_lrelu && a < 0.f) ? an : a;
+          bq = (pre_lrelu && bq < 0.f) ? bn : bq;
           a *= sc; bq *= sc;
           if constexpr (NP == 2) {
-            // |a| < 2^15 (sc carries S_x): g0 = fp16(a), g1 = fp16(a - g0); the remainder is exact in fp32
-            const unsigned u1 = x3_pack(a, bq);
-            const xf32x2 f1 = x3_unpack(u1);
-            p1[w] = u1; p2[w] = x3_pack(a - f1[0], bq - f1[1]);
+            unsigned u1, u2;
+            split2_f16(a, bq, u1, u2);                  // |a| < 2^15: sc carries S_x
+            p1[w] = u1; p2[w] = u2;
             continue;
           }
-          // plane 1 saturates at the largest bf16 (x6_split, bv2_kernels.h): a finite value never rounds to +-inf, its remainder
-          // a - h1 (< 2^120) is exact in planes 2 and 3; inf / NaN leave the clamp finite but their remainders are inf / NaN
-          const unsigned u1 = x6_pack(__builtin_amdgcn_fmed3f(a, -X6_BF16_MAX, X6_BF16_MAX), __builtin_amdgcn_fmed3f(bq, -X6_BF16_MAX, X6_BF16_MAX));
-          a -= x6_lo(u1); bq -= x6_hi(u1);
-          const unsigned u2 = x6_pack(a, bq);
-          a -= x6_lo(u2); bq -= x6_hi(u2);
-          p1[w] = u1; p2[w] = u2; p3[w] = x6_pack(a, bq);
+          // split3_bf16 (device_helpers.h), open-coded: through the call the loader-wave x6 kernel's instructions come out in another order
+          const unsigned u1 = bf_pack(__builtin_amdgcn_fmed3f(a, -X6_BF16_MAX, X6_BF16_MAX), __builtin_amdgcn_fmed3f(bq, -X6_BF16_MAX, X6_BF16_MAX));
+          a -= bf_lo(u1); bq -= bf_hi(u1);
+          const unsigned u2 = bf_pack(a, bq);
+          a -= bf_lo(u2); bq -= bf_hi(u2);
+          p1[w] = u1; p2[w] = u2; p3[w] = bf_pack(a, bq);
         }
         unsigned short* dst = xs + buf * BUFSZ + (rg * 64 + lane) * PITCH + (sw + STW * o) * 8;
-        *reinterpret_cast<xu32x4*>(dst) = p1;
-        *reinterpret_cast<xu32x4*>(dst + PLANE) = p2;
-        if constexpr (NP == 3) *reinterpret_cast<xu32x4*>(dst + 2 * PLANE) = p3;
+        *reinterpret_cast<u32x4*>(dst) = p1;
+        *reinterpret_cast<u32x4*>(dst + PLANE) = p2;
+        if constexpr (NP == 3) *reinterpret_cast<u32x4*>(dst + 2 * PLANE) = p3;
       }
     }
   };
@@ -376,7 +327,7 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
 #define X6_PROD(WP, XP)                                                                                              \
         _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                                            \
         _Pragma("unroll") for (int ni = 0; ni < NI; ++ni)                                                            \
-          acc[mi][ni] = x6_mfma(ar[g][SL][mi][WP], bb[g & 1][ni][XP], acc[mi][ni]);
+          acc[mi][ni] = mfma_32x32x16(ar[g][SL][mi][WP], bb[g & 1][ni][XP], acc[mi][ni]);
         if constexpr (NP == 3) { X6_PROD(2, 0) X6_PROD(1, 1) X6_PROD(0, 2) }
         X6_PROD(1, 0) X6_PROD(0, 1) X6_PROD(0, 0)
 #undef X6_PROD
@@ -463,7 +414,7 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
       const int col = t0 + wn * (NI * 32) + ni * 32 + l31;
       colok[ni] = col < Lout;
       const int colc = colok[ni] ? col : Lout - 1;
-      omr[ni] = x6_ld(omaskp, m_om ? 4u * (unsigned)colc : 0u);
+      omr[ni] = ld_off(omaskp, m_om ? 4u * (unsigned)colc : 0u);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
         const int row0 = m0 + wm * (MI * 32) + mi * 32 + 4 * lh;
@@ -477,12 +428,12 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
       for (int r = 0; r < 16; ++r) {
         const int dr = (r & 3) + 8 * (r >> 2);
         const int row = row0 + dr < cout ? row0 + dr : cout - 1;       // clamped: the load is unconditional, the store is not
-        bs[mi][r] = x6_ld(b1p, m_b1 ? 4u * (unsigned)row : 0u);
-        bs2[mi][r] = x6_ld(b2p, m_b2 ? 4u * (unsigned)row : 0u);
+        bs[mi][r] = ld_off(b1p, m_b1 ? 4u * (unsigned)row : 0u);
+        bs2[mi][r] = ld_off(b2p, m_b2 ? 4u * (unsigned)row : 0u);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
           const unsigned off = row0 + dr < cout ? off0[mi][ni] + (unsigned)dr * o_rs : off0[mi][ni];
-          rv[mi][ni][r] = x6_ld(resb, m_res ? 4u * off : 0u);
+          rv[mi][ni][r] = ld_off(resb, m_res ? 4u * off : 0u);
         }
       }
     }
@@ -516,11 +467,7 @@ conv1d_x6_kernel(const ConvLaunch L, const int mtiles, const int per_xcd, const 
     __builtin_amdgcn_s_waitcnt(0);
     unsigned long long* d = L.dbg + 8ull * (snake_n > 0 ? (unsigned long long)blockIdx.x
                                                         : ((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
-    d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = __builtin_amdgcn_s_memtime();
-    d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);               // HW_ID
-    d[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);              // XCC_ID
-    d[6] = (unsigned long long)k | (tsw << 16);                     // taps | ticks spent in the chunk switches (barrier, split, barrier)
-    d[7] = 1;
+    timeline_record(d, ts0, ts1, ts2, k, tsw);   // ticks: spent in the chunk switches (barrier, split, barrier)
   }
 }
 

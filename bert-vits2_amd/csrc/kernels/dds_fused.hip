@@ -11,12 +11,11 @@
 // + the inverse rational-quadratic spline of transforms.py) to its own output tile.  49 launches -> 15.
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 #include "spline.h"
 
 namespace bv2 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int DDS_NT = 16;                          // time steps per workgroup
 
 __device__ __forceinline__ float gelu_erf(float y) { return 0.5f * y * (1.0f + erff(y * 0.70710678118654752440f)); }

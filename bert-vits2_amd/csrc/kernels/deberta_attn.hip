@@ -17,21 +17,12 @@
 // written to a per-wave LDS table and gathered per score element.  S^T / softmax / PV exactly as in attention.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 constexpr int DQ = 32, DK = 32, DNW = 4, DNS = 4, DTP = 65;     // queries / keys per tile, waves, merge slots, table pitch
-__device__ __forceinline__ float dld(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ f32x4 dld4(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 }  // namespace
 
 template <int DT>   // head dim D = 32 * DT
@@ -70,7 +61,7 @@ __global__ void __launch_bounds__(64 * DNW) deberta_attn_kernel(const DebertaAtt
   const unsigned voff = 4u * (unsigned)(l31 * ld + 4 * lh);
   auto issue_k = [&](int j0) __attribute__((always_inline)) {
 #pragma unroll
-    for (int s = 0; s < D / 2; ++s) kreg[s] = dld(kp, koff + 4u * (unsigned)(j0 + 2 * s * ld));
+    for (int s = 0; s < D / 2; ++s) kreg[s] = ld_off(kp, koff + 4u * (unsigned)(j0 + 2 * s * ld));
     const int jm = j0 + l31;
     mkey = mp[jm < T ? jm : T - 1];
   };
@@ -78,7 +69,7 @@ __global__ void __launch_bounds__(64 * DNW) deberta_attn_kernel(const DebertaAtt
 #pragma unroll
     for (int m = 0; m < DT; ++m)
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) vreg[m][g4] = dld4(vp, voff + 4u * (unsigned)((m * 32) * ld + j0 + 8 * g4));
+      for (int g4 = 0; g4 < 4; ++g4) vreg[m][g4] = ld_off4(vp, voff + 4u * (unsigned)((m * 32) * ld + j0 + 8 * g4));
   };
   if (wid < ntiles) issue_k(wid * DK);
   const float mi = iok ? mp[iq] : 0.f;

@@ -21,20 +21,14 @@
 // Weight stream: cl_w_index (bv2_kernels.h) in fp16, [m-tile][unit = (ci/16)*k + tap][lane][8] — 1 KB per unit.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int HC_PD = 8;          // weight prefetch ring depth (units of NI MFMAs)
 constexpr int HC_CK = 256;        // input channels per LDS chunk
 
+// (not device_helpers.h's f16_pack: its vector conversion compiles to other instructions here)
 __device__ __forceinline__ unsigned h_pack(float a, float b) {       // round-to-nearest-even (v_cvt_f16_f32)
   f16x2 r;
   r[0] = (_Float16)a; r[1] = (_Float16)b;
@@ -71,7 +65,7 @@ __device__ __forceinline__ void hc_gemm(f32x16 (&acc)[NI], const uint16_t* wp, i
         for (int ni = 0; ni < NI; ++ni) bb[(i & 1) ^ 1][ni] = *reinterpret_cast<const f16x8*>(xn + ni * 32 * pitch);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
-          acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[i], bb[i & 1][ni], acc[ni], 0, 0, 0);
+          acc[ni] = mfma_32x32x16(ar[i], bb[i & 1][ni], acc[ni]);
         j = jn; s = sn;
       }
       load_unit(i);
@@ -115,7 +109,7 @@ __device__ __forceinline__ void hc_gemm_tm(f32x16 (&acc)[NI], const uint16_t* wb
       for (int ni = 0; ni < NI; ++ni) bb[(s & 1) ^ 1][ni] = *reinterpret_cast<const f16x8*>(xn + ni * 32 * PITCH);
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[s], bb[s & 1][ni], acc[ni], 0, 0, 0);
+        acc[ni] = mfma_32x32x16(ar[s], bb[s & 1][ni], acc[ni]);
       ar[s] = *(const GlobalFragH*)(reinterpret_cast<const char*>(wq[s]) + wlane_bytes);
       wq[s] += step;
       __builtin_amdgcn_sched_group_barrier(0x100, NI, 0);
@@ -568,10 +562,7 @@ __global__ void __launch_bounds__(64 * WN * KS) conv_f16_kernel(const HcLaunch L
   if (L.dbg && tid == 0) {
     __builtin_amdgcn_s_waitcnt(0);
     unsigned long long* d = L.dbg + 8ull * ((unsigned long long)blockIdx.y * gridDim.x + blockIdx.x);
-    d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = __builtin_amdgcn_s_memtime();
-    d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-    d[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    d[6] = (unsigned long long)k; d[7] = 1;
+    timeline_record(d, ts0, ts1, ts2, k);
   }
 }
 

@@ -16,14 +16,13 @@
 // dependent float4 loads per 12-24 FMAs) the launch took as long as the three it replaces (3.758 -> 3.747 ms per step only).
 // The LayerNorm part is layernorm_kernel's, instruction for instruction (same reduction order: bit-identical statistics).
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
 
 namespace {
 constexpr int FB_TT = 8;          // time steps per workgroup
 constexpr int FB_G = 32;          // row groups (threads along channels)
-typedef float fb_f32x4 __attribute__((ext_vector_type(4)));
 }  // namespace
 
 // CPT = C / 32 channels per thread in the LayerNorm part; C1 = post's output channels = pre's input channels (C / 2)
@@ -34,13 +33,13 @@ __global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
   constexpr int WV4 = C * C1 / 4;                  // float4 of one weight matrix (both are C x C1 elements)
   constexpr int WPT = WV4 / 256;                   // per thread
   static_assert(WV4 % 256 == 0, "whole float4 per thread");
-  extern __shared__ __attribute__((aligned(16))) fb_f32x4 wl[];   // [WV4] W_post, [WV4] W_pre (fragment order, as packed)
+  extern __shared__ __attribute__((aligned(16))) f32x4 wl[];   // [WV4] W_post, [WV4] W_pre (fragment order, as packed)
   __shared__ float red[2][4][FB_TT];
   __shared__ float ys[C][FB_TT];                   // LayerNorm output (masked): post's input
   __shared__ float x1s[C1][FB_TT];                 // updated x1 (masked): pre's input
-  fb_f32x4 wreg[WPT];
+  f32x4 wreg[WPT];
   {
-    const fb_f32x4* wg = reinterpret_cast<const fb_f32x4*>(A.post_w) + threadIdx.x;
+    const f32x4* wg = reinterpret_cast<const f32x4*>(A.post_w) + threadIdx.x;
 #pragma unroll
     for (int i = 0; i < WPT; ++i) wreg[i] = wg[i * 256];
   }
@@ -113,7 +112,7 @@ __global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
 #pragma unroll
   for (int i = 0; i < WPT; ++i) wl[threadIdx.x + i * 256] = wreg[i];
   if (A.pre_w) {                                   // W_pre: in flight under the post product
-    const fb_f32x4* wg = reinterpret_cast<const fb_f32x4*>(A.pre_w) + threadIdx.x;
+    const f32x4* wg = reinterpret_cast<const f32x4*>(A.pre_w) + threadIdx.x;
 #pragma unroll
     for (int i = 0; i < WPT; ++i) wreg[i] = wg[i * 256];
   }
@@ -125,10 +124,10 @@ __global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
 #pragma unroll
     for (int i = 0; i < R1; ++i) acc[i] = 0.f;
     constexpr int G8 = C / 8;
-    const fb_f32x4* wp = wl + ty;
+    const f32x4* wp = wl + ty;
 #pragma unroll 4
     for (int gp = 0; gp < 2 * G8; ++gp) {          // gp = 2 g + par
-      fb_f32x4 w[R1];
+      f32x4 w[R1];
 #pragma unroll
       for (int i = 0; i < R1; ++i) w[i] = wp[(i * 2 * G8 + gp) * 32];
       const int c0 = (gp >> 1) * 8 + (gp & 1);
@@ -154,10 +153,10 @@ __global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
 #pragma unroll
     for (int i = 0; i < CPT; ++i) acc[i] = 0.f;
     constexpr int G8 = C1 / 8;
-    const fb_f32x4* wp = wl + WV4 + ty;
+    const f32x4* wp = wl + WV4 + ty;
 #pragma unroll 2
     for (int gp = 0; gp < 2 * G8; ++gp) {
-      fb_f32x4 w[CPT];
+      f32x4 w[CPT];
 #pragma unroll
       for (int i = 0; i < CPT; ++i) w[i] = wp[(i * 2 * G8 + gp) * 32];
       const int c0 = (gp >> 1) * 8 + (gp & 1);

@@ -18,7 +18,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
-#include "../bv2_kernels.h"
 #include "cl_bf16.h"
 
 namespace bv2 {
@@ -224,10 +223,7 @@ conv_cl_bf16_kernel(const ClLaunch L, const int ngrp) {
   if (L.dbg && tid == 0) {
     __builtin_amdgcn_s_waitcnt(0);
     unsigned long long* d = L.dbg + 8ull * (((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
-    d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = __builtin_amdgcn_s_memtime();
-    d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-    d[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    d[6] = (unsigned long long)k; d[7] = 1;
+    timeline_record(d, ts0, ts1, ts2, k);
   }
 }
 

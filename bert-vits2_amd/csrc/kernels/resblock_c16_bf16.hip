@@ -22,29 +22,16 @@
 // Weight stream (bv2_model.cpp, rb16_w_index): per branch [d][conv e][unit u < (k+1)/2][lane 64][8 bf16]; lane = c_out + 16 q,
 // q = 2 (tap & 1) + c_in / 8, element c_in % 8, tap = 2u + (q >> 1) (zero where tap >= k).  Bias fp32 [2 nd][16].
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) bf16x8 R16GlobalFrag;   // explicit global address space: a FLAT load would also count on lgkmcnt
 
 namespace {
 
-__device__ __forceinline__ float r16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float r16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ unsigned r16_pack(float a, float b) {     // round-to-nearest-even (v_cvt_pk_bf16_f32)
-  bf16x2 r;
-  r[0] = (__bf16)a; r[1] = (__bf16)b;
-  return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ float r16_lrelu(float v, float slope) { return v < 0.f ? v * slope : v; }
 __device__ __forceinline__ unsigned r16_act(unsigned u, float slope) {   // bf16 pair -> bf16(lrelu(.)) pair
-  return r16_pack(r16_lrelu(r16_lo(u), slope), r16_lrelu(r16_hi(u), slope));
+  return bf_pack(lrelu(bf_lo(u), slope), lrelu(bf_hi(u), slope));
 }
 
 constexpr int R16_G = 32;            // guard rows on each side of the LDS tiles (dilated taps reach <= 30 rows outside)
@@ -138,14 +125,14 @@ __device__ __forceinline__ void r16_conv(R16Ctx c, bf16x8 (&W)[KU], const uint16
       const bool inside = tg >= 0 && tg < c.Lseq;
       if (MODE == 1) {
         u32x2 o;
-        o.x = r16_act(r16_pack(acc[nb][0], acc[nb][1]), c.slope);
-        o.y = r16_act(r16_pack(acc[nb][2], acc[nb][3]), c.slope);
+        o.x = r16_act(bf_pack(acc[nb][0], acc[nb][1]), c.slope);
+        o.y = r16_act(bf_pack(acc[nb][2], acc[nb][3]), c.slope);
         if (!inside) o = u32x2{0u, 0u};
         r16_wr64(wr0 + ni * R16_BLK, o);
       } else {
         u32x2 x;
-        x.x = r16_pack(acc[nb][0] + r16_lo(xr[ni][0]), acc[nb][1] + r16_hi(xr[ni][0]));
-        x.y = r16_pack(acc[nb][2] + r16_lo(xr[ni][1]), acc[nb][3] + r16_hi(xr[ni][1]));
+        x.x = bf_pack(acc[nb][0] + bf_lo(xr[ni][0]), acc[nb][1] + bf_hi(xr[ni][0]));
+        x.y = bf_pack(acc[nb][2] + bf_lo(xr[ni][1]), acc[nb][3] + bf_hi(xr[ni][1]));
         if (!inside) x = u32x2{0u, 0u};
         xr[ni][0] = x.x; xr[ni][1] = x.y;
         if (last) {
@@ -156,9 +143,9 @@ __device__ __forceinline__ void r16_conv(R16Ctx c, bf16x8 (&W)[KU], const uint16
               // hand-over: the running sum of the earlier branches — this LANE's own store of the previous iteration (same tile origin for
               // every branch), read back from L2 — plus this branch's output
               const u32x2 pv = *og;
-              float s0 = r16_lo(pv.x) + r16_lo(x.x), s1 = r16_hi(pv.x) + r16_hi(x.x), s2 = r16_lo(pv.y) + r16_lo(x.y), s3 = r16_hi(pv.y) + r16_hi(x.y);
+              float s0 = bf_lo(pv.x) + bf_lo(x.x), s1 = bf_hi(pv.x) + bf_hi(x.x), s2 = bf_lo(pv.y) + bf_lo(x.y), s3 = bf_hi(pv.y) + bf_hi(x.y);
               if (c.sum_mode == 3) { s0 *= c.sum_scale; s1 *= c.sum_scale; s2 *= c.sum_scale; s3 *= c.sum_scale; }
-              x.x = r16_pack(s0, s1); x.y = r16_pack(s2, s3);
+              x.x = bf_pack(s0, s1); x.y = bf_pack(s2, s3);
             }
             *og = x;
           }

@@ -19,27 +19,11 @@
 // Weights: ONE contiguous bf16 fragment stream per (stage, branch) [d][conv][tap-major unit, padded to 8][lane][8] (+8 tail units),
 // streamed global -> registers through an 8-deep ring that is never drained between the 6 convs.
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
-
-__device__ __forceinline__ float rb_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float rb_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ unsigned rb_pack(float a, float b) {     // round-to-nearest-even (v_cvt_pk_bf16_f32)
-  bf16x2 r;
-  r[0] = (__bf16)a; r[1] = (__bf16)b;
-  return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ float rb_lrelu(float v, float slope) { return v < 0.f ? v * slope : v; }
 
 constexpr int RB_G = 32;          // guard rows on each side of the LDS tiles (dilated taps reach <= 25 rows outside)
 // (Round 3, measured and not kept: 4 waves and half the rows per workgroup — R = 384 / 512, 72 / 55 KB of LDS — so that TWO
@@ -85,7 +69,7 @@ __device__ __forceinline__ void rb_gemm(f32x16 (&acc)[NI], Ring& ring, int U, in
         for (int ni = 0; ni < NI; ++ni) bb[(i & 1) ^ 1][ni] = *reinterpret_cast<const bf16x8*>(xn + ni * 32 * PITCH);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
-          acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ring.ar[i], bb[i & 1][ni], acc[ni], 0, 0, 0);
+          acc[ni] = mfma_32x32x16(ring.ar[i], bb[i & 1][ni], acc[ni]);
         if (last_of_tap) xrow += tap_step;
       }
       ring.load(i);
@@ -158,7 +142,7 @@ __global__ void __launch_bounds__(64 * NW) resblock_cl_bf16_kernel(const RbClLau
       if (!inb[q]) continue;
       u32x4 raw = ok[q] ? v[q] : u32x4{0u, 0u, 0u, 0u}, act;
 #pragma unroll
-      for (int w = 0; w < 4; ++w) act[w] = rb_pack(rb_lrelu(rb_lo(raw[w]), slope), rb_lrelu(rb_hi(raw[w]), slope));
+      for (int w = 0; w < 4; ++w) act[w] = bf_pack(lrelu(bf_lo(raw[w]), slope), lrelu(bf_hi(raw[w]), slope));
       *reinterpret_cast<u32x4*>(TA + dst[q]) = raw;
       *reinterpret_cast<u32x4*>(XA + dst[q]) = act;
     }
@@ -173,7 +157,7 @@ __global__ void __launch_bounds__(64 * NW) resblock_cl_bf16_kernel(const RbClLau
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
       const u32x2 u = *reinterpret_cast<const u32x2*>(TA + (RB_G + row) * PITCH + 8 * g + 4 * lh);
-      xr[ni][g][0] = rb_lo(u.x); xr[ni][g][1] = rb_hi(u.x); xr[ni][g][2] = rb_lo(u.y); xr[ni][g][3] = rb_hi(u.y);
+      xr[ni][g][0] = bf_lo(u.x); xr[ni][g][1] = bf_hi(u.x); xr[ni][g][2] = bf_lo(u.y); xr[ni][g][3] = bf_hi(u.y);
     }
   }
   __syncthreads();                                // every wave has its X before conv1 overwrites TA
@@ -214,10 +198,10 @@ __global__ void __launch_bounds__(64 * NW) resblock_cl_bf16_kernel(const RbClLau
           float v0 = acc[ni][4 * g] + bv.x, v1 = acc[ni][4 * g + 1] + bv.y, v2 = acc[ni][4 * g + 2] + bv.z,
                 v3 = acc[ni][4 * g + 3] + bv.w;
           // t = bf16(conv1 + b1); conv2's operand = bf16(lrelu(t))
-          const unsigned q0 = rb_pack(v0, v1), q1 = rb_pack(v2, v3);
+          const unsigned q0 = bf_pack(v0, v1), q1 = bf_pack(v2, v3);
           u32x2 o;
-          o.x = rb_pack(rb_lrelu(rb_lo(q0), slope), rb_lrelu(rb_hi(q0), slope));
-          o.y = rb_pack(rb_lrelu(rb_lo(q1), slope), rb_lrelu(rb_hi(q1), slope));
+          o.x = bf_pack(lrelu(bf_lo(q0), slope), lrelu(bf_hi(q0), slope));
+          o.y = bf_pack(lrelu(bf_lo(q1), slope), lrelu(bf_hi(q1), slope));
           if (!inside) o = u32x2{0u, 0u};
           *reinterpret_cast<u32x2*>(TA + (RB_G + row) * PITCH + 8 * g + 4 * lh) = o;
         }
@@ -249,15 +233,15 @@ __global__ void __launch_bounds__(64 * NW) resblock_cl_bf16_kernel(const RbClLau
           const float v0 = acc[ni][4 * g] + bv.x + xr[ni][g][0], v1 = acc[ni][4 * g + 1] + bv.y + xr[ni][g][1],
                       v2 = acc[ni][4 * g + 2] + bv.z + xr[ni][g][2], v3 = acc[ni][4 * g + 3] + bv.w + xr[ni][g][3];
           u32x2 q;
-          q.x = rb_pack(v0, v1); q.y = rb_pack(v2, v3);
+          q.x = bf_pack(v0, v1); q.y = bf_pack(v2, v3);
           if (!inside) q = u32x2{0u, 0u};
-          xr[ni][g][0] = rb_lo(q.x); xr[ni][g][1] = rb_hi(q.x); xr[ni][g][2] = rb_lo(q.y); xr[ni][g][3] = rb_hi(q.y);
+          xr[ni][g][0] = bf_lo(q.x); xr[ni][g][1] = bf_hi(q.x); xr[ni][g][2] = bf_lo(q.y); xr[ni][g][3] = bf_hi(q.y);
           if (last) {
             if (store) *reinterpret_cast<u32x2*>(outg + (int64_t)t * C + 8 * g + 4 * lh) = q;
           } else {
             u32x2 o;
-            o.x = rb_pack(rb_lrelu(xr[ni][g][0], slope), rb_lrelu(xr[ni][g][1], slope));
-            o.y = rb_pack(rb_lrelu(xr[ni][g][2], slope), rb_lrelu(xr[ni][g][3], slope));
+            o.x = bf_pack(lrelu(xr[ni][g][0], slope), lrelu(xr[ni][g][1], slope));
+            o.y = bf_pack(lrelu(xr[ni][g][2], slope), lrelu(xr[ni][g][3], slope));
             *reinterpret_cast<u32x2*>(XA + (RB_G + row) * PITCH + 8 * g + 4 * lh) = o;
           }
         }

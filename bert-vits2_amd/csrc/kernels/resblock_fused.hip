@@ -15,19 +15,9 @@
 // Zero padding: x outside [0, L) is staged as 0; the intermediate outside [0, L) is FORCED to 0 (it is conv2's padding,
 // not conv1 applied to padding).
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 rf_ld4(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ float rf_ld(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 
 constexpr int RF_BN = 224;        // output columns per tile
 constexpr int RF_TW = 256;        // intermediate columns per tile
@@ -54,7 +44,7 @@ __device__ __forceinline__ void rf_prime(RfRing& R, const float* wp, unsigned w_
 #pragma unroll
   for (int i = 0; i < RF_PD; ++i) {
     const int uc = R.lu < U ? R.lu : U - 1;
-    R.ar[i] = rf_ld4(wp, w_lane + (unsigned)uc * 1024u);
+    R.ar[i] = ld_off4(wp, w_lane + (unsigned)uc * 1024u);
     ++R.lu;
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -71,7 +61,7 @@ __device__ __forceinline__ void rf_gemm(f32x16& acc, RfRing& R, const float* wp,
   int& lu = R.lu;
   auto load_unit = [&](int slot) __attribute__((always_inline)) {
     const int uc = lu < U ? lu : U - 1;                           // past the end: re-read the last unit, result unused
-    ar[slot] = rf_ld4(wp, w_lane + (unsigned)uc * 1024u);
+    ar[slot] = ld_off4(wp, w_lane + (unsigned)uc * 1024u);
     ++lu;
   };
   // operands of unit u+1 are read from LDS before unit u's MFMAs are issued (software pipeline, order pinned below)
@@ -126,7 +116,7 @@ __device__ __forceinline__ void rf_gemm16(f32x4 (&acc)[2], RfRing& R, const floa
   int& lu = R.lu;
   auto load_tap = [&](int slot) __attribute__((always_inline)) {
     const int uc = lu < k ? lu : k - 1;                             // past the end: re-read the last tap, result unused
-    ar[slot] = rf_ld4(wp, w_lane + (unsigned)uc * 1024u);
+    ar[slot] = ld_off4(wp, w_lane + (unsigned)uc * 1024u);
     ++lu;
   };
   float bq[2][4][2];
@@ -204,14 +194,14 @@ __global__ void __launch_bounds__(512) resblock_fused_kernel(const FusedLaunch F
       int row = wid * 4 + r;
       row = row < C ? row : C - 1;
 #pragma unroll
-      for (int s = 0; s < RF_XS; ++s) xr[r][s] = rf_ld(xp, (unsigned)row * 4u * (unsigned)L + tc[s]);
+      for (int s = 0; s < RF_XS; ++s) xr[r][s] = ld_off(xp, (unsigned)row * 4u * (unsigned)L + tc[s]);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int s = 0; s < RF_XS; ++s) {
         float v = xr[r][s];
-        v = v < 0.f ? v * slope : v;
+        v = v < 0.f ? v * slope : v;                // lrelu (device_helpers.h) open-coded: the call changes the instruction order here
         Xs[(wid * 4 + r) * RF_XP + lane + 64 * s] = (ok[s] && wid * 4 + r < C) ? v : 0.f;
       }
   }
@@ -235,7 +225,7 @@ __global__ void __launch_bounds__(512) resblock_fused_kernel(const FusedLaunch F
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float v = acc[nb][r] + bv[r];
-        v = v < 0.f ? v * slope : v;
+        v = v < 0.f ? v * slope : v;                // open-coded lrelu, as above: the call changes the instruction order
         Tm[(4 * rg + r) * RF_TP + col] = tin ? v : 0.f;
       }
     }
@@ -263,7 +253,7 @@ __global__ void __launch_bounds__(512) resblock_fused_kernel(const FusedLaunch F
       for (int r = 0; r < 8; ++r) {
         int row = (r & 3) + 8 * ((r + 8 * hb) >> 2) + 4 * lh;
         row = row < C ? row : C - 1;
-        b1v[r] = rf_ld(b1p, 4u * (unsigned)row);
+        b1v[r] = ld_off(b1p, 4u * (unsigned)row);
       }
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
@@ -271,7 +261,7 @@ __global__ void __launch_bounds__(512) resblock_fused_kernel(const FusedLaunch F
         const int row = (rr & 3) + 8 * (rr >> 2) + 4 * lh;
         if (row < C) {
           float v = acc[rr] + b1v[r];
-          v = v < 0.f ? v * slope : v;
+          v = v < 0.f ? v * slope : v;                // open-coded lrelu, as above: the call changes the instruction order
           Tm[row * RF_TP + 32 * wid + l31] = tin ? v : 0.f;
         }
       }
@@ -296,7 +286,7 @@ __global__ void __launch_bounds__(512) resblock_fused_kernel(const FusedLaunch F
       tt[nb] = t0 + 32 * wid + 16 * nb + n;
       const int tc = tt[nb] < L ? tt[nb] : L - 1;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) xv[nb][r] = rf_ld(xp, 4u * ((unsigned)(4 * rg + r) * (unsigned)L + (unsigned)tc));
+      for (int r = 0; r < 4; ++r) xv[nb][r] = ld_off(xp, 4u * ((unsigned)(4 * rg + r) * (unsigned)L + (unsigned)tc));
     }
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
@@ -322,7 +312,7 @@ __global__ void __launch_bounds__(512) resblock_fused_kernel(const FusedLaunch F
         int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
         row = row < C ? row : C - 1;
         bv[r] = b2p[row];
-        xv[r] = rf_ld(xp, 4u * ((unsigned)row * (unsigned)L + (unsigned)t));
+        xv[r] = ld_off(xp, 4u * ((unsigned)row * (unsigned)L + (unsigned)t));
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -334,10 +324,7 @@ __global__ void __launch_bounds__(512) resblock_fused_kernel(const FusedLaunch F
   if (F.dbg && tid == 0) {
     __builtin_amdgcn_s_waitcnt(0);
     unsigned long long* d = F.dbg + 8ull * (((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
-    d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = __builtin_amdgcn_s_memtime();
-    d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-    d[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    d[6] = (unsigned long long)k; d[7] = 1;
+    timeline_record(d, ts0, ts1, ts2, k);
   }
 }
 

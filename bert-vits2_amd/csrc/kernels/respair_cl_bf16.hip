@@ -20,7 +20,6 @@
 // tests/test_respair_gpu.py compares the two with torch.equal.
 // out must not alias x (a tile's halo rows are another tile's outputs): the host ping-pongs between two buffers per branch.
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
 #include "cl_bf16.h"
 
 namespace bv2 {
@@ -220,6 +219,7 @@ respair_cl_bf16_kernel(const RpClLaunch L, const int per_xcd, const int mix) {
   if (L.dbg && threadIdx.x == 0) {
     __builtin_amdgcn_s_waitcnt(0);
     unsigned long long* d = L.dbg + 8ull * (((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+    // timeline_record (device_helpers.h) open-coded: with the ticks as an argument the kernel's instructions come out in another order
     d[0] = ts0; d[1] = ts1; d[2] = ts3; d[3] = __builtin_amdgcn_s_memtime();
     d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
     d[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
@@ -361,7 +361,7 @@ __device__ __forceinline__ void rp2_run(f32x16 (&acc)[2][4], bf16x8 (&ar)[RP2_RS
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[i][mi], bb[i & 1][ni], acc[mi][ni], 0, 0, 0);
+            acc[mi][ni] = mfma_32x32x16(ar[i][mi], bb[i & 1][ni], acc[mi][ni]);
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
           ar[i][mi] = *(const GlobalFrag*)(reinterpret_cast<const char*>(wq[i][mi]) + wlane_bytes);
@@ -613,10 +613,11 @@ respair2_cl_bf16_kernel(const RpClLaunch L, const int per_xcd, const int mix) {
   if (dbg && threadIdx.x == 0) {
     __builtin_amdgcn_s_waitcnt(0);
     unsigned long long* d = L.dbg + 8ull * (((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+    // timeline_record (device_helpers.h) open-coded: with the ticks as an argument the kernel's instructions come out in another order
     d[0] = ts0; d[1] = ts1; d[2] = ts3; d[3] = __builtin_amdgcn_s_memtime();
     d[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
     d[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    d[6] = (unsigned long long)kdbg | ((ts2 - ts1) << 16);
+    d[6] = (unsigned long long)kdbg | ((ts2 - ts1) << 16);        // taps | ticks of conv1's GEMM
     d[7] = 1;
   }
 }

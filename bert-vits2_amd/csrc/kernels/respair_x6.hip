@@ -19,56 +19,18 @@
 // -> 61.8 / 36.2 / 32.7 us per launch at batch 1.  NP = 3 (the text above) stays as "conv_x3" = 0 and is the form that is bit-identical to
 // the layer-wise launches.
 #include <hip/hip_runtime.h>
-#include "../bv2_kernels.h"
+#include "device_helpers.h"
 
 namespace bv2 {
 
 namespace {
 
-typedef __bf16 pxbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 pxbf16x2 __attribute__((ext_vector_type(2)));
-typedef float pxf32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned pxu32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned pxu32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 pxf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 pxf16x2 __attribute__((ext_vector_type(2)));
-typedef float pxf32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ pxf32x16 px_mfma(pxbf16x8 a, pxbf16x8 b, pxf32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ pxf32x16 px_mfma(pxf16x8 a, pxf16x8 b, pxf32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-// the x3 form (bv2_kernels.h): the two fp16 halves of a pair of SCALED values (|a|, |b| < 2^15), round-to-nearest-even
-__device__ __forceinline__ void px_split2h(float a, float b, unsigned& u1, unsigned& u2) {
-  const pxf16x2 g = __builtin_convertvector((pxf32x2){a, b}, pxf16x2);
-  const pxf32x2 f = __builtin_convertvector(g, pxf32x2);
-  u1 = __builtin_bit_cast(unsigned, g);
-  u2 = __builtin_bit_cast(unsigned, __builtin_convertvector((pxf32x2){a - f[0], b - f[1]}, pxf16x2));
-}
 // workgroup-wide max of a per-thread magnitude: wave butterflies, one float per wave through `red` (the caller's barrier in between)
 __device__ __forceinline__ void px_wave_max_to(float* red, int wid, int lane, float m) {
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
+  for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));       // wave_max (device_helpers.h) open-coded: the call moves an instruction
   if (lane == 0) red[wid] = m;
 }
-
-__device__ __forceinline__ float px_ld(const float* base, unsigned byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ unsigned px_pack(float a, float b) {     // round-to-nearest-even (v_cvt_pk_bf16_f32)
-  pxbf16x2 r;
-  r[0] = (__bf16)a; r[1] = (__bf16)b;
-  return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ float px_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float px_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-// the three planes of a pair of values (conv_x6.hip store_x: plane 1 saturates at the largest bf16)
-__device__ __forceinline__ void px_split2(float a, float b, unsigned& u1, unsigned& u2, unsigned& u3) {
-  constexpr float M = 3.38953139e38f;
-  u1 = px_pack(__builtin_amdgcn_fmed3f(a, -M, M), __builtin_amdgcn_fmed3f(b, -M, M));
-  a -= px_lo(u1); b -= px_hi(u1);
-  u2 = px_pack(a, b);
-  a -= px_lo(u2); b -= px_hi(u2);
-  u3 = px_pack(a, b);
-}
-
 
 }  // namespace
 
@@ -85,7 +47,7 @@ template <int PX_C, int WNT, int NP = 3>
 __global__ void __launch_bounds__((PX_C >= 32 ? PX_C / 32 : 1) * WNT * 64, PX_C <= 32 ? 2 : 1)
 respair_x6_kernel(const FusedLaunch L, const int per_xcd) {
   constexpr int PX_UNIT = NP * 512;               // elements of one (group, tap) unit: NP planes x 64 lanes x 8
-  typedef typename std::conditional<NP == 2, pxf16x8, pxbf16x8>::type frag_t;
+  typedef typename std::conditional<NP == 2, f16x8, bf16x8>::type frag_t;
   typedef __attribute__((address_space(1))) frag_t GlobalFragT;
   constexpr int NI = 2, PX_HT = 64 * WNT, PX_XR = PX_HT + 64, NRG = PX_XR / 64;
   constexpr int MB = PX_C >= 32 ? PX_C / 32 : 1;  // 32-row blocks
@@ -174,7 +136,7 @@ respair_x6_kernel(const FusedLaunch L, const int per_xcd) {
       for (int o = 0; o < OPW; ++o) {
         const unsigned row0 = (unsigned)((oct0 + NW * o) * 8) * x_rs4;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) xr[i][o][e] = px_ld(x0p, row0 + (unsigned)e * x_rs4 + tc);
+        for (int e = 0; e < 8; ++e) xr[i][o][e] = ld_off(x0p, row0 + (unsigned)e * x_rs4 + tc);
       }
     }
     if constexpr (NP == 2) {
@@ -202,7 +164,7 @@ respair_x6_kernel(const FusedLaunch L, const int per_xcd) {
       const int rg = rg0 + CGS * i;
 #pragma unroll
       for (int o = 0; o < OPW; ++o) {
-        pxu32x4 q1, q2, q3;
+        u32x4 q1, q2, q3;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
           float a = xr[i][o][2 * w], bq = xr[i][o][2 * w + 1];
@@ -211,22 +173,22 @@ respair_x6_kernel(const FusedLaunch L, const int per_xcd) {
           bq = bq < 0.f ? bn : bq;
           a *= colsc[i]; bq *= colsc[i];
           unsigned u1, u2, u3 = 0;
-          if constexpr (NP == 2) px_split2h(a, bq, u1, u2);
-          else px_split2(a, bq, u1, u2, u3);
+          if constexpr (NP == 2) split2_f16(a, bq, u1, u2);
+          else split3_bf16(a, bq, u1, u2, u3);
           q1[w] = u1; q2[w] = u2; q3[w] = u3;
         }
         if (CGS == 1 || rg < NRG) {
           unsigned short* dst = xs + (rg * 64 + lane) * PX_PITCH + (oct0 + NW * o) * 8;
-          *reinterpret_cast<pxu32x4*>(dst) = q1;
-          *reinterpret_cast<pxu32x4*>(dst + PX_PLANE) = q2;
-          if constexpr (NP == 3) *reinterpret_cast<pxu32x4*>(dst + 2 * PX_PLANE) = q3;
+          *reinterpret_cast<u32x4*>(dst) = q1;
+          *reinterpret_cast<u32x4*>(dst + PX_PLANE) = q2;
+          if constexpr (NP == 3) *reinterpret_cast<u32x4*>(dst + 2 * PX_PLANE) = q3;
         }
       }
     }
   }
   __syncthreads();
 
-  pxf32x16 acc[NI];
+  f32x16 acc[NI];
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
@@ -263,7 +225,7 @@ respair_x6_kernel(const FusedLaunch L, const int per_xcd) {
           }
 #define PX_PROD(WP, XP)                                                                                              \
           _Pragma("unroll") for (int ni = 0; ni < NI; ++ni)                                                          \
-            acc[ni] = px_mfma(ar[gl][SL][WP], bb[cur][ni][XP], acc[ni]);
+            acc[ni] = mfma_32x32x16(ar[gl][SL][WP], bb[cur][ni][XP], acc[ni]);
           if constexpr (NP == 3) { PX_PROD(2, 0) PX_PROD(1, 1) PX_PROD(0, 2) }
           PX_PROD(1, 0) PX_PROD(0, 1) PX_PROD(0, 0)
 #undef PX_PROD
@@ -344,11 +306,11 @@ respair_x6_kernel(const FusedLaunch L, const int per_xcd) {
         v[i] = t * ok;
       }
       unsigned a1, a2, a3 = 0, c1, c2, c3 = 0;
-      if constexpr (NP == 2) { px_split2h(v[0], v[1], a1, a2); px_split2h(v[2], v[3], c1, c2); }
-      else { px_split2(v[0], v[1], a1, a2, a3); px_split2(v[2], v[3], c1, c2, c3); }
-      *reinterpret_cast<pxu32x2*>(dst + 8 * j) = pxu32x2{a1, c1};
-      *reinterpret_cast<pxu32x2*>(dst + 8 * j + PX_PLANE) = pxu32x2{a2, c2};
-      if constexpr (NP == 3) *reinterpret_cast<pxu32x2*>(dst + 8 * j + 2 * PX_PLANE) = pxu32x2{a3, c3};
+      if constexpr (NP == 2) { split2_f16(v[0], v[1], a1, a2); split2_f16(v[2], v[3], c1, c2); }
+      else { split3_bf16(v[0], v[1], a1, a2, a3); split3_bf16(v[2], v[3], c1, c2, c3); }
+      *reinterpret_cast<u32x2*>(dst + 8 * j) = u32x2{a1, c1};
+      *reinterpret_cast<u32x2*>(dst + 8 * j + PX_PLANE) = u32x2{a2, c2};
+      if constexpr (NP == 3) *reinterpret_cast<u32x2*>(dst + 8 * j + 2 * PX_PLANE) = u32x2{a3, c3};
     }
   }
 #pragma unroll
@@ -376,7 +338,7 @@ respair_x6_kernel(const FusedLaunch L, const int per_xcd) {
       const int t = t0 + (colok[ni] ? oc : 0);
       off0[ni] = (unsigned)(wm * 32 + 4 * lh) * (unsigned)L.L + (unsigned)t;
 #pragma unroll
-      for (int r = 0; r < 4 * NJ; ++r) rv[ni][r] = px_ld(x0p, 4u * (off0[ni] + (unsigned)((r & 3) + 8 * (r >> 2)) * (unsigned)L.L));
+      for (int r = 0; r < 4 * NJ; ++r) rv[ni][r] = ld_off(x0p, 4u * (off0[ni] + (unsigned)((r & 3) + 8 * (r >> 2)) * (unsigned)L.L));
     }
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni)

@@ -196,6 +196,11 @@ SYMBOLS = [
     ("bv2_bert_forward", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64]),
 ]
 
+# the one entry point of include/bv2_testing.h bound here (tests declare the kernel launchers they call themselves)
+TESTING_SYMBOLS = [
+    ("bv2_test_convert", C.c_int, [C.c_int, _P, _P, C.c_int64]),      # kind 0 / 1 / 2 = f2bf / f2h / h2f over an array
+]
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -240,7 +245,7 @@ def load(build_if_missing: bool = True, path: Optional[str] = None) -> C.CDLL:
     elif not os.path.exists(path):
         raise RuntimeError(f"{path}: no such library")
     lib = C.CDLL(path)
-    for name, res, args in SYMBOLS:
+    for name, res, args in SYMBOLS + TESTING_SYMBOLS:
         fn = getattr(lib, name)         # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

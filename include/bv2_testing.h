@@ -35,6 +35,9 @@ int64_t bv2_test_x3_omax_off(int cin, int cout, int k);
 
 /* v = h[0] + h[1] + h[2] exactly as bf16 bit patterns: the host-side split the packer applies to the x6 weight planes (host only) */
 void bv2_test_x6_split(float v, uint16_t* h3);
+/* the host number formats of the packer over an array of n elements (host only): kind 0 = fp32 -> bf16 bits, 1 = fp32 -> fp16 bits
+ * (both round to nearest even), 2 = fp16 bits -> fp32.  Returns 0, or -1 for a bad argument. */
+int bv2_test_convert(int kind, const void* in, void* out, int64_t n);
 /* where the packed blob holds x6 weight planes: float offset / float count of every region ([unit][plane 3][64 lanes][8] uint16); returns
  * the number of regions (host only; layout is known after bv2_create) */
 int bv2_test_x6_regions(const bv2_handle* h, int64_t* off_floats, int64_t* n_floats, int max_regions);
