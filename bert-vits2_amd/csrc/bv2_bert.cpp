@@ -31,21 +31,10 @@ namespace {
 constexpr int64_t kBertMagic = 0x42563242455254ll;      // "BV2BERT"
 constexpr int kBertLayout = 1;
 
-struct Lin { int cin = 0, cin_pad = 0, cout = 0, cout_pad = 0, w_ld = 0, k = 1; int64_t w_off = -1, b_off = -1; };
-struct LayerW { Lin qkv, o, ffn1, ffn2; int64_t g1 = -1, b1 = -1, g2 = -1, b2 = -1, pk = -1, pq = -1; };   // pk / pq: DeBERTa [H][D][2 span]
+// a Linear is a k = 1 ConvW (bv2_internal.h; the Generator-only stream offsets stay -1)
+struct LayerW { ConvW qkv, o, ffn1, ffn2; int64_t g1 = -1, b1 = -1, g2 = -1, b2 = -1, pk = -1, pq = -1; };   // pk / pq: DeBERTa [H][D][2 span]
 
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
-struct Carve {
-  char* base; int64_t off = 0, cap;
-  Carve(void* b, int64_t c) : base(static_cast<char*>(b)), cap(c) {}
-  float* get(int64_t n) {
-    float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off += (n * 4 + 255) / 256 * 256;
-    return p;
-  }
-  bool ok() const { return !base || off <= cap; }
-};
 
 }  // namespace
 
@@ -55,7 +44,7 @@ struct bv2_bert {
   const float* blob = nullptr;
   int64_t word = 0, pos = 0, type = 0, emb_g = 0, emb_b = 0, erv = 0, total = 0;
   int64_t tab = -1, conv_g = -1, conv_b = -1;           // DeBERTa-v2: relative index table, ConvLayer LayerNorm
-  Lin conv;                                             // DeBERTa-v2 ConvLayer (k = conv_kernel_size)
+  ConvW conv;                                           // DeBERTa-v2 ConvLayer (k = conv_kernel_size)
   std::vector<LayerW> layer;
   int prefetch = 3;                                     // bv2_bert_set_option("prefetch"): bit 0 LayerNorm / embedding launches, bit 1 GEMM launches carry the next GEMM's weights
   bool deberta() const { return cfg.arch == BV2_BERT_ARCH_DEBERTA_V2; }
@@ -67,7 +56,7 @@ struct bv2_bert {
 
 static thread_local std::string g_bert_create_err;
 
-static void lay_lin(Lin& l, int cin, int cout, int64_t& off, int k = 1) {
+static void lay_lin(ConvW& l, int cin, int cout, int64_t& off, int k = 1) {
   l.cin = cin; l.cin_pad = rup(cin, 16); l.cout = cout; l.cout_pad = rup(cout, 32); l.w_ld = rup(cout, 128); l.k = k;
   l.w_off = off; off += (int64_t)k * l.cin_pad * l.w_ld;
   l.b_off = off; off += l.w_ld;
@@ -163,7 +152,7 @@ const char* bv2_bert_last_error(const bv2_bert* h) { return h ? h->err.c_str() :
 int64_t bv2_bert_packed_bytes(const bv2_bert* h) { return h ? h->total * 4 : -1; }
 
 // place W [cout_src][cin] (PyTorch Linear) at output rows [row0, row0 + cout_src) of a fused projection, fragment order
-static void put_linear(float* blob, const Lin& l, int row0, const float* w, int rows, float scale) {
+static void put_linear(float* blob, const ConvW& l, int row0, const float* w, int rows, float scale) {
   for (int co = 0; co < rows; ++co)
     for (int ci = 0; ci < l.cin; ++ci)
       blob[l.w_off + conv_w_index(0, ci, row0 + co, l.cin_pad, 1)] = w[(size_t)co * l.cin + ci] * scale;
@@ -226,7 +215,7 @@ int bv2_bert_pack_tensor(bv2_bert* h, void* host_blob, int64_t blob_bytes, const
       LayerW& L = h->layer[li];
       // BERT: scores / sqrt(d); DeBERTa-v2: (QK + c2p + p2c) / sqrt(3 d) — folded into the query rows (QK and c2p) and into pos_query (p2c)
       const float qs = 1.0f / std::sqrt((float)h->D() * (h->deberta() ? 3.0f : 1.0f));
-      auto lin = [&](const Lin& l, int row0, int rows, int cin, float scale, bool is_w) {
+      auto lin = [&](const ConvW& l, int row0, int rows, int cin, float scale, bool is_w) {
         if (is_w) { if (!is2(rows, cin)) return bad(); put_linear(blob, l, row0, data, rows, scale); }
         else { if (!is1(rows)) return bad(); for (int r = 0; r < rows; ++r) blob[l.b_off + row0 + r] = data[r] * scale; }
         return 0;
@@ -287,20 +276,20 @@ int bv2_bert_attach_weights(bv2_bert* h, const void* dev_blob, int64_t bytes) {
 }
 
 struct BertPlan { float *x, *x1, *att, *qkv, *s, *f1, *mask, *emb; int64_t slab; int ld; };
-static BertPlan plan(const bv2_bert* h, Carve& A, int B, int S) {
+static BertPlan plan(const bv2_bert* h, Arena& A, int B, int S) {
   const bv2_bert_config& c = h->cfg;
   BertPlan p;
   const int64_t C = c.hidden_size, BS = (int64_t)B * S;
   p.ld = rup(S, 32);
   p.slab = BS * C;
-  p.x = A.get(BS * C);
-  p.x1 = A.get(BS * C);
-  p.att = A.get(BS * C);
-  p.qkv = A.get((int64_t)B * h->qkv_rows() * p.ld);
-  p.s = A.get(BV2_MAX_KSPLIT * BS * C);
-  p.f1 = A.get(BS * c.intermediate_size);
-  p.mask = A.get(BS);
-  p.emb = (h->deberta() && c.conv_kernel_size > 0) ? A.get(BS * C) : nullptr;     // the ConvLayer reads the embeddings after layer 0
+  p.x = A.get<float>(BS * C);
+  p.x1 = A.get<float>(BS * C);
+  p.att = A.get<float>(BS * C);
+  p.qkv = A.get<float>((int64_t)B * h->qkv_rows() * p.ld);
+  p.s = A.get<float>(BV2_MAX_KSPLIT * BS * C);
+  p.f1 = A.get<float>(BS * c.intermediate_size);
+  p.mask = A.get<float>(BS);
+  p.emb = (h->deberta() && c.conv_kernel_size > 0) ? A.get<float>(BS * C) : nullptr;     // the ConvLayer reads the embeddings after layer 0
   return p;
 }
 
@@ -313,7 +302,7 @@ int bv2_bert_set_option(bv2_bert* h, const char* key, int value) {
 
 int64_t bv2_bert_workspace_bytes(const bv2_bert* h, int B, int S) {
   if (!h || B < 1 || S < 1) return -1;
-  Carve A(nullptr, 0);
+  Arena A(nullptr, 0);
   (void)plan(h, A, B, S);
   return A.off;
 }
@@ -325,7 +314,7 @@ int bv2_bert_forward(bv2_bert* h, void* stream, int B, int S, const int64_t* inp
     const bv2_bert_config& c = h->cfg;
     if (!h->blob) { h->err = "bv2_bert_forward: no weights attached"; return -2; }
     if (B < 1 || S < 1 || S > c.max_position || !input_ids || !out || !workspace) { h->err = "bv2_bert_forward: bad argument (S <= max_position)"; return -1; }
-    Carve A(workspace, workspace_bytes);
+    Arena A(workspace, workspace_bytes);
     const BertPlan P = plan(h, A, B, S);
     if (!A.ok()) { h->err = "workspace too small for bv2_bert_forward"; return -5; }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -336,11 +325,8 @@ int bv2_bert_forward(bv2_bert* h, void* stream, int B, int S, const int64_t* inp
 
     const bool deb = h->deberta();
     if (deb && S > c.max_position) { h->err = "bv2_bert_forward: S exceeds the relative-position table (max_position)"; return -1; }
-    // the packed stream of a GEMM's weights as a prefetch target (bv2_kernels.h Prefetch): batch 1 only
-    auto pf_of = [&](const Lin* l, int bit) -> Prefetch {
-      if (!l || B != 1 || !(h->prefetch & bit) || l->w_off < 0) return Prefetch{nullptr, 0};
-      return Prefetch{W + l->w_off, (unsigned)((int64_t)(l->cout_pad / 32) * (l->cin_pad / 8) * l->k * 1024)};
-    };
+    // the packed stream of a GEMM's weights as a prefetch target: batch 1 only
+    auto pf_of = [&](const ConvW* l, int bit) { return weight_prefetch(l, W, B == 1 && (h->prefetch & bit)); };
     float* x_in = P.emb ? P.emb : P.x;               // layer 0 reads the embeddings from here (kept for the DeBERTa ConvLayer)
     BertEmbedArgs e;
     e.input_ids = input_ids; e.token_type_ids = token_type_ids;
@@ -353,19 +339,14 @@ int bv2_bert_forward(bv2_bert* h, void* stream, int B, int S, const int64_t* inp
     chk(launch_seq_mask(s, lengths, P.mask, B, S), "bert.mask");
 
     // y = W x + b as a k = 1 conv on [B][cin][S]; slabs > 1: K split across workgroups, the LayerNorm sums the partial slabs
-    auto gemm = [&](const Lin& l, const float* x, float* y, int act, const float* res, bool slabs, int out_rs, int64_t out_bs,
-                    const char* what, const float* out_mask = nullptr, const Lin* next = nullptr) -> int {
+    auto gemm = [&](const ConvW& l, const float* x, float* y, int act, const float* res, bool slabs, int out_rs, int64_t out_bs,
+                    const char* what, const float* out_mask = nullptr, const ConvW* next = nullptr) -> int {
       ConvLaunch cl;
       std::memset(&cl, 0, sizeof(cl));
       ConvProb& p = cl.p[0];
-      p.x[0] = x; p.nsrc = 1; p.in_scale = 1.f;
-      p.x_bstride = (int64_t)l.cin * S; p.x_rstride = S; p.Lin = S;
-      p.in_mask_bstride = S; p.out_mask_bstride = S;
-      p.w = W + l.w_off; p.bias = W + l.b_off;
-      p.out = y; p.out_bstride = out_bs; p.out_rstride = out_rs; p.out_tstride = 1; p.out_toff = 0;
-      p.res = res; p.res_bstride = out_bs; p.res_mode = res ? RES_ADD : RES_NONE;
-      p.cin = l.cin; p.cin_pad = l.cin_pad; p.cout = l.cout; p.cout_pad = l.cout_pad; p.w_ld = l.w_ld;
-      p.k = l.k; p.dil = 1; p.pad_left = (l.k - 1) / 2; p.slope = 0.1f; p.act = act;
+      p = conv_prob(l, W, x, y, S);
+      p.out_bstride = out_bs; p.out_rstride = out_rs; p.res_bstride = out_bs;
+      p.act = act; p.res = res; p.res_mode = res ? RES_ADD : RES_NONE;
       p.out_mask = out_mask; p.mask_pre = out_mask ? 1 : 0;          // (act(Wx + b)) * mask, then + residual
       cl.nprob = 1; cl.B = B; cl.L = S; cl.ksplit = 1; cl.slab_stride = P.slab;
       cl.pf = pf_of(next, 2);
@@ -374,7 +355,7 @@ int bv2_bert_forward(bv2_bert* h, void* stream, int B, int S, const int64_t* inp
       return cl.ksplit;
     };
     auto ln = [&](const float* a, int nslab, int64_t g, int64_t b, float* y, const char* what, const float* mask = nullptr,
-                  const Lin* next = nullptr) {
+                  const ConvW* next = nullptr) {
       BertLnArgs l;
       l.pf = pf_of(next, 1);
       l.a = a; l.nslab = nslab; l.slab_stride = P.slab; l.gamma = W + g; l.beta = W + b; l.eps = c.layer_norm_eps; l.mask = mask;
@@ -388,7 +369,7 @@ int bv2_bert_forward(bv2_bert* h, void* stream, int B, int S, const int64_t* inp
       const float* xin = i == 0 ? x_in : P.x;
       const bool last = i + 1 == c.num_layers_run;
       const bool conv_here = deb && i == 0 && c.conv_kernel_size > 0;
-      const Lin* next_qkv = (!last && !conv_here) ? &h->layer[i + 1].qkv : nullptr;
+      const ConvW* next_qkv = (!last && !conv_here) ? &h->layer[i + 1].qkv : nullptr;
       gemm(L.qkv, xin, P.qkv, ACT_NONE, nullptr, false, P.ld, (int64_t)R * P.ld, "bert.qkv", nullptr, &L.o);
       if (deb) {
         DebertaAttnArgs a;

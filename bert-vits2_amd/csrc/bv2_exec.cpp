@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "bv2_internal.h"
 
@@ -12,18 +13,14 @@ namespace bv2 {
 
 namespace {
 
-struct Arena {
-  char* base;
-  int64_t off = 0, cap;
-  Arena(void* b, int64_t c) : base(static_cast<char*>(b)), cap(c) {}
-  template <class T> T* get(int64_t n) {
-    const int64_t bytes = (n * (int64_t)sizeof(T) + 255) / 256 * 256;
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += bytes;
-    return p;
-  }
-  bool ok() const { return base == nullptr || off <= cap; }
-};
+// the shape part of a prof_mode 3 row (bench.py reads these keys): a conv launch's, and a ResBlock launch's
+inline std::string conv_shape(int nprob, int cin, int cout, int k, int L, int B) {
+  return " n" + std::to_string(nprob) + " " + std::to_string(cin) + ">" + std::to_string(cout) + " k" + std::to_string(k) + " L" +
+         std::to_string(L) + " B" + std::to_string(B);
+}
+inline std::string resblock_shape(int nb, int C, int k, int L, int B) {
+  return " n" + std::to_string(nb) + " C" + std::to_string(C) + " k" + std::to_string(k) + " L" + std::to_string(L) + " B" + std::to_string(B);
+}
 
 struct Ctx {
   bv2_handle* h;
@@ -50,7 +47,6 @@ struct Ctx {
     return i;
   }
   void prof_end(int i, const char* name, double flops, double bytes) {
-    if (i < 0) return;
     (void)hipEventRecord(h->prof_pool[i].e1, s);
     std::string key = name;
     if (h->prof_mode >= 3) key = std::string(cur_tag) + "|" + name + cur_shape;   // one row per launch site and shape
@@ -61,29 +57,45 @@ struct Ctx {
     h->prof_pool[i].fam = fam; h->prof_pool[i].flops = flops; h->prof_pool[i].bytes = bytes;
   }
 
-  void tap(const char* name, const float* src, int64_t n) {
-    if (h->taps.empty()) return;
-    auto it = h->taps.find(name);
-    if (it == h->taps.end()) return;
-    const int64_t c = n < it->second.cap ? n : it->second.cap;
-    (void)hipMemcpyAsync(it->second.dst, src, sizeof(float) * (size_t)c, hipMemcpyDeviceToDevice, s);
+  // The one timed launch: nothing once a launch has failed; the event records sit immediately around go(), which returns the launcher's
+  // code.  name: the row's name, or the const char** the launcher fills with the variant it picked.  shape: a callable returning the
+  // row's shape string, run only at prof_mode >= 3, or nullptr.  flops / bytes: values, or callables run only for a recorded launch.
+  // A site without a shape leaves cur_shape alone, so at mode 3 its row carries the shape of the conv launched before it (the attention
+  // and flow.boundary rows; bench.py reads the keys as they are — to be fixed on its own).
+  static const char* name_of(const char* n) { return n; }
+  static const char* name_of(const char** n) { return *n; }
+  template <class V> static double value_of(const V& v) {
+    if constexpr (std::is_arithmetic_v<V>) return v; else return v();
+  }
+  template <class Name, class Shape, class Flops, class Bytes, class Go>
+  void timed(const char* tag, Name name, const Shape& shape, const Flops& flops, const Bytes& bytes, const Go& go) {
+    if (rc) return;
+    const int pi = prof_begin(tag);
+    if constexpr (!std::is_same_v<Shape, std::nullptr_t>)
+      if (pi >= 0 && h->prof_mode >= 3) cur_shape = shape();
+    const int r = go();
+    if (pi >= 0) prof_end(pi, name_of(name), value_of(flops), value_of(bytes));
+    if (r) fail(tag, r);
   }
 
-  // conv problem with the defaults of a "same"-padded Conv1d on a dense [B,C,L] tensor
-  ConvProb prob(const ConvW& w, const float* x, float* out, int L, int dil = 1) const {
-    ConvProb p;
-    std::memset(&p, 0, sizeof(p));
-    p.x[0] = x; p.nsrc = 1; p.in_scale = 1.f;
-    p.x_bstride = (int64_t)w.cin * L; p.x_rstride = L; p.Lin = L;
-    p.in_mask_bstride = L; p.out_mask_bstride = L;
-    p.w = W(w.w_off); p.bias = W(w.b_off);
-    p.out = out; p.out_bstride = (int64_t)w.cout * L; p.out_rstride = L; p.out_tstride = 1; p.out_toff = 0;
-    p.res_bstride = p.out_bstride;
-    p.cin = w.cin; p.cin_pad = w.cin_pad; p.cout = w.cout; p.cout_pad = w.cout_pad; p.w_ld = w.w_ld;
-    p.k = w.k; p.dil = dil; p.pad_left = ((w.k - 1) / 2) * dil;
-    p.slope = 0.1f;
-    return p;
+  // debug taps (tests).  The name is the parts joined, ints in decimal; it is built only when a tap is set (never in the product)
+  static void name_part(std::string& s, const char* p) { s += p; }
+  static void name_part(std::string& s, int v) { s += std::to_string(v); }
+  template <class... Parts> const Tap* find_tap(const Parts&... parts) const {
+    if (h->taps.empty()) return nullptr;
+    std::string name;
+    (name_part(name, parts), ...);
+    const auto it = h->taps.find(name);
+    return it == h->taps.end() ? nullptr : &it->second;
   }
+  template <class... Parts> void tap(const float* src, int64_t n, const Parts&... parts) {
+    const Tap* t = find_tap(parts...);
+    if (!t) return;
+    const int64_t c = n < t->cap ? n : t->cap;
+    (void)hipMemcpyAsync(t->dst, src, sizeof(float) * (size_t)c, hipMemcpyDeviceToDevice, s);
+  }
+
+  ConvProb prob(const ConvW& w, const float* x, float* out, int L, int dil = 1) const { return conv_prob(w, blob, x, out, L, dil); }
   // Launch; returns the number of partial slabs written per output (1 unless the split-K kernel was allowed to split K
   // across workgroups: max_split > 1 means the CONSUMER sums `slab_stride`-spaced slabs).
   int conv(ConvLaunch& L, const char* tag, int max_split = 1, int64_t slab_stride = 0) {
@@ -91,15 +103,8 @@ struct Ctx {
     L.ksplit = 1; L.slab_stride = slab_stride;
     if (max_split > 1 && conv_use_splitk(L)) L.ksplit = conv_pick_ksplit(L, max_split);
     const char* vn = "conv1d_mfma";
-    const int pi = prof_begin(tag);
-    if (pi >= 0 && h->prof_mode >= 3) {
-      const ConvProb& q = L.p[0];
-      cur_shape = " n" + std::to_string(L.nprob) + " " + std::to_string(q.cin) + ">" + std::to_string(q.cout) + " k" +
-                  std::to_string(q.k) + " L" + std::to_string(L.L) + " B" + std::to_string(L.B) + " s" + std::to_string(L.ksplit);
-    }
-    const int r = launch_conv1d(s, L, TILE_AUTO, &vn);
-    prof_end(pi, vn, conv_flops(L), conv_bytes(L));
-    if (r) fail(tag, r);
+    timed(tag, &vn, [&] { return conv_shape(L.nprob, L.p[0].cin, L.p[0].cout, L.p[0].k, L.L, L.B) + " s" + std::to_string(L.ksplit); },
+          [&] { return conv_flops(L); }, [&] { return conv_bytes(L); }, [&] { return launch_conv1d(s, L, TILE_AUTO, &vn); });
     return L.ksplit;
   }
   int conv1(const ConvProb& p, int B, int L, const char* tag, int max_split = 1, int64_t slab_stride = 0,
@@ -108,12 +113,8 @@ struct Ctx {
     cl.p[0] = p; cl.nprob = 1; cl.B = B; cl.L = L; cl.lens = lens; cl.len_mul = len_mul; cl.pf = pf;
     return conv(cl, tag, max_split, slab_stride);
   }
-  // the packed fp32 stream of a conv (m-tile-major: what the split-K kernel's XCDs read in contiguous eighths) as a prefetch target;
-  // bit 0 of the "prefetch" option: LayerNorm launches carry one, bit 1: split-K launches do.  Batch 1 only.
-  Prefetch pf_of(const ConvW& w, int B, int bit) const {
-    if (B != 1 || !(h->prefetch & bit) || w.w_off < 0) return Prefetch{nullptr, 0};
-    return Prefetch{W(w.w_off), (unsigned)((int64_t)(w.cout_pad / 32) * (w.cin_pad / 8) * w.k * 1024)};
-  }
+  // bit 0 of the "prefetch" option: LayerNorm launches carry a conv's weight stream, bit 1: split-K launches do.  Batch 1 only.
+  Prefetch pf_of(const ConvW& w, int B, int bit) const { return weight_prefetch(&w, blob, B == 1 && (h->prefetch & bit)); }
   // fp16 Encoder conv (kernels/enc_f16.hip) on dense tensors: in_ct/out_ct select fp32 [B][C][T] vs fp16 [B][T][C]
   HcProb hprob(const ConvW& w, const void* x, bool in_ct, void* out, bool out_ct, int L) const {
     HcProb p;
@@ -130,19 +131,13 @@ struct Ctx {
   // the batch fills the eight XCDs about evenly
   bool xcd_affine(int B) const { return !h->no_xcd_affine && B >= 8 && (B % 8 == 0 || B >= 32); }
   void conv_h(const HcProb& p, int B, int L, const char* tag, const HcProb* p2 = nullptr, bool xcd = false) {
-    if (rc) return;
     HcLaunch hl;
     hl.p[0] = p; hl.nprob = 1; hl.B = B; hl.L = L; hl.xcd_b = xcd ? 1 : 0; hl.no_ksplit = h->no_f16_ksplit ? 1 : 0;
     hl.wn_pref = h->f16_wn; hl.ni_pref = h->f16_ni;
     if (p2) { hl.p[1] = *p2; hl.nprob = 2; }
     const char* vn = "conv_f16";
-    const int pi = prof_begin(tag);
-    if (pi >= 0 && h->prof_mode >= 3)
-      cur_shape = " n1 " + std::to_string(p.cin) + ">" + std::to_string(p.cout) + " k" + std::to_string(p.k) + " L" +
-                  std::to_string(L) + " B" + std::to_string(B);
-    const int r = launch_conv_f16(s, hl, &vn);
-    prof_end(pi, vn, conv_f16_flops(hl), conv_f16_bytes(hl));
-    if (r) fail(tag, r);
+    timed(tag, &vn, [&] { return conv_shape(1, p.cin, p.cout, p.k, L, B); },      // "n1" also with p2: the row keys stay as they are
+          [&] { return conv_f16_flops(hl); }, [&] { return conv_f16_bytes(hl); }, [&] { return launch_conv_f16(s, hl, &vn); });
   }
   void ln(const LnArgs& a, const char* tag) {
     if (rc) return;
@@ -210,12 +205,8 @@ void run_encoder(Ctx& c, const EncoderW& e, const EncBufs& b, const float* mask,
       if (ks > 1) { a.ksplit = ks; a.ml_out = b.ml; }
       else { a.bo = c.W(L.o.b_off); a.res = b.x; }
     }
-    if (!c.rc) {
-      const int pi = c.prof_begin("attention");
-      const int r = launch_attention(c.s, a);
-      c.prof_end(pi, "attention_relpos", attention_flops(a), 4.0 * B * 4 * H * (double)T);
-      if (r) c.fail("attention", r);
-    }
+    c.timed("attention", "attention_relpos", nullptr, [&] { return attention_flops(a); }, 4.0 * B * 4 * H * (double)T,
+            [&] { return launch_attention(c.s, a); });
     int ns = 1;
     if (fuse_o) {
       ns = e.heads * ks;
@@ -263,7 +254,7 @@ void run_encoder(Ctx& c, const EncoderW& e, const EncBufs& b, const float* mask,
       ns = c.conv1(p, B, T, "enc.ffn2", kSlabs, b.slab);
     }
     if (ln2_in_conv) {                             // x already holds LN2's output
-      if (tapname) c.tap((std::string(tapname) + ".layer." + std::to_string(i)).c_str(), b.x, (int64_t)B * H * T);
+      if (tapname) c.tap(b.x, (int64_t)B * H * T, tapname, ".layer.", i);
       continue;
     }
     l.a = b.s; l.nslab = ns; l.gamma = c.W(L.g2.off); l.beta = c.W(L.b2.off);
@@ -279,20 +270,12 @@ void run_encoder(Ctx& c, const EncoderW& e, const EncBufs& b, const float* mask,
       fb->mask = mask; fb->B = B; fb->C = H; fb->T = T;
       fb->launched = flow_boundary_supported(*fb) ? 1 : 0;
     }
-    if (fb && i + 1 == e.n_layers && fb->launched) {
-      if (!c.rc) {
-        const int pi = c.prof_begin("flow.boundary");
-        const int r = launch_flow_boundary(c.s, *fb);
-        c.prof_end(pi, "flow_boundary", 2.0 * B * T * (double)H * fb->C1 * (fb->pre_w ? 2 : 1),
-                   4.0 * B * T * ((double)H * (l.nslab + (fb->pre_w ? 1 : 0)) + 2.0 * fb->C1));
-        if (r) c.fail("flow.boundary", r);
-      }
-    } else
-    c.ln(l, "enc.ln2");
-    if (tapname) {
-      const std::string tn = std::string(tapname) + ".layer." + std::to_string(i);
-      c.tap(tn.c_str(), b.x, (int64_t)B * H * T);
-    }
+    if (fb && i + 1 == e.n_layers && fb->launched)
+      c.timed("flow.boundary", "flow_boundary", nullptr, 2.0 * B * T * (double)H * fb->C1 * (fb->pre_w ? 2 : 1),
+              4.0 * B * T * ((double)H * (l.nslab + (fb->pre_w ? 1 : 0)) + 2.0 * fb->C1), [&] { return launch_flow_boundary(c.s, *fb); });
+    else
+      c.ln(l, "enc.ln2");
+    if (tapname) c.tap(b.x, (int64_t)B * H * T, tapname, ".layer.", i);
   }
 }
 
@@ -489,6 +472,13 @@ PlanS plan_stream(Arena& A, const Model& m, int B, int Ty, int gen_frames, int p
   return p;
 }
 
+// the check that opens every entry with a workspace: 0, or -5 with the entry named in the handle's error when its plan did not fit
+int ws_short(bv2_handle* h, const Arena& A, const char* entry) {
+  if (A.ok()) return 0;
+  h->err = std::string("workspace too small for ") + entry;
+  return -5;
+}
+
 }  // namespace
 
 int64_t workspace_bytes(const Model& m, int B, int T, int Ty) {
@@ -564,7 +554,7 @@ static void enc_p_core(Ctx& c, PlanA& P, const int64_t* x, const int64_t* tone, 
     }
     c.chk(launch_embed(c.s, e), "embed");
   }
-  c.tap("enc.x0", out_x, (int64_t)B * H * T);
+  c.tap(out_x, (int64_t)B * H * T, "enc.x0");
   run_encoder(c, m.enc, P.enc, mask, spk, spk_stride, B, T, "enc", false, dp0, dp_c, spk_stride);
   {
     ConvLaunch cl;
@@ -618,7 +608,7 @@ static void sdp_core(Ctx& c, PlanA& P, const float* x, const float* mask, const 
     p.out_mask = mask; p.mask_post = 1;
     c.conv1(p, B, T, "sdp.proj");
   }
-  c.tap("sdp.x", P.sdp_x, (int64_t)B * H * T);
+  c.tap(P.sdp_x, (int64_t)B * H * T, "sdp.x");
   // Flip, CF, Flip, CF, Flip, CF, Flip, EA: the 2-channel flips are index swaps (src/dst), never data movement
   for (int i = 0; i < kSdpFlowsUsed; ++i) {
     const int src = (i % 2 == 0) ? 1 : 0, dst = 1 - src;
@@ -638,8 +628,7 @@ static void sdp_core(Ctx& c, PlanA& P, const float* x, const float* mask, const 
       c.conv1(p, B, T, "cf.proj");
       c.chk(launch_spline(c.s, P.z, src, dst, P.params, 32, mask, sqrt_fc, 5.0f, B, T), "cf.spline");
     }
-    const std::string tn = "sdp.z." + std::to_string(i);
-    c.tap(tn.c_str(), P.z, (int64_t)B * 2 * T);
+    c.tap(P.z, (int64_t)B * 2 * T, "sdp.z.", i);
   }
 }
 
@@ -667,7 +656,7 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   const int B = in.B, T = in.T, H = cf.hidden_channels;
   Arena A(ws, wsb);
   PlanA P = plan_a(A, m, B, T);
-  if (!A.ok()) { h->err = "workspace too small for bv2_encode_durations"; return -5; }
+  if (int e = ws_short(h, A, "bv2_encode_durations")) return e;
   Ctx c{h, s, m, h->blob};
   const float* mask = out.x_mask;
 
@@ -750,7 +739,7 @@ int run_stage_enc_p(bv2_handle* h, hipStream_t s, int B, int T, const int64_t* x
   const int H = m.cfg.hidden_channels;
   Arena A(ws, wsb);
   PlanA P = plan_a(A, m, B, T);
-  if (!A.ok()) { h->err = "workspace too small for bv2_stage_enc_p"; return -5; }
+  if (int e = ws_short(h, A, "bv2_stage_enc_p")) return e;
   Ctx c{h, s, m, h->blob};
   const GemvW* gw[1] = {&m.enc.spk};
   float* go[1] = {P.gv};
@@ -766,7 +755,7 @@ int run_stage_sdp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, co
   const int H = m.cfg.hidden_channels;
   Arena A(ws, wsb);
   PlanA P = plan_a(A, m, B, T);
-  if (!A.ok()) { h->err = "workspace too small for bv2_stage_sdp"; return -5; }
+  if (int e = ws_short(h, A, "bv2_stage_sdp")) return e;
   Ctx c{h, s, m, h->blob};
   const GemvW* gw[1] = {&m.sdp_cond};
   float* go[1] = {P.gv + H};
@@ -782,7 +771,7 @@ int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, con
   const int H = m.cfg.hidden_channels;
   Arena A(ws, wsb);
   PlanA P = plan_a(A, m, B, T);
-  if (!A.ok()) { h->err = "workspace too small for bv2_stage_dp"; return -5; }
+  if (int e = ws_short(h, A, "bv2_stage_dp")) return e;
   Ctx c{h, s, m, h->blob};
   const GemvW* gw[1] = {&m.dp_cond};
   float* go[1] = {P.gv + 2 * H};
@@ -888,19 +877,30 @@ static void flow_core(Ctx& c, const PlanB& P, float* z, const float* ymask, cons
       }
       hres = P.outacc;
     }
-    {
-      const std::string tn = "flow." + std::to_string(a) + ".enc";
-      c.tap(tn.c_str(), hres, (int64_t)B * H * Ty);
-    }
+    c.tap(hres, (int64_t)B * H * Ty, "flow.", a, ".enc");
     p = c.prob(K.post, hres, x1, Ty);                          // x1 = (x1 - post(h)) * mask, written in place
     p.out_bstride = (int64_t)C * Ty; p.res = x1; p.res_bstride = (int64_t)C * Ty; p.res_mode = RES_RSUB;
     p.out_mask = ymask; p.mask_post = 1;
     c.conv1(p, B, Ty, "flow.post");
-    {
-      const std::string tn = "flow." + std::to_string(a) + ".z";
-      c.tap(tn.c_str(), z, (int64_t)B * C * Ty);
-    }
+    c.tap(z, (int64_t)B * C * Ty, "flow.", a, ".z");
   }
+}
+
+// The buffers of one ResBlock branch of a Generator stage at dilation step d (S: the stage's buffer set, x: the stage's input).  Branches
+// are launched widest kernel first: slot jj of a launch is branch j = nb - 1 - jj.  A branch owns S[1 + j] and S[1 + nb + j] and always ends
+// in S[1 + j], by one of two schemes.  Two convs per step: tmp = conv_1(in), cur = conv_2(tmp) + in, so every step reads and writes `cur`.
+// One launch per step (a tile reads its neighbours' halo, so never in place): the step reads pp_in and writes pp_out, which ping-pong
+// between the two buffers so that the last step writes S[1 + j].
+template <class T> struct BranchBufs { int j; T *cur, *tmp; const T *in, *pp_in; T* pp_out; };
+template <class T> BranchBufs<T> branch_bufs(float* const* S, int nb, int n_rbd, const T* x, int jj, int d) {
+  BranchBufs<T> b;
+  b.j = nb - 1 - jj;
+  b.cur = reinterpret_cast<T*>(S[1 + b.j]); b.tmp = reinterpret_cast<T*>(S[1 + nb + b.j]);
+  const bool to_cur = ((n_rbd - 1 - d) & 1) == 0;
+  b.in = d == 0 ? x : b.cur;
+  b.pp_in = d == 0 ? x : (to_cur ? b.tmp : b.cur);
+  b.pp_out = to_cur ? b.cur : b.tmp;
+  return b;
 }
 
 // Generator.forward (reference models.py:538-557)
@@ -917,7 +917,7 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
     p.bias2 = P.gv; p.bias2_bstride = P.gv_stride;
     c.conv1(p, B, L, "dec.conv_pre", 1, 0, lens, 1);
   }
-  c.tap("dec.pre", P.pre, (int64_t)B * c0 * L);
+  c.tap(P.pre, (int64_t)B * c0 * L, "dec.pre");
   const float* src[3] = {P.pre, nullptr, nullptr};
   int nsrc = 1;
   int Lc = L;
@@ -973,48 +973,36 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
       }
       c.conv(cl, "dec.ups");
     }
-    {
-      const std::string tn = "dec.ups." + std::to_string(i);
-      c.tap(tn.c_str(), x, (int64_t)B * U.cout * Lo);
-    }
-    float* branch_out[BV2_MAX_RESBLOCK_KERNELS];
+    c.tap(x, (int64_t)B * U.cout * Lo, "dec.ups.", i);
     if (rb2) {
       // modules.ResBlock2 (reference modules.py:348-357): for each of the two dilations x = x + conv_d(lrelu(x)) — one conv per launch
-      // with the residual in its epilogue, the branches side by side; branch j ping-pongs between S[1 + nb + j] and S[1 + j] and ends in S[1 + j]
+      // with the residual in its epilogue, the branches side by side (branch_bufs: the ping-pong scheme)
       for (int d = 0; d < m.n_rbd; ++d) {
         ConvLaunch c1;
         c1.nprob = nb; c1.B = B; c1.L = Lo; c1.lens = lens; c1.len_mul = up * U.u;
-        const bool to_cur = ((m.n_rbd - 1 - d) & 1) == 0;
         for (int jj = 0; jj < nb; ++jj) {
-          const int j = nb - 1 - jj;                            // widest kernel first
-          float* cur = S[1 + j];
-          float* tmp = S[1 + nb + j];
-          const float* xin = d == 0 ? x : (to_cur ? tmp : cur);
-          ConvProb p = c.prob(m.rb[i][j][d][0], xin, to_cur ? cur : tmp, Lo, cf.resblock_dilation_sizes[j][d]);
+          const auto bb = branch_bufs<float>(S, nb, m.n_rbd, x, jj, d);
+          const int j = bb.j;
+          ConvProb p = c.prob(m.rb[i][j][d][0], bb.pp_in, bb.pp_out, Lo, cf.resblock_dilation_sizes[j][d]);
           p.pre_act = PRE_LRELU; p.slope = 0.1f;
-          p.res = xin; p.res_mode = RES_ADD;
+          p.res = bb.pp_in; p.res_mode = RES_ADD;
           p.w6 = (!c.h->no_conv_x6 && m.rb[i][j][d][0].wx_off >= 0) ? reinterpret_cast<const uint16_t*>(c.W(m.rb[i][j][d][0].wx_off)) : nullptr;
           c1.p[jj] = p;
         }
         c.conv(c1, "dec.resblock2.conv");
       }
-      for (int j = 0; j < nb; ++j) branch_out[j] = S[1 + j];
     } else if (fused) {
-      // narrow stages: ONE launch per dilation step = the whole (conv, conv) pair of every branch, intermediate in LDS;
-      // the pair ping-pongs between the branch's two buffers (a tile reads its neighbours' halo: no in-place update)
-      for (int j = 0; j < nb; ++j) branch_out[j] = nullptr;
+      // narrow stages: ONE launch per dilation step = the whole (conv, conv) pair of every branch, intermediate in LDS
+      // (branch_bufs: the ping-pong scheme)
       for (int d = 0; d < m.n_rbd; ++d) {
         FusedLaunch F;
         std::memset(&F, 0, sizeof(F));
         F.nprob = nb; F.B = B; F.C = U.cout; F.L = Lo; F.slope = 0.1f; F.lens = lens; F.len_mul = up * U.u;
         for (int jj = 0; jj < nb; ++jj) {
-          const int j = nb - 1 - jj;                            // widest kernel first
-          float* a = S[1 + j];
-          float* b2 = S[1 + nb + j];
-          const float* xin = d == 0 ? x : branch_out[j];
-          float* xout = (xin == a) ? b2 : a;
+          const auto bb = branch_bufs<float>(S, nb, m.n_rbd, x, jj, d);
+          const int j = bb.j;
           FusedProb& p = F.p[jj];
-          p.x = xin; p.out = xout;
+          p.x = bb.pp_in; p.out = bb.pp_out;
           p.w1 = c.W(m.rb[i][j][d][0].w_off); p.b1 = c.W(m.rb[i][j][d][0].b_off);
           p.w2 = c.W(m.rb[i][j][d][1].w_off); p.b2 = c.W(m.rb[i][j][d][1].b_off);
           p.k = m.rb[i][j][d][0].k; p.dil = cf.resblock_dilation_sizes[j][d];
@@ -1027,18 +1015,12 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
               p.w32 = reinterpret_cast<const uint16_t*>(p.w3inv2 + X3_HDR_FLOATS);
             }
           }
-          branch_out[j] = xout;
         }
-        if (!c.rc) {
-          const int pi = c.prof_begin("dec.resblock.fused");
-          if (pi >= 0 && c.h->prof_mode >= 3)
-            c.cur_shape = " n" + std::to_string(nb) + " C" + std::to_string(U.cout) + " k" + std::to_string(F.p[0].k) + " L" +
-                          std::to_string(Lo) + " B" + std::to_string(B);
-          const int r = x6pair ? launch_respair_x6(c.s, F) : launch_resblock_fused(c.s, F);
-          c.prof_end(pi, x6pair ? (F.p[0].w31 ? (U.cout == 16 ? "respair_x3<16>" : U.cout == 32 ? "respair_x3<32>" : (U.cout == 64 ? "respair_x3<64>" : "respair_x3<128>"))
-                                              : (U.cout == 16 ? "respair_x6<16>" : U.cout == 32 ? "respair_x6<32>" : (U.cout == 64 ? "respair_x6<64>" : "respair_x6<128>"))) : "resblock_fused", resblock_fused_flops(F), resblock_fused_bytes(F));
-          if (r) c.fail("dec.resblock.fused", r);
-        }
+        c.timed("dec.resblock.fused",
+                x6pair ? (F.p[0].w31 ? (U.cout == 16 ? "respair_x3<16>" : U.cout == 32 ? "respair_x3<32>" : (U.cout == 64 ? "respair_x3<64>" : "respair_x3<128>"))
+                                              : (U.cout == 16 ? "respair_x6<16>" : U.cout == 32 ? "respair_x6<32>" : (U.cout == 64 ? "respair_x6<64>" : "respair_x6<128>"))) : "resblock_fused",
+                [&] { return resblock_shape(nb, U.cout, F.p[0].k, Lo, B); }, [&] { return resblock_fused_flops(F); },
+                [&] { return resblock_fused_bytes(F); }, [&] { return x6pair ? launch_respair_x6(c.s, F) : launch_resblock_fused(c.s, F); });
       }
     } else {
       // wide stages: 2 launches per dilation step, each carrying all branches
@@ -1048,10 +1030,8 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
         c1.nprob = c2.nprob = nb; c1.B = c2.B = B; c1.L = c2.L = Lo;
         c1.lens = c2.lens = lens; c1.len_mul = c2.len_mul = up * U.u;
         for (int jj = 0; jj < nb; ++jj) {
-          const int j = nb - 1 - jj;                            // widest kernel first: longest workgroups start first
-          float* cur = S[1 + j];
-          float* tmp = S[1 + nb + j];
-          const float* xin = d == 0 ? x : cur;
+          const auto bb = branch_bufs<float>(S, nb, m.n_rbd, x, jj, d);   // widest kernel first: longest workgroups start first
+          const int j = bb.j;
           const bool x6 = !c.h->no_conv_x6;                       // the split-bf16 planes ride along: launch_conv1d picks conv_x6.hip
           auto planes3 = [&](ConvProb& q, const ConvW& w, const unsigned* in_slot, unsigned* out_slot) {
             if (!x3) return;
@@ -1061,14 +1041,14 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
           };
           unsigned* const slot_tmp = x3 ? P.xslots + X3_SLOT_WORDS * next_slot++ : nullptr;
           unsigned* const slot_out = (x3 && d + 1 < m.n_rbd) ? P.xslots + X3_SLOT_WORDS * next_slot++ : nullptr;   // the last step's output feeds no x3 conv
-          ConvProb p = c.prob(m.rb[i][j][d][0], xin, tmp, Lo, cf.resblock_dilation_sizes[j][d]);
+          ConvProb p = c.prob(m.rb[i][j][d][0], bb.in, bb.tmp, Lo, cf.resblock_dilation_sizes[j][d]);
           p.pre_act = PRE_LRELU; p.slope = 0.1f;
           p.w6 = (x6 && m.rb[i][j][d][0].wx_off >= 0) ? reinterpret_cast<const uint16_t*>(c.W(m.rb[i][j][d][0].wx_off)) : nullptr;
           planes3(p, m.rb[i][j][d][0], d == 0 ? slot_x : slot_cur[j], slot_tmp);
           c1.p[jj] = p;
-          p = c.prob(m.rb[i][j][d][1], tmp, cur, Lo, 1);
+          p = c.prob(m.rb[i][j][d][1], bb.tmp, bb.cur, Lo, 1);
           p.pre_act = PRE_LRELU; p.slope = 0.1f;
-          p.res = xin; p.res_mode = RES_ADD;
+          p.res = bb.in; p.res_mode = RES_ADD;
           p.w6 = (x6 && m.rb[i][j][d][1].wx_off >= 0) ? reinterpret_cast<const uint16_t*>(c.W(m.rb[i][j][d][1].wx_off)) : nullptr;
           planes3(p, m.rb[i][j][d][1], slot_tmp, slot_out);
           c2.p[jj] = p;
@@ -1077,13 +1057,9 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
         c.conv(c1, "dec.resblock.convs1");
         c.conv(c2, "dec.resblock.convs2");
       }
-      for (int j = 0; j < nb; ++j) branch_out[j] = S[1 + j];
     }
-    for (int j = 0; j < nb; ++j) {
-      const std::string tn = "dec.rb." + std::to_string(i) + "." + std::to_string(j);
-      c.tap(tn.c_str(), branch_out[j], (int64_t)B * U.cout * Lo);
-    }
-    for (int j = 0; j < 3; ++j) src[j] = j < nb ? branch_out[j] : nullptr;
+    for (int j = 0; j < nb; ++j) c.tap(S[1 + j], (int64_t)B * U.cout * Lo, "dec.rb.", i, ".", j);
+    for (int j = 0; j < 3; ++j) src[j] = j < nb ? S[1 + j] : nullptr;       // every scheme ends branch j in S[1 + j]
     nsrc = nb;
     Lc = Lo;
     up *= U.u;
@@ -1121,17 +1097,9 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
     return p;
   };
   auto launch = [&](ClLaunch& cl, const char* tag, double flops) {
-    if (c.rc) return;
     const char* vn = "conv_cl_bf16";
-    const int pi = c.prof_begin(tag);
-    if (pi >= 0 && c.h->prof_mode >= 3) {
-      const ClProb& q = cl.p[0];
-      c.cur_shape = " n" + std::to_string(cl.nprob) + " " + std::to_string(q.cin) + ">" + std::to_string(q.cout) + " k" +
-                    std::to_string(q.k) + " L" + std::to_string(cl.L) + " B" + std::to_string(cl.B);
-    }
-    const int r = launch_conv_cl_bf16(c.s, cl, &vn);
-    c.prof_end(pi, vn, flops, conv_cl_bytes(cl));
-    if (r) c.fail(tag, r);
+    c.timed(tag, &vn, [&] { return conv_shape(cl.nprob, cl.p[0].cin, cl.p[0].cout, cl.p[0].k, cl.L, cl.B); }, flops,
+            [&] { return conv_cl_bytes(cl); }, [&] { return launch_conv_cl_bf16(c.s, cl, &vn); });
   };
   auto flops_of = [&](const ClLaunch& cl) {
     double f = 0;
@@ -1140,11 +1108,9 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
   };
 
   // debug taps (tests): widen a bf16 channels-last tensor into the caller's fp32 [B][C][L] tap buffer
-  auto tap_cl = [&](const std::string& name, const uint16_t* x, int Cc, int Lc) {
-    if (c.h->taps.empty() || c.rc) return;
-    auto it = c.h->taps.find(name);
-    if (it == c.h->taps.end() || it->second.cap < (int64_t)B * Cc * Lc) return;
-    c.chk(launch_uncast_cl(c.s, x, it->second.dst, B, Cc, Lc), "tap");
+  auto tap_cl = [&](const uint16_t* x, int Cc, int Lc, auto... name_parts) {
+    const Tap* t = c.rc ? nullptr : c.find_tap(name_parts...);
+    if (t && t->cap >= (int64_t)B * Cc * Lc) c.chk(launch_uncast_cl(c.s, x, t->dst, B, Cc, Lc), "tap");
   };
 
   uint16_t* zc = U16(P.set[1][0]);                // dead before stage 1 writes set[1][0]
@@ -1157,7 +1123,7 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
     cl.p[0].bias2 = P.gv; cl.p[0].bias2_bstride = P.gv_stride;
     launch(cl, "dec.conv_pre", flops_of(cl));
   }
-  tap_cl("dec.pre", pre, c0, L);
+  tap_cl(pre, c0, L, "dec.pre");
   const uint16_t* src[3] = {pre, nullptr, nullptr};
   int nsrc = 1, Lc = L, up = 1;
   for (int i = 0; i < m.n_ups; ++i) {
@@ -1185,7 +1151,7 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
       // algorithmic FLOPs: the true taps of the transposed conv (the zero-padded window taps are not counted)
       launch(cl, "dec.ups", 2.0 * U.cin * U.cout * U.k * (double)Lc * B);
     }
-    tap_cl("dec.ups." + std::to_string(i), x, U.cout, Lo);
+    tap_cl(x, U.cout, Lo, "dec.ups.", i);
     const int nb = m.n_rbk;
     const bool rb2 = m.rb_type == 2;
     bool whole = nb <= 3 && !c.h->no_fused_resblock && !rb2;
@@ -1227,18 +1193,12 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
           F.p[jj].w = reinterpret_cast<const uint16_t*>(c.W(m.rb16_w_off[i][j])); F.p[jj].bias = c.W(m.rb16_b_off[i][j]);
         }
       if (c16 && want_sum) { F.sum_out = sum_t; summed = true; }
-      if (!c.rc) {
-        const int pi = c.prof_begin("dec.resblock.whole");
-        if (pi >= 0 && c.h->prof_mode >= 3)
-          c.cur_shape = " n" + std::to_string(nb) + " C" + std::to_string(U.cout) + " k" + std::to_string(F.p[0].k) + " L" +
-                        std::to_string(Lo) + " B" + std::to_string(B);
-        const int r = c16 ? launch_resblock_c16_bf16(c.s, F) : launch_resblock_cl_bf16(c.s, F);
-        c.prof_end(pi, c16 ? "resblock_c16_bf16" : "resblock_cl_bf16", resblock_cl_bf16_flops(F), resblock_cl_bf16_bytes(F));
-        if (r) c.fail("dec.resblock.whole", r);
-      }
+      c.timed("dec.resblock.whole", c16 ? "resblock_c16_bf16" : "resblock_cl_bf16", [&] { return resblock_shape(nb, U.cout, F.p[0].k, Lo, B); },
+              [&] { return resblock_cl_bf16_flops(F); }, [&] { return resblock_cl_bf16_bytes(F); },
+              [&] { return c16 ? launch_resblock_c16_bf16(c.s, F) : launch_resblock_cl_bf16(c.s, F); });
     }
     // wide stages: one (dilated conv, conv) pair per launch, the intermediate in LDS (respair_cl_bf16.hip).  A tile's halo rows are
-    // another tile's outputs, so a pair never runs in place: branch j ping-pongs between S[1 + j] and S[1 + nb + j] and ends in S[1 + j]
+    // another tile's outputs, so a pair never runs in place (branch_bufs: the ping-pong scheme)
     bool pairs = !rb2 && !whole && nb <= 3 && !c.h->no_fused_respair && !narrow_layerwise;
     for (int j = 0; j < nb && pairs; ++j)
       for (int d = 0; d < m.n_rbd && pairs; ++d)
@@ -1250,42 +1210,28 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
       F.nprob = nb; F.B = B; F.C = U.cout; F.L = Lo; F.slope = 0.1f; F.lens = lens; F.len_mul = up * U.u;
       F.mix = c.h->respair_problem_major ? 0 : 1;
       F.form = c.h->respair_form;
-      const bool to_cur = ((m.n_rbd - 1 - d) & 1) == 0;
       if (want_sum && d + 1 == m.n_rbd) { F.sum_out = sum_t; summed = true; }     // the stage's last pair launch leaves the branch mean
       for (int jj = 0; jj < nb; ++jj) {
-        const int j = nb - 1 - jj;                                // widest kernel first
-        uint16_t* cur = U16(S[1 + j]);
-        uint16_t* tmp = U16(S[1 + nb + j]);
+        const auto bb = branch_bufs<uint16_t>(S, nb, m.n_rbd, x, jj, d);
+        const int j = bb.j;
         RpClProb& p = F.p[jj];
-        p.x = d == 0 ? x : (to_cur ? tmp : cur);
-        p.out = to_cur ? cur : tmp;
+        p.x = bb.pp_in; p.out = bb.pp_out;
         p.w1 = Wb(m.rb[i][j][d][0]); p.w2 = Wb(m.rb[i][j][d][1]);
         p.b1 = c.W(m.rb[i][j][d][0].b_off); p.b2 = c.W(m.rb[i][j][d][1].b_off);
         p.k = m.rb[i][j][d][0].k; p.dil = cf.resblock_dilation_sizes[j][d];
       }
-      if (!c.rc) {
-        const char* vn = "respair_cl_bf16";
-        const int pi = c.prof_begin("dec.resblock.pair");
-        if (pi >= 0 && c.h->prof_mode >= 3)
-          c.cur_shape = " n" + std::to_string(nb) + " C" + std::to_string(U.cout) + " k" + std::to_string(F.p[0].k) + " L" +
-                        std::to_string(Lo) + " B" + std::to_string(B);
-        const int r = launch_respair_cl_bf16(c.s, F, &vn);
-        c.prof_end(pi, vn, respair_cl_bf16_flops(F), respair_cl_bf16_bytes(F));
-        if (r) c.fail("dec.resblock.pair", r);
-      }
+      const char* vn = "respair_cl_bf16";
+      c.timed("dec.resblock.pair", &vn, [&] { return resblock_shape(nb, U.cout, F.p[0].k, Lo, B); }, [&] { return respair_cl_bf16_flops(F); },
+              [&] { return respair_cl_bf16_bytes(F); }, [&] { return launch_respair_cl_bf16(c.s, F, &vn); });
     }
     for (int d = 0; d < m.n_rbd && rb2; ++d) {
-      // modules.ResBlock2 in bf16: x = bf16(conv_d(bf16(lrelu(x))) + x), one conv per launch, ending in S[1 + j]
+      // modules.ResBlock2 in bf16: x = bf16(conv_d(bf16(lrelu(x))) + x), one conv per launch (branch_bufs: the ping-pong scheme)
       ClLaunch c1;
       c1.nprob = nb; c1.B = B; c1.L = Lo; c1.lens = lens; c1.len_mul = up * U.u;
-      const bool to_cur = ((m.n_rbd - 1 - d) & 1) == 0;
       for (int jj = 0; jj < nb; ++jj) {
-        const int j = nb - 1 - jj;
-        uint16_t* cur = U16(S[1 + j]);
-        uint16_t* tmp = U16(S[1 + nb + j]);
-        const uint16_t* xin = d == 0 ? x : (to_cur ? tmp : cur);
-        ClProb p = prob(m.rb[i][j][d][0], xin, to_cur ? cur : tmp, Lo, cf.resblock_dilation_sizes[j][d]);
-        p.pre_lrelu = 1; p.res = xin;
+        const auto bb = branch_bufs<uint16_t>(S, nb, m.n_rbd, x, jj, d);
+        ClProb p = prob(m.rb[i][bb.j][d][0], bb.pp_in, bb.pp_out, Lo, cf.resblock_dilation_sizes[bb.j][d]);
+        p.pre_lrelu = 1; p.res = bb.pp_in;
         c1.p[jj] = p;
       }
       launch(c1, "dec.resblock2.conv", flops_of(c1));
@@ -1295,23 +1241,20 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
       c1.nprob = c2.nprob = nb; c1.B = c2.B = B; c1.L = c2.L = Lo;
       c1.lens = c2.lens = lens; c1.len_mul = c2.len_mul = up * U.u;
       for (int jj = 0; jj < nb; ++jj) {
-        const int j = nb - 1 - jj;                              // widest kernel first
-        uint16_t* cur = U16(S[1 + j]);
-        uint16_t* tmp = U16(S[1 + nb + j]);
-        const uint16_t* xin = d == 0 ? x : cur;
-        ClProb p = prob(m.rb[i][j][d][0], xin, tmp, Lo, cf.resblock_dilation_sizes[j][d]);
+        const auto bb = branch_bufs<uint16_t>(S, nb, m.n_rbd, x, jj, d);
+        ClProb p = prob(m.rb[i][bb.j][d][0], bb.in, bb.tmp, Lo, cf.resblock_dilation_sizes[bb.j][d]);
         p.pre_lrelu = 1;
         c1.p[jj] = p;
-        p = prob(m.rb[i][j][d][1], tmp, cur, Lo, 1);
-        p.pre_lrelu = 1; p.res = xin;
+        p = prob(m.rb[i][bb.j][d][1], bb.tmp, bb.cur, Lo, 1);
+        p.pre_lrelu = 1; p.res = bb.in;
         c2.p[jj] = p;
       }
       launch(c1, "dec.resblock.convs1", flops_of(c1));
       launch(c2, "dec.resblock.convs2", flops_of(c2));
     }
     for (int j = 0; j < 3; ++j) src[j] = j < nb && (j == 0 || !summed) ? U16(S[1 + j]) : nullptr;
-    if (summed) tap_cl("dec.stage." + std::to_string(i), src[0], U.cout, Lo);
-    else for (int j = 0; j < nb; ++j) tap_cl("dec.rb." + std::to_string(i) + "." + std::to_string(j), src[j], U.cout, Lo);
+    if (summed) tap_cl(src[0], U.cout, Lo, "dec.stage.", i);
+    else for (int j = 0; j < nb; ++j) tap_cl(src[j], U.cout, Lo, "dec.rb.", i, ".", j);
     nsrc = summed ? 1 : nb;
     Lc = Lo;
     up *= U.u;
@@ -1348,18 +1291,16 @@ static void phase_b_gemv(Ctx& c, const PlanB& P, const float* g, int B) {
   c.chk(launch_gemv(c.s, G), "gemv.B");
 }
 
-int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
-               const bv2_item_controls* ic) {
-  const Model& m = h->model;
-  const bv2_config& cf = m.cfg;
-  const int B = in.B, T = in.T, Ty = in.Ty, C = cf.inter_channels;
-  Arena A(ws, wsb);
-  PlanB P = plan_b(A, m, B, Ty);
-  if (!A.ok()) { h->err = "workspace too small for bv2_decode"; return -5; }
-  Ctx c{h, s, m, h->blob};
-  float* z = out.z ? out.z : P.z;
-  float* ymask = out.y_mask ? out.y_mask : P.ymask;
+// the Generator in the handle's arithmetic: the one place that looks at gen_dtype
+static void run_gen(Ctx& c, const PlanB& P, const float* z, int z_rstride, const float* ymask, int B, int L, float* o, const int64_t* lens) {
+  if (c.h->gen_dtype == BV2_BF16) gen_core_bf16(c, P, z, z_rstride, ymask, B, L, o, lens);
+  else gen_core(c, P, z, z_rstride, ymask, B, L, o, lens);
+}
 
+// the phase-B prologue: expand m_p / logs_p along the durations and draw z_p into `z` (the flow then updates it in place), the speaker
+// GEMVs, the flow.  z / ymask: the caller's tensors or the workspace's
+static void expand_and_flow(Ctx& c, const PlanB& P, const bv2_decode_in& in, const bv2_decode_out& out, const bv2_item_controls* ic,
+                            float* z, float* ymask) {
   ExpandArgs e;
   std::memset(&e, 0, sizeof(e));
   e.w_ceil = in.w_ceil; e.x_mask = in.x_mask; e.y_lengths = in.y_lengths; e.m_p = in.m_p; e.logs_p = in.logs_p;
@@ -1368,18 +1309,30 @@ int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_
   e.noise_scale_b = ic ? ic->noise_scale : nullptr;
   e.frame_idx = P.fidx; e.attn = out.attn; e.y_mask = ymask; e.z_p = z; e.m_e = out.m_p; e.logs_e = out.logs_p;
   e.z_p2 = out.z_p;                                  // the flow updates z in place: z_p is kept as a second store
-  e.B = B; e.C = C; e.T = T; e.Ty = Ty;
-  c.chk(launch_expand(s, e), "expand");
-  phase_b_gemv(c, P, in.g, B);
-  flow_core(c, P, z, ymask, in.g, B, Ty);
+  e.B = in.B; e.C = c.m.cfg.inter_channels; e.T = in.T; e.Ty = in.Ty;
+  c.chk(launch_expand(c.s, e), "expand");
+  phase_b_gemv(c, P, in.g, in.B);
+  flow_core(c, P, z, ymask, in.g, in.B, in.Ty);
+}
+
+int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
+               const bv2_item_controls* ic) {
+  const Model& m = h->model;
+  const int B = in.B, Ty = in.Ty;
+  Arena A(ws, wsb);
+  PlanB P = plan_b(A, m, B, Ty);
+  if (int e = ws_short(h, A, "bv2_decode")) return e;
+  Ctx c{h, s, m, h->blob};
+  float* z = out.z ? out.z : P.z;
+  float* ymask = out.y_mask ? out.y_mask : P.ymask;
+  expand_and_flow(c, P, in, out, ic, z, ymask);
   const int L = (in.max_len > 0 && in.max_len < Ty) ? in.max_len : Ty;
   const int64_t* lens = in.exact_lengths == 1 ? in.y_lengths : nullptr;
   if (in.exact_lengths == 2) {                       // Ty is a bucket >= max(y_lengths): cap the Generator at the longest utterance (bv2.h)
     lens = in.y_lengths;                             // B == 1: the cap is the utterance's own length
     if (B > 1) { c.chk(launch_len_cap(s, in.y_lengths, P.len_cap, B), "len_cap"); lens = P.len_cap; }
   }
-  if (h->gen_dtype == BV2_BF16) gen_core_bf16(c, P, z, Ty, ymask, B, L, out.o, lens);
-  else gen_core(c, P, z, Ty, ymask, B, L, out.o, lens);
+  run_gen(c, P, z, Ty, ymask, B, L, out.o, lens);
   return c.rc;
 }
 
@@ -1388,7 +1341,7 @@ int run_flow(bv2_handle* h, hipStream_t s, int B, int Ty, const float* z_p, cons
   const Model& m = h->model;
   Arena A(ws, wsb);
   PlanB P = plan_b(A, m, B, Ty);
-  if (!A.ok()) { h->err = "workspace too small for bv2_stage_flow"; return -5; }
+  if (int e = ws_short(h, A, "bv2_stage_flow")) return e;
   Ctx c{h, s, m, h->blob};
   const float* ymask = y_mask;
   if (!ymask) {
@@ -1408,7 +1361,7 @@ int run_generator(bv2_handle* h, hipStream_t s, int B, int Ty, int L, const floa
   if (L < 1 || L > Ty) { h->err = "bv2_stage_generator: need 1 <= L <= Ty"; return -1; }
   Arena A(ws, wsb);
   PlanB P = plan_b(A, m, B, Ty);
-  if (!A.ok()) { h->err = "workspace too small for bv2_stage_generator"; return -5; }
+  if (int e = ws_short(h, A, "bv2_stage_generator")) return e;
   Ctx c{h, s, m, h->blob};
   const float* ymask = nullptr;                    // y_lengths == null: z_in is taken as it is (the exported dec graph)
   if (y_lengths) {
@@ -1416,8 +1369,7 @@ int run_generator(bv2_handle* h, hipStream_t s, int B, int Ty, int L, const floa
     ymask = P.ymask;
   }
   phase_b_gemv(c, P, g, B);
-  if (h->gen_dtype == BV2_BF16) gen_core_bf16(c, P, z, Ty, ymask, B, L, o, nullptr);
-  else gen_core(c, P, z, Ty, ymask, B, L, o, nullptr);
+  run_gen(c, P, z, Ty, ymask, B, L, o, nullptr);
   return c.rc;
 }
 
@@ -1475,26 +1427,13 @@ int64_t stream_workspace_bytes(const Model& m, int B, int T, int Ty, int window_
 int run_stream_begin(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
                      const bv2_item_controls* ic) {
   const Model& m = h->model;
-  const bv2_config& cf = m.cfg;
-  const int B = in.B, T = in.T, Ty = in.Ty, C = cf.inter_channels;
+  const int B = in.B, Ty = in.Ty, C = m.cfg.inter_channels;
   Arena A(ws, wsb);
   PlanS S = plan_stream(A, m, B, Ty, 1, 1);
-  if (!A.ok()) { h->err = "workspace too small for bv2_stream_begin"; return -5; }
+  if (int e = ws_short(h, A, "bv2_stream_begin")) return e;
   const PlanB& P = S.b;
   Ctx c{h, s, m, h->blob};
-
-  ExpandArgs e;
-  std::memset(&e, 0, sizeof(e));
-  e.w_ceil = in.w_ceil; e.x_mask = in.x_mask; e.y_lengths = in.y_lengths; e.m_p = in.m_p; e.logs_p = in.logs_p;
-  e.noise = in.noise_z; e.nz_bstride = in.nz_bstride; e.nz_cstride = in.nz_cstride; e.nz_tstride = in.nz_tstride;
-  e.noise_scale = in.noise_scale;
-  e.noise_scale_b = ic ? ic->noise_scale : nullptr;
-  e.frame_idx = P.fidx; e.attn = out.attn; e.y_mask = P.ymask; e.z_p = P.z; e.m_e = out.m_p; e.logs_e = out.logs_p;
-  e.z_p2 = out.z_p;
-  e.B = B; e.C = C; e.T = T; e.Ty = Ty;
-  c.chk(launch_expand(s, e), "expand");
-  phase_b_gemv(c, P, in.g, B);
-  flow_core(c, P, P.z, P.ymask, in.g, B, Ty);
+  expand_and_flow(c, P, in, out, ic, P.z, P.ymask);
   if (c.rc) return c.rc;
   // the caller's copies (bv2_decode writes them in place; here the workspace's are the ones the windows read)
   if (out.z && hipMemcpyAsync(out.z, P.z, sizeof(float) * (size_t)B * C * Ty, hipMemcpyDeviceToDevice, s) != hipSuccess) c.fail("stream.z", -1);
@@ -1512,7 +1451,7 @@ int run_stream_chunk(bv2_handle* h, hipStream_t s, const bv2_stream_chunk_args& 
   const int W = w1 - w0;
   Arena A(ws, wsb);
   PlanS S = plan_stream(A, m, B, Ty, W, 2);
-  if (!A.ok()) { h->err = "workspace too small for bv2_stream_chunk"; return -5; }
+  if (int e = ws_short(h, A, "bv2_stream_chunk")) return e;
   const PlanB& P = S.b;
   Ctx c{h, s, m, h->blob};
   const int64_t* lens = nullptr;
@@ -1520,8 +1459,7 @@ int run_stream_chunk(bv2_handle* h, hipStream_t s, const bv2_stream_chunk_args& 
     c.chk(launch_stream_window_lens(s, a.y_lengths, S.wlens, w0, W, B), "stream.window_lens");
     lens = S.wlens;
   }
-  if (h->gen_dtype == BV2_BF16) gen_core_bf16(c, P, P.z + w0, Ty, P.ymask + w0, B, W, S.wout, lens);
-  else gen_core(c, P, P.z + w0, Ty, P.ymask + w0, B, W, S.wout, lens);
+  run_gen(c, P, P.z + w0, Ty, P.ymask + w0, B, W, S.wout, lens);
   if (c.rc) return c.rc;
   c.chk(launch_stream_emit(s, S.wout, (int64_t)W * U, (int64_t)(a.t0 - w0) * U, a.y_lengths, U, (int64_t)a.t0 * U, B,
                            (int64_t)(a.t1 - a.t0) * U, a.dst, a.dst16, a.dst ? a.dst_bstride : a.dst16_bstride,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -120,6 +121,43 @@ struct Model {
   int64_t total_floats = 0;
   uint32_t cfg_hash = 0;
 };
+
+// ---- shared by the two host executors (bv2_exec.cpp, bv2_bert.cpp) ----
+// a caller's workspace carved in 256-byte steps; base == nullptr: sizes only
+struct Arena {
+  char* base;
+  int64_t off = 0, cap;
+  Arena(void* b, int64_t c) : base(static_cast<char*>(b)), cap(c) {}
+  template <class T> T* get(int64_t n) {
+    const int64_t bytes = (n * (int64_t)sizeof(T) + 255) / 256 * 256;
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += bytes;
+    return p;
+  }
+  bool ok() const { return base == nullptr || off <= cap; }
+};
+
+// conv problem with the defaults of a "same"-padded Conv1d on a dense [B,C,L] tensor (an offset < 0 is a null pointer)
+inline ConvProb conv_prob(const ConvW& w, const float* blob, const float* x, float* out, int L, int dil = 1) {
+  ConvProb p;
+  std::memset(&p, 0, sizeof(p));
+  p.x[0] = x; p.nsrc = 1; p.in_scale = 1.f;
+  p.x_bstride = (int64_t)w.cin * L; p.x_rstride = L; p.Lin = L;
+  p.in_mask_bstride = L; p.out_mask_bstride = L;
+  p.w = w.w_off < 0 ? nullptr : blob + w.w_off; p.bias = w.b_off < 0 ? nullptr : blob + w.b_off;
+  p.out = out; p.out_bstride = (int64_t)w.cout * L; p.out_rstride = L; p.out_tstride = 1; p.out_toff = 0;
+  p.res_bstride = p.out_bstride;
+  p.cin = w.cin; p.cin_pad = w.cin_pad; p.cout = w.cout; p.cout_pad = w.cout_pad; p.w_ld = w.w_ld;
+  p.k = w.k; p.dil = dil; p.pad_left = ((w.k - 1) / 2) * dil;
+  p.slope = 0.1f;
+  return p;
+}
+// the packed fp32 stream of a conv (m-tile-major: what the split-K kernel's XCDs read in contiguous eighths) as the prefetch target of the
+// launch before it (bv2_kernels.h Prefetch); nothing when `on` is false or there is no such conv
+inline Prefetch weight_prefetch(const ConvW* w, const float* blob, bool on) {
+  if (!on || !w || w->w_off < 0) return Prefetch{nullptr, 0};
+  return Prefetch{blob + w->w_off, (unsigned)((int64_t)(w->cout_pad / 32) * (w->cin_pad / 8) * w->k * 1024)};
+}
 
 struct HostTensor { std::vector<float> data; std::vector<int64_t> shape; };
 
