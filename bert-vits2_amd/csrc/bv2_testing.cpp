@@ -554,6 +554,98 @@ int bv2_test_layernorm(void* stream, const float* a, const float* add, int mode,
   return launch_layernorm(static_cast<hipStream_t>(stream), l);
 }
 
+// ---- the Encoder layer's fused launch forms (tests/test_encoder_forms_gpu.py): the three launchers above with every field of the
+// fused forms exposed.  Status of the kernel launchers is passed through unchanged.
+int bv2_test_attention_ex(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out, int B, int H, int D,
+                          int T, int W, int f16, const void* kh, const void* vh, const float* wo_host, float* wo_pack_dev,
+                          const float* bo, const float* res, float* o_out, int64_t o_slab_stride, int Co, int ksplit, float* ml_out) {
+  try {
+    AttnArgs a;
+    a.qkv = qkv; a.ld = ld; a.mask = mask; a.erv = erv; a.out = out; a.B = B; a.H = H; a.D = D; a.T = T; a.W = W; a.f16 = f16;
+    a.kh = static_cast<const uint16_t*>(kh); a.vh = static_cast<const uint16_t*>(vh);
+    if (wo_host) {
+      if (!wo_pack_dev || Co < 1 || H < 1 || D < 1) return -1;
+      const int cin = H * D, cin_pad = t_round_up(cin, 16);
+      std::vector<float> pk((size_t)t_round_up(Co, 32) * cin_pad, 0.f);      // rows padded to whole 32-row tiles (zero)
+      for (int co = 0; co < Co; ++co)
+        for (int ci = 0; ci < cin; ++ci) pk[(size_t)conv_w_index(0, ci, co, cin_pad, 1)] = wo_host[(size_t)co * cin + ci];
+      if (hipMemcpy(wo_pack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
+      a.wo = wo_pack_dev; a.wo_groups = cin_pad / 8;
+    }
+    a.bo = bo; a.res = res; a.o_out = o_out; a.o_slab_stride = o_slab_stride; a.Co = Co;
+    a.ksplit = ksplit; a.ml_out = ml_out;
+    return launch_attention(static_cast<hipStream_t>(stream), a);
+  } catch (...) { return -100; }
+}
+
+int bv2_test_layernorm_ex(void* stream, const float* a, const float* add, int mode, const float* dww, const float* dwb, int dil,
+                          const float* in_mask, const float* gamma, const float* beta, int post_gelu, const float* res,
+                          const float* vec, const float* mask, float* out, int B, int C, int T, int nslab, int64_t slab_stride,
+                          const float* ml, int ml_H, int ml_ks, const float* bias, float* out2, const float* vec2,
+                          const void* pf_ptr, unsigned pf_bytes) {
+  LnArgs l;
+  std::memset(&l, 0, sizeof(l));
+  l.a = a; l.add = add; l.nslab = nslab; l.slab_stride = slab_stride; l.mode = mode; l.dww = dww; l.dwb = dwb; l.dil = dil; l.in_mask = in_mask;
+  l.gamma = gamma; l.beta = beta; l.eps = 1e-5f; l.post_gelu = post_gelu; l.res = res; l.vec = vec; l.vec_bstride = C;
+  l.mask = mask; l.out = out; l.B = B; l.C = C; l.T = T;
+  l.ml = ml; l.ml_H = ml_H; l.ml_ks = ml_ks; l.bias = bias;
+  l.out2 = out2; l.vec2 = vec2; l.vec2_bstride = C;
+  l.pf = Prefetch{pf_ptr, pf_bytes};
+  return launch_layernorm(static_cast<hipStream_t>(stream), l);
+}
+
+int bv2_test_conv_f16_ex(void* stream, const void* x, int in_ct, const float* in_mask, const float* w_host, const float* bias_host,
+                         void* wpack_dev, void* out, int out_ct, const float* res, int res_mode, const float* out_mask, int mask_pre,
+                         int mask_post, int act, int B, int cin, int cout, int k, int dil, int L, int out_rstride,
+                         const float* ln_gamma, const float* ln_beta, const float* ln_vec, const float* ln_mask, void* k16, void* v16,
+                         int kv_row0, int kv_rows, int k16_ld, const float* bias2, int bias2_bstride, int no_ksplit,
+                         const float* p1_w_host, const float* p1_bias_host, void* p1_out, const float* p1_res, int p1_res_mode) {
+  try {
+    if (!conv_f16_supported(cin, cout, k, dil, !out_ct)) return -2;
+    const int cout_pad = t_round_up(cout, 32);
+    const int64_t ne = cl_w_elems(cin, cout_pad, k);
+    const int64_t one = bv2_test_conv_cl_pack_bytes(cin, cout, k);          // problem i's weights + bias at wpack_dev + i * one
+    HcLaunch hl;
+    std::memset(&hl, 0, sizeof(hl));
+    hl.nprob = p1_w_host ? 2 : 1;
+    const float* ws[2] = {w_host, p1_w_host};
+    const float* bs[2] = {bias_host, p1_bias_host};
+    for (int i = 0; i < hl.nprob; ++i) {
+      char* base = static_cast<char*>(wpack_dev) + (size_t)i * one;
+      std::vector<uint16_t> pk((size_t)ne, 0);
+      for (int j = 0; j < k; ++j)
+        for (int ci = 0; ci < cin; ++ci)
+          for (int co = 0; co < cout; ++co) {
+            const _Float16 hv = (_Float16)ws[i][((size_t)co * cin + ci) * k + j];
+            std::memcpy(&pk[(size_t)cl_w_index(j, ci, co, cin, k)], &hv, 2);
+          }
+      std::vector<float> bb((size_t)cout_pad, 0.f);
+      if (bs[i]) for (int co = 0; co < cout; ++co) bb[(size_t)co] = bs[i][co];
+      if (hipMemcpy(base, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
+      if (hipMemcpy(base + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
+      HcProb& p = hl.p[i];
+      p.x = x; p.in_ct = in_ct; p.x_bstride = (int64_t)cin * L; p.x_rstride = L; p.Lin = L;
+      p.in_mask = in_mask; p.in_mask_bstride = L;
+      p.w = reinterpret_cast<const uint16_t*>(base);
+      p.bias = bs[i] ? reinterpret_cast<const float*>(base + ne * 2) : nullptr;
+      p.out_ct = out_ct;
+      p.out_rstride = out_ct ? (out_rstride > 0 ? out_rstride : L) : 0;
+      p.out_bstride = out_ct ? (int64_t)cout * p.out_rstride : (int64_t)(act == ACT_GATE ? cout / 2 : cout) * L;
+      p.res_bstride = p.out_bstride;
+      p.out_mask = out_mask; p.out_mask_bstride = L; p.mask_pre = mask_pre; p.mask_post = mask_post; p.act = act;
+      p.cin = cin; p.cout = cout; p.cout_pad = cout_pad; p.k = k; p.dil = dil; p.pad_left = ((k - 1) / 2) * dil;
+    }
+    HcProb& p = hl.p[0];
+    p.out = out; p.res = res; p.res_mode = res_mode;
+    p.bias2 = bias2; p.bias2_bstride = bias2_bstride;
+    p.ln_gamma = ln_gamma; p.ln_beta = ln_beta; p.ln_eps = 1e-5f; p.ln_vec = ln_vec; p.ln_vec_bstride = cout; p.ln_mask = ln_mask;
+    p.k16 = static_cast<uint16_t*>(k16); p.v16 = static_cast<uint16_t*>(v16); p.kv_row0 = kv_row0; p.kv_rows = kv_rows; p.k16_ld = k16_ld;
+    if (hl.nprob == 2) { hl.p[1].out = p1_out; hl.p[1].res = p1_res; hl.p[1].res_mode = p1_res_mode; }
+    hl.B = B; hl.L = L; hl.no_ksplit = no_ksplit;
+    return launch_conv_f16(static_cast<hipStream_t>(stream), hl, nullptr);
+  } catch (...) { return -100; }
+}
+
 void bv2_test_conv_timeline(void* dev_buf, long long capacity_u64) {
   conv_set_timeline(static_cast<unsigned long long*>(dev_buf), capacity_u64);
 }

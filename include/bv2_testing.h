@@ -123,6 +123,35 @@ int bv2_test_layernorm(void* stream, const float* a, const float* add, int mode,
                        const float* in_mask, const float* gamma, const float* beta, int post_gelu, const float* res,
                        const float* vec, const float* mask, float* out, int B, int C, int T, int nslab, int64_t slab_stride);
 
+/* The Encoder layer's fused launch forms, one field of AttnArgs / LnArgs / HcProb per argument (bv2_kernels.h has their meaning); the
+ * kernel launcher's status is returned unchanged (-1 = refused combination, nothing launched).
+ *
+ * bv2_test_attention_ex: bv2_test_attention plus f16 (0 / 1) and the fp16 K / V hand-over kh [B][ld][H*D] / vh [B][H*D][ld] (DEVICE fp16);
+ * the fused conv_o wo_host [Co][H*D] (HOST, packed into wo_pack_dev: round_up(Co, 32) * round_up(H*D, 16) DEVICE floats; NULL = plain
+ * output in `out`), bo [Co], res [B][Co][T], partial slabs o_out (slab s at o_out + s * o_slab_stride); the key split ksplit / ml_out
+ * [B][H][ksplit][2][T]. */
+int bv2_test_attention_ex(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out, int B, int H, int D,
+                          int T, int W, int f16, const void* kh, const void* vh, const float* wo_host, float* wo_pack_dev,
+                          const float* bo, const float* res, float* o_out, int64_t o_slab_stride, int Co, int ksplit, float* ml_out);
+/* bv2_test_layernorm plus the weighted slabs of the key split (ml [B][ml_H][ml_ks][2][T], bias [C]), the second output out2 with vec2
+ * [B][C], and the B == 1 weight prefetch (pf_ptr / pf_bytes: DEVICE memory that is only read) */
+int bv2_test_layernorm_ex(void* stream, const float* a, const float* add, int mode, const float* dww, const float* dwb, int dil,
+                          const float* in_mask, const float* gamma, const float* beta, int post_gelu, const float* res,
+                          const float* vec, const float* mask, float* out, int B, int C, int T, int nslab, int64_t slab_stride,
+                          const float* ml, int ml_H, int ml_ks, const float* bias, float* out2, const float* vec2,
+                          const void* pf_ptr, unsigned pf_bytes);
+/* bv2_test_conv_f16 plus: the LayerNorm epilogue (ln_gamma / ln_beta [cout], eps 1e-5, ln_vec [B][cout], ln_mask [B][L]; out may be res);
+ * the K / V routing of the q/k/v projection (k16 [B][k16_ld][kv_rows], v16 [B][kv_rows][k16_ld] DEVICE fp16); the gate (act 2: out is fp16
+ * [B][L][cout/2]) with its per-batch bias bias2 [B][bias2_bstride]; no_ksplit; and an optional second problem on the same input, masks
+ * and activation (p1_w_host / p1_bias_host HOST, p1_out / p1_res DEVICE; p1_w_host NULL = one problem).  wpack_dev needs
+ * bv2_test_conv_cl_pack_bytes(cin, cout, k) bytes per problem. */
+int bv2_test_conv_f16_ex(void* stream, const void* x, int in_ct, const float* in_mask, const float* w_host, const float* bias_host,
+                         void* wpack_dev, void* out, int out_ct, const float* res, int res_mode, const float* out_mask, int mask_pre,
+                         int mask_post, int act, int B, int cin, int cout, int k, int dil, int L, int out_rstride,
+                         const float* ln_gamma, const float* ln_beta, const float* ln_vec, const float* ln_mask, void* k16, void* v16,
+                         int kv_row0, int kv_rows, int k16_ld, const float* bias2, int bias2_bstride, int no_ksplit,
+                         const float* p1_w_host, const float* p1_bias_host, void* p1_out, const float* p1_res, int p1_res_mode);
+
 /* one fused DDSConv layer (kernels/dds_fused.hip) on x [B][C][T] -> out [B][C][T] (out != x): depthwise k=3 conv (dww_host [C][3],
  * dwb_host [C], dilation dil) + LN1 (g1/b1) + GELU + 1x1 conv (w_host [C][C], bias_host [C]) + LN2 (g2/b2) + GELU + residual,
  * times mask when last_mask.  Optional ConvFlow.pre input transform: pre_w/pre_b HOST [C] with z [B][2][T], z_src and g [B][C][T]

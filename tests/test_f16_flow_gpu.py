@@ -296,7 +296,8 @@ def test_f16_kv_handover_on_and_off(name):
     zs = {}
     for v in (1, 0):
         m.set_option("f16_kv", v)
-        # poison the workspace between the runs: stale K / V rows must not be what makes them agree
+        # (that no stale or tail K / V row reaches a sum is held at kernel level, on NaN-filled buffers: test_attention_kv16 and
+        # test_projection_kv_routing in tests/test_encoder_forms_gpu.py)
         zs[v] = m.stage_flow(gold["z_p"], gold["y_lengths"], g).cpu() * ym
         torch.cuda.synchronize()
     m.set_option("f16_kv", 1)

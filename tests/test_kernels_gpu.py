@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.encoder_refs import ref_attention as _ref_attention
+
 pytestmark = pytest.mark.gpu
 
 
@@ -169,32 +171,6 @@ def test_resblock_fused_pair(B, Cc, k, dil, L):
     assert lib.bv2_test_resblock_fused(None, P(xg), P(out), P(w1), P(b1), P(w2), P(b2), P(wp), B, Cc, k, dil, L, 0.1) == 0
     torch.cuda.synchronize()
     assert rel_err(out, ref) < 2e-5
-
-
-def _ref_attention(qkv, mask, erk, erv, H, W):
-    B, C3, T = qkv.shape
-    HD = C3 // 3
-    D = HD // H
-    q, k, v = [t.view(B, H, D, T).transpose(2, 3).double() for t in qkv.split(HD, 1)]
-    qs = q / math.sqrt(D)
-    s = qs @ k.transpose(-1, -2)
-    idx = torch.arange(T)
-    rel = idx[None, :] - idx[:, None]
-    band = rel.abs() <= W
-    ql = qs @ erk.double().t()
-    s = s + torch.where(band, ql.gather(-1, (rel + W).clamp(0, 2 * W).expand(B, H, T, T)), torch.zeros((), dtype=torch.float64))
-    pair = (mask[:, None, :, None] * mask[:, None, None, :]) != 0
-    s = torch.where(pair, s, torch.full((), -1e4, dtype=torch.float64))
-    p = torch.softmax(s, -1)
-    o = p @ v
-    relw = torch.zeros(B, H, T, 2 * W + 1, dtype=torch.float64)
-    for r in range(-W, W + 1):
-        lo, hi = max(0, -r), min(T, T - r)
-        if hi > lo:
-            i = torch.arange(lo, hi)
-            relw[:, :, lo:hi, r + W] = p[:, :, i, i + r]
-    o = o + relw @ erv.double()
-    return o.transpose(2, 3).reshape(B, HD, T)
 
 
 @pytest.mark.parametrize("B,T,lens", [(1, 128, [128]), (2, 100, [100, 37]), (1, 3, [3]), (3, 33, [33, 1, 20]), (1, 400, [400]),
