@@ -232,7 +232,7 @@ static int check_encode(bv2_handle* h, const bv2_encode_in* in, const bv2_encode
   const std::string w(what);
   if (!in || !out || in->B < 1 || in->T < 1) { h->err = w + ": bad argument"; return -1; }
   if (!in->x || !in->x_lengths || (!g && !in->sid) || !in->tone || !in->language || !in->bert || !in->ja_bert || !in->en_bert ||
-      !in->noise_w || !out->g || !out->x || !out->m_p || !out->logs_p || !out->x_mask || !out->logw || !out->w_ceil ||
+      !out->g || !out->x || !out->m_p || !out->logs_p || !out->x_mask || !out->logw || !out->w_ceil ||
       !out->y_lengths) { h->err = w + ": null tensor pointer"; return -1; }
   for (int f = 0; f < 3; ++f)
     if (in->bert_index[f] && (in->bert_cols[f] < 1 || in->bert_cols[f] > in->T)) {
@@ -839,6 +839,8 @@ int bv2_set_option(bv2_handle* h, const char* key, int value) {
   else if (k == "fused_attn_o") h->no_fused_attn_o = value == 0;
   else if (k == "attn_ksplit") h->attn_ksplit = value;
   else if (k == "overlap_dp") h->no_overlap_dp = value == 0;
+  else if (k == "lean_durations") h->no_lean_durations = value == 0;
+  else if (k == "phase_b_front") h->no_phase_b_front = value == 0;
   else { h->err = "bv2_set_option: unknown key '" + k + "'"; return -1; }
   return 0;
   BV2_CATCH(h)

@@ -632,11 +632,15 @@ static void sdp_core(Ctx& c, PlanA& P, const float* x, const float* mask, const 
   }
 }
 
+// skip_sdp / skip_dp (run_encode): that predictor did not run — its buffer (P.z / logw_dp) is not read
 static void run_durations(Ctx& c, const PlanA& P, const float* logw_dp, const float* mask, float sdp_ratio, float length_scale,
                           float* logw_sdp, float* logw, float* w_ceil, int64_t* y_lengths, int B, int T,
-                          const bv2_item_controls* ic = nullptr) {
+                          const bv2_item_controls* ic = nullptr, bool skip_sdp = false, bool skip_dp = false) {
   const Model& m = c.m;
   DurArgs d;
+  d.no_sdp = skip_sdp; d.no_dp = skip_dp;
+  if (skip_dp) logw_dp = nullptr;
+  if (skip_sdp) logw_sdp = nullptr;
   d.z = P.z; d.ea_m = c.W(m.ea_m.off); d.ea_logs = c.W(m.ea_logs.off);
   d.logw_dp = logw_dp; d.mask = mask;
   d.sdp_ratio = sdp_ratio; d.one_minus_ratio = (float)(1.0 - (double)sdp_ratio); d.length_scale = length_scale;
@@ -660,14 +664,23 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   Ctx c{h, s, m, h->blob};
   const float* mask = out.x_mask;
 
+  // Run only the predictor the mix can see (include/bv2.h, bv2_encode_out): logw = sdp * r + dp * (1 - r), so at r == 0 the stochastic
+  // predictor's 13 launches — and at r == 1 the deterministic one's 5 — compute a value that is multiplied by 0.0f.  The host must
+  // know r (per-item ratios live on the device), nobody may have asked for the skipped side's output, and no tap may be waiting for
+  // one of its intermediates.  "lean_durations" = 0 runs both, always.
+  const bool lean = !h->no_lean_durations && !(ic && ic->sdp_ratio) && h->taps.empty();
+  const bool skip_sdp = lean && in.sdp_ratio == 0.0f && !out.logw_sdp;
+  const bool skip_dp = lean && in.sdp_ratio == 1.0f && !out.logw_dp;
+  if (!skip_sdp && !in.noise_w) { h->err = "bv2_encode_durations: noise_w is NULL but the stochastic duration predictor runs"; return -1; }
+
   // ONE front launch: g = emb_g(sid), x_mask, every g-conditioned vector of this phase, and the scaled SDP noise
   float *spk = P.gv, *sdp_c = P.gv + H, *dp_c = P.gv + 2 * H;
   {
     const GemvW* gw[3] = {&m.enc.spk, &m.sdp_cond, &m.dp_cond};
     float* go[3] = {spk, sdp_c, dp_c};
     // a caller's g (a ReferenceEncoder result, a blend, ...) takes the place of the table row: same GEMV code, sid is not read
-    run_front(c, g_in ? nullptr : in.sid, g_in, out.g, gw, go, 3, 3 * H, in.x_lengths, out.x_mask, B, T, in.noise_w, P.z, in.noise_scale_w,
-              ic ? ic->noise_scale_w : nullptr);
+    run_front(c, g_in ? nullptr : in.sid, g_in, out.g, gw, go, 3, 3 * H, in.x_lengths, out.x_mask, B, T, skip_sdp ? nullptr : in.noise_w,
+              skip_sdp ? nullptr : P.z, in.noise_scale_w, ic ? ic->noise_scale_w : nullptr);
   }
   const float* berts[3] = {in.bert, in.ja_bert, in.en_bert};
   enc_p_core(c, P, in.x, in.tone, in.language, berts, mask, spk, 3 * H, B, T, out.x, out.m_p, out.logs_p, P.dp0, dp_c,
@@ -675,9 +688,9 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   float* logw_dp = out.logw_dp ? out.logw_dp : P.logw_dp;
   // The two duration predictors only share their input (the encoder output).  Optional ("overlap_dp", default off — measured
   // slower, see bv2_internal.h): the deterministic one (5 short launches) on the handle's side stream beside the stochastic one
-  // (17 launches), joined before the durations kernel.  Disjoint workspace.
+  // (17 launches), joined before the durations kernel.  Disjoint workspace.  Nothing to overlap when one of them is skipped.
   bool forked = false;
-  if (!h->no_overlap_dp && !c.rc) {
+  if (!h->no_overlap_dp && !skip_sdp && !skip_dp && !c.rc) {
     if (!h->side_stream) {
       if (hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking) != hipSuccess ||
           hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -695,11 +708,11 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
       forked = true;
     }
   }
-  if (!forked) dp_core(c, P, P.dp0, mask, B, T, logw_dp);
-  sdp_core(c, P, out.x, mask, sdp_c, 3 * H, B, T);
+  if (!forked && !skip_dp) dp_core(c, P, P.dp0, mask, B, T, logw_dp);
+  if (!skip_sdp) sdp_core(c, P, out.x, mask, sdp_c, 3 * H, B, T);
   if (forked && hipStreamWaitEvent(s, h->ev_join, 0) != hipSuccess) c.fail("dp join", -6);
   run_durations(c, P, logw_dp, mask, in.sdp_ratio, in.length_scale, out.logw_sdp ? out.logw_sdp : P.logw_sdp, out.logw,
-                out.w_ceil, out.y_lengths, B, T, ic);
+                out.w_ceil, out.y_lengths, B, T, ic, skip_sdp, skip_dp);
   return c.rc;
 }
 
@@ -903,9 +916,18 @@ template <class T> BranchBufs<T> branch_bufs(float* const* S, int nb, int n_rbd,
   return b;
 }
 
-// Generator.forward (reference models.py:538-557)
+// x3 slots one fp32 decode can use (conv_x6.hip): those of the stages with 128-row tiles; 0 = the x3 form is not in use
+static int x3_slot_count(const Ctx& c) {
+  const Model& m = c.m;
+  int n_slots = 0;
+  for (int i = 0; i < m.n_ups && !c.h->no_conv_x3 && !c.h->no_conv_x6; ++i)
+    if (m.ups[i].cout % 128 == 0 && m.rb[i][0][0][0].wy_off >= 0) n_slots += 1 + 2 * m.n_rbk * m.n_rbd;
+  return n_slots;
+}
+
+// Generator.forward (reference models.py:538-557).  slots_clear: the caller's phase_b_front launch has already zeroed the x3 slots
 static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, const float* ymask, int B, int L, float* o,
-                     const int64_t* lens) {
+                     const int64_t* lens, bool slots_clear = false) {
   const Model& m = c.m;
   const bv2_config& cf = m.cfg;
   const int C = cf.inter_channels, c0 = cf.upsample_initial_channel;
@@ -925,11 +947,9 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
   // x3 form of the wide-stage convs (conv_x6.hip, two scaled fp16 planes): every conv input needs the slot its producer's epilogue
   // filled with max |x|; the slots of one decode are distinct and zeroed here
   int next_slot = 0;
-  int n_slots = 0;                                // slots this decode can use: stages with 128-row tiles
-  for (int i = 0; i < m.n_ups && !c.h->no_conv_x3 && !c.h->no_conv_x6; ++i)
-    if (m.ups[i].cout % 128 == 0 && m.rb[i][0][0][0].wy_off >= 0) n_slots += 1 + 2 * m.n_rbk * m.n_rbd;
+  const int n_slots = x3_slot_count(c);
   const bool any_x3 = n_slots > 0;
-  if (any_x3 && !c.rc) c.chk(launch_x3_zero_slots(c.s, P.xslots, n_slots), "dec.x3_slots");
+  if (any_x3 && !slots_clear && !c.rc) c.chk(launch_x3_zero_slots(c.s, P.xslots, n_slots), "dec.x3_slots");
   for (int i = 0; i < m.n_ups; ++i) {
     const UpW& U = m.ups[i];
     float* const* S = P.set[i & 1];
@@ -1270,7 +1290,8 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
   c.chk(launch_conv_post_cl(c.s, a), "dec.conv_post");
 }
 
-static void phase_b_gemv(Ctx& c, const PlanB& P, const float* g, int B) {
+// the speaker GEMVs of phase B: dec.cond and every coupling's conditioning vector
+static GemvLaunch phase_b_gemv_args(Ctx& c, const PlanB& P, const float* g, int B) {
   const Model& m = c.m;
   const bv2_config& cf = m.cfg;
   GemvLaunch G;
@@ -1288,19 +1309,23 @@ static void phase_b_gemv(Ctx& c, const PlanB& P, const float* g, int B) {
     else add(m.coupling[a].wn_cond, gf + (int64_t)a * 2 * cf.hidden_channels * cf.n_flow_layer);
   }
   G.nprob = n; G.B = B; G.g = g; G.g_bstride = cf.gin_channels;
-  c.chk(launch_gemv(c.s, G), "gemv.B");
+  return G;
 }
+static void phase_b_gemv(Ctx& c, const PlanB& P, const float* g, int B) { c.chk(launch_gemv(c.s, phase_b_gemv_args(c, P, g, B)), "gemv.B"); }
 
 // the Generator in the handle's arithmetic: the one place that looks at gen_dtype
-static void run_gen(Ctx& c, const PlanB& P, const float* z, int z_rstride, const float* ymask, int B, int L, float* o, const int64_t* lens) {
+static void run_gen(Ctx& c, const PlanB& P, const float* z, int z_rstride, const float* ymask, int B, int L, float* o, const int64_t* lens,
+                    bool slots_clear = false) {
   if (c.h->gen_dtype == BV2_BF16) gen_core_bf16(c, P, z, z_rstride, ymask, B, L, o, lens);
-  else gen_core(c, P, z, z_rstride, ymask, B, L, o, lens);
+  else gen_core(c, P, z, z_rstride, ymask, B, L, o, lens, slots_clear);
 }
 
 // the phase-B prologue: expand m_p / logs_p along the durations and draw z_p into `z` (the flow then updates it in place), the speaker
-// GEMVs, the flow.  z / ymask: the caller's tensors or the workspace's
-static void expand_and_flow(Ctx& c, const PlanB& P, const bv2_decode_in& in, const bv2_decode_out& out, const bv2_item_controls* ic,
-                            float* z, float* ymask) {
+// GEMVs, the flow.  z / ymask: the caller's tensors or the workspace's.  gen_follows: the Generator of this same call runs behind the
+// flow.  One launch (phase_b_front; "phase_b_front" = 0: frame_index, expand, attn_path and gemv as launches of their own) which then
+// also zeroes the fp32 Generator's x3 slots — returns true when it did, for run_gen's slots_clear.
+static bool expand_and_flow(Ctx& c, const PlanB& P, const bv2_decode_in& in, const bv2_decode_out& out, const bv2_item_controls* ic,
+                            float* z, float* ymask, bool gen_follows) {
   ExpandArgs e;
   std::memset(&e, 0, sizeof(e));
   e.w_ceil = in.w_ceil; e.x_mask = in.x_mask; e.y_lengths = in.y_lengths; e.m_p = in.m_p; e.logs_p = in.logs_p;
@@ -1310,9 +1335,21 @@ static void expand_and_flow(Ctx& c, const PlanB& P, const bv2_decode_in& in, con
   e.frame_idx = P.fidx; e.attn = out.attn; e.y_mask = ymask; e.z_p = z; e.m_e = out.m_p; e.logs_e = out.logs_p;
   e.z_p2 = out.z_p;                                  // the flow updates z in place: z_p is kept as a second store
   e.B = in.B; e.C = c.m.cfg.inter_channels; e.T = in.T; e.Ty = in.Ty;
-  c.chk(launch_expand(c.s, e), "expand");
-  phase_b_gemv(c, P, in.g, in.B);
+  bool slots_clear = false;
+  if (c.h->no_phase_b_front) {
+    c.chk(launch_expand(c.s, e), "expand");
+    phase_b_gemv(c, P, in.g, in.B);
+  } else {
+    PhaseBFrontArgs F;
+    std::memset(&F, 0, sizeof(F));
+    F.G = phase_b_gemv_args(c, P, in.g, in.B); F.E = e;
+    const int n_slots = (gen_follows && c.h->gen_dtype != BV2_BF16) ? x3_slot_count(c) : 0;
+    if (n_slots > 0) { F.slots = P.xslots; F.slot_words = n_slots * X3_SLOT_WORDS; slots_clear = true; }
+    c.chk(launch_phase_b_front(c.s, F), "phase_b_front");
+    if (c.rc) slots_clear = false;
+  }
   flow_core(c, P, z, ymask, in.g, in.B, in.Ty);
+  return slots_clear;
 }
 
 int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
@@ -1325,14 +1362,14 @@ int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_
   Ctx c{h, s, m, h->blob};
   float* z = out.z ? out.z : P.z;
   float* ymask = out.y_mask ? out.y_mask : P.ymask;
-  expand_and_flow(c, P, in, out, ic, z, ymask);
+  const bool slots_clear = expand_and_flow(c, P, in, out, ic, z, ymask, true);
   const int L = (in.max_len > 0 && in.max_len < Ty) ? in.max_len : Ty;
   const int64_t* lens = in.exact_lengths == 1 ? in.y_lengths : nullptr;
   if (in.exact_lengths == 2) {                       // Ty is a bucket >= max(y_lengths): cap the Generator at the longest utterance (bv2.h)
     lens = in.y_lengths;                             // B == 1: the cap is the utterance's own length
     if (B > 1) { c.chk(launch_len_cap(s, in.y_lengths, P.len_cap, B), "len_cap"); lens = P.len_cap; }
   }
-  run_gen(c, P, z, Ty, ymask, B, L, out.o, lens);
+  run_gen(c, P, z, Ty, ymask, B, L, out.o, lens, slots_clear);
   return c.rc;
 }
 
@@ -1433,7 +1470,7 @@ int run_stream_begin(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, cons
   if (int e = ws_short(h, A, "bv2_stream_begin")) return e;
   const PlanB& P = S.b;
   Ctx c{h, s, m, h->blob};
-  expand_and_flow(c, P, in, out, ic, P.z, P.ymask);
+  expand_and_flow(c, P, in, out, ic, P.z, P.ymask, false);   // the windows' Generator runs zero their own x3 slots
   if (c.rc) return c.rc;
   // the caller's copies (bv2_decode writes them in place; here the workspace's are the ones the windows read)
   if (out.z && hipMemcpyAsync(out.z, P.z, sizeof(float) * (size_t)B * C * Ty, hipMemcpyDeviceToDevice, s) != hipSuccess) c.fail("stream.z", -1);

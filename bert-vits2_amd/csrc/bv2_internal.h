@@ -209,6 +209,9 @@ struct bv2_handle {
   bool no_overlap_dp = true;         // "overlap_dp" = 1: the (independent) DurationPredictor on an internal side stream, forked from and
   // joined back into the caller's stream with events (created on first use; capturable).  OFF by default: measured on MI355X at
   // batch 1 the fork/join costs more than the 5 short launches it hides (4.70 -> 4.82 ms per step eager, 4.75 -> 4.78 replayed).
+  bool no_lean_durations = false;    // "lean_durations" = 0: both duration predictors always run (default: at a host-known sdp_ratio of exactly 0 or 1 the one
+  // whose term is multiplied by 0.0f is not launched, run_encode)
+  bool no_phase_b_front = false;     // "phase_b_front" = 0: the head of phase B as five launches (frame_index, expand, attn_path, gemv, x3 slots) instead of one
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // profiling

@@ -634,6 +634,10 @@ struct DurArgs {
   const float* length_scale_b;  // [B] per-utterance length_scale, or null = length_scale
   float* logw_sdp; float* logw; float* w_ceil; int64_t* y_lengths;
   int B, T;
+  // a predictor the mix cannot see was not run (bv2_exec.cpp encode_skip): no_sdp — sdp_ratio == 0, z holds anything and is not read,
+  // logw = logw_dp * one_minus_ratio; no_dp — sdp_ratio == 1, logw_dp is null and logw = logw_sdp * sdp_ratio.  Never both.  (A null
+  // logw_dp WITHOUT no_dp keeps its meaning: bv2_stage_sdp wants the ElementwiseAffine inverse only.)
+  bool no_sdp = false, no_dp = false;
 };
 int launch_durations(hipStream_t stream, const DurArgs& a);
 
@@ -675,6 +679,13 @@ struct ExpandArgs {
   int B, C, T, Ty;
 };
 int launch_expand(hipStream_t stream, const ExpandArgs& a);
+// the head of phase B as ONE launch (kernels/misc.hip): launch_gemv(G) + launch_expand(E) + launch_x3_zero_slots, same results bit for bit
+struct PhaseBFrontArgs {
+  GemvLaunch G; ExpandArgs E;
+  unsigned* slots; int slot_words;                     // x3 slot words to zero (0: none)
+  int gemv_gx, gemv_layers, e_chunks, e_groups;        // the roles' block counts: filled by the launcher
+};
+int launch_phase_b_front(hipStream_t stream, const PhaseBFrontArgs& a);
 
 // --- 16-bit PCM of the valid samples, peak-normalised per utterance (gradio convert_to_16_bit_wav, reference webui.py:86) ---
 int launch_pcm16(hipStream_t stream, const float* wave, int64_t bstride, const int64_t* y_lengths, int hop, int B, int64_t S,

@@ -183,16 +183,18 @@ __device__ __forceinline__ void gemv_row(const float* w, int cin, int B, int lan
 
 static inline int gemv_layers(int B) { const int g = (B + 3) / 4; return g < 1 ? 1 : (g > 16 ? 16 : g); }   // grid.z: groups of four batch items side by side
 
-__global__ void __launch_bounds__(256) gemv_kernel(const GemvLaunch L) {
-  const GemvProb& P = L.p[blockIdx.y];
+// block (bx, by, bz) of gemv_kernel's grid (rows / 4, nprob, nbz layers)
+__device__ __forceinline__ void gemv_block(const GemvLaunch& L, const int bx, const int by, const int bz, const int nbz) {
+  const GemvProb& P = L.p[by];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int row = blockIdx.x * 4 + wid;
+  const int row = bx * 4 + wid;
   if (row >= P.cout) return;
   const float* w = P.w + (int64_t)row * P.cin;
   const float* gbase = L.g;
   const int64_t gs = L.g_bstride;
-  gemv_row(w, P.cin, L.B, lane, P.bias ? P.bias[row] : 0.f, P.out + row, P.out_bstride, [=](int b) { return gbase + (int64_t)b * gs; }, blockIdx.z, gridDim.z);
+  gemv_row(w, P.cin, L.B, lane, P.bias ? P.bias[row] : 0.f, P.out + row, P.out_bstride, [=](int b) { return gbase + (int64_t)b * gs; }, bz, nbz);
 }
+__global__ void __launch_bounds__(256) gemv_kernel(const GemvLaunch L) { gemv_block(L, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z); }
 
 int launch_gemv(hipStream_t stream, const GemvLaunch& L) {
   if (L.nprob < 1 || L.nprob > 16) return -1;
@@ -449,22 +451,28 @@ __global__ void __launch_bounds__(256) durations_kernel(const DurArgs A) {
   float r = A.sdp_ratio, omr = A.one_minus_ratio, lsc = A.length_scale;
   if (A.sdp_ratio_b) { r = A.sdp_ratio_b[b]; omr = (float)(1.0 - (double)r); }   // the host's rounding of 1 - r (bv2_exec.cpp)
   if (A.length_scale_b) lsc = A.length_scale_b[b];
+  const bool mix = A.logw_dp || A.no_dp;           // kernel-uniform; false for bv2_stage_sdp: only the ElementwiseAffine inverse is wanted
   float s = 0.f;
   for (int t = threadIdx.x; t < A.T; t += 256) {
     const int64_t bt = (int64_t)b * A.T + t;
     const float mk = A.mask[bt];
-    const float ls = (A.z[((int64_t)b * 2) * A.T + t] - m0) * il0 * mk;
-    if (A.logw_sdp) A.logw_sdp[bt] = ls;
-    if (!A.logw_dp) continue;                      // bv2_stage_sdp: only the ElementwiseAffine inverse is wanted
-    const float ld = A.logw_dp[bt];
-    const float lw = ls * r + ld * omr;
+    float ls = 0.f;
+    if (!A.no_sdp) {                               // no_sdp: z was not produced and is not read
+      ls = (A.z[((int64_t)b * 2) * A.T + t] - m0) * il0 * mk;
+      if (A.logw_sdp) A.logw_sdp[bt] = ls;
+    }
+    if (!mix) continue;
+    float lw;
+    if (A.no_sdp) lw = A.logw_dp[bt] * omr;        // the skipped side's term is exactly 0 * finite
+    else if (A.no_dp) lw = ls * r;
+    else lw = ls * r + A.logw_dp[bt] * omr;
     const float w = expf(lw) * mk * lsc;
     const float wc = ceilf(w);
     A.logw[bt] = lw;
     A.w_ceil[bt] = wc;
     s += wc;
   }
-  if (!A.logw_dp) return;                          // kernel-uniform
+  if (!mix) return;
   part[threadIdx.x] = s;
   __syncthreads();
   for (int off = 128; off > 0; off >>= 1) {
@@ -477,6 +485,7 @@ __global__ void __launch_bounds__(256) durations_kernel(const DurArgs A) {
   }
 }
 int launch_durations(hipStream_t stream, const DurArgs& a) {
+  if ((a.no_sdp && (a.no_dp || !a.logw_dp)) || (a.no_dp && (a.logw_dp || !a.z)) || (!a.no_sdp && !a.z)) return -1;
   hipLaunchKernelGGL(durations_kernel, dim3(a.B), dim3(256), 0, stream, a);
   return BV2_CHECK_LAUNCH();
 }
@@ -486,19 +495,12 @@ int launch_durations(hipStream_t stream, const DurArgs& a) {
 // m_p / logs_p by it (commons.py:126-140, models.py:1061-1069); here frame j looks its symbol up directly:
 // symbol i owns frames [cum[i-1], cum[i]).  Pass 1 (one workgroup per utterance): scan + scatter frame->symbol.
 // Pass 2: gather + prior sampling z_p = m + noise*exp(logs)*noise_scale (models.py:1071).
-__global__ void __launch_bounds__(256) frame_index_kernel(const ExpandArgs A) {
-  __shared__ int part[256];
-  __shared__ int carry_s;
-  const int b = blockIdx.x;
-  const int ylen = (int)A.y_lengths[b];
-  int* fi = A.frame_idx + (int64_t)b * A.Ty;
-  for (int j = threadIdx.x; j < A.Ty; j += 256) {
-    fi[j] = -1;
-    if (A.y_mask) A.y_mask[(int64_t)b * A.Ty + j] = j < ylen ? 1.f : 0.f;
-  }
-  if (threadIdx.x == 0) carry_s = 0;
+// utterance b's symbols in chunks of 256 (any T): inclusive scan of the durations in `part`, the running total in *carry_s; symbol i
+// then meets own(i, start, end) with its frames [start, end).  All 256 threads of the workgroup call it.
+template <class F>
+__device__ __forceinline__ void duration_scan(const ExpandArgs& A, const int b, int* part, int* carry_s, F own) {
+  if (threadIdx.x == 0) *carry_s = 0;
   __syncthreads();
-  // symbols in chunks of 256: inclusive scan of durations, then each symbol writes its own frames
   for (int base = 0; base < A.T; base += 256) {
     const int i = base + threadIdx.x;
     int d = 0;
@@ -511,20 +513,32 @@ __global__ void __launch_bounds__(256) frame_index_kernel(const ExpandArgs A) {
       part[threadIdx.x] += v;
       __syncthreads();
     }
-    const int end = carry_s + part[threadIdx.x];
-    const int start = end - d;
-    for (int j = start; j < end && j < ylen && j < A.Ty; ++j) fi[j] = i;
+    const int end = *carry_s + part[threadIdx.x];
+    own(i, end - d, end);
     __syncthreads();
-    if (threadIdx.x == 255) carry_s = end;
+    if (threadIdx.x == 255) *carry_s = end;
     __syncthreads();
   }
 }
 
-__global__ void expand_kernel(const ExpandArgs A) {
-  const int b = blockIdx.z, c = blockIdx.y;
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= A.Ty) return;
-  const int i = A.frame_idx[(int64_t)b * A.Ty + j];
+__global__ void __launch_bounds__(256) frame_index_kernel(const ExpandArgs A) {
+  __shared__ int part[256];
+  __shared__ int carry_s;
+  const int b = blockIdx.x;
+  const int ylen = (int)A.y_lengths[b];
+  int* fi = A.frame_idx + (int64_t)b * A.Ty;
+  for (int j = threadIdx.x; j < A.Ty; j += 256) {
+    fi[j] = -1;
+    if (A.y_mask) A.y_mask[(int64_t)b * A.Ty + j] = j < ylen ? 1.f : 0.f;
+  }
+  // each symbol writes its own frames
+  duration_scan(A, b, part, &carry_s, [&](const int i, const int start, const int end) {
+    for (int j = start; j < end && j < ylen && j < A.Ty; ++j) fi[j] = i;
+  });
+}
+
+// frame j of (b, c) whose symbol is i (-1: none): gather + prior sampling
+__device__ __forceinline__ void expand_one(const ExpandArgs& A, const int b, const int c, const int j, const int i, const float ns) {
   float m = 0.f, lg = 0.f;
   if (i >= 0) {
     m = A.m_p[((int64_t)b * A.C + c) * A.T + i];
@@ -532,12 +546,19 @@ __global__ void expand_kernel(const ExpandArgs A) {
   }
   const int64_t off = ((int64_t)b * A.C + c) * A.Ty + j;
   const float nz = A.noise[(int64_t)b * A.nz_bstride + (int64_t)c * A.nz_cstride + (int64_t)j * A.nz_tstride];
-  const float ns = A.noise_scale_b ? A.noise_scale_b[b] : A.noise_scale;   // workgroup-uniform (b = blockIdx.z)
   const float zp = m + nz * expf(lg) * ns;
   A.z_p[off] = zp;
   if (A.z_p2) A.z_p2[off] = zp;
   if (A.m_e) A.m_e[off] = m;
   if (A.logs_e) A.logs_e[off] = lg;
+}
+
+__global__ void expand_kernel(const ExpandArgs A) {
+  const int b = blockIdx.z, c = blockIdx.y;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= A.Ty) return;
+  const float ns = A.noise_scale_b ? A.noise_scale_b[b] : A.noise_scale;   // workgroup-uniform (b = blockIdx.z)
+  expand_one(A, b, c, j, A.frame_idx[(int64_t)b * A.Ty + j], ns);
 }
 
 __global__ void attn_path_kernel(const int* frame_idx, float* attn, int T, int Ty) {
@@ -555,6 +576,80 @@ int launch_expand(hipStream_t stream, const ExpandArgs& a0) {
   if (a.attn)
     hipLaunchKernelGGL(attn_path_kernel, dim3((a.T + 255) / 256, a.Ty, a.B), dim3(256), 0, stream, a.frame_idx, a.attn,
                        a.T, a.Ty);
+  return BV2_CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The head of phase B in ONE launch (the five it replaces each did microseconds of work behind a launch boundary of its own); the
+// workgroups of a 1-D grid take one of three roles, as front_kernel's do in phase A:
+//   GEMV     gemv_kernel's grid (rows / 4, nprob, layers), flattened: the same row code, bit-identical outputs.
+//   expand   one workgroup per (utterance, 256 frames, PBF_CG channels).  It first rebuilds the utterance's duration scan in LDS
+//            (duration_scan, as frame_index_kernel) keeping the frame -> symbol entries of its own 256 frames, then gathers its channels
+//            (expand_one, as expand_kernel).  Channel group 0 also writes frame_idx and y_mask; the attn rows of the 256 frames are
+//            dealt round-robin to the channel groups.  Nothing is read that another workgroup of this launch writes.
+//   slots    zeroes the fp32 Generator's x3 slot words (conv_x6.hip: by stores of a launch, never a memset node).
+constexpr int PBF_CG = 8;
+__global__ void __launch_bounds__(256) phase_b_front_kernel(const PhaseBFrontArgs A) {
+  __shared__ int part[256];
+  __shared__ int fi_s[256];
+  __shared__ int carry_s;
+  int blk = blockIdx.x;
+  const int n_gemv = A.gemv_gx * A.G.nprob * A.gemv_layers;
+  if (blk < n_gemv) {
+    gemv_block(A.G, blk % A.gemv_gx, (blk / A.gemv_gx) % A.G.nprob, blk / (A.gemv_gx * A.G.nprob), A.gemv_layers);
+    return;
+  }
+  blk -= n_gemv;
+  const ExpandArgs& E = A.E;
+  const int n_exp = E.B * A.e_chunks * A.e_groups;
+  if (blk < n_exp) {
+    const int cg = blk % A.e_groups, j0 = ((blk / A.e_groups) % A.e_chunks) * 256, b = blk / (A.e_groups * A.e_chunks);
+    const int ylen = (int)E.y_lengths[b];
+    int hi_all = j0 + 256;                         // frames this workgroup keeps: [j0, hi_all), inside the utterance and the tensor
+    hi_all = hi_all < ylen ? hi_all : ylen;
+    hi_all = hi_all < E.Ty ? hi_all : E.Ty;
+    fi_s[threadIdx.x] = -1;
+    duration_scan(E, b, part, &carry_s, [&](const int i, const int start, const int end) {
+      const int hi = end < hi_all ? end : hi_all;
+      for (int j = start > j0 ? start : j0; j < hi; ++j) fi_s[j - j0] = i;
+    });                                            // ends in a barrier: fi_s is complete
+    const int j = j0 + threadIdx.x;
+    if (j < E.Ty) {
+      const int i = fi_s[threadIdx.x];
+      if (cg == 0) {
+        E.frame_idx[(int64_t)b * E.Ty + j] = i;
+        if (E.y_mask) E.y_mask[(int64_t)b * E.Ty + j] = j < ylen ? 1.f : 0.f;
+      }
+      const float ns = E.noise_scale_b ? E.noise_scale_b[b] : E.noise_scale;
+      const int c1 = (cg + 1) * PBF_CG < E.C ? (cg + 1) * PBF_CG : E.C;
+      for (int c = cg * PBF_CG; c < c1; ++c) expand_one(E, b, c, j, i, ns);
+    }
+    if (E.attn)
+      for (int r = cg; r < 256 && j0 + r < E.Ty; r += A.e_groups) {
+        const int fr = fi_s[r];
+        float* row = E.attn + ((int64_t)b * E.Ty + j0 + r) * E.T;
+        for (int i = threadIdx.x; i < E.T; i += 256) row[i] = fr == i ? 1.f : 0.f;
+      }
+    return;
+  }
+  blk -= n_exp;
+  const int w = blk * 256 + threadIdx.x;
+  if (w < A.slot_words) A.slots[w] = 0u;
+}
+
+int launch_phase_b_front(hipStream_t stream, const PhaseBFrontArgs& a0) {
+  PhaseBFrontArgs a = a0;
+  const ExpandArgs& E = a.E;
+  if (a.G.nprob < 1 || a.G.nprob > 16 || a.G.B < 1 || a.G.B != E.B || E.C < 1 || E.T < 1 || E.Ty < 1) return -1;
+  if (a.slot_words < 0 || (a.slot_words > 0 && !a.slots)) return -1;
+  if (a.E.nz_tstride <= 0) a.E.nz_tstride = 1;
+  int maxc = 0;
+  for (int i = 0; i < a.G.nprob; ++i) maxc = a.G.p[i].cout > maxc ? a.G.p[i].cout : maxc;
+  a.gemv_gx = (maxc + 3) / 4; a.gemv_layers = gemv_layers(a.G.B);
+  a.e_chunks = (E.Ty + 255) / 256; a.e_groups = (E.C + PBF_CG - 1) / PBF_CG;
+  const int64_t blocks = (int64_t)a.gemv_gx * a.G.nprob * a.gemv_layers + (int64_t)E.B * a.e_chunks * a.e_groups + (a.slot_words + 255) / 256;
+  if (blocks < 1 || blocks > 0x7fffffff) return -1;
+  hipLaunchKernelGGL(phase_b_front_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
   return BV2_CHECK_LAUNCH();
 }
 

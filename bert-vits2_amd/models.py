@@ -21,6 +21,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import numbers
+import weakref
 from typing import Dict, Optional
 
 import torch
@@ -34,7 +35,8 @@ from .schema import param_shapes
 def draw_noise_w(B: int, T: int, device) -> torch.Tensor:
     """Draw #1 of reference infer(), models.py:248-251: ``torch.randn(B, 2, T).to(device=..., dtype=...)`` — taken from the
     global CPU generator even when the model sits on a GPU, then uploaded.  Same call, same stream position: a seeded
-    reference run and a seeded run of this shim draw the same SDP noise (RNG contract)."""
+    reference run and a seeded run of this shim draw the same SDP noise (RNG contract).  ``device`` None: the draw
+    stays on the host (``encode_durations(lean=True)`` uploads it only when the stochastic predictor runs)."""
     return torch.randn(B, 2, T).to(device=device, dtype=torch.float32)
 
 
@@ -94,6 +96,31 @@ class _Node(nn.Module):
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class _LastEncode(dict):
+    """``SynthesizerTrn.last_encode``: what phase A of the last ``infer`` / ``infer_stream`` returned.  They ask for the lean form
+    (``encode_durations(lean=True)``), which at ``sdp_ratio`` 0 carries no ``logw_sdp`` and at 1 no ``logw_dp``; a reader that indexes the
+    missing one gets it computed on first access by that predictor's single-stage call (``stage_sdp`` / ``stage_dp``) on the kept encoder
+    output — parity tests and debugging, off the hot path.  It is not among ``keys()`` until then."""
+
+    def __init__(self, enc, model, noise_w, noise_scale_w):
+        super().__init__(enc)
+        self._model, self._noise_w, self._noise_scale_w = weakref.ref(model), noise_w, noise_scale_w
+
+    def __missing__(self, key):
+        m = self._model()
+        if key not in ("logw_sdp", "logw_dp") or m is None:
+            raise KeyError(key)
+        if key == "logw_dp":
+            v = m.stage_dp(self["x"], self["x_mask"], self["g"])[:, 0]
+        else:
+            B = self["x"].shape[0]
+            scale, per_item = item_control("noise_scale_w", self._noise_scale_w, B, m.device)
+            zin = self._noise_w.to(m.device, torch.float32) * (scale if per_item is None else per_item.reshape(B, 1, 1))
+            v = m.stage_sdp(self["x"], self["x_mask"], zin, self["g"])[:, 0]
+        self[key] = v
+        return v
 
 
 class SynthesisStream:
@@ -548,8 +575,15 @@ class SynthesizerTrn(nn.Module):
     # ------------------------------------------------------------------ the two phases
     @torch.no_grad()
     def encode_durations(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w, noise_scale_w=0.8,
-                         sdp_ratio=0.0, length_scale=1.0, bert_index=None, g=None) -> Dict[str, torch.Tensor]:
+                         sdp_ratio=0.0, length_scale=1.0, bert_index=None, g=None, lean=False) -> Dict[str, torch.Tensor]:
         """Phase A = reference models.py:1045-1057.  ``noise_w`` [B,2,T] is the draw of models.py:248-251.
+
+        ``lean`` (what ``infer`` asks for): the output the mix ``logw = sdp * r + dp * (1 - r)`` cannot see is not asked for, which lets the
+        library run only the other predictor (include/bv2.h, ``bv2_encode_out``): at a scalar ``sdp_ratio`` of exactly 0 there is no
+        ``logw_sdp``, the stochastic predictor is not launched and ``noise_w`` is neither uploaded nor read (it may stay on the host); at
+        exactly 1 there is no ``logw_dp`` and the deterministic one is not launched.  Any other ratio or per-utterance ratios: all ten
+        outputs, as in the full form.  With a tap set or ``set_option("lean_durations", 0)`` both predictors run as well.  What is returned
+        is bit for bit what the full form returns (``logw``: by value, a zero may differ in sign).
 
         ``g`` (optional, [B, gin] or [B, gin, 1]): the speaker vectors to condition on instead of ``emb_g(sid)`` — ``sid`` is then not
         read and may be None (``bv2_encode_durations_g``).  A model with ``n_speakers=0`` has no table and needs it.
@@ -573,7 +607,7 @@ class SynthesizerTrn(nn.Module):
         sid = None if sid is None else i64(sid)
         if g is None and sid is None:
             raise ValueError("sid must be given (or g)")
-        bert, ja_bert, en_bert, noise_w = f32(bert), f32(ja_bert), f32(en_bert), f32(noise_w)
+        bert, ja_bert, en_bert = f32(bert), f32(ja_bert), f32(en_bert)
         bidx = [None, None, None] if bert_index is None else [None if t is None else t.to(dev, torch.int32).contiguous() for t in bert_index]
         for feat, ix in zip((bert, ja_bert, en_bert), bidx):
             want = (B, H.BERT_DIM, T) if ix is None else (B, H.BERT_DIM, feat.shape[2])
@@ -586,7 +620,7 @@ class SynthesizerTrn(nn.Module):
                 ein.bert_index[i] = None if bidx[i] is None else ptr_of(i)
                 ein.bert_cols[i] = cols[i]
             return ein
-        if noise_w.shape != (B, 2, T):
+        if tuple(noise_w.shape) != (B, 2, T):
             raise ValueError("noise_w must be [B,2,T]")
         # per-utterance controls: if any of the three is a [B] tensor, all three go to the library as [B] arrays (rows 0-2 of a
         # [4, B] buffer, bv2_item_controls); otherwise the scalar call runs exactly as before
@@ -604,16 +638,24 @@ class SynthesizerTrn(nn.Module):
             noise_scale_w = sdp_ratio = length_scale = 0.0        # ignored by the library: every member of the controls is set
         else:
             noise_scale_w, sdp_ratio, length_scale = (v for v, _ in ctrl)
+        # the library's rule for leaving the stochastic predictor out (bv2_exec.cpp run_encode), mirrored to know whether noise_w is read
+        skip_sdp = bool(lean and ctl is None and sdp_ratio == 0.0 and not self._taps and self._options.get("lean_durations", 1))
+        noise_w = None if skip_sdp else f32(noise_w)
         hp = self.hp
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         okeys = ("g", "x", "m_p", "logs_p", "x_mask", "logw_sdp", "logw_dp", "logw", "w_ceil", "y_lengths")
+        # lean: the output of the predictor the mix cannot see is NULL in bv2_encode_out and absent from the result
+        unseen = {0.0: "logw_sdp", 1.0: "logw_dp"}.get(sdp_ratio) if lean and ctl is None else None
         mk_out = lambda: dict(g=e(B, hp.gin_channels), x=e(B, hp.hidden_channels, T), m_p=e(B, hp.inter_channels, T),
-                              logs_p=e(B, hp.inter_channels, T), x_mask=e(B, T), logw_sdp=e(B, T), logw_dp=e(B, T),
+                              logs_p=e(B, hp.inter_channels, T), x_mask=e(B, T),
+                              **{k: e(B, T) for k in ("logw_sdp", "logw_dp") if k != unseen},
                               logw=e(B, T), w_ceil=e(B, T), y_lengths=torch.empty(B, dtype=torch.int64, device=dev))
         if self._graphs_on and not self._taps:
             ws = self._workspace(B, T, 1)
             ins = dict(x=x, x_lengths=x_lengths, sid=sid, tone=tone, language=language, bert=bert, ja_bert=ja_bert,
                        en_bert=en_bert, noise_w=noise_w)
+            if noise_w is None:
+                del ins["noise_w"]                  # not read: neither staged nor moved
             if g is not None:
                 del ins["sid"]                      # not read
                 ins["g"] = g                        # the graph owns a [B, gin] copy, refilled before every replay like the controls
@@ -634,7 +676,7 @@ class SynthesizerTrn(nn.Module):
                                                                     "en_bert", "noise_w")],
                                  float(noise_scale_w), float(sdp_ratio), float(length_scale))
                 with_index(ein, lambda i: sin[f"bert_index{i}"].data_ptr())
-                eout = L.EncodeOut(*[_ptr(sout[k]) for k in okeys])
+                eout = L.EncodeOut(*[_ptr(sout.get(k)) for k in okeys])
                 icp = None if ctl is None else _controls_ptr(sin["ctl"], (0, 1, 2))
                 with torch.cuda.device(dev):
                     if g is not None:
@@ -651,7 +693,7 @@ class SynthesizerTrn(nn.Module):
             ptrs = tuple(ins[k].data_ptr() for k in ins if k not in moving) if static else ()
             # per-utterance controls and a given g: the key carries the fact ("ctl" / "g" in ins), not the values
             scal = ("item",) if ctl is not None else (float(noise_scale_w), float(sdp_ratio), float(length_scale))
-            ent = self._graph_entry(("A", B, T) + scal + (tuple(cols), tuple(sorted(ins))), build, ptrs)
+            ent = self._graph_entry(("A", B, T, bool(lean)) + scal + (tuple(cols), tuple(sorted(ins))), build, ptrs)
             for k in ent["staged"]:
                 ent["sin"][k].copy_(ins[k], non_blocking=True)
             with torch.cuda.device(dev):
@@ -664,7 +706,7 @@ class SynthesizerTrn(nn.Module):
         ein = L.EncodeIn(B, T, _ptr(x), _ptr(x_lengths), _ptr(sid), _ptr(tone), _ptr(language), _ptr(bert), _ptr(ja_bert),
                          _ptr(en_bert), _ptr(noise_w), float(noise_scale_w), float(sdp_ratio), float(length_scale))
         with_index(ein, lambda i: bidx[i].data_ptr())
-        eout = L.EncodeOut(*[_ptr(out[k]) for k in okeys])
+        eout = L.EncodeOut(*[_ptr(out.get(k)) for k in okeys])
         ws = self._workspace(B, T, 1)
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -845,10 +887,10 @@ class SynthesizerTrn(nn.Module):
                 raise ValueError("this model has no speaker table (n_speakers=0): infer() needs y (the reference spectrogram) or g")
             g = self.reference_embedding(y, y_lengths)
         if noise_w is None:
-            noise_w = draw_noise_w(B, T, dev)
+            noise_w = draw_noise_w(B, T, None)         # drawn either way (the RNG stream stays the reference's); uploaded only if read
         enc = self.encode_durations(x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w,
                                     noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, length_scale=length_scale,
-                                    bert_index=bert_index, g=g)
+                                    bert_index=bert_index, g=g, lean=True)
         if w_ceil is not None:
             wc = w_ceil.to(dev, torch.float32).reshape(B, T).contiguous()
             enc["w_ceil"] = wc
@@ -859,7 +901,7 @@ class SynthesizerTrn(nn.Module):
             noise_z = noise_z.to(dev, torch.float32)
         dec = self.decode(enc, noise_z, Ty, noise_scale=noise_scale, max_len=max_len, want_attn=want_attn,
                           exact_lengths=exact_lengths, ty_bucket=ty_bucket)
-        self.last_encode = enc
+        self.last_encode = _LastEncode(enc, self, noise_w, noise_scale_w)
         return dec["o"], dec["attn"], dec["y_mask"], (dec["z"], dec["z_p"], dec["m_p"], dec["logs_p"])
 
     @torch.no_grad()
@@ -897,10 +939,10 @@ class SynthesizerTrn(nn.Module):
                 raise ValueError("this model has no speaker table (n_speakers=0): infer_stream() needs y (the reference spectrogram) or g")
             g = self.reference_embedding(y, y_lengths)
         if noise_w is None:
-            noise_w = draw_noise_w(B, T, dev)
+            noise_w = draw_noise_w(B, T, None)         # drawn either way (the RNG stream stays the reference's); uploaded only if read
         enc = self.encode_durations(x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w,
                                     noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, length_scale=length_scale,
-                                    bert_index=bert_index, g=g)
+                                    bert_index=bert_index, g=g, lean=True)
         if w_ceil is not None:
             wc = w_ceil.to(dev, torch.float32).reshape(B, T).contiguous()
             enc["w_ceil"] = wc
@@ -939,7 +981,7 @@ class SynthesizerTrn(nn.Module):
             t1 = min(frames, t + (first if t == 0 else chunk_frames))
             bounds.append((t, t1))
             t = t1
-        self.last_encode = enc
+        self.last_encode = _LastEncode(enc, self, noise_w, noise_scale_w)
         st = SynthesisStream(self, enc, ws, Ty, frames, bounds, window, exact_lengths, as_pcm16, pcm_gain, aux, output_rate)
         st.y_lengths_host = yl_host
         return st
@@ -1049,7 +1091,7 @@ class SynthesizerTrn(nn.Module):
         return o
 
     def set_option(self, key: str, value: int) -> None:
-        """Kernel-selection switches of ``bv2_set_option`` ("fused_resblock", "fused_dds"); tests only."""
+        """Kernel-selection switches of ``bv2_set_option`` ("fused_resblock", "fused_dds", "lean_durations"); tests and A/B runs."""
         self._ensure_handle()
         self._check(self._lib.bv2_set_option(self._handle, key.encode(), int(value)), "bv2_set_option")
         self._options[key] = int(value)

@@ -127,7 +127,8 @@ typedef struct bv2_encode_in {
   const float* bert;         /* [B,bert_dim,T] */
   const float* ja_bert;      /* [B,bert_dim,T] */
   const float* en_bert;      /* [B,bert_dim,T] */
-  const float* noise_w;      /* [B,2,T]  N(0,1): the torch.randn of models.py:248-251, drawn by the caller */
+  const float* noise_w;      /* [B,2,T]  N(0,1): the torch.randn of models.py:248-251, drawn by the caller; may be NULL exactly when the
+                              * stochastic predictor is not run (see bv2_encode_out), otherwise NULL is an error (-1) */
   float noise_scale_w, sdp_ratio, length_scale;
   /* Optional WORD-level BERT features.  The reference runs the BERT model, copies hidden_states[-3] to the host,
    * repeats word i's row word2ph[i] times (text/chinese_bert.py:37, 48-58) and uploads [1024, T] again.  With
@@ -147,6 +148,13 @@ typedef struct bv2_encode_out {   /* all DEVICE, caller-allocated */
   float* x_mask;     /* [B,T] (1.0 / 0.0)                                  models.py:392-394 */
   float* logw_sdp;   /* [B,T]  sdp(...) before mixing (may be NULL) */
   float* logw_dp;    /* [B,T]  dp(...)  before mixing (may be NULL) */
+  /* Only the predictor the mix can see is run.  logw = logw_sdp * r + logw_dp * (1 - r) with r = sdp_ratio, so with
+   *   - the scalar bv2_encode_in.sdp_ratio exactly 0.0f (no per-utterance bv2_item_controls.sdp_ratio: those values live on the device),
+   *   - logw_sdp == NULL, no tap set (bv2_set_tap) and the option "lean_durations" on (default),
+   * the StochasticDurationPredictor is not launched, noise_w is not read and logw = logw_dp * 1.  In the same way sdp_ratio exactly 1.0f
+   * with logw_dp == NULL leaves the DurationPredictor out.  Every other request runs both.  The one difference from the reference's
+   * `sdp * 0 + dp`: a non-finite value of the skipped predictor cannot reach logw, and a zero in logw may differ in sign; w_ceil,
+   * y_lengths and everything downstream are the same. */
   float* logw;       /* [B,T]                                              models.py:1052-1054 */
   float* w_ceil;     /* [B,T]  ceil(exp(logw)*mask*length_scale)           models.py:1055-1056 */
   int64_t* y_lengths;/* [B]    clamp_min(sum(w_ceil),1)                    models.py:1057 */
@@ -541,6 +549,9 @@ void bv2_graph_destroy(bv2_graph* graph);
  *                     0 / 1: no key split; 2 / 4: that many ranges where the slabs allow it
  *   "overlap_dp"      default 0: 1 runs the DurationPredictor on an internal side stream beside the stochastic one (fork / join
  *                     with events on the caller's stream; measured slower at batch 1, kept for experiments)
+ *   "lean_durations"  default 1: phase A runs only the duration predictor the mix can see (bv2_encode_out); 0: both, always
+ *   "phase_b_front"   default 1: the head of phase B (length regulation, prior sampling, attn path, speaker GEMVs, the fp32 Generator's
+ *                     x3 slot words) is one launch; 0: five launches.  Bit-identical either way
  * Captured graphs keep whatever was selected when they were recorded. */
 int bv2_set_option(bv2_handle* h, const char* key, int value);
 
