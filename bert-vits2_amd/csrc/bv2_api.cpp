@@ -838,6 +838,10 @@ int bv2_set_option(bv2_handle* h, const char* key, int value) {
   else if (k == "fused_dds") h->no_fused_dds = value == 0;
   else if (k == "fused_attn_o") h->no_fused_attn_o = value == 0;
   else if (k == "attn_ksplit") h->attn_ksplit = value;
+  else if (k == "attn_qtile") {
+    if (value != 0 && value != 16 && value != 32) { h->err = "bv2_set_option: attn_qtile is 0, 16 or 32"; return -1; }
+    h->attn_qtile = value;
+  }
   else if (k == "overlap_dp") h->no_overlap_dp = value == 0;
   else if (k == "lean_durations") h->no_lean_durations = value == 0;
   else if (k == "phase_b_front") h->no_phase_b_front = value == 0;

@@ -188,6 +188,7 @@ void run_encoder(Ctx& c, const EncoderW& e, const EncBufs& b, const float* mask,
     a.qkv = b.qkv; a.ld = ld; a.mask = mask; a.erv = c.W(L.erv.off); a.out = b.att;
     a.B = B; a.H = e.heads; a.D = H / e.heads; a.T = T; a.W = kAttnWindow; a.f16 = f16 ? 1 : 0; a.xcd_b = xcd ? 1 : 0;
     if (kv16) { a.kh = b.k16; a.vh = b.v16; }
+    if (!f16) a.qtile = c.h->attn_qtile;
     // small-N regime (the one where `s` holds partial slabs): conv_o runs inside the attention kernel, head h -> slab h
     const bool fuse_o = !f16 && !c.h->no_fused_attn_o && n_slabs(B, T) >= e.heads && L.o.k == 1 && L.o.cin == H;
     // key split (batch 1, long sequences): the key tiles of a (head, query tile) go to `ks` workgroups, each writing its own partial

@@ -566,10 +566,12 @@ struct AttnArgs {
   // workgroup r writes its LOCALLY normalised partial through conv_o into slab h*ksplit + r and (max, sum) of its key range to
   // ml_out [B][H][ksplit][2][T]; the consumer (LnArgs::ml) merges the slabs with the flash-decoding weights
   int ksplit = 1; float* ml_out = nullptr;
+  int qtile = 0;            // queries per workgroup: 0 = attention_pick_qtile, 16 (fp32 only) or 32 forced ("attn_qtile", tests)
   unsigned long long* dbg = nullptr;   // tools/timeline.py only
   int xcd_b = 0; int xcd_gx = 0, xcd_per = 0;   // batch item -> XCD affinity (HcLaunch::xcd_b); xcd_gx / xcd_per: filled by the launcher
 };
 int attention_pick_ksplit(int B, int H, int T, int max_slabs);   // key ranges per (head, query tile) that fill the chip at small batch
+int attention_pick_qtile(int B, int H, int T, int D, int ksplit, bool f16);   // 16 or 32 queries per workgroup, from the shape and dtype alone
 int launch_attention(hipStream_t stream, const AttnArgs& a);
 double attention_flops(const AttnArgs& a);
 

@@ -559,8 +559,20 @@ int bv2_test_layernorm(void* stream, const float* a, const float* add, int mode,
 int bv2_test_attention_ex(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out, int B, int H, int D,
                           int T, int W, int f16, const void* kh, const void* vh, const float* wo_host, float* wo_pack_dev,
                           const float* bo, const float* res, float* o_out, int64_t o_slab_stride, int Co, int ksplit, float* ml_out) {
+  return bv2_test_attention_q(stream, qkv, ld, mask, erv, out, B, H, D, T, W, f16, kh, vh, wo_host, wo_pack_dev, bo, res, o_out, o_slab_stride,
+                              Co, ksplit, ml_out, 0);
+}
+
+int bv2_test_attention_pick_qtile(int B, int H, int T, int D, int ksplit, int f16) {
+  return attention_pick_qtile(B, H, T, D, ksplit, f16 != 0);
+}
+
+int bv2_test_attention_q(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out, int B, int H, int D,
+                         int T, int W, int f16, const void* kh, const void* vh, const float* wo_host, float* wo_pack_dev,
+                         const float* bo, const float* res, float* o_out, int64_t o_slab_stride, int Co, int ksplit, float* ml_out, int qtile) {
   try {
     AttnArgs a;
+    a.qtile = qtile;
     a.qkv = qkv; a.ld = ld; a.mask = mask; a.erv = erv; a.out = out; a.B = B; a.H = H; a.D = D; a.T = T; a.W = W; a.f16 = f16;
     a.kh = static_cast<const uint16_t*>(kh); a.vh = static_cast<const uint16_t*>(vh);
     if (wo_host) {

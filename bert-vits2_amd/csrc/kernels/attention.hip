@@ -33,8 +33,10 @@
 
 namespace bv2 {
 
-constexpr int AQ = 32;          // queries per workgroup
+constexpr int AQ_WIDE = 32;     // queries per workgroup: the 32x32x2 matrix form (and every fp16 form)
+constexpr int AQ_NARROW = 16;   // ... the 16x16x4 form (fp32 only): half the serial chain per workgroup, twice the workgroups
 constexpr int AK = 32;          // keys per tile
+constexpr int ATTN_CUS = 256;   // compute units of the part the tile choice is tuned for
 constexpr int AMAXW = 8;        // max window
 constexpr int ANS = 4;          // merge slots
 
@@ -52,15 +54,30 @@ constexpr int ANS = 4;          // merge slots
 // key's row (6 loads of 16 B per key tile at D = 96 instead of 48 dword loads + 48 conversions), V channel-major [B][HD][ld] (the two groups of
 // four consecutive keys a step needs are two 8-byte loads: half the bytes of the fp32 float4s).  The values are the same fp16 numbers (the
 // rounding moved from this kernel's registers to the projection's epilogue); only the K-index <-> channel assignment of the S^T MFMAs differs.
-template <int DT, int NW, bool F16, bool ONE, bool KV16 = false>   // D = 32*DT head channels, NW waves; ONE: at most one key tile per wave (no loop)
+//
+// QT = 16 (fp32 only; batch 1, where a launch of 32-query tiles leaves most of the chip empty and a workgroup's life is its serial MFMA
+// chains): a workgroup owns 16 queries and the products run on v_mfma_f32_16x16x4_f32 — A[m = l & 15][k = l >> 4], B[k = l >> 4][n = l & 15],
+// D register i = row 4 (l >> 4) + i, column l & 15.  The 32-key tile stays; everything above carries over with lane group g = l >> 4:
+//   S^T   two independent blocks [16 keys x 16 queries] of D/4 MFMAs (K-step s: channel 4s + g); the lane holds one query column and the
+//         4 key rows 16 bk + 4g + i of each block: row max / sum are in-lane + shfl_xor(16), shfl_xor(32).
+//   O^T   D/16 independent blocks [16 channels x 16 queries]; K-step i of key block bk pairs the keys {16 bk + 4g + i : g}, so group g's B
+//         operand is its own probability register and its A operands v[c][16 bk + 4g .. + 3] are one aligned float4.
+//   conv_o  C_out / 16 row blocks dealt over the waves, D/4 MFMAs each; K-step (t, q) takes channel 16t + 8 (g >> 1) + (g & 1) + 2q from
+//         group g, which is component q of ONE float4 of the 32-row fragment order (conv_w_index): no second packed view.
+template <int DT, int NW, bool F16, bool ONE, bool KV16 = false, int QT = AQ_WIDE>   // D = 32*DT head channels, NW waves; ONE: at most one key tile per wave (no loop); QT queries per workgroup
 __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   static_assert(!KV16 || F16, "fp16 K / V only feed the fp16 matrix products");
+  static_assert(QT == AQ_WIDE || (QT == AQ_NARROW && !F16), "the fp16 forms stay on 32 queries");
   constexpr int D = 32 * DT;
   constexpr int NT = 64 * NW;
+  constexpr int AQ = QT, QSH = QT == 32 ? 5 : 4;    // e >> QSH, e & (AQ - 1): row and query of element e of an [..][AQ] tile
+  constexpr int NS = AK * AQ / 64;                  // logits per lane of a 32-key tile
+  constexpr int CPI = NT / AQ;                      // channels the workgroup covers per pass of the epilogue loops
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: keeps everything derived from it in SGPRs
   const int l31 = lane & 31, lh = lane >> 5;
+  const int lq = lane & (AQ - 1), lg = lane >> QSH; // query column and lane group of the MFMA layouts (QT = 32: l31, lh)
   const int KS = A.ksplit > 1 ? A.ksplit : 1;
   int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
   if (A.xcd_b) {                                             // batch item -> XCD affinity (bv2_kernels.h xcd_decode)
@@ -91,7 +108,7 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   const float* qe = base + (int64_t)(3 * HD + h * NR) * ld;
   const float* mp = A.mask + (int64_t)b * T;
 
-  const int iq = i0 + l31;                          // this lane's query
+  const int iq = i0 + lq;                           // this lane's query
   const bool iok = iq < T;
   const int ntiles_all = (T + AK - 1) / AK;
   const int kt0 = (ntiles_all * kr) / KS, kt1 = (ntiles_all * (kr + 1)) / KS;   // key tiles [kt0, kt1) are this workgroup's
@@ -106,13 +123,18 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   const uint16_t* const khp = KV16 ? A.kh + (int64_t)b * ld * HD + h * D : nullptr;
   const uint16_t* const vhp = KV16 ? A.vh + ((int64_t)b * HD + h * D) * ld : nullptr;
   float mkey = 0.f;
-  const unsigned koff = 4u * (unsigned)(lh * ld + l31);         // per-lane byte offsets, shared by every load of a tile
-  const unsigned voff = 4u * (unsigned)(l31 * ld + 4 * lh);
+  const unsigned koff = 4u * (unsigned)(lg * ld + lq);          // per-lane byte offsets, shared by every load of a tile
+  const unsigned voff = 4u * (unsigned)(lq * ld + 4 * lg);
   auto issue_k = [&](int j0) __attribute__((always_inline)) {
     if constexpr (KV16) {
       const uint16_t* kr_ = khp + (int64_t)(j0 + l31) * HD + 8 * lh;     // rows up to ld exist (ld = T rounded up to 32)
 #pragma unroll
       for (int t = 0; t < D / 16; ++t) kq[t] = *reinterpret_cast<const u32x4*>(kr_ + 16 * t);
+    } else if constexpr (QT == 16) {                // kreg[bk D/4 + s] = k[4s + g][j0 + 16 bk + (l & 15)]
+#pragma unroll
+      for (int bk = 0; bk < 2; ++bk)
+#pragma unroll
+        for (int s = 0; s < D / 4; ++s) kreg[bk * (D / 4) + s] = ld_off(kp, koff + 4u * (unsigned)(j0 + 16 * bk + 4 * s * ld));
     } else {
 #pragma unroll
     for (int s = 0; s < D / 2; ++s) kreg[s] = ld_off(kp, koff + 4u * (unsigned)(j0 + 2 * s * ld));
@@ -131,6 +153,12 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
           vq[m][s2][1] = *reinterpret_cast<const u32x2*>(vr_ + 16 * s2 + 8);
         }
       }
+    } else if constexpr (QT == 16) {                // vreg[m][g4]: channel block cb = 2m + (g4 >> 1), key block bk = g4 & 1
+#pragma unroll
+      for (int m = 0; m < DT; ++m)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+          vreg[m][g4] = ld_off4(vp, voff + 4u * (unsigned)((m * 32 + 16 * (g4 >> 1)) * ld + j0 + 16 * (g4 & 1)));
     } else {
 #pragma unroll
     for (int m = 0; m < DT; ++m)
@@ -157,7 +185,7 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
     for (int q = 0; q < QPT; ++q) {
       int e = tid + q * NT;
       e = e < D * AQ ? e : D * AQ - 1;
-      qv[q] = qp[(e >> 5) * ld + i0 + (e & 31)];    // columns beyond T: finite-or-not garbage, dead columns below
+      qv[q] = qp[(e >> QSH) * ld + i0 + (e & (AQ - 1))];    // columns beyond T (< ld: i0 + AQ <= ld): finite-or-not garbage, dead columns below
     }
     // ... and so are the relative-value table and the relative-key logit rows of the tile (ISA of round 2: each `for (e = tid; ...)
     // LDS[e] = global[e]` loop iteration was a load -> s_waitcnt vmcnt(0) -> ds_write of its own, four serial round trips behind the
@@ -174,8 +202,8 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
     for (int q = 0; q < QEPT; ++q) {
       int e = tid + q * NT;
       e = e < NR * AQ ? e : NR * AQ - 1;
-      const int ic = i0 + (e & 31) < T ? i0 + (e & 31) : T - 1;
-      qev[q] = qe[(e >> 5) * ld + ic];
+      const int ic = i0 + (e & (AQ - 1)) < T ? i0 + (e & (AQ - 1)) : T - 1;
+      qev[q] = qe[(e >> QSH) * ld + ic];
     }
 #pragma unroll
     for (int q = 0; q < EVPT; ++q) {
@@ -185,13 +213,13 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
 #pragma unroll
     for (int q = 0; q < QEPT; ++q) {
       const int e = tid + q * NT;
-      if (e < NR * AQ) Qe[e] = (i0 + (e & 31) < T) ? qev[q] : 0.f;
+      if (e < NR * AQ) Qe[e] = (i0 + (e & (AQ - 1)) < T) ? qev[q] : 0.f;
     }
 #pragma unroll
     for (int q = 0; q < QPT; ++q) {
       const int e = tid + q * NT;
       if (e >= D * AQ) continue;
-      const int c = e >> 5, i = e & 31;
+      const int c = e >> QSH, i = e & (AQ - 1);
       if (F16 && KV16) {
         Qh[i * QP + c] = (_Float16)((i0 + i < T) ? qv[q] : 0.f);       // natural order: K-index 16t + 8lh + e is channel 16t + 8lh + e
       } else if (F16) {
@@ -209,11 +237,14 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   if (A.dbg) ts1 = __builtin_amdgcn_s_memtime();
   const float mi = iok ? mi_raw : 0.f;
 
-  f32x16 O[DT];
+  f32x16 O[QT == 32 ? DT : 1];                      // QT = 32: [32 channels x 32 queries] blocks
+  f32x4 O4[QT == 16 ? 2 * DT : 1];                  // QT = 16: [16 channels x 16 queries] blocks
 #pragma unroll
-  for (int m = 0; m < DT; ++m)
+  for (int m = 0; m < (QT == 32 ? DT : 1); ++m)
 #pragma unroll
     for (int r = 0; r < 16; ++r) O[m][r] = 0.f;
+#pragma unroll
+  for (int cb = 0; cb < (QT == 16 ? 2 * DT : 1); ++cb) O4[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;
 
 #pragma unroll 1
@@ -237,6 +268,23 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
         const f16x8 qf = *reinterpret_cast<const f16x8*>(Qh + l31 * QP + t * 16 + lh * 8);
         S = mfma_32x32x16(ka, qf, S);
       }
+    } else if constexpr (QT == 16) {
+      // two independent [16 keys x 16 queries] blocks share each Q operand; S[4 bk + i] = key row 16 bk + 4g + i (elements 8.. unused)
+      f32x4 S4[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+      float qb[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) qb[s] = Qs[(4 * s + lg) * AQ + lq];
+#pragma unroll
+      for (int s = 0; s < D / 4; ++s) {
+        const float qcur = qb[s & 3];
+        if (s + 4 < D / 4) qb[s & 3] = Qs[(4 * (s + 4) + lg) * AQ + lq];
+        S4[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(kreg[s], qcur, S4[0], 0, 0, 0);
+        S4[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(kreg[D / 4 + s], qcur, S4[1], 0, 0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 8; ++r) S[r] = S4[r >> 2][r & 3];
     } else {
     // the Q operand streams from LDS a few K-steps ahead of the MFMAs (pinned: hoisting all D/2 reads costs registers)
     float qb[4];
@@ -258,17 +306,17 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
     const bool near_band = (j0 - i0 <= AQ - 1 + W) && (i0 - j0 <= AK - 1 + W);     // wave-uniform
     float tmax = -INFINITY;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int jr = (r & 3) + 8 * (r >> 2) + 4 * lh;
+    for (int r = 0; r < NS; ++r) {
+      const int jr = (r & 3) + (AK / (NS / 4)) * (r >> 2) + 4 * lg;   // D-layout row of register r: groups of 4 rows, 8 (QT = 16: 16) apart
       const int j = j0 + jr;
       float sv = S[r];
       const float mj = __shfl(mkey, jr);                       // key mask of row jr (lane jr loaded key j0+jr)
       if (near_band) {
         const int rel = j - iq;
         const bool inband = (rel >= -W) && (rel <= W) && iok && j < T;
-        if (inband) sv += Qe[(rel + W) * AQ + l31];
+        if (inband) sv += Qe[(rel + W) * AQ + lq];
         if (!(mi != 0.f && mj != 0.f)) sv = -1e4f;              // masked_fill(mask == 0, -1e4), attentions.py:297
-        if (inband) Sb[(rel + W) * AQ + l31] = sv;
+        if (inband) Sb[(rel + W) * AQ + lq] = sv;
       } else {
         if (!(mi != 0.f && mj != 0.f)) sv = -1e4f;
       }
@@ -277,24 +325,31 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
       S[r] = sv;
       tmax = fmaxf(tmax, sv);
     }
+    if (QT == 16) tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
     const float m_new = fmaxf(m_run, tmax);
     const float alpha = __expf(m_run - m_new);                  // first tile: exp(-inf) = 0
     float psum = 0.f;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
+    for (int r = 0; r < NS; ++r) {
       const float p = __expf(S[r] - m_new);
       psum += p;
       S[r] = p;
     }
+    if (QT == 16) psum += __shfl_xor(psum, 16);
     psum += __shfl_xor(psum, 32);
     l_run = l_run * alpha + psum;
     m_run = m_new;
     if (!ONE && kt >= NW) {
+      if constexpr (QT == 16) {
+#pragma unroll
+        for (int cb = 0; cb < 2 * DT; ++cb) O4[cb] *= alpha;
+      } else {
 #pragma unroll
       for (int m = 0; m < DT; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) O[m][r] *= alpha;
+      }
     }
     // ---- O^T += V P^T, K-steps in D-layout row order
     if (F16) {
@@ -329,6 +384,29 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
           O[m] = mfma_32x32x16(vf, pf[s2], O[m]);
         }
       }
+    } else if constexpr (QT == 16) {
+      // K-step i of key block bk pairs the keys 16 bk + 4g + i: B = this lane's S[4 bk + i]; the 2 DT channel blocks are independent chains
+#pragma unroll
+      for (int bk = 0; bk < 2; ++bk) {
+        const int jb = j0 + 16 * bk + 4 * lg;
+        f32x4 v4[2 * DT];
+#pragma unroll
+        for (int cb = 0; cb < 2 * DT; ++cb) {
+          v4[cb] = vreg[cb >> 1][2 * (cb & 1) + bk];
+          if (jb + 3 >= T) {                                  // tile tail: keys that do not exist contribute exactly 0
+            v4[cb].x = jb + 0 < T ? v4[cb].x : 0.f; v4[cb].y = jb + 1 < T ? v4[cb].y : 0.f;
+            v4[cb].z = jb + 2 < T ? v4[cb].z : 0.f; v4[cb].w = jb + 3 < T ? v4[cb].w : 0.f;
+          }
+        }
+#pragma unroll
+        for (int cb = 0; cb < 2 * DT; ++cb) O4[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(v4[cb].x, S[4 * bk + 0], O4[cb], 0, 0, 0);
+#pragma unroll
+        for (int cb = 0; cb < 2 * DT; ++cb) O4[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(v4[cb].y, S[4 * bk + 1], O4[cb], 0, 0, 0);
+#pragma unroll
+        for (int cb = 0; cb < 2 * DT; ++cb) O4[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(v4[cb].z, S[4 * bk + 2], O4[cb], 0, 0, 0);
+#pragma unroll
+        for (int cb = 0; cb < 2 * DT; ++cb) O4[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(v4[cb].w, S[4 * bk + 3], O4[cb], 0, 0, 0);
+      }
     } else {
 #pragma unroll
     for (int m = 0; m < DT; ++m) {
@@ -353,32 +431,43 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   // fused conv_o: this wave's first 32-row tile of W_o (12 float4 per lane at D = 96) goes in flight NOW — the K / V registers are
   // dead — and lands under the merge below; loaded where it is used it was an exposed L2 round trip after the last barrier
   // (tools/timeline.py: normalise + conv_o + store 16-21k cycles of a 46-59k-cycle workgroup)
-  f32x4 wr0[D / 8];
-  const bool pre_w = A.wo != nullptr && wid * 32 < A.Co;
+  // W_o row block `blk` (AQ rows: the MFMA is square) of head h, this lane's float4 of K-group 0; K-group t is WSTR float4s further.
+  // QT = 32: 32-row m-tile blk, the lane's (lh, row l31) float4 of 8-channel group t.  QT = 16: rows 16 (blk & 1) .. + 15 of m-tile
+  // blk >> 1; lane group g reads the (lh = g & 1) float4 of 8-channel group 2t + (g >> 1): channels 16t + 8 (g >> 1) + (g & 1) + 2q.
+  constexpr int WG = QT == 32 ? D / 8 : D / 16, WSTR = QT == 32 ? 64 : 128;
+  auto wo_frag = [&](int blk) __attribute__((always_inline)) -> const f32x4* {
+    if constexpr (QT == 32)
+      return reinterpret_cast<const f32x4*>(A.wo) + ((int64_t)blk * A.wo_groups + h * (D / 8)) * 64 + lh * 32 + l31;
+    else
+      return reinterpret_cast<const f32x4*>(A.wo) + ((int64_t)(blk >> 1) * A.wo_groups + h * (D / 8) + (lg >> 1)) * 64 + (lg & 1) * 32 +
+             16 * (blk & 1) + lq;
+  };
+  f32x4 wr0[WG];
+  const bool pre_w = A.wo != nullptr && wid * AQ < A.Co;
   if (pre_w) {
-    const f32x4* wp = reinterpret_cast<const f32x4*>(A.wo) + ((int64_t)wid * A.wo_groups + h * (D / 8)) * 64 + lh * 32 + l31;
+    const f32x4* wp = wo_frag(wid);
 #pragma unroll
-    for (int g = 0; g < D / 8; ++g) wr0[g] = wp[g * 64];
+    for (int g = 0; g < WG; ++g) wr0[g] = wp[g * WSTR];
   }
   // ---- merge the waves' partials: (max, sum) first, then the rescaled O tiles through ANS slots in fixed order
-  if (lh == 0) { Mw[wid * AQ + l31] = m_run; Lw[wid * AQ + l31] = l_run; }
+  if (lg == 0) { Mw[wid * AQ + lq] = m_run; Lw[wid * AQ + lq] = l_run; }
   __syncthreads();
   float m_tot = -INFINITY;
 #pragma unroll
-  for (int w = 0; w < NW; ++w) m_tot = fmaxf(m_tot, Mw[w * AQ + l31]);
+  for (int w = 0; w < NW; ++w) m_tot = fmaxf(m_tot, Mw[w * AQ + lq]);
   float l_tot = 0.f;
 #pragma unroll
   for (int w = 0; w < NW; ++w) {
-    const float mw = Mw[w * AQ + l31];
-    l_tot += (mw == -INFINITY) ? 0.f : Lw[w * AQ + l31] * __expf(mw - m_tot);
+    const float mw = Mw[w * AQ + lq];
+    l_tot += (mw == -INFINITY) ? 0.f : Lw[w * AQ + lq] * __expf(mw - m_tot);
   }
-  const float il = 1.0f / l_tot;                    // per lane: query l31 (== tid & 31 below since AQ == 32)
+  const float il = 1.0f / l_tot;                    // per lane: query lq (== tid & (AQ - 1) below: NT is a multiple of 64)
   const float fac = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_tot);
   // band logits -> band probabilities p[i][i+r] (each (r, i) once)
-  // (element e = tid + n NT belongs to query e & 31 == tid & 31 == l31 — NT is a multiple of 64 — so the query's totals are the m_tot / l_tot this
+  // (element e = tid + n NT belongs to query e & (AQ - 1) == tid & (AQ - 1) == lq — NT is a multiple of 64 — so the query's totals are the m_tot / l_tot this
   // lane has just formed: re-deriving them per element was 16 LDS reads and 8 exponentials each)
   for (int e = tid; e < NR * AQ; e += NT) {
-    const int r = e >> 5;
+    const int r = e >> QSH;
     const int j = iq + r - W;
     // key split: a band key outside [kt0, kt1) belongs to another workgroup (its Sb slot was never written here)
     const bool mine = j >= kt0 * AK && j < kt1 * AK;
@@ -387,15 +476,30 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   if (KS > 1 && tid < AQ && i0 + tid < T) {
     // (m_r, l_r) of this key range for the merge in the LayerNorm: [b][h][kr][2][T]
     float* ml = A.ml_out + ((((int64_t)b * A.H + h) * KS + kr) * 2) * T + i0 + tid;
-    ml[0] = m_tot;                                 // tid < 32: lane l31 == tid, so m_tot / l_tot are query tid's
+    ml[0] = m_tot;                                 // tid < AQ: lane lq == tid, so m_tot / l_tot are query tid's
     ml[T] = l_tot;
   }
   if (A.dbg) ts3 = __builtin_amdgcn_s_memtime();
+  // Only waves with a key tile (wid < nwt, uniform across the workgroup) hold a partial: a round none of them is in is not run (its
+  // barrier had nothing to wait for) and `normalise` sums the slots that were written.  What is dropped is `+ 0.0f` (an empty wave's
+  // O * fac is +0): the sums keep their bits, since each starts from +0.0f and so never sees the one case where x + 0.0f != x, x = -0.0f.
   constexpr int ROUNDS = (NW + ANS - 1) / ANS;
+  const int nwt = ntiles < NW ? ntiles : NW;
 #pragma unroll
   for (int rd = 0; rd < ROUNDS; ++rd) {
-    if (wid / ANS == rd) {
+    if (rd * ANS >= nwt) break;
+    if (wid / ANS == rd && wid < nwt) {
       float* slot = Os + (wid % ANS) * (D * AQ);
+      if constexpr (QT == 16) {
+#pragma unroll
+        for (int cb = 0; cb < 2 * DT; ++cb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = cb * 16 + 4 * lg + r;
+            const float val = O4[cb][r] * fac;
+            if (rd == 0) slot[c * AQ + lq] = val; else slot[c * AQ + lq] += val;
+          }
+      } else {
 #pragma unroll
       for (int m = 0; m < DT; ++m)
 #pragma unroll
@@ -404,19 +508,21 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
           const float val = O[m][r] * fac;
           if (rd == 0) slot[c * AQ + l31] = val; else slot[c * AQ + l31] += val;
         }
+      }
     }
     __syncthreads();
   }
-  constexpr int NSLOT = NW < ANS ? NW : ANS;
+  const int nslot = nwt < ANS ? nwt : ANS;          // slots written
   if (A.dbg) ts4 = __builtin_amdgcn_s_memtime();
 
   // ---- normalise, add relative-value term, store (coalesced over queries)
   float* op = A.out + (int64_t)b * HD * T + (int64_t)(h * D) * T;
-  const int i = tid & 31, ig = i0 + i;
+  constexpr int NSLOT = NW < ANS ? NW : ANS;
+  const int i = tid & (AQ - 1), ig = i0 + i;
   if (A.wo) {
-    // Fused output projection (conv_o, attentions.py:269): the head's normalised [D][32 queries] tile goes to LDS (the query tile's
+    // Fused output projection (conv_o, attentions.py:269): the head's normalised [D][AQ queries] tile goes to LDS (the query tile's
     // region: every wave is past the main loop) and the workgroup multiplies it by ITS K-slice of W_o — columns [hD, hD + D) of
-    // the fragment-ordered 1x1 weight — on the fp32 matrix core: one 32-row tile per wave, D/2 MFMAs.  Head h writes partial slab
+    // the fragment-ordered 1x1 weight — on the fp32 matrix core: one 32-row tile per wave, D/2 MFMAs (QT = 16: 16-row blocks, D/4 MFMAs).  Head h writes partial slab
     // h of the [B][C_out][T] output (head 0 adds the bias and the residual); the LayerNorm that follows sums the H slabs exactly as
     // it sums split-K slabs.  Removes the conv_o launch (and its HBM round trip of the attention output) from every layer.
     float* Of = Qs;
@@ -432,14 +538,17 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
         const float pv = Sb[(r < NR ? r : 0) * AQ + i];
         sbv[r] = r < NR ? pv : 0.f;
       }
-      const int c0 = tid >> 5;
+      const int c0 = tid >> QSH;
 #pragma unroll 1
-      for (int it = 0; it < (D + 2 * NW - 1) / (2 * NW); ++it) {   // rolled: unrolled it keeps 6 x 21 loads live (222 registers, half the occupancy)
-        const int c = c0 + it * 2 * NW;
+      for (int it = 0; it < (D + CPI - 1) / CPI; ++it) {   // rolled: unrolled it keeps 6 x 21 loads live (222 registers, half the occupancy)
+        const int c = c0 + it * CPI;
         const int cc = c < D ? c : D - 1;
         float o = 0.f;
 #pragma unroll
-        for (int sl = 0; sl < NSLOT; ++sl) o += Os[sl * (D * AQ) + cc * AQ + i];
+        for (int sl = 0; sl < NSLOT; ++sl) {         // every slot READ (the loads stay one batch), the written ones summed
+          const float ov = Os[sl * (D * AQ) + cc * AQ + i];
+          o += sl < nslot ? ov : 0.f;
+        }
         o *= il;
 #pragma unroll
         for (int r = 0; r < NRM; ++r) o += sbv[r] * Ev[(r < NR ? r : 0) * D + cc];
@@ -448,21 +557,46 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
     };
     if (NR <= 9) normalise(std::integral_constant<int, 9>{});
     else normalise(std::integral_constant<int, 2 * AMAXW + 1>{});
-    const int Co = A.Co, G = A.wo_groups;
-    const float* const wo = A.wo;
+    const int Co = A.Co;
     const float* const bo = h == 0 ? A.bo : nullptr;
     const float* const resp = h == 0 && A.res ? A.res + (int64_t)b * Co * T : nullptr;
     float* const ob = A.o_out + (int64_t)(h * KS + kr) * A.o_slab_stride + (int64_t)b * Co * T;
     __syncthreads();
-    for (int mt = wid; mt * 32 < Co; mt += NW) {
-      f32x4 wr[D / 8];
+    for (int mt = wid; mt * AQ < Co; mt += NW) {     // row blocks of AQ rows
+      f32x4 wr[WG];
       if (mt == wid) {                               // prefetched above
 #pragma unroll
-        for (int g = 0; g < D / 8; ++g) wr[g] = wr0[g];
+        for (int g = 0; g < WG; ++g) wr[g] = wr0[g];
       } else {
-        const f32x4* wp = reinterpret_cast<const f32x4*>(wo) + ((int64_t)mt * G + h * (D / 8)) * 64 + lh * 32 + l31;
+        const f32x4* wp = wo_frag(mt);
 #pragma unroll
-        for (int g = 0; g < D / 8; ++g) wr[g] = wp[g * 64];
+        for (int g = 0; g < WG; ++g) wr[g] = wp[g * WSTR];
+      }
+      if constexpr (QT == 16) {
+        float bs[4], rv[4];                          // epilogue operands in flight under the MFMAs
+        const int row0 = mt * 16 + 4 * lg;
+        const int igc = iok ? iq : T - 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = row0 + r < Co ? row0 + r : Co - 1;
+          bs[r] = bo ? bo[row] : 0.f;
+          rv[r] = resp ? resp[(int64_t)row * T + igc] : 0.f;
+        }
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < WG; ++t) {               // group g's channel of K-step (t, q): 16t + 8 (g >> 1) + (g & 1) + 2q
+          const float* ob4 = Of + (16 * t + 8 * (lg >> 1) + (lg & 1)) * AQ + lq;
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[t].x, ob4[0 * AQ], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[t].y, ob4[2 * AQ], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[t].z, ob4[4 * AQ], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[t].w, ob4[6 * AQ], acc, 0, 0, 0);
+        }
+        if (iok) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (row0 + r < Co) ob[(int64_t)(row0 + r) * T + iq] = (acc[r] + bs[r]) + rv[r];
+        }
+        continue;
       }
       // epilogue operands in flight under the MFMAs
       float bs[16], rv[16];
@@ -507,10 +641,13 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
         sbv[r] = r < NR ? pv : 0.f;
       }
 #pragma unroll 2
-      for (int c = tid >> 5; c < D; c += 2 * NW) {
+      for (int c = tid >> QSH; c < D; c += CPI) {
         float o = 0.f;
 #pragma unroll
-        for (int sl = 0; sl < NSLOT; ++sl) o += Os[sl * (D * AQ) + c * AQ + i];
+        for (int sl = 0; sl < NSLOT; ++sl) {         // every slot READ (the loads stay one batch), the written ones summed
+          const float ov = Os[sl * (D * AQ) + c * AQ + i];
+          o += sl < nslot ? ov : 0.f;
+        }
         o *= il;
 #pragma unroll
         for (int r = 0; r < NRM; ++r) o += sbv[r] * Ev[(r < NR ? r : 0) * D + c];
@@ -531,73 +668,97 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   }
 }
 
-static size_t attn_lds_bytes(int D, int NW) {
+static size_t attn_lds_bytes(int D, int NW, int AQ) {
   return sizeof(float) * (size_t)(ANS * D * AQ + D * AQ + (2 * AMAXW + 1) * D + 2 * (2 * AMAXW + 1) * AQ + 2 * NW * AQ);
 }
 
-template <int DT, int NW, bool F16, bool ONE, bool KV16 = false>
+template <int DT, int NW, bool F16, bool ONE, bool KV16 = false, int QT = AQ_WIDE>
 static int launch_attn_variant2(hipStream_t stream, const AttnArgs& a, dim3 grid) {
-  const size_t lds = attn_lds_bytes(32 * DT, NW);
-  auto kern = attention_kernel<DT, NW, F16, ONE, KV16>;
+  const size_t lds = attn_lds_bytes(32 * DT, NW, QT);
+  auto kern = attention_kernel<DT, NW, F16, ONE, KV16, QT>;
   ensure_dyn_lds((const void*)kern, lds);
   AttnArgs at = a;
   if (a.xcd_b) {
     at.xcd_gx = (int)grid.x; at.xcd_per = (int)(grid.x * grid.y);
     grid = dim3(xcd_grid(a.B, at.xcd_per), 1, 1);
   }
-  at.dbg = timeline_slice(grid.x, grid.y, grid.z, 77000 + 10 * DT + NW, 0, a.D, a.T);    // tile id 77xxx: attention
+  at.dbg = timeline_slice(grid.x, grid.y, grid.z, 77000 + (QT == AQ_NARROW ? 100 : 0) + 10 * DT + NW, 0, a.D, a.T);    // tile id 77xxx: attention (771xx: 16 queries)
   hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, stream, at);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template <int DT, int NW, bool ONE>
-static int launch_attn_variant(hipStream_t stream, const AttnArgs& a, dim3 grid) {
+static int launch_attn_variant(hipStream_t stream, const AttnArgs& a, dim3 grid, int qt) {
   if (a.f16 && a.kh && a.vh) return launch_attn_variant2<DT, NW, true, ONE, true>(stream, a, grid);
-  return a.f16 ? launch_attn_variant2<DT, NW, true, ONE>(stream, a, grid) : launch_attn_variant2<DT, NW, false, ONE>(stream, a, grid);
+  if (a.f16) return launch_attn_variant2<DT, NW, true, ONE>(stream, a, grid);
+  // (head dim 128 has no eight-wave 16-query form — see launch_attn_d — so it is not instantiated: a scratch segment is not allowed)
+  if constexpr (!(DT == 4 && NW == 8))
+    if (qt == AQ_NARROW) return launch_attn_variant2<DT, NW, false, ONE, false, AQ_NARROW>(stream, a, grid);
+  return launch_attn_variant2<DT, NW, false, ONE>(stream, a, grid);
 }
 
 template <int DT>
-static int launch_attn_d(hipStream_t stream, const AttnArgs& a, dim3 grid, int ntiles) {
+static int launch_attn_d(hipStream_t stream, const AttnArgs& a, dim3 grid, int ntiles, int qt) {
   // ntiles = key tiles per workgroup (of its key range when the keys are split)
   // Up to 8 key tiles: one per wave, no loop (T = 128: 19.4 -> 16.9 us).  More: 8 waves round-robin.  Measured at T_y = 384
   // (12 tiles) and NOT kept: 12 waves with one tile each (53 spilled registers: 27 -> 41 us) and 6 waves with two tiles each
   // (balanced, but 27 -> 31 us: the merge wait that tools/timeline.py shows is not the 1-vs-2-tile imbalance).
-  // fused conv_o: its C_out / 32 row tiles are dealt to the waves — with more than 4 of them (hidden 192: 6) eight waves finish them
-  // in one round even if only 4 have a key tile
-  if (ntiles <= 4 && !(a.wo && a.Co > 128)) return launch_attn_variant<DT, 4, true>(stream, a, grid);
-  if (ntiles <= 8) return launch_attn_variant<DT, 8, true>(stream, a, grid);
+  // fused conv_o: its C_out / 32 row tiles (16 queries: C_out / 16 row blocks) are dealt to the waves — with more than 4 of them
+  // (hidden 192: 6) eight waves finish them in one round even if only 4 have a key tile
+  if (ntiles <= 4 && !(a.wo && a.Co > 128)) return launch_attn_variant<DT, 4, true>(stream, a, grid, qt);
+  // head dim 128 on 16 queries: the eight-wave form spilled 3 registers (K 64 + V 64 + W_o prefetch 32 + O 32 against 256); the four-wave
+  // loop form below takes any number of key tiles
+  if (ntiles <= 8 && !(DT == 4 && qt == AQ_NARROW)) return launch_attn_variant<DT, 8, true>(stream, a, grid, qt);
   // head dim 128 with more than 8 key tiles: four waves walking the tiles (one wave per SIMD: 512 registers each) — the eight-wave loop form
   // spilled 29 registers there (K tile 64 + V 64 + O 64 + S 16 per wave against 256), and a scratch segment is not allowed on any path
-  if constexpr (DT == 4) return launch_attn_variant<DT, 4, false>(stream, a, grid);
-  else return launch_attn_variant<DT, 8, false>(stream, a, grid);
+  if constexpr (DT == 4) return launch_attn_variant<DT, 4, false>(stream, a, grid, qt);
+  else return launch_attn_variant<DT, 8, false>(stream, a, grid, qt);
+}
+
+// Queries per workgroup.  16 (the 16x16x4 matrix form) halves every serial chain of a workgroup and doubles the workgroups: it pays
+// where the launch is a latency chain on a mostly empty chip — the 32-query grid leaves at least half of the compute units without
+// a workgroup — and costs K / V reads (each key tile is read by twice as many workgroups) where the chip is full.  fp32 only.
+// A function of the shape and the dtype alone: launches of equal shape run the same code in every graph / eager / stream mode.
+int attention_pick_qtile(int B, int H, int T, int D, int ksplit, bool f16) {
+  if (f16 || D < 32 || D > 128 || D % 32) return AQ_WIDE;
+  const int ks = ksplit > 1 ? ksplit : 1, qtiles = (T + AQ_WIDE - 1) / AQ_WIDE;
+  return (long)B * H * qtiles * ks * 2 <= ATTN_CUS ? AQ_NARROW : AQ_WIDE;
 }
 
 int launch_attention(hipStream_t stream, const AttnArgs& a) {
   if (a.W > AMAXW || a.W < 0 || a.T < 1 || a.B < 1 || a.H < 1 || a.ld % 32 || a.ld < a.T) return -1;
   if ((a.kh != nullptr) != (a.vh != nullptr) || (a.kh && !a.f16)) return -1;                  // fp16 K / V: both, and only for the fp16 products
   if (a.wo && (a.f16 || !a.o_out || a.Co < 1 || a.wo_groups * 8 < a.H * a.D)) return -1;   // fused conv_o: fp32 form only
+  if ((a.qtile != 0 && a.qtile != AQ_NARROW && a.qtile != AQ_WIDE) || (a.qtile == AQ_NARROW && a.f16)) return -1;   // 16 queries: fp32 only
   const int ks = a.ksplit > 1 ? a.ksplit : 1;
   const int ntiles_all = (a.T + AK - 1) / AK;
   if (ks > 1 && (!a.wo || !a.ml_out || a.bo || a.res || ks > ntiles_all)) return -1;        // key split: partial slabs merged by the LayerNorm
-  dim3 grid(((a.T + AQ - 1) / AQ) * ks, a.H, a.B);
+  const int qt = a.qtile ? a.qtile : attention_pick_qtile(a.B, a.H, a.T, a.D, ks, a.f16 != 0);   // the ONE place the tile is chosen
+  dim3 grid(((a.T + qt - 1) / qt) * ks, a.H, a.B);
   const int ntiles = (ntiles_all + ks - 1) / ks;                                            // the largest key range
   switch (a.D) {
-    case 32: return launch_attn_d<1>(stream, a, grid, ntiles);
-    case 64: return launch_attn_d<2>(stream, a, grid, ntiles);
-    case 96: return launch_attn_d<3>(stream, a, grid, ntiles);
-    case 128: return launch_attn_d<4>(stream, a, grid, ntiles);
+    case 32: return launch_attn_d<1>(stream, a, grid, ntiles, qt);
+    case 64: return launch_attn_d<2>(stream, a, grid, ntiles, qt);
+    case 96: return launch_attn_d<3>(stream, a, grid, ntiles, qt);
+    case 128: return launch_attn_d<4>(stream, a, grid, ntiles, qt);
     default: return -2;   // head dim must be a multiple of 32 up to 128
   }
 }
 
 // Key ranges per (head, query tile).  Splitting pays only when a wave would otherwise walk several key tiles in turn (more tiles
 // than the 8 waves of a workgroup) and the launch is far from filling the chip; the target is one key tile per SIMD (4 per
-// workgroup).  H * ks partial slabs must be a count the slab-summing LayerNorm has (2, 4 or 8) and fit `max_slabs`.
+// workgroup).  H * ks partial slabs must be a count the slab-summing LayerNorm has (2, 4 or 8) and fit `max_slabs`.  The grid a
+// candidate is held to is the one its launch would have: the query tile follows attention_pick_qtile (fp32: the split exists for the
+// fused conv_o form only).
 int attention_pick_ksplit(int B, int H, int T, int max_slabs) {
-  const int ntiles = (T + AK - 1) / AK, qtiles = (T + AQ - 1) / AQ;
+  const int ntiles = (T + AK - 1) / AK;
   if (ntiles <= 8 || H < 1 || (H & (H - 1))) return 1;
   int ks = 1;
-  while (ks * 4 < ntiles && H * ks * 2 <= max_slabs && H * ks * 2 <= 8 && (long)B * H * qtiles * ks * 2 <= 512) ks *= 2;
+  auto wgs = [&](int k) {
+    const int qt = attention_pick_qtile(B, H, T, 32, k, false);
+    return (long)B * H * ((T + qt - 1) / qt) * k;
+  };
+  while (ks * 4 < ntiles && H * ks * 2 <= max_slabs && H * ks * 2 <= 8 && wgs(ks * 2) <= 512) ks *= 2;
   return ks;
 }
 

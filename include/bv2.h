@@ -547,6 +547,9 @@ void bv2_graph_destroy(bv2_graph* graph);
  *   "attn_ksplit"     -1 (default): the key ranges per (head, query tile) of the fused attention are picked per shape (2 or 4 at batch 1 and long
  *                     sequences: each range's workgroup writes its own partial slab, LayerNorm-1 merges them with the flash-decoding weights);
  *                     0 / 1: no key split; 2 / 4: that many ranges where the slabs allow it
+ *   "attn_qtile"      0 (default): the queries per workgroup of the fp32 attention are picked per shape — 16 (the 16x16x4 matrix form) where
+ *                     32-query tiles would leave at least half of the compute units without a workgroup, else 32; 16 / 32: that tile for
+ *                     every fp32 attention launch (the fp16 forms always use 32)
  *   "overlap_dp"      default 0: 1 runs the DurationPredictor on an internal side stream beside the stochastic one (fork / join
  *                     with events on the caller's stream; measured slower at batch 1, kept for experiments)
  *   "lean_durations"  default 1: phase A runs only the duration predictor the mix can see (bv2_encode_out); 0: both, always

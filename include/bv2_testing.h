@@ -133,6 +133,12 @@ int bv2_test_layernorm(void* stream, const float* a, const float* add, int mode,
 int bv2_test_attention_ex(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out, int B, int H, int D,
                           int T, int W, int f16, const void* kh, const void* vh, const float* wo_host, float* wo_pack_dev,
                           const float* bo, const float* res, float* o_out, int64_t o_slab_stride, int Co, int ksplit, float* ml_out);
+/* bv2_test_attention_ex plus the queries per workgroup (AttnArgs::qtile: 0 = picked per shape, 16 — fp32 only — or 32; anything else is
+ * refused), and the pick itself: a function of the shape and the dtype alone, no device needed. */
+int bv2_test_attention_q(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out, int B, int H, int D,
+                         int T, int W, int f16, const void* kh, const void* vh, const float* wo_host, float* wo_pack_dev,
+                         const float* bo, const float* res, float* o_out, int64_t o_slab_stride, int Co, int ksplit, float* ml_out, int qtile);
+int bv2_test_attention_pick_qtile(int B, int H, int T, int D, int ksplit, int f16);
 /* bv2_test_layernorm plus the weighted slabs of the key split (ml [B][ml_H][ml_ks][2][T], bias [C]), the second output out2 with vec2
  * [B][C], and the B == 1 weight prefetch (pf_ptr / pf_bytes: DEVICE memory that is only read) */
 int bv2_test_layernorm_ex(void* stream, const float* a, const float* add, int mode, const float* dww, const float* dwb, int dil,
