@@ -926,6 +926,64 @@ static int x3_slot_count(const Ctx& c) {
   return n_slots;
 }
 
+ConvLaunch ups_conv_launch(const UpW& U, const float* blob, const float* const src[3], int nsrc, float* x, int B, int Lc,
+                           const int64_t* lens, int up, unsigned* omax) {
+  const int Lo = Lc * U.u;
+  ConvLaunch cl;
+  std::memset(&cl, 0, sizeof(cl));
+  cl.nprob = U.u; cl.B = B; cl.L = Lc; cl.lens = lens; cl.len_mul = up; cl.ksplit = 1;
+  for (int ph = 0; ph < U.u; ++ph) {
+    ConvProb p = conv_prob(U.phase[ph], blob, src[0], x, Lc);
+    p.x[1] = src[1]; p.x[2] = src[2]; p.nsrc = nsrc; p.in_scale = 1.f / (float)nsrc;
+    p.pre_act = PRE_LRELU; p.slope = 0.1f;
+    p.pad_left = U.pad_left[ph];
+    p.out_bstride = (int64_t)U.cout * Lo; p.out_rstride = Lo; p.out_tstride = U.u; p.out_toff = ph;
+    p.omax = omax;
+    cl.p[ph] = p;
+  }
+  return cl;
+}
+
+ClLaunch ups_cl_launch(const UpW& U, const float* blob, const uint16_t* const src[3], int nsrc, uint16_t* x, int B, int Lc,
+                       const int64_t* lens, int up, bool phase_taps) {
+  ClLaunch cl;
+  std::memset(&cl, 0, sizeof(cl));
+  cl.nprob = 1; cl.B = B; cl.L = Lc; cl.lens = lens; cl.len_mul = up; cl.ups = 1;
+  ClProb p = cl_prob(U.cl, blob, src[0], x, Lc, 1);
+  p.x[1] = src[1]; p.x[2] = src[2]; p.nsrc = nsrc; p.in_scale = 1.f / (float)nsrc;
+  p.pre_lrelu = 1; p.pad_left = U.cl_pad_left;
+  UpsGeom G;
+  unsigned long long offs = 0;                                   // phase ph's taps inside the union window: [off, off + ntaps)
+  if (phase_taps && ups_geometry(U.u, U.k, G) && G.ph_offs(&offs)) { p.ph_cout = U.cout; p.ph_ntaps = U.ntaps; p.ph_offs = offs; }
+  cl.p[0] = p;
+  return cl;
+}
+
+// conv_post + tanh on the mean of the last stage's branches [B][C][L] / bf16 [B][L][C] -> out [B][L]
+ConvPostArgs conv_post_args(const float* const src[3], int nsrc, const float* w, float* out, int C, int k, int B, int L,
+                            const int64_t* lens, int len_mul) {
+  ConvPostArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.lens = lens; a.len_mul = len_mul;
+  for (int j = 0; j < 3; ++j) a.x[j] = src[j];
+  a.nsrc = nsrc; a.in_scale = 1.f / (float)nsrc; a.x_bstride = (int64_t)C * L; a.x_rstride = L;
+  a.w = w; a.out = out; a.out_bstride = L; a.C = C; a.k = k; a.L = L; a.B = B;
+  a.slope = 0.01f;                                            // F.leaky_relu default (models.py:553)
+  return a;
+}
+ConvPostClArgs conv_post_cl_args(const uint16_t* const src[3], int nsrc, const float* w, float* out, int C, int k, int B, int L,
+                                 const int64_t* lens, int len_mul, bool generic) {
+  ConvPostClArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.lens = lens; a.len_mul = len_mul;
+  for (int j = 0; j < 3; ++j) a.x[j] = src[j];
+  a.nsrc = nsrc; a.in_scale = 1.f / (float)nsrc;
+  a.w = w; a.out = out; a.C = C; a.k = k; a.L = L; a.B = B;
+  a.slope = 0.01f;                                            // F.leaky_relu default (models.py:553)
+  a.generic = generic ? 1 : 0;
+  return a;
+}
+
 // Generator.forward (reference models.py:538-557).  slots_clear: the caller's phase_b_front launch has already zeroed the x3 slots
 static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, const float* ymask, int B, int L, float* o,
                      const int64_t* lens, bool slots_clear = false) {
@@ -981,17 +1039,7 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
     unsigned* const slot_x = x3 ? P.xslots + X3_SLOT_WORDS * next_slot++ : nullptr;
     {
       // x = ConvTranspose1d(leaky_relu(mean of the previous stage's branches)) as U.u polyphase stride-1 convs
-      ConvLaunch cl;
-      cl.nprob = U.u; cl.B = B; cl.L = Lc; cl.lens = lens; cl.len_mul = up;
-      for (int ph = 0; ph < U.u; ++ph) {
-        ConvProb p = c.prob(U.phase[ph], src[0], x, Lc);
-        p.x[1] = src[1]; p.x[2] = src[2]; p.nsrc = nsrc; p.in_scale = 1.f / (float)nsrc;
-        p.pre_act = PRE_LRELU; p.slope = 0.1f;
-        p.pad_left = U.pad_left[ph];
-        p.out_bstride = (int64_t)U.cout * Lo; p.out_rstride = Lo; p.out_tstride = U.u; p.out_toff = ph;
-        p.omax = slot_x;
-        cl.p[ph] = p;
-      }
+      ConvLaunch cl = ups_conv_launch(U, c.blob, src, nsrc, x, B, Lc, lens, up, slot_x);
       c.conv(cl, "dec.ups");
     }
     c.tap(x, (int64_t)B * U.cout * Lo, "dec.ups.", i);
@@ -1085,14 +1133,7 @@ static void gen_core(Ctx& c, const PlanB& P, const float* z, int z_rstride, cons
     Lc = Lo;
     up *= U.u;
   }
-  ConvPostArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.lens = lens; a.len_mul = up;
-  for (int j = 0; j < 3; ++j) a.x[j] = src[j];
-  a.nsrc = nsrc; a.in_scale = 1.f / (float)nsrc; a.x_bstride = (int64_t)m.post_c * Lc; a.x_rstride = Lc;
-  a.w = c.W(m.conv_post.off); a.out = o; a.out_bstride = Lc; a.C = m.post_c; a.k = m.post_k; a.L = Lc; a.B = B;
-  a.slope = 0.01f;                                            // F.leaky_relu default (models.py:553)
-  c.chk(launch_conv_post(c.s, a), "dec.conv_post");
+  c.chk(launch_conv_post(c.s, conv_post_args(src, nsrc, c.W(m.conv_post.off), o, m.post_c, m.post_k, B, Lc, lens, up)), "dec.conv_post");
 }
 
 // Generator.forward in bf16, channels-last (kernels/gen_bf16.hip).  Same launch structure as the wide-stage fp32 path: per
@@ -1107,16 +1148,7 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
   const int C = cf.inter_channels, c0 = cf.upsample_initial_channel;
   auto U16 = [](float* p) { return reinterpret_cast<uint16_t*>(p); };
   auto Wb = [&](const ConvW& w) { return reinterpret_cast<const uint16_t*>(c.W(w.wb_off)); };
-  auto prob = [&](const ConvW& w, const uint16_t* x, uint16_t* out, int Lc, int dil) {
-    ClProb p;
-    std::memset(&p, 0, sizeof(p));
-    p.x[0] = x; p.nsrc = 1; p.in_scale = 1.f; p.x_bstride = (int64_t)w.cin * Lc; p.Lin = Lc;
-    p.w = Wb(w); p.bias = c.W(w.b_off);
-    p.out = out; p.out_bstride = (int64_t)w.cout * Lc; p.res_bstride = p.out_bstride;
-    p.cin = w.cin; p.cout = w.cout; p.cout_pad = w.cout_pad; p.k = w.k; p.dil = dil; p.pad_left = ((w.k - 1) / 2) * dil;
-    p.slope = 0.1f;
-    return p;
-  };
+  auto prob = [&](const ConvW& w, const uint16_t* x, uint16_t* out, int Lc, int dil) { return cl_prob(w, c.blob, x, out, Lc, dil); };
   auto launch = [&](ClLaunch& cl, const char* tag, double flops) {
     const char* vn = "conv_cl_bf16";
     c.timed(tag, &vn, [&] { return conv_shape(cl.nprob, cl.p[0].cin, cl.p[0].cout, cl.p[0].k, cl.L, cl.B); }, flops,
@@ -1153,22 +1185,7 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
     uint16_t* x = U16(S[0]);
     const int Lo = Lc * U.u;
     {
-      ClLaunch cl;
-      cl.nprob = 1; cl.B = B; cl.L = Lc; cl.lens = lens; cl.len_mul = up; cl.ups = 1;
-      ClProb p = prob(U.cl, src[0], x, Lc, 1);
-      p.x[1] = src[1]; p.x[2] = src[2]; p.nsrc = nsrc; p.in_scale = 1.f / (float)nsrc;
-      p.pre_lrelu = 1; p.pad_left = U.cl_pad_left;
-      if (!c.h->no_ups_phase_taps && U.u <= 16) {                  // phase ph's taps inside the union window: [off, off + ntaps)
-        unsigned long long offs = 0;
-        bool fits = true;
-        for (int ph = 0; ph < U.u; ++ph) {
-          const int off = U.cl_pad_left - U.pad_left[ph];
-          fits = fits && off >= 0 && off <= 15;
-          offs |= (unsigned long long)(off & 15) << (4 * ph);
-        }
-        if (fits) { p.ph_cout = U.cout; p.ph_ntaps = U.ntaps; p.ph_offs = offs; }
-      }
-      cl.p[0] = p;
+      ClLaunch cl = ups_cl_launch(U, c.blob, src, nsrc, x, B, Lc, lens, up, !c.h->no_ups_phase_taps);
       // algorithmic FLOPs: the true taps of the transposed conv (the zero-padded window taps are not counted)
       launch(cl, "dec.ups", 2.0 * U.cin * U.cout * U.k * (double)Lc * B);
     }
@@ -1280,15 +1297,8 @@ static void gen_core_bf16(Ctx& c, const PlanB& P, const float* z, int z_rstride,
     Lc = Lo;
     up *= U.u;
   }
-  ConvPostClArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.lens = lens; a.len_mul = up;
-  for (int j = 0; j < 3; ++j) a.x[j] = src[j];
-  a.nsrc = nsrc; a.in_scale = 1.f / (float)nsrc;
-  a.w = c.W(m.conv_post.off); a.out = o; a.C = m.post_c; a.k = m.post_k; a.L = Lc; a.B = B;
-  a.slope = 0.01f;                                            // F.leaky_relu default (models.py:553)
-  a.generic = c.h->no_conv_post_rows ? 1 : 0;
-  c.chk(launch_conv_post_cl(c.s, a), "dec.conv_post");
+  c.chk(launch_conv_post_cl(c.s, conv_post_cl_args(src, nsrc, c.W(m.conv_post.off), o, m.post_c, m.post_k, B, Lc, lens, up,
+                                                   c.h->no_conv_post_rows)), "dec.conv_post");
 }
 
 // the speaker GEMVs of phase B: dec.cond and every coupling's conditioning vector

@@ -72,6 +72,47 @@ struct UpW {
   int cl_pad_left = 0;
 };
 
+// Polyphase geometry of ConvTranspose1d(stride u, kernel k, padding (k - u) / 2), said once for the packer (bv2_model.cpp), the executors
+// (bv2_exec.cpp) and the tests' entry points (bv2_testing.cpp).  Output n = u*s + ph gathers x[s + shift - mtap] * W[ci][co][pp + u*mtap]
+// (SURVEY.md §7.3 K2): phase ph is a stride-1 conv of ntaps = k / u taps with pad_left = ntaps - 1 - shift whose tap j reads W[..][tap(ph, j)].
+// Channels-last form: ONE conv over the union of the phases' tap windows, cl_k = cl_pad_left + max right reach + 1 taps, in which phase ph
+// owns the window taps [cl_off, cl_off + ntaps), cl_off = cl_pad_left - pad_left[ph] (the other taps of its rows are zero).
+struct UpsGeom {
+  int u = 1, k = 1, ntaps = 1, pad = 0;
+  int pp[BV2_MAX_UPS], shift[BV2_MAX_UPS], pad_left[BV2_MAX_UPS];
+  int cl_pad_left = 0, cl_k = 1, cl_off[BV2_MAX_UPS];
+  // index into the k taps of the ConvTranspose1d weight: tap j of phase ph / window tap jw of phase ph (-1: a zero of the window)
+  int tap(int ph, int j) const { return pp[ph] + u * (ntaps - 1 - j); }
+  int cl_tap(int ph, int jw) const { const int j = jw - cl_off[ph]; return j < 0 || j >= ntaps ? -1 : tap(ph, j); }
+  // ClProb::ph_offs: nibble ph = cl_off[ph]; false when a phase or an offset does not fit a nibble
+  bool ph_offs(unsigned long long* out) const {
+    unsigned long long offs = 0;
+    bool fits = u <= 16;
+    for (int ph = 0; ph < u && fits; ++ph) {
+      fits = cl_off[ph] >= 0 && cl_off[ph] <= 15;
+      offs |= (unsigned long long)(cl_off[ph] & 15) << (4 * ph);
+    }
+    if (fits) *out = offs;
+    return fits;
+  }
+};
+// false outside the envelope (bv2_model.cpp validate_config: u = 2..8, k = 1..4 x u, (k - u) even)
+inline bool ups_geometry(int u, int k, UpsGeom& g) {
+  if (u < 2 || u > BV2_MAX_UPS || k < u || k % u || (k - u) % 2 || k / u > 4) return false;
+  g.u = u; g.k = k; g.ntaps = k / u; g.pad = (k - u) / 2;
+  int plmax = 0, right = 0;
+  for (int ph = 0; ph < u; ++ph) {
+    g.pp[ph] = (ph + g.pad) % u; g.shift[ph] = (ph + g.pad) / u;
+    g.pad_left[ph] = (g.ntaps - 1) - g.shift[ph];
+    plmax = g.pad_left[ph] > plmax ? g.pad_left[ph] : plmax;
+    const int r = g.ntaps - 1 - g.pad_left[ph];
+    right = r > right ? r : right;
+  }
+  g.cl_pad_left = plmax; g.cl_k = plmax + right + 1;
+  for (int ph = 0; ph < u; ++ph) g.cl_off[ph] = plmax - g.pad_left[ph];
+  return true;
+}
+
 // ReferenceEncoder (n_speakers == 0 only; kernels/ref_enc.hip)
 struct RefEncW {
   bool present = false;
@@ -149,6 +190,17 @@ inline ConvProb conv_prob(const ConvW& w, const float* blob, const float* x, flo
   p.res_bstride = p.out_bstride;
   p.cin = w.cin; p.cin_pad = w.cin_pad; p.cout = w.cout; p.cout_pad = w.cout_pad; p.w_ld = w.w_ld;
   p.k = w.k; p.dil = dil; p.pad_left = ((w.k - 1) / 2) * dil;
+  p.slope = 0.1f;
+  return p;
+}
+// the same for the bf16 channels-last path (kernels/gen_bf16.hip): x / out [B][L][C]
+inline ClProb cl_prob(const ConvW& w, const float* blob, const uint16_t* x, uint16_t* out, int L, int dil = 1) {
+  ClProb p;
+  std::memset(&p, 0, sizeof(p));
+  p.x[0] = x; p.nsrc = 1; p.in_scale = 1.f; p.x_bstride = (int64_t)w.cin * L; p.Lin = L;
+  p.w = w.wb_off < 0 ? nullptr : reinterpret_cast<const uint16_t*>(blob + w.wb_off); p.bias = w.b_off < 0 ? nullptr : blob + w.b_off;
+  p.out = out; p.out_bstride = (int64_t)w.cout * L; p.res_bstride = p.out_bstride;
+  p.cin = w.cin; p.cout = w.cout; p.cout_pad = w.cout_pad; p.k = w.k; p.dil = dil; p.pad_left = ((w.k - 1) / 2) * dil;
   p.slope = 0.1f;
   return p;
 }
@@ -252,6 +304,19 @@ int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, con
                  void* ws, int64_t wsb);
 int run_generator(bv2_handle* h, hipStream_t s, int B, int Ty, int L, const float* z, const int64_t* y_lengths,
                   const float* g, float* o, void* ws, int64_t wsb);
+// The Generator's ConvTranspose1d launches, built in one place for the executors and for the tests' entry points (bv2_testing.cpp): x =
+// ConvTranspose1d(lrelu_0.1(mean of the nsrc sources)) on Lc input columns, `up` samples per latent frame at the input's resolution.
+// fp32: U.u polyphase problems of one ConvLaunch writing [B][cout][Lc * u] (omax: the shared max |out| slot or null; ksplit is the caller's).
+ConvLaunch ups_conv_launch(const UpW& U, const float* blob, const float* const src[3], int nsrc, float* x, int B, int Lc,
+                           const int64_t* lens, int up, unsigned* omax);
+// bf16: one channels-last conv over the union tap window writing [B][Lc * u][cout]; phase_taps: each wave multiplies through its phases' taps only
+ClLaunch ups_cl_launch(const UpW& U, const float* blob, const uint16_t* const src[3], int nsrc, uint16_t* x, int B, int Lc,
+                       const int64_t* lens, int up, bool phase_taps);
+// ... and its conv_post + tanh launches (slope 0.01: F.leaky_relu's default, models.py:553); generic: the any-width bf16 kernel also at C = 16
+ConvPostArgs conv_post_args(const float* const src[3], int nsrc, const float* w, float* out, int C, int k, int B, int L,
+                            const int64_t* lens, int len_mul);
+ConvPostClArgs conv_post_cl_args(const uint16_t* const src[3], int nsrc, const float* w, float* out, int C, int k, int B, int L,
+                                 const int64_t* lens, int len_mul, bool generic);
 // streamed decode: the flow once (run_stream_begin), the Generator window by window (run_stream_chunk)
 int generator_halo(const Model& m);
 int64_t stream_plan_bytes(const Model& m, int B, int Ty, int window_frames);            // what a stream itself needs (without phase A)

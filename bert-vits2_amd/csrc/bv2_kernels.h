@@ -153,6 +153,11 @@ enum { TILE_AUTO = 0, TILE_128x128 = 1, TILE_64x128 = 2, TILE_64x64 = 3, TILE_32
 // (13 was TILE_SPLITK_X6, the split-K kernel's split-bf16 form: measured at +0.4 % on config 2 for +195 MB of blob and deleted in round 6 —
 //  DESIGN.md "measured and not kept", profiles/r05_ab_splitk_x6_not_kept.txt)
 int launch_conv1d(hipStream_t stream, const ConvLaunch& L, int tile, const char** variant_name);
+// tests only: how the last launch_conv1d of this process mapped workgroups to (column tile, problem) — the plain grid, contiguous per-XCD
+// column ranges (always for the split-K kernel), or the cost-sorted snake (conv_mfma.hip launch_variant / conv_x6.hip launch_x6_variant)
+enum { PLACE_PLAIN = 0, PLACE_PER_XCD = 1, PLACE_SNAKE = 2 };
+void conv_note_placement(int place);
+int conv_last_placement();
 // fp32 conv on the bf16 matrix core (kernels/conv_x6.hip): every fp32 operand is the exact sum of three bf16 values
 // (v = h1 + h2 + h3, 8 + 8 + 8 significand bits), and the product is accumulated from the six largest of the nine cross terms
 // (w1x1, w1x2, w2x1, w1x3, w2x2, w3x1 — the three dropped ones are below 2^-23 of the product, the rounding of an fp32 multiply).

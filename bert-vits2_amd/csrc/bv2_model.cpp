@@ -463,46 +463,30 @@ int pack_all(Model& m, Packer& P) {
     UpW& U = m.ups[i];
     U.u = c.upsample_rates[i]; U.k = c.upsample_kernel_sizes[i];
     U.cin = c0 >> i; U.cout = c0 >> (i + 1);
-    U.ntaps = U.k / U.u;
-    const int pad = (U.k - U.u) / 2;
+    UpsGeom G;                                     // the polyphase split, bv2_internal.h (validate() has admitted the pair)
+    if (!ups_geometry(U.u, U.k, G)) return -1;
+    U.ntaps = G.ntaps;
     m.total_up *= U.u;
     std::vector<float> w;                          // folded ConvTranspose1d weight [cin][cout][k]
     const bool ok = P.folded("dec.ups." + std::to_string(i), U.cin, U.cout, U.k, w);
     const HostTensor* bt = P.get("dec.ups." + std::to_string(i) + ".bias", {U.cout});
     P.emit_bf16 = false;                           // the bf16 path uses the single channels-last form below, not the phases
+    const int kfull = U.k, cout = U.cout;
     for (int ph = 0; ph < U.u; ++ph) {
-      // output n = u*s + ph gathers x[s + shift - mtap] * W[ci][co][pp + u*mtap]   
-      const int pp = (ph + pad) % U.u, shift = (ph + pad) / U.u;
-      U.pad_left[ph] = (U.ntaps - 1) - shift;
-      const int nt = U.ntaps, uu = U.u, kk = U.k, cout = U.cout;
-      U.phase[ph] = P.conv(U.cout, U.cin, nt, true,
-                           [&, pp, nt, uu, kk, cout](int co, int ci, int j) {
-                             return w[((int64_t)ci * cout + co) * kk + pp + uu * (nt - 1 - j)];
-                           },
+      U.pad_left[ph] = G.pad_left[ph];
+      U.phase[ph] = P.conv(U.cout, U.cin, G.ntaps, true,
+                           [&, ph, kfull, cout](int co, int ci, int j) { return w[((int64_t)ci * cout + co) * kfull + G.tap(ph, j)]; },
                            [&](int co) { return bt->data[co]; }, ok && bt);
     }
     P.emit_bf16 = true;
-    {
-      // channels-last form: tap window = union over phases; phase ph uses window taps [off, off + ntaps), off = plmax - pad_left[ph]
-      int plmax = 0, right = 0;
-      for (int ph = 0; ph < U.u; ++ph) {
-        plmax = U.pad_left[ph] > plmax ? U.pad_left[ph] : plmax;
-        const int r = U.ntaps - 1 - U.pad_left[ph];
-        right = r > right ? r : right;
-      }
-      const int kk = plmax + right + 1, nt = U.ntaps, uu = U.u, kfull = U.k, cout = U.cout, pad_ = pad;
-      U.cl_pad_left = plmax;
-      const int* pl = U.pad_left;
-      U.cl = P.conv_cl(U.u * U.cout, U.cin, kk,
-                       [&, plmax, nt, uu, kfull, cout, pad_, pl](int cop, int ci, int jw) -> float {
-                         const int ph = cop / cout, co = cop % cout;
-                         const int j = jw - (plmax - pl[ph]);
-                         if (j < 0 || j >= nt) return 0.f;
-                         const int pp = (ph + pad_) % uu;
-                         return w[((int64_t)ci * cout + co) * kfull + pp + uu * (nt - 1 - j)];
-                       },
-                       [&, cout](int cop) { return bt->data[cop % cout]; }, ok && bt);
-    }
+    // channels-last form: tap window = union over phases; phase ph uses window taps [cl_off, cl_off + ntaps)
+    U.cl_pad_left = G.cl_pad_left;
+    U.cl = P.conv_cl(U.u * U.cout, U.cin, G.cl_k,
+                     [&, kfull, cout](int cop, int ci, int jw) -> float {
+                       const int tap = G.cl_tap(cop / cout, jw);
+                       return tap < 0 ? 0.f : w[((int64_t)ci * cout + cop % cout) * kfull + tap];
+                     },
+                     [&, cout](int cop) { return bt->data[cop % cout]; }, ok && bt);
     ch = U.cout;
     for (int j = 0; j < m.n_rbk; ++j) {
       const int k = c.resblock_kernel_sizes[j];

@@ -73,6 +73,54 @@ static int64_t t_x3_off(int cin, int cout, int k) {                 // the x3 re
 }
 int64_t bv2_test_x3_omax_off(int cin, int cout, int k) { return t_x3_off(cin, cout, k) + X3_SLOT_WORDS; }
 
+// one conv w_host [cout][cin][k] + bias_host [cout] (or null) into a zeroed region of bv2_test_conv_pack_floats(cin, cout, k) floats: the
+// packed fp32 stream (conv_w_index), the bias behind it, with x6 the three bf16 planes at t_x6_off, and with x3 the region at t_x3_off:
+// [max |x| slot] [max |out| slot] (X3_SLOT_WORDS each, left zero) [1 / S_w] (X3_HDR_FLOATS) [the two scaled fp16 planes]
+static void t_pack_conv(float* pk, const float* w_host, const float* bias_host, int cin, int cout, int k, bool x6, bool x3 = false) {
+  const int cin_pad = t_round_up(cin, 16), ld = t_round_up(cout, 128);
+  for (int j = 0; j < k; ++j)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int co = 0; co < cout; ++co)
+        pk[(size_t)conv_w_index(j, ci, co, cin_pad, k)] = w_host[((size_t)co * cin + ci) * k + j];
+  const size_t boff = (size_t)k * cin_pad * ld;
+  if (bias_host) for (int co = 0; co < cout; ++co) pk[boff + co] = bias_host[co];
+  if (!x6) return;
+  uint16_t* wx = reinterpret_cast<uint16_t*>(pk + t_x6_off(cin, cout, k));
+  for (int j = 0; j < k; ++j)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int co = 0; co < cout; ++co) {
+        uint16_t hh[3];
+        x6_split(w_host[((size_t)co * cin + ci) * k + j], hh);
+        for (int pl = 0; pl < 3; ++pl) wx[x6_w_index(j, ci, co, cin, k, pl)] = hh[pl];
+      }
+  if (!x3) return;
+  float wmax = 0.f;
+  for (size_t i = 0; i < (size_t)cout * cin * k; ++i) wmax = std::max(wmax, std::fabs(w_host[i]));
+  uint32_t mb;
+  std::memcpy(&mb, &wmax, 4);
+  const unsigned e = x3_scale_exp(mb);
+  float* reg = pk + t_x3_off(cin, cout, k);
+  reg[2 * X3_SLOT_WORDS] = x3_scale_inv(e);
+  uint16_t* wy = reinterpret_cast<uint16_t*>(reg + 2 * X3_SLOT_WORDS + X3_HDR_FLOATS);
+  for (int j = 0; j < k; ++j)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int co = 0; co < cout; ++co) {
+        const float v = w_host[((size_t)co * cin + ci) * k + j] * x3_scale(e);
+        const _Float16 g0 = (_Float16)v;
+        const _Float16 g1 = (_Float16)(v - (float)g0);
+        std::memcpy(&wy[x3_w_index(j, ci, co, cin, k, 0)], &g0, 2);
+        std::memcpy(&wy[x3_w_index(j, ci, co, cin, k, 1)], &g1, 2);
+      }
+}
+// the descriptor of a conv packed by t_pack_conv at float offset `off` of a scratch that plays the blob
+static ConvW t_conv_w(int64_t off, int cin, int cout, int k, bool bias, bool x6) {
+  ConvW w;
+  w.cin = cin; w.cin_pad = t_round_up(cin, 16); w.cout = cout; w.cout_pad = t_round_up(cout, 32); w.w_ld = t_round_up(cout, 128); w.k = k;
+  w.w_off = off; w.b_off = bias ? off + (int64_t)k * w.cin_pad * w.w_ld : -1;
+  w.wx_off = x6 ? off + t_x6_off(cin, cout, k) : -1;
+  return w;
+}
+
 int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const float* bias_host, float* out, float* wpack_dev,
                     int B, int cin, int cout, int k, int dil, int pad_left, int L, int tile, float lrelu_slope, int relu,
                     const float* res, int res_mode, const float* in_mask, const float* out_mask, int mask_pre,
@@ -81,44 +129,12 @@ int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const flo
   try {
     const int cin_pad = t_round_up(cin, 16), ld = t_round_up(cout, 128), cout_pad = t_round_up(cout, 32);
     std::vector<float> pk;
-    if (w_host) pk.assign((size_t)bv2_test_conv_pack_floats(cin, cout, k), 0.f);
-    if (w_host)                                   // w_host == NULL: wpack_dev already holds the packed weight (timing loops)
-    for (int j = 0; j < k; ++j)
-      for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < cout; ++co)
-          pk[(size_t)conv_w_index(j, ci, co, cin_pad, k)] = w_host[((size_t)co * cin + ci) * k + j];
     const size_t boff = (size_t)k * cin_pad * ld;
-    if (w_host && bias_host) for (int co = 0; co < cout; ++co) pk[boff + co] = bias_host[co];
     const bool x6 = tile >= TILE_X6 && cin % 32 == 0;
-    if (w_host && x6) {
-      uint16_t* wx = reinterpret_cast<uint16_t*>(pk.data() + t_x6_off(cin, cout, k));
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co) {
-            uint16_t hh[3];
-            x6_split(w_host[((size_t)co * cin + ci) * k + j], hh);
-            for (int pl = 0; pl < 3; ++pl) wx[x6_w_index(j, ci, co, cin, k, pl)] = hh[pl];
-          }
-    }
     const bool x3 = tile == TILE_X3 && x6;
-    if (w_host && x3) {
-      float wmax = 0.f;
-      for (size_t i = 0; i < (size_t)cout * cin * k; ++i) wmax = std::max(wmax, std::fabs(w_host[i]));
-      uint32_t mb;
-      std::memcpy(&mb, &wmax, 4);
-      const unsigned e = x3_scale_exp(mb);
-      float* reg = pk.data() + t_x3_off(cin, cout, k);
-      reg[2 * X3_SLOT_WORDS] = x3_scale_inv(e);
-      uint16_t* wy = reinterpret_cast<uint16_t*>(reg + 2 * X3_SLOT_WORDS + X3_HDR_FLOATS);
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co) {
-            const float v = w_host[((size_t)co * cin + ci) * k + j] * x3_scale(e);
-            const _Float16 g0 = (_Float16)v;
-            const _Float16 g1 = (_Float16)(v - (float)g0);
-            std::memcpy(&wy[x3_w_index(j, ci, co, cin, k, 0)], &g0, 2);
-            std::memcpy(&wy[x3_w_index(j, ci, co, cin, k, 1)], &g1, 2);
-          }
+    if (w_host) {                                 // w_host == NULL: wpack_dev already holds the packed weight (timing loops)
+      pk.assign((size_t)bv2_test_conv_pack_floats(cin, cout, k), 0.f);
+      t_pack_conv(pk.data(), w_host, bias_host, cin, cout, k, x6, x3);
     }
     if (w_host && hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
     ConvLaunch cl;
@@ -715,6 +731,179 @@ int bv2_test_dds_layer(void* stream, const float* x, const float* pre_w_host, co
     a.B = B; a.C = C; a.T = T;
     return launch_dds_layer(static_cast<hipStream_t>(stream), a);
   } catch (...) { return -100; }
+}
+
+// ---- the Generator's stage glue: ConvTranspose1d, multi-problem conv launches, conv_post (tests/test_generator_glue_*.py)
+// dense weights of the polyphase split from the ConvTranspose1d weight w [cin][cout][k]: phase ph's conv [cout][cin][ntaps] and the
+// channels-last union-window conv [u * cout][cin][cl_k], through UpsGeom's tap maps like the packer (bv2_model.cpp)
+static void t_ups_phase_dense(const UpsGeom& G, int ph, int cin, int cout, const float* w, float* out) {
+  for (int co = 0; co < cout; ++co)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int j = 0; j < G.ntaps; ++j) out[((size_t)co * cin + ci) * G.ntaps + j] = w[((size_t)ci * cout + co) * G.k + G.tap(ph, j)];
+}
+static void t_ups_cl_dense(const UpsGeom& G, int cin, int cout, const float* w, float* out) {
+  for (int cop = 0; cop < G.u * cout; ++cop)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int jw = 0; jw < G.cl_k; ++jw) {
+        const int tap = G.cl_tap(cop / cout, jw);
+        out[((size_t)cop * cin + ci) * G.cl_k + jw] = tap < 0 ? 0.f : w[((size_t)ci * cout + cop % cout) * G.k + tap];
+      }
+}
+static int64_t t_region(int cin, int cout, int k) { return (bv2_test_conv_pack_floats(cin, cout, k) + 63) / 64 * 64; }
+
+int bv2_test_ups_split(int u, int k, int cin, int cout, const float* w, float* phase_w, int32_t* pad_left, float* cl_w, int32_t* cl_dims,
+                       int32_t* cl_offs) {
+  UpsGeom G;
+  if (!ups_geometry(u, k, G)) return -2;
+  if (cin < 1 || cout < 1) return -1;
+  for (int ph = 0; ph < u; ++ph) {
+    if (pad_left) pad_left[ph] = G.pad_left[ph];
+    if (cl_offs) cl_offs[ph] = G.cl_off[ph];
+    if (w && phase_w) t_ups_phase_dense(G, ph, cin, cout, w, phase_w + (size_t)ph * cout * cin * G.ntaps);
+  }
+  if (cl_dims) { cl_dims[0] = G.cl_pad_left; cl_dims[1] = G.cl_k; }
+  if (w && cl_w) t_ups_cl_dense(G, cin, cout, w, cl_w);
+  return 0;
+}
+
+int64_t bv2_test_conv_multi_pack_floats(int cin, int cout, const int32_t* k, int nprob) {
+  int64_t n = 0;
+  for (int i = 0; i < nprob; ++i) n += t_region(cin, cout, k[i]);
+  return n;
+}
+int bv2_test_conv_multi(void* stream, const bv2_test_conv_prob* probs, int nprob, int cin, int cout, const float* x0, const float* x1,
+                        const float* x2, int nsrc, float in_scale, float lrelu_slope, const int64_t* lens, int len_mul, int B, int L,
+                        int tile, int ksplit, int64_t slab_stride, const float* out_mask, unsigned* omax, float* wpack_dev, int32_t* info) {
+  try {
+    if (!probs || nprob < 1 || nprob > BV2_MAX_PROBS || nsrc < 1 || nsrc > 3) return -2;
+    if (tile == TILE_SPLITK && nsrc != 1) return -2;             // the split-K kernel reads x[0] only
+    const bool x6 = tile >= TILE_X6 && cin % 32 == 0;
+    const bool x3 = tile == TILE_X3 && x6;                       // every problem reads max |x| from a slot of its own region, filled here
+    if (x3 && nsrc != 1) return -2;
+    ConvLaunch cl;
+    std::memset(&cl, 0, sizeof(cl));
+    int64_t off = 0;
+    for (int i = 0; i < nprob; ++i) {
+      const bv2_test_conv_prob& q = probs[i];
+      if (!q.w_host || q.k < 1 || q.dil < 1 || !q.out) return -2;
+      std::vector<float> pk((size_t)t_region(cin, cout, q.k), 0.f);
+      t_pack_conv(pk.data(), q.w_host, q.bias_host, cin, cout, q.k, x6, x3);
+      if (hipMemcpy(wpack_dev + off, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
+      const ConvW w = t_conv_w(off, cin, cout, q.k, q.bias_host != nullptr, x6);
+      ConvProb p = conv_prob(w, wpack_dev, x0, q.out, L, q.dil);
+      p.x[1] = x1; p.x[2] = x2; p.nsrc = nsrc; p.in_scale = in_scale;
+      if (x6) p.w6 = reinterpret_cast<const uint16_t*>(wpack_dev + w.wx_off);
+      if (x3) {
+        float* reg = wpack_dev + off + t_x3_off(cin, cout, q.k);
+        if (launch_absmax(static_cast<hipStream_t>(stream), x0, (int64_t)B * cin * L, reinterpret_cast<unsigned*>(reg))) return -6;
+        p.xmax = reinterpret_cast<const unsigned*>(reg);
+        p.w3inv = reg + 2 * X3_SLOT_WORDS; p.w3 = reinterpret_cast<const uint16_t*>(reg + 2 * X3_SLOT_WORDS + X3_HDR_FLOATS);
+      }
+      if (q.pad_left >= 0) p.pad_left = q.pad_left;
+      p.out_rstride = q.out_rstride; p.out_bstride = (int64_t)cout * q.out_rstride; p.out_tstride = q.out_tstride; p.out_toff = q.out_toff;
+      p.res = q.res; p.res_bstride = p.out_bstride; p.res_mode = q.res_mode;
+      p.out_mask = out_mask; p.mask_post = out_mask ? 1 : 0;
+      p.pre_act = lrelu_slope != 0.f ? PRE_LRELU : PRE_NONE; p.slope = lrelu_slope;
+      p.omax = omax;
+      cl.p[i] = p;
+      off += t_region(cin, cout, q.k);
+    }
+    cl.nprob = nprob; cl.B = B; cl.L = L; cl.lens = lens; cl.len_mul = len_mul < 1 ? 1 : len_mul;
+    cl.ksplit = ksplit >= 1 ? ksplit : conv_pick_ksplit(cl, BV2_MAX_KSPLIT);      // ksplit 0: the split the executor would take (Ctx::conv)
+    cl.slab_stride = slab_stride;
+    const char* vn = nullptr;
+    const int rc = launch_conv1d(static_cast<hipStream_t>(stream), cl, tile, &vn);
+    if (info) { info[0] = conv_last_placement(); info[1] = cl.ksplit; }
+    return rc;
+  } catch (...) { return -100; }
+}
+
+int64_t bv2_test_conv_transpose_pack_floats(int u, int k, int cin, int cout) {
+  UpsGeom G;
+  return ups_geometry(u, k, G) ? (int64_t)u * t_region(cin, cout, G.ntaps) : -2;
+}
+int bv2_test_conv_transpose(void* stream, const float* w_host, const float* bias_host, int u, int k, int cin, int cout, const float* x0,
+                            const float* x1, const float* x2, int nsrc, float* out, const int64_t* lens, int len_mul, int B, int L,
+                            int tile, int only_phase, unsigned* omax, float* wpack_dev, int32_t* info) {
+  try {
+    UpsGeom G;
+    if (!ups_geometry(u, k, G) || !w_host || nsrc < 1 || nsrc > 3 || only_phase >= u || tile >= TILE_X6) return -2;
+    UpW U;
+    U.u = u; U.k = k; U.cin = cin; U.cout = cout; U.ntaps = G.ntaps; U.cl_pad_left = G.cl_pad_left;
+    const int64_t one = t_region(cin, cout, G.ntaps);
+    std::vector<float> pk((size_t)(u * one), 0.f), dense((size_t)cout * cin * G.ntaps);
+    for (int ph = 0; ph < u; ++ph) {
+      t_ups_phase_dense(G, ph, cin, cout, w_host, dense.data());
+      t_pack_conv(pk.data() + ph * one, dense.data(), bias_host, cin, cout, G.ntaps, false);
+      U.phase[ph] = t_conv_w(ph * one, cin, cout, G.ntaps, bias_host != nullptr, false);
+      U.pad_left[ph] = G.pad_left[ph];
+    }
+    if (hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
+    const float* src[3] = {x0, nsrc > 1 ? x1 : nullptr, nsrc > 2 ? x2 : nullptr};
+    ConvLaunch cl = ups_conv_launch(U, wpack_dev, src, nsrc, out, B, L, lens, len_mul < 1 ? 1 : len_mul, omax);
+    if (only_phase >= 0) { cl.p[0] = cl.p[only_phase]; cl.nprob = 1; }
+    const char* vn = nullptr;
+    const int rc = launch_conv1d(static_cast<hipStream_t>(stream), cl, tile, &vn);
+    if (info) { info[0] = conv_last_placement(); info[1] = cl.ksplit; }
+    return rc;
+  } catch (...) { return -100; }
+}
+
+int64_t bv2_test_conv_transpose_cl_pack_bytes(int u, int k, int cin, int cout) {
+  UpsGeom G;
+  if (!ups_geometry(u, k, G) || cin % 16) return -2;
+  const int cout_pad = t_round_up(u * cout, 32);
+  return cl_w_elems(cin, cout_pad, G.cl_k) * 2 + (int64_t)cout_pad * 4;
+}
+int bv2_test_conv_transpose_cl(void* stream, const float* w_host, const float* bias_host, int u, int k, int cin, int cout, const void* x0,
+                               const void* x1, const void* x2, int nsrc, void* out, const int64_t* lens, int len_mul, int B, int L,
+                               int phase_taps, void* wpack_dev) {
+  try {
+    UpsGeom G;
+    if (!ups_geometry(u, k, G) || !w_host || !bias_host || nsrc < 1 || nsrc > 3) return -2;
+    if (!conv_cl_bf16_supported(cin, u * cout, G.cl_k, 1)) return -2;
+    const int cout_pad = t_round_up(u * cout, 32);
+    const int64_t ne = cl_w_elems(cin, cout_pad, G.cl_k);
+    std::vector<float> dense((size_t)u * cout * cin * G.cl_k);
+    t_ups_cl_dense(G, cin, cout, w_host, dense.data());
+    std::vector<uint16_t> pk((size_t)ne, 0);
+    for (int j = 0; j < G.cl_k; ++j)
+      for (int ci = 0; ci < cin; ++ci)
+        for (int co = 0; co < u * cout; ++co)
+          pk[(size_t)cl_w_index(j, ci, co, cin, G.cl_k)] = f2bf(dense[((size_t)co * cin + ci) * G.cl_k + j]);
+    std::vector<float> bb((size_t)cout_pad, 0.f);
+    for (int co = 0; co < u * cout; ++co) bb[(size_t)co] = bias_host[co % cout];
+    if (hipMemcpy(wpack_dev, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
+    if (hipMemcpy(static_cast<char*>(wpack_dev) + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
+    UpW U;
+    U.u = u; U.k = k; U.cin = cin; U.cout = cout; U.ntaps = G.ntaps; U.cl_pad_left = G.cl_pad_left;
+    for (int ph = 0; ph < u; ++ph) U.pad_left[ph] = G.pad_left[ph];
+    U.cl.cin = cin; U.cl.cin_pad = cin; U.cl.cout = u * cout; U.cl.cout_pad = cout_pad; U.cl.k = G.cl_k;
+    U.cl.wb_off = 0; U.cl.b_off = ne / 2;                        // float offsets from wpack_dev, which plays the blob
+    const uint16_t* src[3] = {static_cast<const uint16_t*>(x0), nsrc > 1 ? static_cast<const uint16_t*>(x1) : nullptr,
+                              nsrc > 2 ? static_cast<const uint16_t*>(x2) : nullptr};
+    const ClLaunch cl = ups_cl_launch(U, static_cast<const float*>(wpack_dev), src, nsrc, static_cast<uint16_t*>(out), B, L, lens,
+                                      len_mul < 1 ? 1 : len_mul, phase_taps != 0);
+    if (phase_taps && !cl.p[0].ph_cout) return -2;               // the restriction was asked for and does not fit its nibbles
+    return launch_conv_cl_bf16(static_cast<hipStream_t>(stream), cl, nullptr);
+  } catch (...) { return -100; }
+}
+
+int bv2_test_conv_post(void* stream, const float* x0, const float* x1, const float* x2, int nsrc, const float* w_host, float* w_dev,
+                       float* out, const int64_t* lens, int len_mul, int B, int C, int k, int L) {
+  if (!w_host || !w_dev || nsrc < 1 || nsrc > 3 || C < 1 || k < 1) return -2;
+  if (hipMemcpy(w_dev, w_host, sizeof(float) * (size_t)C * k, hipMemcpyHostToDevice) != hipSuccess) return -6;
+  const float* src[3] = {x0, nsrc > 1 ? x1 : nullptr, nsrc > 2 ? x2 : nullptr};
+  return launch_conv_post(static_cast<hipStream_t>(stream), conv_post_args(src, nsrc, w_dev, out, C, k, B, L, lens, len_mul < 1 ? 1 : len_mul));
+}
+int bv2_test_conv_post_cl(void* stream, const void* x0, const void* x1, const void* x2, int nsrc, const float* w_host, float* w_dev,
+                          float* out, const int64_t* lens, int len_mul, int B, int C, int k, int L, int generic) {
+  if (!w_host || !w_dev || nsrc < 1 || nsrc > 3 || C < 1 || k < 1) return -2;
+  if (hipMemcpy(w_dev, w_host, sizeof(float) * (size_t)C * k, hipMemcpyHostToDevice) != hipSuccess) return -6;
+  const uint16_t* src[3] = {static_cast<const uint16_t*>(x0), nsrc > 1 ? static_cast<const uint16_t*>(x1) : nullptr,
+                            nsrc > 2 ? static_cast<const uint16_t*>(x2) : nullptr};
+  return launch_conv_post_cl(static_cast<hipStream_t>(stream),
+                             conv_post_cl_args(src, nsrc, w_dev, out, C, k, B, L, lens, len_mul < 1 ? 1 : len_mul, generic != 0));
 }
 
 int bv2_test_spline(void* stream, float* z, int src, int dst, const float* params, int prow, const float* mask,

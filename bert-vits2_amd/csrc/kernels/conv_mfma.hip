@@ -679,6 +679,10 @@ void conv_set_tuning(int splitk_waves, int force_ck, long tile_target) {
   g_tune_no_snake = force_ck >= 100 ? 1 : 0;                        // force_ck + 100: plain z-major placement (A/B comparisons)
 }
 
+static int g_last_placement = PLACE_PLAIN;
+void conv_note_placement(int place) { g_last_placement = place; }
+int conv_last_placement() { return g_last_placement; }
+
 static unsigned long long* g_tl_buf = nullptr;
 static long long g_tl_cap = 0, g_tl_off = 0;
 struct TlMeta { long long off; int gx, gy, gz, tile, ks, cin, L; };
@@ -738,6 +742,7 @@ static int launch_variant(hipStream_t stream, const ConvLaunch& L0, int ck, int 
       grid = dim3(snake_n * 8, 1, 1);
     }
   }
+  conv_note_placement(snake_n > 0 ? PLACE_SNAKE : (per_xcd ? PLACE_PER_XCD : PLACE_PLAIN));
   const ConvLaunch L = with_timeline(Ls, grid, BM * 1000 + BN);
   const int nxbuf = max_chunks > 1 ? 2 : 1;     // a single-chunk problem never re-stages its X tile
   // weights go global -> registers; LDS holds only the (double-buffered) X chunk
@@ -825,6 +830,7 @@ static int launch_splitk(hipStream_t stream, const ConvLaunch& L0, int max_cout_
     if (L.p[i].act == ACT_GATE && nw == 16) nw = 8;   // the gate pairs rows inside one thread: at most 16 rows per pass
   if (variant_name) *variant_name = nw == 16 ? "conv1d_splitk<32x32,16w>" : (nw == 8 ? "conv1d_splitk<32x32,8w>" : "conv1d_splitk<32x32,4w>");
   const dim3 grid(per_xcd * 8 + (L.pf.ptr && L.pf.bytes ? PF_BLOCKS : 0));
+  conv_note_placement(PLACE_PER_XCD);
   // LDSX form: every problem has taps to re-use (k > 1), the staged tile fits (32 + (k-1)*dil <= SK_XP columns, <= SK_RPW rows
   // per wave) and a lane's 32-bit byte offsets reach every element
   bool ldsx = !g_tune_no_ldsx;

@@ -544,6 +544,7 @@ static int launch_x6_variant(hipStream_t stream, const ConvLaunch& L0, int max_c
       grid = dim3(snake_n * 8, 1, 1);
     }
   }
+  conv_note_placement(snake_n > 0 ? PLACE_SNAKE : (per_xcd ? PLACE_PER_XCD : PLACE_PLAIN));
   if (Ls.dbg == nullptr) {                        // tools/timeline.py: a slice of the stamp buffer while one is set
     int ks = 0;
     for (int i = 0; i < Ls.nprob && i < 3; ++i) ks |= (Ls.p[i].k & 255) << (8 * i);

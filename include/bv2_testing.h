@@ -1,6 +1,8 @@
 /*
- * bv2_testing.h — kernel-level entry points of libbv2.so used ONLY by tests/ (unit parity of single kernels against
- * torch fp32 references).  Not part of the drop-in boundary; synchronous where noted.
+ * bv2_testing.h — kernel-level entry points of libbv2.so used ONLY by tests/ and tools/: unit parity of single kernels and of single
+ * launches the executors build (the Encoder layer's fused forms, the Generator's ConvTranspose1d / multi-problem / conv_post launches)
+ * against torch fp32 and fp64 references, and the host-side packers and number formats on a CPU-only box.  Not part of the drop-in
+ * boundary; synchronous where noted.
  */
 #ifndef BV2_TESTING_H
 #define BV2_TESTING_H
@@ -171,6 +173,60 @@ int bv2_test_dds_layer(void* stream, const float* x, const float* pre_w_host, co
                        const float* bias_host, float* out, int dil, int last_mask, const float* post_w_host,
                        const float* post_b_host, int post_cout, float* post_out, float* zio, int z_dst, float* wpack_dev,
                        int B, int C, int T);
+
+/* ---- the Generator's stage glue (tests/test_generator_glue_cpu.py, tests/test_generator_glue_fp64_gpu.py).  Conventions as above: HOST
+ * weights, DEVICE tensors, packed synchronously into a caller-sized scratch, the launcher's status returned unchanged, -2 = unsupported.
+ * lens: optional DEVICE int64 [B] (item b's input is valid on [0, lens[b] * len_mul)).  omax: optional DEVICE slot of 256 zeroed words,
+ * 128-byte aligned (ConvProb::omax: max |out| as fp32 bits, one word per XCD 32 words apart — the value is their max).
+ * info (optional, HOST int32 [2]) = {placement the launcher took: 0 plain grid / 1 per-XCD column ranges / 2 cost-sorted snake, ksplit}. */
+
+/* The polyphase split of ConvTranspose1d(stride u, kernel k, padding (k - u) / 2) the packer applies to w [cin][cout][k] (host only): the
+ * dense phase convs phase_w [u][cout][cin][k/u] with pad_left [u], and the dense channels-last window conv cl_w [u*cout][cin][kk] with
+ * cl_dims = {cl_pad_left, kk} and each phase's window offset cl_offs [u].  Any output may be NULL (query cl_dims first: kk <= 7).
+ * -2 outside the envelope ((k - u) odd, k % u != 0, k / u > 4, u < 2, u > 8). */
+int bv2_test_ups_split(int u, int k, int cin, int cout, const float* w, float* phase_w, int32_t* pad_left, float* cl_w, int32_t* cl_dims,
+                       int32_t* cl_offs);
+
+/* One ConvLaunch of 1..8 problems on shared inputs x0 / x1 / x2 [B][cin][L] (nsrc of them are summed and scaled by in_scale, then
+ * leaky-ReLU of lrelu_slope unless 0).  Problem i: w_host [cout][cin][k], bias_host [cout] or NULL, pad_left < 0 = "same"; element (b, co,
+ * t) of its result goes to out[(b * cout + co) * out_rstride + t * out_tstride + out_toff]; res is indexed like out (res_mode 0 / 1 / 2 =
+ * none / add / rsub).  out_mask [B][L] multiplies after the residual op.  tile as in bv2_test_conv1d (tiles >= 8 also pack the x6 planes, 14
+ * the x3 planes with max |x0| reduced into each problem's slot; tile 6 with nsrc != 1 is refused); ksplit 0 = the split the executor would take (conv_pick_ksplit), slab s of a split at out +
+ * s * slab_stride.  wpack_dev needs bv2_test_conv_multi_pack_floats(cin, cout, k[], nprob) floats. */
+typedef struct bv2_test_conv_prob {
+  const float* w_host; const float* bias_host;
+  int32_t k, dil, pad_left;
+  float* out; int32_t out_rstride, out_tstride, out_toff;
+  const float* res; int32_t res_mode;
+} bv2_test_conv_prob;
+int64_t bv2_test_conv_multi_pack_floats(int cin, int cout, const int32_t* k, int nprob);
+int bv2_test_conv_multi(void* stream, const bv2_test_conv_prob* probs, int nprob, int cin, int cout, const float* x0, const float* x1,
+                        const float* x2, int nsrc, float in_scale, float lrelu_slope, const int64_t* lens, int len_mul, int B, int L,
+                        int tile, int ksplit, int64_t slab_stride, const float* out_mask, unsigned* omax, float* wpack_dev, int32_t* info);
+
+/* The fp32 Generator's ConvTranspose1d stage launch, built by the executor's own function (ups_conv_launch): out [B][cout][L * u] =
+ * ConvTranspose1d(lrelu_0.1(mean of the nsrc sources [B][cin][L])), w_host [cin][cout][k], bias_host [cout] or NULL.  tile 0 = the
+ * product's pick, 1..7 forced; only_phase >= 0 launches that phase alone (it writes out[.., t] with t % u == only_phase and nothing else).
+ * wpack_dev needs bv2_test_conv_transpose_pack_floats(u, k, cin, cout) floats. */
+int64_t bv2_test_conv_transpose_pack_floats(int u, int k, int cin, int cout);
+int bv2_test_conv_transpose(void* stream, const float* w_host, const float* bias_host, int u, int k, int cin, int cout, const float* x0,
+                            const float* x1, const float* x2, int nsrc, float* out, const int64_t* lens, int len_mul, int B, int L,
+                            int tile, int only_phase, unsigned* omax, float* wpack_dev, int32_t* info);
+/* ... and the bf16 path's (ups_cl_launch): sources / out DEVICE bf16 channels-last [B][L][cin] / [B][L * u][cout]; phase_taps 0 = the wave
+ * multiplies through the zero taps of the union window (ClProb::ph_cout = 0).  wpack_dev needs bv2_test_conv_transpose_cl_pack_bytes bytes. */
+int64_t bv2_test_conv_transpose_cl_pack_bytes(int u, int k, int cin, int cout);
+int bv2_test_conv_transpose_cl(void* stream, const float* w_host, const float* bias_host, int u, int k, int cin, int cout, const void* x0,
+                               const void* x1, const void* x2, int nsrc, void* out, const int64_t* lens, int len_mul, int B, int L,
+                               int phase_taps, void* wpack_dev);
+
+/* conv_post + tanh as the executors launch it (conv_post_args / conv_post_cl_args: leaky-ReLU slope 0.01): out [B][L] = tanh(conv1d(lrelu(
+ * mean of the nsrc sources), w [C][k], "same" padding, no bias)); w_host HOST, uploaded into w_dev (C * k DEVICE floats).
+ * fp32 (kernels/misc.hip): sources [B][C][L]. */
+int bv2_test_conv_post(void* stream, const float* x0, const float* x1, const float* x2, int nsrc, const float* w_host, float* w_dev,
+                       float* out, const int64_t* lens, int len_mul, int B, int C, int k, int L);
+/* bf16 (kernels/gen_bf16.hip): sources DEVICE bf16 channels-last [B][L][C]; generic 1 = the any-width kernel also at C = 16, k = 7 */
+int bv2_test_conv_post_cl(void* stream, const void* x0, const void* x1, const void* x2, int nsrc, const float* w_host, float* w_dev,
+                          float* out, const int64_t* lens, int len_mul, int B, int C, int k, int L, int generic);
 
 /* tuning experiments (tools/kbench.py): force the split-K wave count / C_in chunk / tile-count target of the fp32 conv; 0 = default */
 void bv2_test_set_tuning(int splitk_waves, int force_ck, long tile_target);
