@@ -136,6 +136,105 @@ int bv2_detach_weights(bv2_handle* h) {
   return 0;
 }
 
+// ---- the posterior encoder's own blob (enc_q.*; the inference blob, its size and its header are untouched) ---------------------
+static int posterior_layout(bv2_handle* h, int spec_channels, const char* what) {
+  if (h->post.spec == spec_channels && h->post.total_floats > 0) return 0;
+  PosteriorW w;
+  std::string e;
+  if (int rc = build_posterior_layout(h->model.cfg, spec_channels, w, e)) { h->err = std::string(what) + ": " + e; return rc; }
+  h->post = w;
+  h->post_blob = nullptr;              // a blob attached for another width no longer fits
+  return 0;
+}
+
+int64_t bv2_posterior_packed_bytes(bv2_handle* h, int spec_channels) {
+  if (!h) return -1;
+  BV2_TRY
+  if (posterior_layout(h, spec_channels, "bv2_posterior_packed_bytes")) return -1;
+  return h->post.total_floats * (int64_t)sizeof(float);
+  BV2_CATCH(h)
+}
+
+int bv2_posterior_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
+  if (!h) return -1;
+  BV2_TRY
+  if (!key || !host_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { h->err = "bv2_posterior_load_tensor: bad argument"; return -1; }
+  if (std::strncmp(key, "enc_q.", 6) != 0) return 1;            // not a posterior-encoder tensor: ignored
+  HostTensor t;
+  int64_t n = 1;
+  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= shape[i]; }
+  t.data.resize((size_t)n);
+  if (dtype == BV2_F32) std::memcpy(t.data.data(), host_ptr, sizeof(float) * (size_t)n);
+  else if (dtype == BV2_F16) {
+    const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
+    for (int64_t i = 0; i < n; ++i) t.data[(size_t)i] = h2f(s[i]);
+  } else if (dtype == BV2_BF16) {
+    const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
+    for (int64_t i = 0; i < n; ++i) { uint32_t b = (uint32_t)s[i] << 16; std::memcpy(&t.data[(size_t)i], &b, 4); }
+  } else { h->err = "bv2_posterior_load_tensor: unknown dtype"; return -1; }
+  h->post_tensors[key] = std::move(t);
+  return 0;
+  BV2_CATCH(h)
+}
+
+int bv2_posterior_pack(bv2_handle* h, int spec_channels, void* host_blob, int64_t bytes) {
+  if (!h) return -1;
+  BV2_TRY
+  if (int rc = posterior_layout(h, spec_channels, "bv2_posterior_pack")) return rc;
+  if (!host_blob || bytes < h->post.total_floats * (int64_t)sizeof(float)) { h->err = "bv2_posterior_pack: buffer too small"; return -1; }
+  return pack_posterior_blob(h->model.cfg, h->post, h->post_tensors, static_cast<float*>(host_blob), h->err);
+  BV2_CATCH(h)
+}
+
+int bv2_posterior_attach(bv2_handle* h, int spec_channels, const void* dev_blob, int64_t bytes) {
+  if (!h) return -1;
+  BV2_TRY
+  if (int rc = posterior_layout(h, spec_channels, "bv2_posterior_attach")) return rc;
+  if (!dev_blob || bytes < h->post.total_floats * (int64_t)sizeof(float)) { h->err = "bv2_posterior_attach: blob too small for this config"; return -1; }
+  uint32_t hdr[8];
+  if (hipMemcpy(hdr, dev_blob, sizeof(hdr), hipMemcpyDeviceToHost) != hipSuccess) {
+    h->err = "bv2_posterior_attach: cannot read the blob header (is this a device pointer on the current GPU?)";
+    return -6;
+  }
+  int64_t tf;
+  std::memcpy(&tf, hdr + 4, sizeof(tf));
+  if (hdr[0] != kPosteriorMagic || hdr[1] != BV2_ABI_VERSION || hdr[2] != h->post.cfg_hash || hdr[3] != BV2_POSTERIOR_LAYOUT ||
+      tf != h->post.total_floats) {
+    h->err = "bv2_posterior_attach: blob header does not match this handle's config and spec_channels (not a posterior blob, or packed for another model)";
+    return -7;
+  }
+  h->post_blob = static_cast<const float*>(dev_blob);
+  return 0;
+  BV2_CATCH(h)
+}
+
+int bv2_posterior_detach(bv2_handle* h) {
+  if (!h) return -1;
+  h->post_blob = nullptr;
+  return 0;
+}
+
+int64_t bv2_posterior_workspace_bytes(const bv2_handle* h, int B, int Ty) {
+  if (!h || B < 1 || Ty < 1) return -1;
+  return posterior_workspace_bytes(h->model, B, Ty);
+}
+
+int bv2_posterior_encode(bv2_handle* h, bv2_stream stream, int B, int Ty, const float* y, const int64_t* y_lengths, const float* g,
+                         const float* noise_q, float noise_scale_q, float* z, float* m_q, float* logs_q, float* y_mask,
+                         void* ws, int64_t wsb) {
+  if (!h) return -1;
+  BV2_TRY
+  if (!h->post_blob) {
+    h->err = "bv2_posterior_encode: no posterior weights attached (bv2_posterior_pack + bv2_posterior_attach; release checkpoints "
+             "written by compress_model.py are stripped of enc_q.*)";
+    return -8;
+  }
+  if (B < 1 || Ty < 1 || !y || !y_lengths || !g || !z || !ws) { h->err = "bv2_posterior_encode: bad argument"; return -1; }
+  return run_posterior_encode(h, static_cast<hipStream_t>(stream), B, Ty, y, y_lengths, g, noise_q, noise_scale_q, z, m_q, logs_q, y_mask,
+                              ws, wsb);
+  BV2_CATCH(h)
+}
+
 int bv2_set_generator_dtype(bv2_handle* h, int dtype) {
   if (!h) return -1;
   if (dtype != BV2_F32 && dtype != BV2_BF16) { h->err = "bv2_set_generator_dtype: BV2_F32 or BV2_BF16"; return -1; }
@@ -336,7 +435,18 @@ int bv2_stage_flow(bv2_handle* h, bv2_stream stream, int B, int Ty, const float*
   if (B < 1 || Ty < 1 || !z_p || !g || !z || ((y_lengths != nullptr) == (y_mask != nullptr))) {
     h->err = "bv2_stage_flow: bad argument (exactly one of y_lengths / y_mask)"; return -1;
   }
-  return run_flow(h, static_cast<hipStream_t>(stream), B, Ty, z_p, y_lengths, y_mask, g, z, ws, wsb);
+  return run_flow(h, static_cast<hipStream_t>(stream), B, Ty, z_p, y_lengths, y_mask, g, z, ws, wsb, false);
+  BV2_CATCH(h)
+}
+
+int bv2_stage_flow_forward(bv2_handle* h, bv2_stream stream, int B, int Ty, const float* z, const int64_t* y_lengths,
+                           const float* y_mask, const float* g, float* z_p, void* ws, int64_t wsb) {
+  if (int rc = ready(h, ws)) return rc;
+  BV2_TRY
+  if (B < 1 || Ty < 1 || !z || !g || !z_p || ((y_lengths != nullptr) == (y_mask != nullptr))) {
+    h->err = "bv2_stage_flow_forward: bad argument (exactly one of y_lengths / y_mask)"; return -1;
+  }
+  return run_flow(h, static_cast<hipStream_t>(stream), B, Ty, z, y_lengths, y_mask, g, z_p, ws, wsb, true);
   BV2_CATCH(h)
 }
 
@@ -720,6 +830,106 @@ int bv2_resample(bv2_stream stream, const bv2_resample_config* cfg, const float*
     if (launch_resample(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
     return 0;
   } catch (...) { return fail("exception", -100); }
+}
+
+// ---- forced alignment (kernels/align.hip) ----------------------------------------------------------------------
+int bv2_neg_cent(bv2_stream stream, int32_t B, int32_t inter, int32_t T, int32_t Ty, const float* z_p, const float* m_p,
+                 const float* logs_p, const int64_t* x_lengths, const int64_t* y_lengths, float* neg_cent) {
+  auto fail = [&](const std::string& m, int rc) { g_create_err = "bv2_neg_cent: " + m; return rc; };
+  if (!z_p || !m_p || !logs_p || !neg_cent) return fail("z_p, m_p, logs_p and neg_cent must not be null", -1);
+  if (B < 1 || B > 65535) return fail("B must be in [1, 65535]", -1);
+  if (inter < 4 || inter % 4 || inter > NC_MAX_D) return fail("inter must be a multiple of 4 in [4, " + std::to_string(NC_MAX_D) + "]", -1);
+  if (T < 1 || Ty < 1 || Ty > 65535 * 64) return fail("T must be >= 1 and Ty in [1, 4194240]", -1);
+  try {
+    NegCentArgs a;
+    a.z_p = z_p; a.m_p = m_p; a.logs_p = logs_p; a.x_lengths = x_lengths; a.y_lengths = y_lengths; a.out = neg_cent;
+    a.B = B; a.D = inter; a.T = T; a.Ty = Ty;
+    if (launch_neg_cent(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
+int64_t bv2_maximum_path_workspace_bytes(int32_t B, int32_t T, int32_t Ty) {
+  if (B < 1 || B > 65535 || T < 1 || T > MP_MAX_T || Ty < 1) {
+    g_create_err = "bv2_maximum_path_workspace_bytes: B must be in [1, 65535], T in [1, " + std::to_string(MP_MAX_T) + "] and Ty >= 1";
+    return -1;
+  }
+  return maximum_path_workspace_bytes(B, T, Ty);
+}
+
+int bv2_maximum_path(bv2_stream stream, int32_t B, int32_t T, int32_t Ty, const float* neg_cent, const int64_t* x_lengths,
+                     const int64_t* y_lengths, int64_t* durations, float* attn, float* score, void* workspace, int64_t workspace_bytes) {
+  auto fail = [&](const std::string& m, int rc) { g_create_err = "bv2_maximum_path: " + m; return rc; };
+  if (!neg_cent || !durations) return fail("neg_cent and durations must not be null", -1);
+  if (B < 1 || B > 65535) return fail("B must be in [1, 65535]", -1);
+  if (T < 1 || T > MP_MAX_T) return fail("T must be in [1, " + std::to_string(MP_MAX_T) + "]", -1);
+  if (Ty < 1) return fail("Ty must be >= 1", -1);
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7u)) return fail("workspace must be a DEVICE pointer aligned to 8 bytes", -1);
+  if (workspace_bytes < maximum_path_workspace_bytes(B, T, Ty)) return fail("workspace too small (bv2_maximum_path_workspace_bytes)", -5);
+  try {
+    MaxPathArgs a;
+    a.neg_cent = neg_cent; a.x_lengths = x_lengths; a.y_lengths = y_lengths; a.durations = durations; a.attn = attn; a.score = score;
+    a.bits = static_cast<unsigned long long*>(workspace); a.B = B; a.T = T; a.Ty = Ty;
+    if (launch_maximum_path(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
+// spectrogram + phase A's prior -> durations in one call: enc_q, the forward flow, neg_cent, maximum_path on one workspace
+namespace {
+struct PlanAlign { float *z, *zp, *nc; unsigned long long* bits; void* sub; int64_t sub_bytes; };
+PlanAlign plan_align(Arena& A, const Model& m, int B, int T, int Ty) {
+  PlanAlign p;
+  const int64_t BT = (int64_t)B * Ty;
+  p.z = A.get<float>(BT * m.cfg.inter_channels);
+  p.zp = A.get<float>(BT * m.cfg.inter_channels);
+  p.nc = A.get<float>(BT * T);
+  p.bits = A.get<unsigned long long>(maximum_path_workspace_bytes(B, T, Ty) / 8);
+  const int64_t a = posterior_workspace_bytes(m, B, Ty), b = workspace_bytes(m, B, 1, Ty);   // enc_q, then the flow, share one region
+  p.sub_bytes = a > b ? a : b;
+  p.sub = A.get<char>(p.sub_bytes);
+  return p;
+}
+}  // namespace
+
+int64_t bv2_align_workspace_bytes(const bv2_handle* h, int B, int T, int Ty) {
+  if (!h || B < 1 || T < 1 || T > MP_MAX_T || Ty < 1) return -1;
+  Arena A(nullptr, 0);
+  plan_align(A, h->model, B, T, Ty);
+  return A.off + 256;
+}
+
+int bv2_align(bv2_handle* h, bv2_stream stream, int B, int T, int Ty, const float* m_p, const float* logs_p, const int64_t* x_lengths,
+              const float* y, const int64_t* y_lengths, const float* g, const float* noise_q, int64_t* durations, float* attn,
+              float* score, void* ws, int64_t wsb) {
+  if (int rc = ready(h, ws)) return rc;
+  BV2_TRY
+  if (!h->post_blob) {
+    h->err = "bv2_align: no posterior weights attached (bv2_posterior_pack + bv2_posterior_attach; release checkpoints written by "
+             "compress_model.py are stripped of enc_q.*)";
+    return -8;
+  }
+  if (B < 1 || B > 65535 || T < 1 || T > MP_MAX_T || Ty < 1 || !m_p || !logs_p || !x_lengths || !y || !y_lengths || !g || !durations) {
+    h->err = "bv2_align: bad argument (T <= " + std::to_string(MP_MAX_T) + ")";
+    return -1;
+  }
+  const int C = h->model.cfg.inter_channels;
+  if (C % 4 || C > NC_MAX_D) { h->err = "bv2_align: inter_channels must be a multiple of 4, at most " + std::to_string(NC_MAX_D); return -1; }
+  Arena A(ws, wsb);
+  PlanAlign P = plan_align(A, h->model, B, T, Ty);
+  if (!A.ok()) { h->err = "workspace too small for bv2_align"; return -5; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = run_posterior_encode(h, s, B, Ty, y, y_lengths, g, noise_q, 1.f, P.z, nullptr, nullptr, nullptr, P.sub, P.sub_bytes)) return rc;
+  if (int rc = run_flow(h, s, B, Ty, P.z, y_lengths, nullptr, g, P.zp, P.sub, P.sub_bytes, true)) return rc;
+  NegCentArgs n;
+  n.z_p = P.zp; n.m_p = m_p; n.logs_p = logs_p; n.x_lengths = x_lengths; n.y_lengths = y_lengths; n.out = P.nc; n.B = B; n.D = C; n.T = T; n.Ty = Ty;
+  if (launch_neg_cent(s, n)) { h->err = "bv2_align: neg_cent launch failed"; return -6; }
+  MaxPathArgs a;
+  a.neg_cent = P.nc; a.x_lengths = x_lengths; a.y_lengths = y_lengths; a.durations = durations; a.attn = attn; a.score = score;
+  a.bits = P.bits; a.B = B; a.T = T; a.Ty = Ty;
+  if (launch_maximum_path(s, a)) { h->err = "bv2_align: maximum_path launch failed"; return -6; }
+  return 0;
+  BV2_CATCH(h)
 }
 
 // ---- hipGraph capture -----------------------------------------------------------------------------------------

@@ -795,22 +795,55 @@ int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, con
   return c.rc;
 }
 
+// WN.forward (modules.py:185-210) in fp32, 2 launches per layer: in_layer + g_l + gate (ACT_GATE epilogue), then res_skip as two
+// problems of one launch — x = (x + rs[:H]) * mask in place, output += rs[H:] (first layer: =; last layer: all H rows, * mask).
+// The residual flow's couplings and the posterior encoder (16 layers) run on it; gl: the layers' conditioning rows [nl][2H] per item.
+static void run_wn(Ctx& c, const ConvW* wn_in, const ConvW* wn_res, const ConvW* wn_skip, int nl, const float* gl, int gl_bstride,
+                   float* x, float* acts, float* outacc, const float* mask, int B, int H, int Ty) {
+  for (int i = 0; i < nl; ++i) {
+    const bool last = i == nl - 1;
+    ConvProb p = c.prob(wn_in[i], x, acts, Ty);
+    p.bias2 = gl + (int64_t)i * 2 * H; p.bias2_bstride = gl_bstride;
+    p.act = ACT_GATE; p.out_bstride = (int64_t)H * Ty;
+    c.conv1(p, B, Ty, "wn.in+gate");
+    ConvLaunch cl;
+    cl.B = B; cl.L = Ty; cl.nprob = 0;
+    if (!last) {
+      ConvProb r = c.prob(wn_res[i], acts, x, Ty);
+      r.res = x; r.res_mode = RES_ADD; r.out_mask = mask; r.mask_post = 1;
+      cl.p[cl.nprob++] = r;
+    }
+    ConvProb sk = c.prob(wn_skip[i], acts, outacc, Ty);
+    if (i > 0) { sk.res = outacc; sk.res_mode = RES_ADD; }
+    if (last) { sk.out_mask = mask; sk.mask_post = 1; }
+    cl.p[cl.nprob++] = sk;
+    c.conv(cl, "wn.res_skip");
+  }
+}
+
 // ===============================================================================================================
-// flow reverse (reference models.py:138-145 / 438-445); z is updated in place
-static void flow_core(Ctx& c, const PlanB& P, float* z, const float* ymask, const float* g, int B, int Ty) {
+// the flow (reference models.py:138-145 / 438-445); z is updated in place.  Reverse (infer) is the default.  `forward` is the direction
+// of SynthesizerTrn.forward(), z -> z_p: every step of the reverse walk undone, last to first — a coupling leaves its x0 half alone, so
+// its h is the same in both directions and only `post` changes sign, x1 = (x1 + post(h)) * mask (mean_only in both variants,
+// modules.py ResidualCouplingLayer / TransformerCouplingLayer) — and the odd-count channel flip at the end instead of the beginning.
+// The forward direction takes the unfused boundary: flow_boundary.hip has the subtraction baked in and hands `h` to the coupling that
+// follows in ASCENDING order, and this direction is no serving hot path.
+static void flow_core(Ctx& c, const PlanB& P, float* z, const float* ymask, const float* g, int B, int Ty, bool forward = false) {
   const Model& m = c.m;
   const bv2_config& cf = m.cfg;
   const int H = cf.hidden_channels, C = cf.inter_channels, half = C / 2;
   float* gv_flow = P.gv + cf.upsample_initial_channel;
   bool pre_done = false;                            // the previous coupling's boundary launch already wrote this coupling's h
-  if (m.flow_flip_first) c.chk(launch_flip_channels(c.s, z, B, C, Ty), "flow.flip");   // odd coupling count: see bv2_model.cpp
-  for (int a = 0; a < m.n_coupling; ++a) {
+  const bool f16 = !forward && c.h->flow_dtype == BV2_F16;   // the forward direction is fp32 whatever bv2_set_flow_dtype says
+  if (m.flow_flip_first && !forward) c.chk(launch_flip_channels(c.s, z, B, C, Ty), "flow.flip");   // odd coupling count: see bv2_model.cpp
+  for (int step = 0; step < m.n_coupling; ++step) {
+    const int a = forward ? m.n_coupling - 1 - step : step;
     const CouplingW& K = m.coupling[a];
     float* x0 = z + (K.flipped ? (int64_t)half * Ty : 0);
     float* x1 = z + (K.flipped ? 0 : (int64_t)half * Ty);
     // small-N fp32 regime: LayerNorm-2 of the last Encoder layer + post + the NEXT coupling's pre run as one launch (flow_boundary.hip);
     // the next coupling's x0 is this coupling's x1 (the Flip is folded into the weights), so its `h` is ready when its turn comes
-    bool fuse_b = cf.use_transformer_flow && c.h->flow_dtype != BV2_F16 && !c.h->no_fused_boundary && c.h->taps.empty() &&
+    bool fuse_b = !forward && cf.use_transformer_flow && !f16 && !c.h->no_fused_boundary && c.h->taps.empty() &&
                   n_slabs(B, Ty) > 1 && H == 192 && half * 2 == C && half * 2 == H && K.post.cin == H && K.post.cout == half && K.post.k == 1 &&
                   K.pre.cin == half && K.pre.cout == H && K.pre.k == 1 && K.post.cin_pad == H && K.pre.cin_pad == half;
     const CouplingW* Kn = a + 1 < m.n_coupling ? &m.coupling[a + 1] : nullptr;
@@ -835,11 +868,11 @@ static void flow_core(Ctx& c, const PlanB& P, float* z, const float* ymask, cons
         F.post_w = c.W(K.post.w_off); F.post_b = c.W(K.post.b_off);
         if (Kn) { F.pre_w = c.W(Kn->pre.w_off); F.pre_b = c.W(Kn->pre.b_off); F.pre_out = P.h; pre_done = true; }
       }
-      run_encoder(c, K.enc, P.enc, ymask, gv_flow + a * H, P.gv_stride, B, Ty, nullptr, c.h->flow_dtype == BV2_F16, nullptr, nullptr, 0,
+      run_encoder(c, K.enc, P.enc, ymask, gv_flow + a * H, P.gv_stride, B, Ty, nullptr, f16, nullptr, nullptr, 0,
                   fuse_b ? &F : nullptr);
       if (fuse_b && F.launched) continue;                        // post (and the next pre) are done
       pre_done = false;                                          // the boundary kernel declined these arguments: LayerNorm ran, post follows
-    } else if (c.h->flow_dtype == BV2_F16) {
+    } else if (f16) {
       // WN.forward on the fp16 matrix core (bv2_set_flow_dtype(BV2_F16)): in_layer reads the fp32 x (rounded while staged), adds
       // bias + g_l and gates in fp32, writes the gate output as fp16 channels-last — it is only ever res_skip's input; res_skip
       // runs as two problems of one launch on that tensor with the fp32 epilogues of the fp32 path (x update in place with the
@@ -866,38 +899,18 @@ static void flow_core(Ctx& c, const PlanB& P, float* z, const float* ymask, cons
       }
       hres = P.outacc;
     } else {
-      const int nl = K.wn_layers;
-      const float* gl = gv_flow + (int64_t)a * 2 * H * nl;
-      // WN.forward (modules.py:185-210), 2 launches per layer: in_layer + g_l + gate (ACT_GATE epilogue), then res_skip as two
-      // problems of one launch — x = (x + rs[:H]) * mask in place, output += rs[H:] (first layer: =; last layer: all H rows, * mask)
-      for (int i = 0; i < nl; ++i) {
-        const bool last = i == nl - 1;
-        p = c.prob(K.wn_in[i], P.h, P.acts, Ty);
-        p.bias2 = gl + (int64_t)i * 2 * H; p.bias2_bstride = P.gv_stride;
-        p.act = ACT_GATE; p.out_bstride = (int64_t)H * Ty;
-        c.conv1(p, B, Ty, "wn.in+gate");
-        ConvLaunch cl;
-        cl.B = B; cl.L = Ty; cl.nprob = 0;
-        if (!last) {
-          ConvProb r = c.prob(K.wn_res[i], P.acts, P.h, Ty);
-          r.res = P.h; r.res_mode = RES_ADD; r.out_mask = ymask; r.mask_post = 1;
-          cl.p[cl.nprob++] = r;
-        }
-        ConvProb sk = c.prob(K.wn_skip[i], P.acts, P.outacc, Ty);
-        if (i > 0) { sk.res = P.outacc; sk.res_mode = RES_ADD; }
-        if (last) { sk.out_mask = ymask; sk.mask_post = 1; }
-        cl.p[cl.nprob++] = sk;
-        c.conv(cl, "wn.res_skip");
-      }
+      run_wn(c, K.wn_in, K.wn_res, K.wn_skip, K.wn_layers, gv_flow + (int64_t)a * 2 * H * K.wn_layers, P.gv_stride, P.h, P.acts, P.outacc,
+             ymask, B, H, Ty);
       hres = P.outacc;
     }
     c.tap(hres, (int64_t)B * H * Ty, "flow.", a, ".enc");
-    p = c.prob(K.post, hres, x1, Ty);                          // x1 = (x1 - post(h)) * mask, written in place
-    p.out_bstride = (int64_t)C * Ty; p.res = x1; p.res_bstride = (int64_t)C * Ty; p.res_mode = RES_RSUB;
+    p = c.prob(K.post, hres, x1, Ty);                          // x1 = (x1 -+ post(h)) * mask, written in place
+    p.out_bstride = (int64_t)C * Ty; p.res = x1; p.res_bstride = (int64_t)C * Ty; p.res_mode = forward ? RES_ADD : RES_RSUB;
     p.out_mask = ymask; p.mask_post = 1;
     c.conv1(p, B, Ty, "flow.post");
     c.tap(z, (int64_t)B * C * Ty, "flow.", a, ".z");
   }
+  if (m.flow_flip_first && forward) c.chk(launch_flip_channels(c.s, z, B, C, Ty), "flow.flip");
 }
 
 // The buffers of one ResBlock branch of a Generator stage at dilation step d (S: the stage's buffer set, x: the stage's input).  Branches
@@ -1385,11 +1398,11 @@ int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_
 }
 
 int run_flow(bv2_handle* h, hipStream_t s, int B, int Ty, const float* z_p, const int64_t* y_lengths, const float* y_mask,
-             const float* g, float* z, void* ws, int64_t wsb) {
+             const float* g, float* z, void* ws, int64_t wsb, bool forward) {
   const Model& m = h->model;
   Arena A(ws, wsb);
   PlanB P = plan_b(A, m, B, Ty);
-  if (int e = ws_short(h, A, "bv2_stage_flow")) return e;
+  if (int e = ws_short(h, A, forward ? "bv2_stage_flow_forward" : "bv2_stage_flow")) return e;
   Ctx c{h, s, m, h->blob};
   const float* ymask = y_mask;
   if (!ymask) {
@@ -1399,7 +1412,72 @@ int run_flow(bv2_handle* h, hipStream_t s, int B, int Ty, const float* z_p, cons
   if (z != z_p)
     (void)hipMemcpyAsync(z, z_p, sizeof(float) * (size_t)B * m.cfg.inter_channels * Ty, hipMemcpyDeviceToDevice, s);
   phase_b_gemv(c, P, g, B);
-  flow_core(c, P, z, ymask, g, B, Ty);
+  flow_core(c, P, z, ymask, g, B, Ty, forward);
+  return c.rc;
+}
+
+// ===============================================================================================================
+// PosteriorEncoder.forward (reference models.py:479-487): x = pre(y) * mask; x = WN(x, mask, g); stats = proj(x) * mask; m, logs = split;
+// z = (m + noise_q * exp(logs) * noise_scale_q) * mask.  Weights: the handle's posterior blob.  37 launches: mask, cond_layer GEMV, pre,
+// 16 x (in+gate, res_skip), proj (m and logs as two problems of one launch), sample.
+namespace {
+struct PlanQ { float *ymask, *gv, *h, *acts, *outacc, *m, *logs; };
+PlanQ plan_q(Arena& A, const Model& m, int B, int Ty) {
+  const int64_t H = m.cfg.hidden_channels, BT = (int64_t)B * Ty;
+  PlanQ p;
+  p.ymask = A.get<float>(BT);
+  p.gv = A.get<float>((int64_t)B * 2 * H * kPosteriorLayers);
+  p.h = A.get<float>(BT * H);
+  p.acts = A.get<float>(BT * H);
+  p.outacc = A.get<float>(BT * H);
+  p.m = A.get<float>(BT * m.cfg.inter_channels);
+  p.logs = A.get<float>(BT * m.cfg.inter_channels);
+  return p;
+}
+}  // namespace
+
+int64_t posterior_workspace_bytes(const Model& m, int B, int Ty) {
+  Arena a(nullptr, 0);
+  plan_q(a, m, B, Ty);
+  return a.off + 256;
+}
+
+int run_posterior_encode(bv2_handle* h, hipStream_t s, int B, int Ty, const float* y, const int64_t* y_lengths, const float* g,
+                         const float* noise_q, float noise_scale_q, float* z, float* m_q, float* logs_q, float* y_mask, void* ws, int64_t wsb) {
+  const Model& m = h->model;
+  const PosteriorW& Q = h->post;
+  const int H = m.cfg.hidden_channels, C = m.cfg.inter_channels;
+  Arena A(ws, wsb);
+  PlanQ P = plan_q(A, m, B, Ty);
+  if (int e = ws_short(h, A, "bv2_posterior_encode")) return e;
+  Ctx c{h, s, m, h->post_blob};
+  float* ymask = y_mask ? y_mask : P.ymask;
+  float* mq = m_q ? m_q : P.m;
+  float* lq = logs_q ? logs_q : P.logs;
+  c.chk(launch_seq_mask(s, y_lengths, ymask, B, Ty), "y_mask");
+  {
+    GemvLaunch G;                                    // cond_layer(g): every layer's conditioning rows, as phase B computes the flow's
+    std::memset(&G, 0, sizeof(G));
+    G.p[0].w = c.W(Q.cond.w_off); G.p[0].bias = c.W(Q.cond.b_off); G.p[0].out = P.gv; G.p[0].cout = Q.cond.cout; G.p[0].cin = Q.cond.cin;
+    G.p[0].out_bstride = Q.cond.cout;
+    G.nprob = 1; G.B = B; G.g = g; G.g_bstride = m.cfg.gin_channels;
+    c.chk(launch_gemv(s, G), "enc_q.cond");
+  }
+  ConvProb p = c.prob(Q.pre, y, P.h, Ty);            // odd spec_channels: rows >= cin of the padded K range read as zero (cin_pad route)
+  p.out_mask = ymask; p.mask_post = 1;
+  c.conv1(p, B, Ty, "enc_q.pre");
+  c.tap(P.h, (int64_t)B * H * Ty, "enc_q.pre");
+  run_wn(c, Q.wn_in, Q.wn_res, Q.wn_skip, kPosteriorLayers, P.gv, Q.cond.cout, P.h, P.acts, P.outacc, ymask, B, H, Ty);
+  c.tap(P.outacc, (int64_t)B * H * Ty, "enc_q.enc");
+  {
+    ConvLaunch cl;
+    cl.nprob = 2; cl.B = B; cl.L = Ty;
+    cl.p[0] = c.prob(Q.proj_m, P.outacc, mq, Ty);
+    cl.p[1] = c.prob(Q.proj_logs, P.outacc, lq, Ty);
+    for (int i = 0; i < 2; ++i) { cl.p[i].out_mask = ymask; cl.p[i].mask_post = 1; }
+    c.conv(cl, "enc_q.proj");
+  }
+  c.chk(launch_posterior_sample(s, mq, lq, noise_q, noise_scale_q, ymask, z, B, C, Ty), "enc_q.sample");
   return c.rc;
 }
 

@@ -121,6 +121,19 @@ struct RefEncW {
   VecW pw, pb;                       // proj [gin][128]
 };
 
+// PosteriorEncoder enc_q (reference models.py:448-487): its own, optional blob — the inference blob does not carry it
+constexpr uint32_t kPosteriorMagic = 0x71765642u;  // "BVvq"
+constexpr int kPosteriorLayers = 16;               // modules.WN(hidden, 5, 1, 16): = kMaxLayers
+struct PosteriorW {
+  int spec = 0;                      // spec_channels: pre's input rows (odd widths ride on cin_pad, rows >= cin read as zero)
+  ConvW pre;                         // Conv1d(spec -> hidden, 1)
+  GemvW cond;                        // enc.cond_layer: 2 * hidden * 16 rows, in gate order like CouplingW::wn_cond
+  ConvW wn_in[kMaxLayers], wn_res[kMaxLayers], wn_skip[kMaxLayers];   // as CouplingW's
+  ConvW proj_m, proj_logs;           // proj (hidden -> 2 inter, 1) split into its halves
+  int64_t total_floats = 0;
+  uint32_t cfg_hash = 0;
+};
+
 struct Model {
   bv2_config cfg;
   bool flow_flip_first = false;      // odd number of couplings: the reverse pass starts with a real channel Flip of z (bv2_model.cpp)
@@ -223,6 +236,10 @@ struct bv2_handle {
   bv2::Model model;
   std::map<std::string, bv2::HostTensor> tensors;
   const float* blob = nullptr;       // device
+  // the posterior encoder's own weights (bv2_posterior_*): layout once spec_channels is known, host tensors, attached device blob
+  bv2::PosteriorW post;
+  std::map<std::string, bv2::HostTensor> post_tensors;
+  const float* post_blob = nullptr;  // device
   std::string err;
   std::map<std::string, bv2::Tap> taps;
   int gen_dtype = BV2_F32;           // Generator arithmetic: BV2_F32 (conv_mfma.hip) or BV2_BF16 (gen_bf16.hip)
@@ -281,6 +298,8 @@ namespace bv2 {
 int build_layout(Model& m, std::string& err);                       // fills every descriptor + total_floats
 int pack_blob(const Model& m, const std::map<std::string, HostTensor>& t, float* blob, std::string& err);
 bool key_in_schema(const Model& m, const std::string& key);
+int build_posterior_layout(const bv2_config& cfg, int spec_channels, PosteriorW& w, std::string& err);
+int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w, const std::map<std::string, HostTensor>& t, float* blob, std::string& err);
 
 // bv2_exec.cpp
 int64_t workspace_bytes(const Model& m, int B, int T, int Ty);
@@ -293,7 +312,11 @@ int run_ref_encode(bv2_handle* h, hipStream_t s, const float* y, const int64_t* 
 int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_decode_out& out, void* ws, int64_t wsb,
                const bv2_item_controls* ic = nullptr);
 int run_flow(bv2_handle* h, hipStream_t s, int B, int Ty, const float* z_p, const int64_t* y_lengths, const float* y_mask,
-             const float* g, float* z, void* ws, int64_t wsb);
+             const float* g, float* z, void* ws, int64_t wsb, bool forward = false);   // forward: z -> z_p (SynthesizerTrn.forward)
+int64_t posterior_workspace_bytes(const Model& m, int B, int Ty);
+// enc_q(y, y_lengths, g) (models.py:479-487): y [B][spec][Ty] dense; noise_q null = z = m * mask
+int run_posterior_encode(bv2_handle* h, hipStream_t s, int B, int Ty, const float* y, const int64_t* y_lengths, const float* g,
+                         const float* noise_q, float noise_scale_q, float* z, float* m_q, float* logs_q, float* y_mask, void* ws, int64_t wsb);
 int run_stage_emb_g(bv2_handle* h, hipStream_t s, int B, const int64_t* sid, float* g);
 int run_stage_enc_p(bv2_handle* h, hipStream_t s, int B, int T, const int64_t* x, const int64_t* tone, const int64_t* lang,
                     const float* b0, const float* b1, const float* b2, const float* g, const int64_t* x_lengths, float* xout,

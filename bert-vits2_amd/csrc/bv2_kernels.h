@@ -746,4 +746,29 @@ struct ResampleArgs {
 };
 int launch_resample(hipStream_t stream, const ResampleArgs& a);
 
+// --- forced alignment (reference models.py:960-991, monotonic_align/core.py; kernels/align.hip) ---
+constexpr int NC_MAX_D = 256;                        // inter_channels: the B operand [2 D][16] lives in LDS (34 KB at 256)
+constexpr int MP_MAX_T = 4096;                       // symbols: two rows of cumulative values live in LDS (32 KB at 4096)
+struct NegCentArgs {
+  const float *z_p, *m_p, *logs_p;                   // [B][D][Ty], [B][D][T], [B][D][T]
+  const int64_t *x_lengths, *y_lengths;              // [B] each, or null = T / Ty
+  float* out;                                        // [B][Ty][T]; cells outside (y_lengths, x_lengths) are written as 0
+  int B, D, T, Ty;
+};
+int launch_neg_cent(hipStream_t stream, const NegCentArgs& a);
+struct MaxPathArgs {
+  const float* neg_cent;                             // [B][Ty][T], only read
+  const int64_t *x_lengths, *y_lengths;              // [B] each, or null = T / Ty
+  int64_t* durations;                                // [B][T]
+  float* attn;                                       // [B][Ty][T] one-hot, or null
+  float* score;                                      // [B], or null
+  unsigned long long* bits;                          // maximum_path_workspace_bytes(B, T, Ty): one decision bit per cell
+  int B, T, Ty;
+};
+// z = (m + noise * exp(logs) * scale) * mask (PosteriorEncoder, models.py:486); noise null: z = m * mask.  All [B][C][T], mask [B][T]
+int launch_posterior_sample(hipStream_t stream, const float* m, const float* logs, const float* noise, float scale, const float* mask,
+                            float* z, int B, int C, int T);
+int64_t maximum_path_workspace_bytes(int B, int T, int Ty);
+int launch_maximum_path(hipStream_t stream, const MaxPathArgs& a);
+
 }  // namespace bv2

@@ -613,7 +613,65 @@ int validate(const bv2_config& c, std::string& err) {
   return 0;
 }
 
+// enc_q (models.py:448-487) into its own blob: the WN stack exactly as the residual flow's (gate-ordered in_layers, res_skip split into its
+// x-update and output rows, cond_layer permuted the same way), pre with an odd cin on the cin_pad route, proj split into m / logs
+void pack_posterior(const bv2_config& c, PosteriorW& W, Packer& P) {
+  const int hid = c.hidden_channels, inter = c.inter_channels, gin = c.gin_channels, nl = kPosteriorLayers;
+  W.pre = P.conv1d("enc_q.pre", hid, W.spec, 1);
+  const std::function<int(int)> gate_row = [hid](int n) { const int mt = n / 32, j = n % 32; return j < 16 ? 16 * mt + j : hid + 16 * mt + (j - 16); };
+  const std::function<int(int)> cond_row = [hid, &gate_row](int n) { return (n / (2 * hid)) * 2 * hid + gate_row(n % (2 * hid)); };
+  W.cond = P.gemv("enc_q.enc.cond_layer", 2 * hid * nl, gin, true, /*wn=*/true, &cond_row);
+  for (int i = 0; i < nl; ++i) {
+    const std::string rsn = "enc_q.enc.res_skip_layers." + std::to_string(i);
+    W.wn_in[i] = P.conv1d("enc_q.enc.in_layers." + std::to_string(i), 2 * hid, hid, kFlowKernel, true, true, 0, -1, false, false, &gate_row);
+    if (i < nl - 1) {
+      W.wn_res[i] = P.conv1d(rsn, 2 * hid, hid, 1, true, true, 0, hid);
+      W.wn_skip[i] = P.conv1d(rsn, 2 * hid, hid, 1, true, true, hid, hid);
+    } else {
+      W.wn_skip[i] = P.conv1d(rsn, hid, hid, 1, true, true);
+    }
+  }
+  W.proj_m = P.conv1d("enc_q.proj", 2 * inter, hid, 1, true, false, 0, inter);
+  W.proj_logs = P.conv1d("enc_q.proj", 2 * inter, hid, 1, true, false, inter, inter);
+  P.alloc(2048);                                  // slack, as the inference blob's
+  W.total_floats = P.cursor;
+}
+
 }  // namespace
+
+int build_posterior_layout(const bv2_config& cfg, int spec_channels, PosteriorW& w, std::string& err) {
+  // the widths pinned against the reference (hparams.ENVELOPE["spec_channels"]), for models with a speaker table too
+  if (spec_channels != 1025 && spec_channels != 513 && spec_channels != 80) {
+    err = "posterior encoder: spec_channels must be 1025, 513 or 80";
+    return -1;
+  }
+  w = PosteriorW();
+  w.spec = spec_channels;
+  Packer P;
+  pack_posterior(cfg, w, P);
+  w.cfg_hash = hash_cfg(cfg) * 16777619u ^ (uint32_t)spec_channels;
+  return 0;
+}
+
+int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w_in, const std::map<std::string, HostTensor>& t, float* blob, std::string& err) {
+  PosteriorW w = w_in;
+  Packer P;
+  P.T = &t;
+  P.blob = blob;
+  std::memset(blob, 0, sizeof(float) * kBlobHeaderFloats);
+  pack_posterior(cfg, w, P);
+  if (!P.missing.empty()) {
+    err = "posterior encoder: missing/invalid tensors (" + std::to_string(P.missing.size()) + "): ";
+    for (size_t i = 0; i < P.missing.size() && i < 12; ++i) err += P.missing[i] + "; ";
+    return -2;
+  }
+  if (w.total_floats != w_in.total_floats) { err = "internal: posterior layout drift between passes"; return -4; }
+  uint32_t* hdr = reinterpret_cast<uint32_t*>(blob);
+  hdr[0] = kPosteriorMagic; hdr[1] = BV2_ABI_VERSION; hdr[2] = w_in.cfg_hash; hdr[3] = BV2_POSTERIOR_LAYOUT;
+  int64_t tf = w.total_floats;
+  std::memcpy(hdr + 4, &tf, sizeof(tf));
+  return 0;
+}
 
 int build_layout(Model& m, std::string& err) {
   if (int rc = validate(m.cfg, err)) return rc;

@@ -132,6 +132,7 @@ SYMBOLS = [
     ("bv2_stage_sdp", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64]),
     ("bv2_stage_dp", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64]),
     ("bv2_stage_flow", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64]),
+    ("bv2_stage_flow_forward", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64]),
     ("bv2_stage_generator", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64]),
     ("bv2_infer", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.c_int64, C.c_int64, C.c_float,
                             C.c_int32, C.c_int32, C.POINTER(DecodeOut), C.POINTER(C.c_int32), _P, C.c_int64]),
@@ -169,6 +170,18 @@ SYMBOLS = [
     ("bv2_resample_taps_f64", C.c_int, [C.POINTER(ResampleConfig), _P]),
     ("bv2_resample", C.c_int, [_P, C.POINTER(ResampleConfig), _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int64, C.c_int64,
                                _P, C.c_int64, _P]),
+    ("bv2_neg_cent", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("bv2_maximum_path_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    ("bv2_maximum_path", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int64]),
+    ("bv2_align_workspace_bytes", C.c_int64, [_P, C.c_int, C.c_int, C.c_int]),
+    ("bv2_align", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64]),
+    ("bv2_posterior_packed_bytes", C.c_int64, [_P, C.c_int]),
+    ("bv2_posterior_load_tensor", C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int, C.c_int]),
+    ("bv2_posterior_pack", C.c_int, [_P, C.c_int, _P, C.c_int64]),
+    ("bv2_posterior_attach", C.c_int, [_P, C.c_int, _P, C.c_int64]),
+    ("bv2_posterior_detach", C.c_int, [_P]),
+    ("bv2_posterior_workspace_bytes", C.c_int64, [_P, C.c_int, C.c_int]),
+    ("bv2_posterior_encode", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, C.c_int64]),
     ("bv2_graph_capture_encode", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_decode", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_encode_ex", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P,

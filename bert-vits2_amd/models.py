@@ -27,8 +27,10 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
+from . import align as _align
 from . import hparams as H
 from . import lib as L
+from .align import with_durations  # noqa: F401  (models.with_durations: an encode dict with its durations replaced)
 from .schema import param_shapes
 
 
@@ -92,6 +94,17 @@ class _Node(nn.Module):
 
     def forward(self, *a, **k):  # pragma: no cover
         raise NotImplementedError("bert_vits2_amd exposes SynthesizerTrn.infer() only; sub-modules are parameter holders")
+
+
+def _substitute_durations(enc, w_ceil, items, B: int, T: int, dev) -> None:
+    """``infer(w_ceil=...)`` / ``infer_stream(w_ceil=...)``: the given durations take the place of phase A's in ``enc`` (in place), with
+    ``y_lengths`` = their sums (at least 1, models.py:1057).  ``items`` [B] bool: only the marked items, the others keep their own."""
+    wc = w_ceil.to(dev, torch.float32).reshape(B, T).contiguous()
+    if items is not None:
+        keep = torch.as_tensor(items).to(dev, torch.bool).reshape(B, 1)
+        wc = torch.where(keep, wc, enc["w_ceil"].reshape(B, T))
+    enc["w_ceil"] = wc
+    enc["y_lengths"] = torch.clamp_min(wc.sum(1), 1).long()
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -859,10 +872,10 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def infer(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_scale=0.667, length_scale=1,
               noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None, *, g=None, y_lengths=None, noise_w=None, noise_z=None,
-              w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, ty_bucket=None):
+              w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, ty_bucket=None, w_ceil_items=None):
         """reference models.py:1026-1074.  Keyword-only extras (not in the reference): ``noise_w`` [B,2,T] and
         ``noise_z`` [B,inter,>=T_y] inject the two N(0,1) draws (parity tests; the reference's ONNX export externalises
-        them the same way), ``w_ceil`` substitutes the durations, ``want_attn=False`` skips materialising the path,
+        them the same way), ``w_ceil`` substitutes the durations (``w_ceil_items`` [B] bool: only for the marked items), ``want_attn=False`` skips materialising the path,
         ``exact_lengths=True`` makes every utterance of a ragged batch come out exactly as if it had been run alone (the
         reference's unmasked decoder lets the padding bleed into an utterance's last ~40 ms; bv2.h ``exact_lengths``),
         ``bert_index`` hands BERT features over at word level (see ``encode_durations``), ``ty_bucket`` runs phase B at T_y rounded up to
@@ -892,9 +905,7 @@ class SynthesizerTrn(nn.Module):
                                     noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, length_scale=length_scale,
                                     bert_index=bert_index, g=g, lean=True)
         if w_ceil is not None:
-            wc = w_ceil.to(dev, torch.float32).reshape(B, T).contiguous()
-            enc["w_ceil"] = wc
-            enc["y_lengths"] = torch.clamp_min(wc.sum(1), 1).long()
+            _substitute_durations(enc, w_ceil, w_ceil_items, B, T, dev)
         # the reference's one host sync (commons.py:120-122).  One utterance: no reduction kernel in front of the copy.
         Ty = int(enc["y_lengths"].item()) if B == 1 else int(enc["y_lengths"].max().item())
         if noise_z is not None:                        # None: decode() draws it (in place in the graph's buffer when replaying)
@@ -908,7 +919,7 @@ class SynthesizerTrn(nn.Module):
     def infer_stream(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_scale=0.667, length_scale=1,
                      noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None, *, g=None, y_lengths=None, noise_w=None, noise_z=None,
                      w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, chunk_frames=64, first_chunk_frames=None,
-                     as_pcm16=False, pcm_gain=32767.0, output_rate=None) -> SynthesisStream:
+                     as_pcm16=False, pcm_gain=32767.0, output_rate=None, w_ceil_items=None) -> SynthesisStream:
         """``infer`` with the audio handed out chunk by chunk (``SynthesisStream``): phase A, the host sync and the flow run here
         (``bv2_stream_begin``), the Generator runs window by window as the caller iterates — ``chunk_frames`` kept frames per chunk
         (``first_chunk_frames`` for the first one: a short first chunk is on the host sooner), each window carrying ``generator_halo``
@@ -944,9 +955,7 @@ class SynthesizerTrn(nn.Module):
                                     noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, length_scale=length_scale,
                                     bert_index=bert_index, g=g, lean=True)
         if w_ceil is not None:
-            wc = w_ceil.to(dev, torch.float32).reshape(B, T).contiguous()
-            enc["w_ceil"] = wc
-            enc["y_lengths"] = torch.clamp_min(wc.sum(1), 1).long()
+            _substitute_durations(enc, w_ceil, w_ceil_items, B, T, dev)
         yl_host = [int(v) for v in enc["y_lengths"].cpu()]           # the reference's one host sync; every length, for the consumer
         Ty = max(yl_host)
         Ci = hp.inter_channels
@@ -1074,6 +1083,25 @@ class SynthesizerTrn(nn.Module):
         return z
 
     @torch.no_grad()
+    def stage_flow_forward(self, z: torch.Tensor, y_lengths: Optional[torch.Tensor], g: torch.Tensor,
+                           y_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``flow(z, y_mask, g=g)`` in the direction of the reference's ``forward()`` (models.py:958) -> z_p: a posterior latent mapped
+        into the prior's space, where ``align_latent`` compares it with the text.  ``stage_flow`` undoes it.  Always fp32."""
+        if self._blob is None:
+            self.repack()
+        B, Ci, Ty = z.shape
+        z = self._f32(z)
+        z_p = torch.empty_like(z)
+        yl = None if y_lengths is None else self._i64(y_lengths)
+        ym = None if y_mask is None else self._f32(y_mask, B, Ty)
+        if (yl is None) == (ym is None):
+            raise ValueError("stage_flow_forward needs exactly one of y_lengths / y_mask")
+        g = self._f32(g, B, -1)
+        self._stage_call(self._lib.bv2_stage_flow_forward, B, Ty, B, Ty, _ptr(z), _ptr(yl), _ptr(ym), _ptr(g), _ptr(z_p),
+                         what="bv2_stage_flow_forward")
+        return z_p
+
+    @torch.no_grad()
     def stage_generator(self, z: torch.Tensor, y_lengths: Optional[torch.Tensor], g: torch.Tensor,
                         L_frames: Optional[int] = None):
         """``dec.run({"z_in","g"})`` -> o [B,1,L*hop].  With ``y_lengths`` the input is (z*y_mask)[:, :, :L] (models.py:1073);
@@ -1089,6 +1117,148 @@ class SynthesizerTrn(nn.Module):
         self._stage_call(self._lib.bv2_stage_generator, B, Ty, B, Ty, Lf, _ptr(z), _ptr(yl), _ptr(g), _ptr(o),
                          what="bv2_stage_generator")
         return o
+
+    # ------------------------------------------------------------------ posterior encoder (reference models.py:448-487)
+    POSTERIOR_HINT = ("no enc_q.* tensors: the posterior encoder is only in TRAINING checkpoints (G_*.pth as utils.save_checkpoint writes "
+                      "them); release checkpoints written by compress_model.py are stripped of enc_q")
+
+    @property
+    def has_posterior(self) -> bool:
+        return getattr(self, "_post_blob", None) is not None
+
+    def pack_posterior_host_blob(self, state_dict) -> torch.Tensor:
+        """The ``enc_q.*`` tensors of ``state_dict`` packed into the posterior encoder's own blob (host, uint8).  CPU-only."""
+        lib = self._ensure_handle()
+        keys = [k for k in state_dict if k.startswith("enc_q.")]
+        if not keys:
+            raise ValueError(self.POSTERIOR_HINT)
+        spec = int(self.hp.spec_channels)
+        n = lib.bv2_posterior_packed_bytes(self._handle, spec)
+        if n < 0:
+            self._check(-1, "bv2_posterior_packed_bytes")
+        for key in keys:
+            t = state_dict[key].detach().to("cpu", torch.float32).contiguous()
+            shape = (C.c_int64 * t.dim())(*t.shape)
+            rc = lib.bv2_posterior_load_tensor(self._handle, key.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), L.F32)
+            if rc < 0:
+                self._check(rc, "bv2_posterior_load_tensor(" + key + ")")
+        blob = torch.empty(n, dtype=torch.uint8)
+        self._check(lib.bv2_posterior_pack(self._handle, spec, C.c_void_p(blob.data_ptr()), n), "bv2_posterior_pack")
+        return blob
+
+    def load_posterior(self, path_or_state_dict) -> None:
+        """Load the posterior encoder ``enc_q`` from a training checkpoint (a path to a ``G_*.pth``, its dict, or a plain state dict): the
+        ``enc_q.*`` keys are packed into a blob of their own and attached; the inference blob is untouched.  Raises ``ValueError`` with a
+        hint at ``compress_model.py`` when the checkpoint has none."""
+        sd = path_or_state_dict
+        if isinstance(sd, (str, bytes)) or hasattr(sd, "__fspath__"):
+            sd = torch.load(sd, map_location="cpu")
+        if isinstance(sd, dict) and "model" in sd and isinstance(sd["model"], dict):
+            sd = sd["model"]
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+        blob = self.pack_posterior_host_blob(sd)
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("load_posterior needs the model on a GPU (model.to('cuda')); there is no CPU fallback")
+        with torch.cuda.device(dev):
+            dblob = blob.to(dev)
+            self._check(self._lib.bv2_posterior_attach(self._handle, int(self.hp.spec_channels), C.c_void_p(dblob.data_ptr()), dblob.numel()),
+                        "bv2_posterior_attach")
+        self._post_blob = dblob
+
+    def _need_posterior(self, what: str) -> None:
+        if not self.has_posterior:
+            raise RuntimeError(f"{what}: the posterior encoder is not loaded (load_posterior(checkpoint)); " + self.POSTERIOR_HINT)
+        if self._post_blob.device != self.device:
+            raise RuntimeError(f"{what}: the model moved to another device after load_posterior(); load it again")
+
+    @torch.no_grad()
+    def posterior_encode(self, y, y_lengths, sid=None, g=None, noise_q=None, noise_scale_q=1.0) -> Dict[str, torch.Tensor]:
+        """``enc_q(y, y_lengths, g=g)`` (reference models.py:957): ``y`` [B, spec_channels, Ty] the recording's linear spectrogram
+        (``audio.spectrogram(wav, ..., net_g.stft_params)``), ``y_lengths`` [B]; the speaker is ``g`` [B, gin] or ``emb_g(sid)``.
+        ``noise_q`` [B, inter, Ty] is the N(0, 1) draw of models.py:486, made by the caller like ``noise_w`` / ``noise_z``; ``None`` gives the
+        deterministic ``z = m_q * mask``.  Returns ``z``, ``m_q``, ``logs_q`` [B, inter, Ty], ``y_mask`` [B, 1, Ty] and ``g``."""
+        self._need_posterior("posterior_encode")
+        if self._blob is None:
+            self.repack()
+        dev, hp = self.device, self.hp
+        y = self._f32(y)
+        B, S, Ty = y.shape
+        if S != hp.spec_channels:
+            raise ValueError(f"y must be [B, {hp.spec_channels}, Ty], got {tuple(y.shape)}")
+        if g is None:
+            if sid is None:
+                raise ValueError("posterior_encode needs sid or g")
+            g = self.stage_emb_g(sid)
+        g = self._speaker_vector(g, B)
+        yl = self._i64(y_lengths).reshape(B)
+        nq = None
+        if noise_q is not None:
+            nq = self._f32(noise_q)
+            if tuple(nq.shape) != (B, hp.inter_channels, Ty):
+                raise ValueError(f"noise_q must be [B, {hp.inter_channels}, Ty]")
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        out = dict(z=e(B, hp.inter_channels, Ty), m_q=e(B, hp.inter_channels, Ty), logs_q=e(B, hp.inter_channels, Ty), y_mask=e(B, 1, Ty))
+        n = self._lib.bv2_posterior_workspace_bytes(self._handle, B, Ty)
+        ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self._check(self._lib.bv2_posterior_encode(self._handle, stream, B, Ty, _ptr(y), _ptr(yl), _ptr(g), _ptr(nq), float(noise_scale_q),
+                                                       _ptr(out["z"]), _ptr(out["m_q"]), _ptr(out["logs_q"]), _ptr(out["y_mask"]),
+                                                       C.c_void_p(ws.data_ptr()), ws.numel()), "bv2_posterior_encode")
+        out["g"] = g
+        return out
+
+    @torch.no_grad()
+    def align(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, y, y_lengths, g=None, noise_q=None,
+              want_attn: bool = False, one_call: bool = False) -> Dict:
+        """Text + recording -> frames per symbol, the reference's own aligner (models.py:950-991): phase A for the text's prior,
+        ``posterior_encode`` and the forward flow for the recording's latent, ``neg_cent`` and ``maximum_path``.  ``y`` [B, spec_channels,
+        Ty] may come straight from ``audio.spectrogram(wav, ..., net_g.stft_params)``.  ``y_lengths`` on the host (list, numpy, CPU
+        tensor) are checked against ``x_lengths``.  Returns ``durations`` [B, T] int64, ``y_lengths``, ``score``, the encode dict ``enc``
+        (``with_durations(out["enc"], out["durations"])`` is ready for ``decode``), the posterior dict ``posterior`` and, with
+        ``want_attn``, ``attn`` and ``neg_cent``.  ``one_call``: everything behind phase A as ONE library call (``bv2_align``: same launches, one
+        workspace, the intermediates stay inside it — ``posterior``, ``z_p`` and ``neg_cent`` are then not returned)."""
+        self._need_posterior("align")
+        B, T = x.shape
+        xl_host = None if (isinstance(x_lengths, torch.Tensor) and x_lengths.is_cuda) else [int(v) for v in x_lengths]
+        _align.check_lengths(xl_host, y_lengths, T, int(y.shape[2]))
+        if g is None and self.hp.n_speakers == 0:
+            g = self.reference_embedding(y, torch.as_tensor(y_lengths))
+        enc = self.encode_durations(x, torch.as_tensor(x_lengths), sid, tone, language, bert, ja_bert, en_bert, draw_noise_w(B, T, None),
+                                    sdp_ratio=0.0, g=g, lean=True)          # the prior does not depend on the duration predictors
+        if one_call:
+            dev = self.device
+            yd, yl, xl = self._f32(y), self._i64(torch.as_tensor(y_lengths)).reshape(B), self._i64(torch.as_tensor(x_lengths)).reshape(B)
+            Ty = int(yd.shape[2])
+            nq = None if noise_q is None else self._f32(noise_q)
+            out = dict(durations=torch.empty(B, T, dtype=torch.int64, device=dev), score=torch.empty(B, dtype=torch.float32, device=dev),
+                       attn=torch.empty(B, 1, Ty, T, dtype=torch.float32, device=dev) if want_attn else None, y_lengths=yl, enc=enc)
+            n = self._lib.bv2_align_workspace_bytes(self._handle, B, T, Ty)
+            ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                self._check(self._lib.bv2_align(self._handle, C.c_void_p(torch.cuda.current_stream().cuda_stream), B, T, Ty, _ptr(enc["m_p"]),
+                                                _ptr(enc["logs_p"]), _ptr(xl), _ptr(yd), _ptr(yl), _ptr(enc["g"]), _ptr(nq),
+                                                _ptr(out["durations"]), _ptr(out["attn"]), _ptr(out["score"]), C.c_void_p(ws.data_ptr()),
+                                                ws.numel()), "bv2_align")
+            return out
+        post = self.posterior_encode(y, torch.as_tensor(y_lengths), g=enc["g"], noise_q=noise_q)
+        z_p = self.stage_flow_forward(post["z"], torch.as_tensor(y_lengths), enc["g"])
+        out = _align.align_latent(enc, z_p, y_lengths, want_attn=want_attn, x_lengths=x_lengths)
+        out["enc"], out["posterior"], out["z_p"] = enc, post, z_p
+        return out
+
+    # ------------------------------------------------------------------ forced alignment (reference models.py:960-991)
+    @torch.no_grad()
+    def align_latent(self, enc: Dict[str, torch.Tensor], z_p: torch.Tensor, y_lengths, want_attn: bool = False, x_lengths=None) -> Dict:
+        """The reference's aligner on a recording's latent: ``enc`` is a phase-A encode dict of the text (``encode_durations``), ``z_p``
+        [B, inter, Ty] the recording's latent in the prior's space (``flow(enc_q(y))`` of a training checkpoint), ``y_lengths`` its frames
+        per item.  Returns ``durations`` [B, T] int64 (frames per symbol), ``y_lengths``, ``score`` and, with ``want_attn``, ``attn``
+        [B, 1, Ty, T] and ``neg_cent`` [B, Ty, T] (``align.neg_cent`` + ``align.maximum_path``: two launches, kernels/align.hip).
+        ``with_durations(enc, durations)`` is then ready for ``decode``: the text spoken with the recording's timing."""
+        if tuple(z_p.shape[:2]) != (enc["m_p"].shape[0], self.hp.inter_channels):
+            raise ValueError(f"z_p must be [B, {self.hp.inter_channels}, Ty] with the encode dict's B")
+        return _align.align_latent(enc, z_p.to(self.device), y_lengths, want_attn=want_attn, x_lengths=x_lengths)
 
     def set_option(self, key: str, value: int) -> None:
         """Kernel-selection switches of ``bv2_set_option`` ("fused_resblock", "fused_dds", "lean_durations"); tests and A/B runs."""

@@ -188,3 +188,33 @@ def n_params(hp: H.HParams) -> int:
             m *= x
         n += m
     return n
+
+
+POSTERIOR_LAYERS = 16        # PosteriorEncoder's WN depth (reference models.py:905-913: kernel 5, dilation rate 1, 16 layers)
+POSTERIOR_KERNEL = 5
+
+
+def posterior_param_shapes(hp) -> "OrderedDict[str, tuple]":
+    """The ``enc_q.*`` tensors of a training checkpoint (PosteriorEncoder, reference models.py:448-487) in the weight-normed form
+    ``utils.save_checkpoint`` writes.  They are NOT part of ``param_shapes`` (the inference schema): they live in a blob of their own
+    (``SynthesizerTrn.load_posterior``)."""
+    from collections import OrderedDict
+    H, C, G, S, nl, k = hp.hidden_channels, hp.inter_channels, hp.gin_channels, hp.spec_channels, POSTERIOR_LAYERS, POSTERIOR_KERNEL
+    d = OrderedDict()
+    d["enc_q.pre.weight"] = (H, S, 1)
+    d["enc_q.pre.bias"] = (H,)
+    d["enc_q.enc.cond_layer.bias"] = (2 * H * nl,)
+    d["enc_q.enc.cond_layer.weight_g"] = (2 * H * nl, 1, 1)
+    d["enc_q.enc.cond_layer.weight_v"] = (2 * H * nl, G, 1)
+    for i in range(nl):
+        d[f"enc_q.enc.in_layers.{i}.bias"] = (2 * H,)
+        d[f"enc_q.enc.in_layers.{i}.weight_g"] = (2 * H, 1, 1)
+        d[f"enc_q.enc.in_layers.{i}.weight_v"] = (2 * H, H, k)
+    for i in range(nl):
+        rows = 2 * H if i < nl - 1 else H
+        d[f"enc_q.enc.res_skip_layers.{i}.bias"] = (rows,)
+        d[f"enc_q.enc.res_skip_layers.{i}.weight_g"] = (rows, 1, 1)
+        d[f"enc_q.enc.res_skip_layers.{i}.weight_v"] = (rows, H, 1)
+    d["enc_q.proj.weight"] = (2 * C, H, 1)
+    d["enc_q.proj.bias"] = (2 * C,)
+    return d

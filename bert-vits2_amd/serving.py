@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -27,7 +27,11 @@ class Utterance:
     synthesis controls are the request's own sliders (hiyoriUI ``/voice``: sdp_ratio, noise, noisew, length); ``None`` takes the value
     ``synthesize`` was called with.  The voice is ``sid`` (a row of the speaker table) unless the utterance carries ``g`` (a speaker vector
     ``[gin]``: a cached ``reference_embedding``, a blend of table rows) or ``ref_spec`` (a reference spectrogram ``[spec_channels, L]`` for a
-    model built with ``n_speakers=0``; utterances that share one tensor object share one encoding)."""
+    model built with ``n_speakers=0``; utterances that share one tensor object share one encoding).  ``durations`` (frames per symbol, one
+    per phone: what ``align.maximum_path`` returns for a recording of the same text) replaces the predicted durations after phase A — the
+    utterance is spoken with that timing and comes back with exactly ``sum(durations) * hop`` samples; ``sdp_ratio``, ``noise_scale_w``
+    and ``length_scale`` then change nothing for it.  Graph replay (``enable_graphs``) supports it: the substitution happens between the
+    two captured phases."""
     phones: torch.Tensor
     tones: torch.Tensor
     lang_ids: torch.Tensor
@@ -41,8 +45,11 @@ class Utterance:
     length_scale: Optional[float] = None
     g: Optional[torch.Tensor] = None
     ref_spec: Optional[torch.Tensor] = None
+    # np.ndarray or Tensor [T], whole non-negative numbers.  An init-only argument that __post_init__ validates and stores as an attribute:
+    # the dataclass FIELDS still end with g, ref_spec (callers that build an Utterance positionally or walk its fields see what they saw)
+    durations: InitVar[Optional[object]] = None
 
-    def __post_init__(self):
+    def __post_init__(self, durations=None):
         if self.g is not None and (not isinstance(self.g, torch.Tensor) or self.g.dim() != 1 or self.g.shape[0] < 1):
             raise ValueError("g must be a 1-D tensor [gin]")
         if self.ref_spec is not None and (not isinstance(self.ref_spec, torch.Tensor) or self.ref_spec.dim() != 2
@@ -56,6 +63,17 @@ class Utterance:
         for f in (self.bert, self.ja_bert, self.en_bert):
             if tuple(f.shape) != (H.BERT_DIM, T):                     # the reference asserts the same (infer.py:124)
                 raise ValueError(f"bert features must be [{H.BERT_DIM}, {T}], got {tuple(f.shape)}")
+        self.durations = None
+        if durations is not None:
+            d = torch.as_tensor(durations).detach().cpu()
+            if d.dim() != 1 or d.shape[0] != T:
+                raise ValueError(f"durations must be 1-D with one entry per phone ({T}), got {tuple(d.shape)}")
+            d64 = d.to(torch.float64)
+            if not bool(torch.isfinite(d64).all()) or bool((d64 < 0).any()) or bool((d64 != d64.round()).any()):
+                raise ValueError("durations must be whole, non-negative frame counts")
+            if float(d64.sum()) < 1:
+                raise ValueError("durations must sum to at least one frame")
+            self.durations = d64.to(torch.float32)          # [T] on the host, as phase B reads w_ceil
 
     @property
     def length(self) -> int:
@@ -308,6 +326,15 @@ def _bucket_inputs(model, utts, idx, dev, noise, gvec):
             nw[r, :, :noise[i][0].shape[1]] = noise[i][0]
             nz[r, :, :noise[i][1].shape[1]] = noise[i][1]
         kw.update(noise_w=nw.to(dev), noise_z=nz.to(dev))
+    if any(utts[i].durations is not None for i in idx):
+        # given durations take the place of the predicted ones after phase A; a bucket may mix both kinds of utterance
+        wc = torch.zeros(len(idx), batch["x"].shape[1])
+        for r, i in enumerate(idx):
+            if utts[i].durations is not None:
+                wc[r, :utts[i].length] = utts[i].durations
+        kw["w_ceil"] = wc.to(dev)
+        if any(utts[i].durations is None for i in idx):
+            kw["w_ceil_items"] = torch.tensor([utts[i].durations is not None for i in idx])
     return batch, kw
 
 
@@ -371,3 +398,53 @@ def synthesize_stream(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_
             waiting = (start, n, host, ev)
         if waiting is not None:
             yield from pieces(*waiting)
+
+
+@torch.no_grad()
+def align(model, utts: Sequence[Utterance], specs: Optional[Sequence[torch.Tensor]] = None, *,
+          latents: Optional[Sequence[torch.Tensor]] = None, max_batch: int = 32, max_pad_ratio: float = 1.25) -> List[np.ndarray]:
+    """Frames per phone of each utterance's recording.  ``specs[i]`` is the recording's linear spectrogram ``[spec_channels, Ty_i]``
+    (``reference_spectrogram(model, wav)``); it goes through the posterior encoder (``model.load_posterior`` first; deterministic,
+    ``z = m_q``) and the forward flow.  Alternatively ``latents[i]`` ``[inter, Ty_i]`` is the recording's latent already in the prior's
+    space.  Utterances are bucketed by length like ``synthesize``; a bucket is ONE ragged batch through phase A (the text's prior), the
+    recording's side, ``align.neg_cent`` and ``align.maximum_path``.  Returns one int64 array ``[T_i]`` per utterance, in input order,
+    ready for ``Utterance(durations=...)``."""
+    from . import align as _align
+    from . import models as _models
+    if model.device.type != "cuda":
+        raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
+    if (specs is None) == (latents is None):
+        raise ValueError("serving.align takes specs or latents=, exactly one of them")
+    from_spec = specs is not None
+    if from_spec:
+        model._need_posterior("serving.align")
+    latents = specs if from_spec else latents
+    if len(latents) != len(utts):
+        raise ValueError("one recording per utterance")
+    dev, Ci = model.device, (model.hp.spec_channels if from_spec else model.hp.inter_channels)
+    for i, (u, z) in enumerate(zip(utts, latents)):
+        if z.dim() != 2 or z.shape[0] != Ci:
+            raise ValueError(f"utterance {i}: the {'spectrogram' if from_spec else 'latent'} must be [{Ci}, Ty], got {tuple(z.shape)}")
+        if u.length > z.shape[1]:
+            raise ValueError(f"utterance {i}: {u.length} phones cannot be aligned to {z.shape[1]} frames")
+    gvec = speaker_vectors(model, utts)
+    results: List[Optional[np.ndarray]] = [None] * len(utts)
+    for idx in plan_batches([u.length for u in utts], max_batch, max_pad_ratio):
+        batch, kw = _bucket_inputs(model, utts, idx, dev, None, gvec)
+        B, T = batch["x"].shape
+        # the prior does not depend on the duration predictors: sdp_ratio 0 runs the deterministic one only, and its noise is not read
+        enc = model.encode_durations(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"], batch["bert"],
+                                     batch["ja_bert"], batch["en_bert"], _models.draw_noise_w(B, T, None), sdp_ratio=0.0, lean=True,
+                                     g=kw.get("g"))
+        y_len = [int(latents[i].shape[1]) for i in idx]
+        z_p = torch.zeros(B, Ci, max(y_len), dtype=torch.float32, device=dev)
+        for r, i in enumerate(idx):
+            z_p[r, :, :y_len[r]] = latents[i].to(dev, torch.float32)
+        if from_spec:
+            yl = torch.tensor(y_len, dtype=torch.int64)
+            z_p = model.stage_flow_forward(model.posterior_encode(z_p, yl, g=enc["g"])["z"], yl, enc["g"])
+        out = _align.align_latent(enc, z_p, y_len, x_lengths=[utts[i].length for i in idx])
+        dur = out["durations"].cpu().numpy()
+        for r, i in enumerate(idx):
+            results[i] = dur[r, :utts[i].length].copy()
+    return results

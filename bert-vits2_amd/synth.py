@@ -231,3 +231,25 @@ def synthetic_reference_wav(n_samples: int, index: int = 0, sampling_rate: int =
     x += 0.01 * torch.randn(n_samples, generator=g, dtype=torch.float64)
     x *= 0.8 / x.abs().max().clamp_min(1e-9)
     return torch.round(x * 32767.0).to(torch.int16)
+
+
+def synthetic_posterior_state_dict(hp: H.HParams, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded synthetic ``enc_q.*`` tensors (``schema.posterior_param_shapes``).  A function of its own with generators of its own: the
+    stream of ``synthetic_state_dict`` (and every hash pinned on it) does not move."""
+    from .schema import posterior_param_shapes
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for key, shape in posterior_param_shapes(hp).items():
+        leaf = key.rsplit(".", 1)[-1]
+        if leaf == "bias":
+            t = _normal(key, seed, shape, 0.02)
+        elif leaf == "weight_g":
+            t = torch.full(shape, 0.7) * (1.0 + 0.05 * torch.randn(shape, generator=_gen(key, seed)))
+        elif leaf == "weight_v":
+            t = _normal(key, seed, shape, 1.0)
+        else:
+            t = _normal(key, seed, shape, 1.0 / math.sqrt(shape[1] * shape[2]))
+        sd[key] = t.contiguous()
+    C = hp.inter_channels
+    sd["enc_q.proj.weight"][C:] *= 0.3           # posterior log-std rows: keep exp(logs_q) moderate, as trained models do
+    sd["enc_q.proj.bias"][C:] -= 0.5
+    return sd

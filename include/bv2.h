@@ -32,6 +32,7 @@ extern "C" {
                                pack-layout version in the blob header */
 #define BV2_PACK_LAYOUT 16   /* bumped whenever bv2_model.cpp changes the order / format of anything inside the packed blob:
                                a blob cached on disk by an older packer is rejected by bv2_attach_weights */
+#define BV2_POSTERIOR_LAYOUT 1   /* the same for the posterior encoder's own blob (bv2_posterior_pack) */
 #define BV2_MAX_UPS 8
 #define BV2_MAX_RESBLOCK_KERNELS 4
 #define BV2_MAX_RESBLOCK_DILATIONS 4
@@ -229,6 +230,13 @@ int bv2_stage_dp(bv2_handle* h, bv2_stream stream, int B, int T, const float* x,
  * modified; z receives the result. */
 int bv2_stage_flow(bv2_handle* h, bv2_stream stream, int B, int Ty, const float* z_p, const int64_t* y_lengths,
                    const float* y_mask, const float* g, float* z, void* workspace, int64_t workspace_bytes);
+/* The same flow in its FORWARD direction, z -> z_p: flow(z, y_mask, g=g) as SynthesizerTrn.forward() calls it (models.py:958; no ONNX graph
+ * has it).  It maps a posterior latent into the prior's space, which is where the aligner below compares a recording with its text.  Both
+ * flow variants; the couplings run first to last with x1 = (x1 + post(h)) * mask and the channel Flips where the reference has them, so
+ * bv2_stage_flow(bv2_stage_flow_forward(z)) returns z up to fp32 round-off on the unmasked frames.  Always fp32: bv2_set_flow_dtype does not
+ * apply, and the fused coupling boundary ("fused_boundary") is not used in this direction.  Arguments as bv2_stage_flow; z is not modified. */
+int bv2_stage_flow_forward(bv2_handle* h, bv2_stream stream, int B, int Ty, const float* z, const int64_t* y_lengths,
+                           const float* y_mask, const float* g, float* z_p, void* workspace, int64_t workspace_bytes);
 /* dec.run({"z_in","g"}) -> o: Generator.forward models.py:538-557 on z_in[:, :, :L] (z_in has row stride Ty); with y_lengths
  * non-NULL the input is (z*y_mask)[:, :, :L] as at models.py:1073, with NULL it is taken as it is (the exported graph).
  * o is [B,1,L*prod(rates)]. */
@@ -450,6 +458,74 @@ int bv2_resample_taps_f64(const bv2_resample_config* cfg, double* out);
 int bv2_resample(bv2_stream stream, const bv2_resample_config* cfg, const float* taps, const void* src, int64_t src_bstride,
                  int64_t src_start, int64_t src_n, const int64_t* src_lengths, int32_t B, int64_t n0, int64_t n1, float* dst,
                  int64_t dst_bstride, int64_t* dst_lengths_out);
+
+/* ---- forced alignment: the reference's own aligner (handle-free; kernels/align.hip) --------------------------------------
+ * SynthesizerTrn.forward() aligns a recording to its text with two steps that need no weights (models.py:960-991): the negative
+ * cross-entropy between every latent frame z_p[:, y] of the recording and every symbol's prior N(m_p[:, x], exp(logs_p[:, x])), and
+ * monotonic_align.maximum_path over that matrix.  The result — frames per symbol — is what bv2_decode_in.w_ceil takes in place of the
+ * predicted durations (timing transfer), and a symbol-level time stamp for the recording.  m_p / logs_p / x_lengths come from phase A
+ * (bv2_encode_out); z_p is the recording's latent in the prior's space: bv2_stage_flow_forward(bv2_posterior_encode(spectrogram)), both
+ * above, or any latent the caller brings.
+ *
+ * bv2_neg_cent: neg_cent[b, y, x] = sum_d [ -1/2 log 2pi - logs_p[d, x] - 1/2 (z_p[d, y] - m_p[d, x])^2 exp(-2 logs_p[d, x]) ], formed
+ * as the reference forms it (one matrix product over K = 2 inter with A rows [-1/2 z_p^2, z_p] and B columns [exp(-2 logs), m exp(-2 logs)]
+ * plus two column constants, added in the reference's order) on v_mfma_f32_16x16x4_f32, exact fp32.  z_p [B, inter, Ty], m_p / logs_p
+ * [B, inter, T], neg_cent [B, Ty, T], all DEVICE fp32 contiguous; x_lengths / y_lengths [B] int64 DEVICE or NULL (= T / Ty).  Cells outside
+ * y < y_lengths[b], x < x_lengths[b] are written as 0 and their inputs are not read.  inter: a multiple of 4, at most 256.  The
+ * noise-scaled-MAS perturbation (use_noise_scaled_mas, models.py:976-982; training only) is not implemented.
+ *
+ * bv2_maximum_path: monotonic_align/core.py maximum_path_jit on the device, one launch, one workgroup per item: the band
+ * max(0, t_x + y - t_y) <= x < min(t_x, y + 1), the -1e9 stand-ins (0 for the cell (0, 0)), plain fp32 add and max — bit for bit the fp32
+ * dynamic programme, whatever the shape — and the reference's tie rule on the way back (a step to x - 1 only when x == y or the left
+ * predecessor is STRICTLY greater).  neg_cent is only read: instead of the cumulative matrix the forward pass records one decision bit
+ * per cell in the workspace (bv2_maximum_path_workspace_bytes: Ty * ceil(T / 64) * 8 bytes per item), and the walk back reads those from
+ * on-chip memory.  durations [B, T] int64 = frames per symbol (0 at and past x_lengths[b]); attn [B, 1, Ty, T] fp32 one-hot path or NULL;
+ * score [B] fp32 = the path's cumulative value or NULL.  T <= 4096.  Precondition: 1 <= x_lengths[b] <= y_lengths[b] (the reference's
+ * band is empty otherwise; the values live on the device, so the CALLER checks — out-of-range lengths are clamped to [0, T] / [0, Ty] and
+ * cannot make the kernel leave its arrays, but the durations of such an item mean nothing).
+ * Both calls: asynchronous on `stream`, no allocation, no host sync, graph-capturable; a failed call returns non-zero (the size query a
+ * negative value) with its message in bv2_last_error(NULL), every argument checked before anything touches the device. */
+int bv2_neg_cent(bv2_stream stream, int32_t B, int32_t inter, int32_t T, int32_t Ty, const float* z_p, const float* m_p,
+                 const float* logs_p, const int64_t* x_lengths, const int64_t* y_lengths, float* neg_cent);
+/* bv2_align: the whole aligner in one call — phase A's m_p / logs_p [B, inter, T] and x_lengths (bv2_encode_out; x_lengths as given to
+ * phase A) plus the recording's spectrogram y [B, spec_channels, Ty] and y_lengths -> durations [B, T] (attn, score optional as above):
+ * bv2_posterior_encode (noise_q NULL = deterministic), bv2_stage_flow_forward, bv2_neg_cent, bv2_maximum_path on one workspace
+ * (bv2_align_workspace_bytes).  Needs both blobs attached.  The same preconditions as the four calls. */
+int64_t bv2_align_workspace_bytes(const bv2_handle* h, int B, int T, int Ty);
+int bv2_align(bv2_handle* h, bv2_stream stream, int B, int T, int Ty, const float* m_p, const float* logs_p, const int64_t* x_lengths,
+              const float* y, const int64_t* y_lengths, const float* g, const float* noise_q, int64_t* durations, float* attn,
+              float* score, void* workspace, int64_t workspace_bytes);
+int64_t bv2_maximum_path_workspace_bytes(int32_t B, int32_t T, int32_t Ty);
+int bv2_maximum_path(bv2_stream stream, int32_t B, int32_t T, int32_t Ty, const float* neg_cent, const int64_t* x_lengths,
+                     const int64_t* y_lengths, int64_t* durations, float* attn, float* score, void* workspace, int64_t workspace_bytes);
+
+/* ---- the posterior encoder enc_q (PosteriorEncoder, models.py:448-487): a recording's spectrogram -> its posterior latent z ----------
+ * enc_q is not part of inference, release checkpoints are stripped of it (compress_model.py), and the packed inference blob is pinned by
+ * size and hash — so its weights live in a SECOND, optional blob of their own: pre (Conv1d spec_channels -> hidden, k = 1), enc (WN: hidden,
+ * k = 5, dilation 1, 16 layers, cond_layer from gin_channels; weight_g / weight_v pairs or folded weights, as everywhere) and proj
+ * (hidden -> 2 inter).  bv2_load_tensor keeps ignoring enc_q.* (returns 1); bv2_posterior_load_tensor takes exactly those keys (others: 1).
+ * spec_channels is given where the blob is sized, packed and attached — 1025, 513 or 80, also for a model with a speaker table, whose
+ * bv2_config does not carry it; bv2_create's validation is untouched.  Pack on the host, upload, attach; bv2_posterior_detach forgets the
+ * blob.  Nothing here changes bv2_packed_bytes, the inference blob or its header.
+ *
+ * bv2_posterior_encode: y [B, spec_channels, Ty] fp32 dense (the linear spectrogram, e.g. bv2_spectrogram's output made contiguous),
+ * y_lengths [B] int64, g [B, gin] ->
+ *   x = pre(y) * mask;  x = WN(x, mask, g);  stats = proj(x) * mask;  m_q, logs_q = split(stats);
+ *   z = (m_q + noise_q * exp(logs_q) * noise_scale_q) * mask                                                    (models.py:479-487)
+ * noise_q [B, inter, Ty] is the caller's N(0, 1) draw (the RNG contract of noise_w / noise_z; the reference scales by 1); NULL gives the
+ * deterministic z = m_q * mask.  z [B, inter, Ty] is required; m_q, logs_q [B, inter, Ty] and y_mask [B, Ty] may be NULL.  Exact fp32 on
+ * the launch forms of the residual flow's WN (in_layer + gate, res_skip) and conv1d_mfma; an odd spec_channels rides on the padded K range
+ * of pre (rows >= spec_channels read as zero).  37 launches, asynchronous on `stream`, no allocation; not meant for graph capture.  Fails
+ * with -8 and a message naming compress_model.py while no posterior blob is attached.  Workspace: bv2_posterior_workspace_bytes(h, B, Ty). */
+int64_t bv2_posterior_packed_bytes(bv2_handle* h, int spec_channels);
+int bv2_posterior_load_tensor(bv2_handle* h, const char* ref_key, const void* host_ptr, const int64_t* shape, int ndim, int dtype);
+int bv2_posterior_pack(bv2_handle* h, int spec_channels, void* host_blob, int64_t bytes);
+int bv2_posterior_attach(bv2_handle* h, int spec_channels, const void* dev_blob, int64_t bytes);
+int bv2_posterior_detach(bv2_handle* h);
+int64_t bv2_posterior_workspace_bytes(const bv2_handle* h, int B, int Ty);
+int bv2_posterior_encode(bv2_handle* h, bv2_stream stream, int B, int Ty, const float* y, const int64_t* y_lengths, const float* g,
+                         const float* noise_q, float noise_scale_q, float* z, float* m_q, float* logs_q, float* y_mask,
+                         void* workspace, int64_t workspace_bytes);
 
 /* ---- hipGraph capture (BASELINE config 3: "hipGraph-captured decode") ----------------------------------------- */
 /* Both phases are fixed launch sequences on the caller's stream with no allocation, host sync or device->host copy,
