@@ -380,7 +380,7 @@ int bv2_decode_ex(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, con
   if (int rc = ready(h, ws)) return rc;
   BV2_TRY
   if (!in || !out || in->B < 1 || in->T < 1 || in->Ty < 1) { h->err = "bv2_decode: bad argument"; return -1; }
-  if (!in->m_p || !in->logs_p || !in->x_mask || !in->w_ceil || !in->y_lengths || !in->g || !in->noise_z || !out->o) {
+  if (!in->m_p || !in->logs_p || !in->x_mask || !in->w_ceil || !in->y_lengths || !in->g || (!in->noise_z && !h->seeds) || !out->o) {
     h->err = "bv2_decode: null tensor pointer"; return -1;
   }
   return run_decode(h, static_cast<hipStream_t>(stream), *in, *out, ws, wsb, ic);
@@ -522,7 +522,7 @@ int bv2_stream_begin(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, 
   BV2_TRY
   if (int rc = check_controls(h, ic, "bv2_stream_begin")) return rc;
   if (!in || !out || in->B < 1 || in->T < 1 || in->Ty < 1) { h->err = "bv2_stream_begin: bad argument"; return -1; }
-  if (!in->m_p || !in->logs_p || !in->x_mask || !in->w_ceil || !in->y_lengths || !in->g || !in->noise_z) {
+  if (!in->m_p || !in->logs_p || !in->x_mask || !in->w_ceil || !in->y_lengths || !in->g || (!in->noise_z && !h->seeds)) {
     h->err = "bv2_stream_begin: null tensor pointer"; return -1;
   }
   if (!h->taps.empty()) { h->err = "bv2_stream_begin: taps are not supported during a stream (bv2_set_tap(h, NULL, ...) clears them)"; return -1; }
@@ -891,6 +891,33 @@ PlanAlign plan_align(Arena& A, const Model& m, int B, int T, int Ty) {
   return p;
 }
 }  // namespace
+
+// ---- per-utterance noise seeds (kernels/rng.h) ---------------------------------------------------------------------
+int bv2_set_noise_seeds(bv2_handle* h, const int64_t* seeds_dev, int32_t B) {
+  if (!h) return -1;
+  BV2_TRY
+  if (!seeds_dev) { h->seeds = nullptr; h->seeds_B = 0; return 0; }
+  if (B < 1) { h->err = "bv2_set_noise_seeds: B must be at least 1 (NULL seeds switch the seeded noise off)"; return -1; }
+  h->seeds = seeds_dev; h->seeds_B = B;
+  return 0;
+  BV2_CATCH(h)
+}
+
+int bv2_seeded_noise(bv2_stream stream, const int64_t* seeds_dev, int32_t B, int32_t which, int32_t rows, int32_t T,
+                     const int64_t* lengths_dev, float* out, int64_t bstride, int64_t rstride, int64_t tstride) {
+  auto bad = [&](const char* m) { g_create_err = std::string("bv2_seeded_noise: ") + m; return -1; };
+  try {
+    if (!seeds_dev) return bad("seeds is null");
+    if (!out) return bad("out is null");
+    if (B < 1 || B > 65535) return bad("need 1 <= B <= 65535");
+    if (which < 0 || which > 2) return bad("which is 0 (noise_w), 1 (noise_z) or 2 (noise_q)");
+    if (rows < 1 || rows > 65535) return bad("need 1 <= rows <= 65535");
+    if (T < 1) return bad("T must be at least 1");
+    if (launch_seeded_noise(static_cast<hipStream_t>(stream), seeds_dev, B, which, rows, T, lengths_dev, out, bstride, rstride, tstride))
+      return bad("kernel launch failed");
+    return 0;
+  } catch (...) { return -100; }
+}
 
 int64_t bv2_align_workspace_bytes(const bv2_handle* h, int B, int T, int Ty) {
   if (!h || B < 1 || T < 1 || T > MP_MAX_T || Ty < 1) return -1;

@@ -495,7 +495,7 @@ int64_t workspace_bytes(const Model& m, int B, int T, int Ty) {
 // the front launch: emb_g lookup (or a given g), the speaker-conditioning GEMVs, x_mask and the scaled SDP noise
 static void run_front(Ctx& c, const int64_t* sid, const float* g_in, float* g_out, const GemvW* const* gw, float* const* go,
                       int n, int out_stride, const int64_t* x_lengths, float* x_mask, int B, int T, const float* noise,
-                      float* z, float noise_scale, const float* noise_scale_b = nullptr) {
+                      float* z, float noise_scale, const float* noise_scale_b = nullptr, const int64_t* seeds = nullptr) {
   const bv2_config& cf = c.m.cfg;
   FrontArgs F;
   std::memset(&F, 0, sizeof(F));
@@ -508,7 +508,7 @@ static void run_front(Ctx& c, const int64_t* sid, const float* g_in, float* g_ou
   F.g_out = g_out;                                 // the looked-up row, or a copy of the given g
   F.lengths = x_lengths; F.mask = x_mask; F.T = T;
   F.noise = noise; F.z = z; F.noise_scale = noise_scale; F.nz = z ? (int64_t)B * 2 * T : 0;
-  F.noise_scale_b = noise_scale_b;
+  F.noise_scale_b = noise_scale_b; F.seeds = seeds;
   c.chk(launch_front(c.s, F), "front");
 }
 
@@ -652,6 +652,21 @@ static void run_durations(Ctx& c, const PlanA& P, const float* logw_dp, const fl
   c.chk(launch_durations(c.s, d), "durations");
 }
 
+int check_seeds(bv2_handle* h, int B, const void* noise, const char* what, const char* noise_name) {
+  if (!h->seeds) return 0;
+  if (B != h->seeds_B) {
+    h->err = std::string(what) + ": B = " + std::to_string(B) + " but bv2_set_noise_seeds was given " + std::to_string(h->seeds_B) +
+             " seeds (one per batch item; bv2_set_noise_seeds(h, NULL, 0) switches them off)";
+    return -1;
+  }
+  if (noise) {
+    h->err = std::string(what) + ": " + noise_name + " is given while noise seeds are active (bv2_set_noise_seeds): pass NULL, or switch "
+             "the seeds off";
+    return -1;
+  }
+  return 0;
+}
+
 // ===============================================================================================================
 // phase A: emb_g, enc_p, sdp, dp, durations
 int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_encode_out& out, void* ws, int64_t wsb,
@@ -672,7 +687,8 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   const bool lean = !h->no_lean_durations && !(ic && ic->sdp_ratio) && h->taps.empty();
   const bool skip_sdp = lean && in.sdp_ratio == 0.0f && !out.logw_sdp;
   const bool skip_dp = lean && in.sdp_ratio == 1.0f && !out.logw_dp;
-  if (!skip_sdp && !in.noise_w) { h->err = "bv2_encode_durations: noise_w is NULL but the stochastic duration predictor runs"; return -1; }
+  if (int e = check_seeds(h, B, in.noise_w, "bv2_encode_durations", "noise_w")) return e;
+  if (!skip_sdp && !in.noise_w && !h->seeds) { h->err = "bv2_encode_durations: noise_w is NULL but the stochastic duration predictor runs"; return -1; }
 
   // ONE front launch: g = emb_g(sid), x_mask, every g-conditioned vector of this phase, and the scaled SDP noise
   float *spk = P.gv, *sdp_c = P.gv + H, *dp_c = P.gv + 2 * H;
@@ -681,7 +697,7 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
     float* go[3] = {spk, sdp_c, dp_c};
     // a caller's g (a ReferenceEncoder result, a blend, ...) takes the place of the table row: same GEMV code, sid is not read
     run_front(c, g_in ? nullptr : in.sid, g_in, out.g, gw, go, 3, 3 * H, in.x_lengths, out.x_mask, B, T, skip_sdp ? nullptr : in.noise_w,
-              skip_sdp ? nullptr : P.z, in.noise_scale_w, ic ? ic->noise_scale_w : nullptr);
+              skip_sdp ? nullptr : P.z, in.noise_scale_w, ic ? ic->noise_scale_w : nullptr, h->seeds);
   }
   const float* berts[3] = {in.bert, in.ja_bert, in.en_bert};
   enc_p_core(c, P, in.x, in.tone, in.language, berts, mask, spk, 3 * H, B, T, out.x, out.m_p, out.logs_p, P.dp0, dp_c,
@@ -1356,6 +1372,7 @@ static bool expand_and_flow(Ctx& c, const PlanB& P, const bv2_decode_in& in, con
   e.noise = in.noise_z; e.nz_bstride = in.nz_bstride; e.nz_cstride = in.nz_cstride; e.nz_tstride = in.nz_tstride;
   e.noise_scale = in.noise_scale;
   e.noise_scale_b = ic ? ic->noise_scale : nullptr;
+  e.seeds = c.h->seeds;
   e.frame_idx = P.fidx; e.attn = out.attn; e.y_mask = ymask; e.z_p = z; e.m_e = out.m_p; e.logs_e = out.logs_p;
   e.z_p2 = out.z_p;                                  // the flow updates z in place: z_p is kept as a second store
   e.B = in.B; e.C = c.m.cfg.inter_channels; e.T = in.T; e.Ty = in.Ty;
@@ -1369,7 +1386,10 @@ static bool expand_and_flow(Ctx& c, const PlanB& P, const bv2_decode_in& in, con
     F.G = phase_b_gemv_args(c, P, in.g, in.B); F.E = e;
     const int n_slots = (gen_follows && c.h->gen_dtype != BV2_BF16) ? x3_slot_count(c) : 0;
     if (n_slots > 0) { F.slots = P.xslots; F.slot_words = n_slots * X3_SLOT_WORDS; slots_clear = true; }
-    c.chk(launch_phase_b_front(c.s, F), "phase_b_front");
+    // a profile row of its own (tools/seeded_noise_bench.py reads it): bytes = the expanded tensors written, z_p twice when kept
+    c.timed("phase_b_front", "phase_b_front", nullptr, 0.0,
+            [&] { return 4.0 * in.B * e.C * in.Ty * (1 + (e.z_p2 != nullptr) + (e.m_e != nullptr) + (e.logs_e != nullptr) + (e.noise != nullptr)); },
+            [&] { return launch_phase_b_front(c.s, F); });
     if (c.rc) slots_clear = false;
   }
   flow_core(c, P, z, ymask, in.g, in.B, in.Ty);
@@ -1380,6 +1400,8 @@ int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_
                const bv2_item_controls* ic) {
   const Model& m = h->model;
   const int B = in.B, Ty = in.Ty;
+  if (int e = check_seeds(h, B, in.noise_z, "bv2_decode", "noise_z")) return e;
+  if (!in.noise_z && !h->seeds) { h->err = "bv2_decode: noise_z is NULL"; return -1; }
   Arena A(ws, wsb);
   PlanB P = plan_b(A, m, B, Ty);
   if (int e = ws_short(h, A, "bv2_decode")) return e;
@@ -1447,6 +1469,7 @@ int run_posterior_encode(bv2_handle* h, hipStream_t s, int B, int Ty, const floa
   const Model& m = h->model;
   const PosteriorW& Q = h->post;
   const int H = m.cfg.hidden_channels, C = m.cfg.inter_channels;
+  if (int e = check_seeds(h, B, noise_q, "bv2_posterior_encode", "noise_q")) return e;
   Arena A(ws, wsb);
   PlanQ P = plan_q(A, m, B, Ty);
   if (int e = ws_short(h, A, "bv2_posterior_encode")) return e;
@@ -1477,7 +1500,7 @@ int run_posterior_encode(bv2_handle* h, hipStream_t s, int B, int Ty, const floa
     for (int i = 0; i < 2; ++i) { cl.p[i].out_mask = ymask; cl.p[i].mask_post = 1; }
     c.conv(cl, "enc_q.proj");
   }
-  c.chk(launch_posterior_sample(s, mq, lq, noise_q, noise_scale_q, ymask, z, B, C, Ty), "enc_q.sample");
+  c.chk(launch_posterior_sample(s, mq, lq, noise_q, noise_scale_q, ymask, z, B, C, Ty, h->seeds), "enc_q.sample");
   return c.rc;
 }
 
@@ -1554,6 +1577,7 @@ int run_stream_begin(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, cons
                      const bv2_item_controls* ic) {
   const Model& m = h->model;
   const int B = in.B, Ty = in.Ty, C = m.cfg.inter_channels;
+  if (int e = check_seeds(h, B, in.noise_z, "bv2_stream_begin", "noise_z")) return e;
   Arena A(ws, wsb);
   PlanS S = plan_stream(A, m, B, Ty, 1, 1);
   if (int e = ws_short(h, A, "bv2_stream_begin")) return e;

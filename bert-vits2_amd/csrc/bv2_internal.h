@@ -282,6 +282,9 @@ struct bv2_handle {
   bool no_lean_durations = false;    // "lean_durations" = 0: both duration predictors always run (default: at a host-known sdp_ratio of exactly 0 or 1 the one
   // whose term is multiplied by 0.0f is not launched, run_encode)
   bool no_phase_b_front = false;     // "phase_b_front" = 0: the head of phase B as five launches (frame_index, expand, attn_path, gemv, x3 slots) instead of one
+  // bv2_set_noise_seeds: [B] device int64, read by the kernels when a call runs (null: off, every call takes its noise tensors)
+  const int64_t* seeds = nullptr;
+  int seeds_B = 0;
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // profiling
@@ -302,6 +305,8 @@ int build_posterior_layout(const bv2_config& cfg, int spec_channels, PosteriorW&
 int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w, const std::map<std::string, HostTensor>& t, float* blob, std::string& err);
 
 // bv2_exec.cpp
+// active seeds (bv2_set_noise_seeds) against a call's batch and its noise pointer: non-zero with h->err set on a mismatch
+int check_seeds(bv2_handle* h, int B, const void* noise, const char* what, const char* noise_name);
 int64_t workspace_bytes(const Model& m, int B, int T, int Ty);
 // ic: per-utterance controls (may be null: the scalars of in); a null member keeps that scalar
 // g_in: a caller's speaker vectors [B][gin] (null: emb_g(in.sid)); copied to out.g

@@ -596,6 +596,8 @@ struct FrontArgs {
   const int64_t* lengths; float* mask; int T;
   const float* noise; float* z; float noise_scale; int64_t nz;
   const float* noise_scale_b;   // [B] per-utterance noise_scale_w (bv2_item_controls), or null = noise_scale; z is [B][2][T]
+  const int64_t* seeds;         // [B] per-utterance noise seeds (bv2_set_noise_seeds), or null; set: noise is not read, the value is
+                                // seeded_normal(seeds[b], RNG_NOISE_W, r, t) (kernels/rng.h)
 };
 int launch_front(hipStream_t stream, const FrontArgs& a);
 
@@ -680,6 +682,8 @@ struct ExpandArgs {
   const float* m_p; const float* logs_p;             // [B][C][T]
   const float* noise; int64_t nz_bstride, nz_cstride, nz_tstride; float noise_scale;
   const float* noise_scale_b;                         // [B] per-utterance noise_scale (bv2_item_controls), or null = noise_scale
+  const int64_t* seeds;                               // [B] per-utterance noise seeds, or null; set: noise is not read, frame j of (b, c) takes
+                                                      // seeded_normal(seeds[b], RNG_NOISE_Z, c, j) inside the utterance and 0 past its end
   int* frame_idx;                                     // [B][Ty] scratch
   float* attn; float* y_mask; float* z_p; float* m_e; float* logs_e;   // outputs (attn/y_mask/m_e/logs_e may be null)
   float* z_p2;                                        // optional second copy of z_p (the flow updates z_p in place)
@@ -693,6 +697,12 @@ struct PhaseBFrontArgs {
   int gemv_gx, gemv_layers, e_chunks, e_groups;        // the roles' block counts: filled by the launcher
 };
 int launch_phase_b_front(hipStream_t stream, const PhaseBFrontArgs& a);
+
+// --- seeded noise as a tensor (kernels/rng.h through the same __device__ function the consumers above call) ---
+// out[b*bstride + r*rstride + t*tstride] = seeded_normal(seeds[b], which, r, t) for r < rows, t < T; lengths (optional, [B]): frames at or
+// past lengths[b] are written as 0
+int launch_seeded_noise(hipStream_t stream, const int64_t* seeds, int B, int which, int rows, int T, const int64_t* lengths, float* out,
+                        int64_t bstride, int64_t rstride, int64_t tstride);
 
 // --- 16-bit PCM of the valid samples, peak-normalised per utterance (gradio convert_to_16_bit_wav, reference webui.py:86) ---
 int launch_pcm16(hipStream_t stream, const float* wave, int64_t bstride, const int64_t* y_lengths, int hop, int B, int64_t S,
@@ -767,7 +777,7 @@ struct MaxPathArgs {
 };
 // z = (m + noise * exp(logs) * scale) * mask (PosteriorEncoder, models.py:486); noise null: z = m * mask.  All [B][C][T], mask [B][T]
 int launch_posterior_sample(hipStream_t stream, const float* m, const float* logs, const float* noise, float scale, const float* mask,
-                            float* z, int B, int C, int T);
+                            float* z, int B, int C, int T, const int64_t* seeds = nullptr);   // seeds [B] set: seeded_normal(seeds[b], RNG_NOISE_Q, c, t) in place of noise[i]
 int64_t maximum_path_workspace_bytes(int B, int T, int Ty);
 int launch_maximum_path(hipStream_t stream, const MaxPathArgs& a);
 

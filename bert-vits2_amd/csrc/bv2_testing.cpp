@@ -7,6 +7,7 @@
 
 #include "bv2_internal.h"
 #include "../../include/bv2_testing.h"
+#include "kernels/rng.h"
 
 using namespace bv2;
 
@@ -910,5 +911,13 @@ int bv2_test_spline(void* stream, float* z, int src, int dst, const float* param
                     float sqrt_fc, float tail, int B, int T) {
   return launch_spline(static_cast<hipStream_t>(stream), z, src, dst, params, prow, mask, sqrt_fc, tail, B, T);
 }
+
+
+// kernels/rng.h on the host
+void bv2_test_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  const Philox4 w = philox4x32_10(Philox4{ctr[0], ctr[1], ctr[2], ctr[3]}, key[0], key[1]);
+  out[0] = w.x; out[1] = w.y; out[2] = w.z; out[3] = w.w;
+}
+float bv2_test_seeded_normal(int64_t seed, int which, int row, int t) { return seeded_normal(seed, which, row, t); }
 
 }  // extern "C"

@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "../bv2_kernels.h"
+#include "rng.h"
 
 namespace bv2 {
 
@@ -236,22 +237,26 @@ __global__ void __launch_bounds__(1024) maximum_path_kernel(const MaxPathArgs A,
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // PosteriorEncoder's last line (models.py:486): z = (m + noise * exp(logs) * scale) * mask; the noise is the caller's draw (null: z = m * mask)
+// or, with seeds [B], the value of (seeds[b], RNG_NOISE_Q, channel, frame) computed here (kernels/rng.h)
 __global__ void __launch_bounds__(256) posterior_sample_kernel(const float* m, const float* logs, const float* noise, float scale,
-                                                               const float* mask, float* z, int C, int T) {
+                                                               const float* mask, float* z, int C, int T, const int64_t* seeds) {
   const int b = blockIdx.z, ch = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
   if (t >= T) return;
   const int64_t i = ((int64_t)b * C + ch) * T + t;
   const float mk = mask[(int64_t)b * T + t];
   float v = m[i];
-  if (noise) v = v + noise[i] * expf(logs[i]) * scale;
+  if (noise || seeds) {
+    const float nz = seeds ? seeded_normal(seeds[b], RNG_NOISE_Q, ch, t) : noise[i];
+    v = v + nz * expf(logs[i]) * scale;
+  }
   z[i] = mk != 0.f ? v * mk : 0.f;                    // a masked frame is selected to zero: its noise may hold anything
 }
 
 int launch_posterior_sample(hipStream_t stream, const float* m, const float* logs, const float* noise, float scale, const float* mask,
-                            float* z, int B, int C, int T) {
+                            float* z, int B, int C, int T, const int64_t* seeds) {
   if (B < 1 || B > 65535 || C < 1 || C > 65535 || T < 1) return -1;
   hipLaunchKernelGGL(posterior_sample_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)C, (unsigned)B), dim3(256), 0, stream, m, logs, noise,
-                     scale, mask, z, C, T);
+                     scale, mask, z, C, T, seeds);
   return BV2_CHECK_LAUNCH();
 }
 

@@ -5,6 +5,7 @@
 #include <math.h>
 #include <cmath>
 #include "../bv2_kernels.h"
+#include "rng.h"
 #include "spline.h"
 
 namespace bv2 {
@@ -248,8 +249,15 @@ __global__ void __launch_bounds__(256) front_kernel(const FrontArgs A) {
       const int b = (int)(i / A.T), t = (int)(i - (int64_t)b * A.T);
       A.mask[i] = (!A.lengths || (int64_t)t < A.lengths[b]) ? 1.f : 0.f;
     }
+  // seeded (A.seeds, bv2_set_noise_seeds): element i = (b, r, t) of z takes the generator's value instead of noise[i]
+  const auto noise_at = [&](const int64_t i, const int b) {
+    if (!A.seeds) return A.noise[i];
+    const int64_t rt = i - (int64_t)b * 2 * A.T;
+    const int r = rt >= A.T ? 1 : 0;
+    return seeded_normal(A.seeds[b], RNG_NOISE_W, r, (int)(rt - (int64_t)r * A.T));
+  };
   if (A.z && !A.noise_scale_b)
-    for (int64_t i = i0; i < A.nz; i += step) A.z[i] = A.noise[i] * A.noise_scale;
+    for (int64_t i = i0; i < A.nz; i += step) A.z[i] = noise_at(i, A.seeds ? (int)(i / ((int64_t)2 * A.T)) : 0) * A.noise_scale;
   if (A.z && A.noise_scale_b) {                    // per-utterance scale: loaded once per item this thread visits
     const int64_t per = (int64_t)2 * A.T;
     int bc = -1;
@@ -257,7 +265,7 @@ __global__ void __launch_bounds__(256) front_kernel(const FrontArgs A) {
     for (int64_t i = i0; i < A.nz; i += step) {
       const int b = (int)(i / per);
       if (b != bc) { bc = b; sc = A.noise_scale_b[b]; }
-      A.z[i] = A.noise[i] * sc;
+      A.z[i] = noise_at(i, b) * sc;
     }
   }
 }
@@ -537,20 +545,28 @@ __global__ void __launch_bounds__(256) frame_index_kernel(const ExpandArgs A) {
   });
 }
 
-// frame j of (b, c) whose symbol is i (-1: none): gather + prior sampling
-__device__ __forceinline__ void expand_one(const ExpandArgs& A, const int b, const int c, const int j, const int i, const float ns) {
+// frame j of (b, c) whose symbol is i (-1: none), its N(0,1) value nz in hand: gather + prior sampling
+__device__ __forceinline__ void expand_put(const ExpandArgs& A, const int b, const int c, const int j, const int i, const float ns,
+                                           const float nz) {
   float m = 0.f, lg = 0.f;
   if (i >= 0) {
     m = A.m_p[((int64_t)b * A.C + c) * A.T + i];
     lg = A.logs_p[((int64_t)b * A.C + c) * A.T + i];
   }
   const int64_t off = ((int64_t)b * A.C + c) * A.Ty + j;
-  const float nz = A.noise[(int64_t)b * A.nz_bstride + (int64_t)c * A.nz_cstride + (int64_t)j * A.nz_tstride];
   const float zp = m + nz * expf(lg) * ns;
   A.z_p[off] = zp;
   if (A.z_p2) A.z_p2[off] = zp;
   if (A.m_e) A.m_e[off] = m;
   if (A.logs_e) A.logs_e[off] = lg;
+}
+// ... with the value loaded from the caller's noise tensor or, seeded, computed here: (seeds[b], RNG_NOISE_Z, c, j) inside the utterance,
+// 0 past its end (the zeroed tail of a bucket's noise buffer: a bucketed run equals an unbucketed one)
+__device__ __forceinline__ void expand_one(const ExpandArgs& A, const int b, const int c, const int j, const int i, const float ns) {
+  float nz;
+  if (A.seeds) nz = (int64_t)j < A.y_lengths[b] ? seeded_normal(A.seeds[b], RNG_NOISE_Z, c, j) : 0.f;
+  else nz = A.noise[(int64_t)b * A.nz_bstride + (int64_t)c * A.nz_cstride + (int64_t)j * A.nz_tstride];
+  expand_put(A, b, c, j, i, ns, nz);
 }
 
 __global__ void expand_kernel(const ExpandArgs A) {
@@ -622,7 +638,19 @@ __global__ void __launch_bounds__(256) phase_b_front_kernel(const PhaseBFrontArg
       }
       const float ns = E.noise_scale_b ? E.noise_scale_b[b] : E.noise_scale;
       const int c1 = (cg + 1) * PBF_CG < E.C ? (cg + 1) * PBF_CG : E.C;
-      for (int c = cg * PBF_CG; c < c1; ++c) expand_one(E, b, c, j, i, ns);
+      if (E.seeds) {                               // one Philox call per four channels of this frame (PBF_CG = 8: two calls)
+        const int64_t seed = E.seeds[b];
+        for (int c = cg * PBF_CG; c < c1; c += 4) {
+          float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+          if (j < ylen) seeded_normal4(seed, RNG_NOISE_Z, c >> 2, j, &v0, &v1, &v2, &v3);
+          expand_put(E, b, c, j, i, ns, v0);
+          if (c + 1 < c1) expand_put(E, b, c + 1, j, i, ns, v1);
+          if (c + 2 < c1) expand_put(E, b, c + 2, j, i, ns, v2);
+          if (c + 3 < c1) expand_put(E, b, c + 3, j, i, ns, v3);
+        }
+      } else {
+        for (int c = cg * PBF_CG; c < c1; ++c) expand_one(E, b, c, j, i, ns);
+      }
     }
     if (E.attn)
       for (int r = cg; r < 256 && j0 + r < E.Ty; r += A.e_groups) {
@@ -650,6 +678,25 @@ int launch_phase_b_front(hipStream_t stream, const PhaseBFrontArgs& a0) {
   const int64_t blocks = (int64_t)a.gemv_gx * a.G.nprob * a.gemv_layers + (int64_t)E.B * a.e_chunks * a.e_groups + (a.slot_words + 255) / 256;
   if (blocks < 1 || blocks > 0x7fffffff) return -1;
   hipLaunchKernelGGL(phase_b_front_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return BV2_CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Seeded noise as a tensor (bv2_seeded_noise): the values the three consumers compute in place (front_kernel, expand_one,
+// posterior_sample_kernel), through the same function, for callers that want the tensor (the single-stage calls take zin / z_p as inputs)
+// and for the tests.  One thread per (frame, row); any strides.
+__global__ void __launch_bounds__(256) seeded_noise_kernel(const int64_t* seeds, int which, int rows, int T, const int64_t* lengths,
+                                                           float* out, int64_t bstride, int64_t rstride, int64_t tstride) {
+  const int b = blockIdx.z, r = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= T || r >= rows) return;
+  const bool in = !lengths || (int64_t)t < lengths[b];
+  out[(int64_t)b * bstride + (int64_t)r * rstride + (int64_t)t * tstride] = in ? seeded_normal(seeds[b], which, r, t) : 0.f;
+}
+int launch_seeded_noise(hipStream_t stream, const int64_t* seeds, int B, int which, int rows, int T, const int64_t* lengths, float* out,
+                        int64_t bstride, int64_t rstride, int64_t tstride) {
+  if (!seeds || !out || B < 1 || B > 65535 || which < 0 || which > 2 || rows < 1 || rows > 65535 || T < 1) return -1;
+  hipLaunchKernelGGL(seeded_noise_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)rows, (unsigned)B), dim3(256), 0, stream, seeds,
+                     which, rows, T, lengths, out, bstride, rstride, tstride);
   return BV2_CHECK_LAUNCH();
 }
 

@@ -173,6 +173,8 @@ SYMBOLS = [
     ("bv2_neg_cent", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("bv2_maximum_path_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     ("bv2_maximum_path", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int64]),
+    ("bv2_set_noise_seeds", C.c_int, [_P, _P, C.c_int32]),
+    ("bv2_seeded_noise", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int64, C.c_int64]),
     ("bv2_align_workspace_bytes", C.c_int64, [_P, C.c_int, C.c_int, C.c_int]),
     ("bv2_align", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64]),
     ("bv2_posterior_packed_bytes", C.c_int64, [_P, C.c_int]),

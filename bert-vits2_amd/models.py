@@ -18,6 +18,7 @@ the built library ``infer()`` raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import numbers
@@ -48,6 +49,56 @@ def draw_noise_z(B: int, C: int, Ty: int, device) -> torch.Tensor:
     with those strides reproduces the reference's values (plain ``torch.randn(B, C, T_y)`` does not); the
     C ABI takes the strides (``bv2_decode_in.nz_*stride``), so the tensor is handed over as it is."""
     return torch.randn_like(torch.empty(B, Ty, C, device=device, dtype=torch.float32).transpose(1, 2))
+
+
+NOISE_W, NOISE_Z, NOISE_Q = 0, 1, 2     # ``which`` of the seeded generator (csrc/kernels/rng.h): the SDP draw, the prior draw, the posterior draw
+
+
+def item_seeds(seeds, B: int, device) -> Optional[torch.Tensor]:
+    """``seeds`` as ``infer`` takes it -> int64 ``[B]`` on ``device`` (None stays None).  An int is applied to every item; a sequence
+    of B ints or an int64 tensor ``[B]`` gives one seed per utterance.  Any int64 is a seed (the generator reads its bit pattern)."""
+    if seeds is None:
+        return None
+    if isinstance(seeds, numbers.Integral) and not isinstance(seeds, bool):
+        seeds = [int(seeds)] * B
+    if not isinstance(seeds, torch.Tensor):
+        try:
+            seeds = torch.tensor([int(v) for v in seeds], dtype=torch.int64)
+        except (TypeError, ValueError, RuntimeError, OverflowError) as e:
+            raise ValueError(f"seeds must be an int, B = {B} ints in the int64 range or an int64 tensor [B]") from e
+    if seeds.dtype != torch.int64 or tuple(seeds.shape) != (B,):
+        raise ValueError(f"seeds must be an int, B = {B} ints or an int64 tensor [B], got {seeds.dtype} {tuple(seeds.shape)}")
+    return seeds.detach().to(device).contiguous()
+
+
+def seeded_noise(seeds, which: int, rows: int, T: int, lengths=None, device=None, transposed: bool = False) -> torch.Tensor:
+    """The seeded generator's N(0,1) values as a tensor ``[B, rows, T]`` (``bv2_seeded_noise``): element (b, r, t) is the value the
+    kernels compute in place for utterance seed ``seeds[b]``, draw ``which`` (``NOISE_W`` / ``NOISE_Z`` / ``NOISE_Q``), row r, frame t —
+    bit for bit, so ``infer(noise_w=seeded_noise(s, 0, 2, T), noise_z=seeded_noise(s, 1, C, Ty, lengths=y_lengths))`` is
+    ``infer(seeds=s)``.  ``seeds``: a sequence of ints or an int64 tensor ``[B]``; ``lengths`` [B]: frames at or past it are 0;
+    ``transposed``: the tensor has the reference's strides ``(T * rows, 1, rows)`` (``draw_noise_z``)."""
+    if isinstance(seeds, numbers.Integral):
+        seeds = [int(seeds)]
+    if device is None:
+        device = seeds.device if isinstance(seeds, torch.Tensor) and seeds.is_cuda else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("bert_vits2_amd.models.seeded_noise needs a GPU: no CPU fallback exists by design")
+    B = int(seeds.shape[0]) if isinstance(seeds, torch.Tensor) else len(seeds)
+    sd = item_seeds(seeds, B, device)
+    rows, T = int(rows), int(T)
+    if B < 1 or rows < 1 or T < 1:
+        raise ValueError("seeded_noise needs B, rows and T of at least 1")
+    ln = None if lengths is None else torch.as_tensor(lengths).to(device, torch.int64).reshape(B).contiguous()
+    out = torch.empty(B, T, rows, dtype=torch.float32, device=device).transpose(1, 2) if transposed else \
+        torch.empty(B, rows, T, dtype=torch.float32, device=device)
+    lib = L.load()
+    with torch.cuda.device(device):
+        rc = lib.bv2_seeded_noise(C.c_void_p(torch.cuda.current_stream().cuda_stream), _ptr(sd), B, int(which), rows, T, _ptr(ln),
+                                  _ptr(out), out.stride(0), out.stride(1), out.stride(2))
+    if rc:
+        raise RuntimeError(f"bv2_seeded_noise failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return out
 
 
 def item_control(name: str, value, B: int, device):
@@ -117,9 +168,9 @@ class _LastEncode(dict):
     missing one gets it computed on first access by that predictor's single-stage call (``stage_sdp`` / ``stage_dp``) on the kept encoder
     output — parity tests and debugging, off the hot path.  It is not among ``keys()`` until then."""
 
-    def __init__(self, enc, model, noise_w, noise_scale_w):
+    def __init__(self, enc, model, noise_w, noise_scale_w, seeds=None):
         super().__init__(enc)
-        self._model, self._noise_w, self._noise_scale_w = weakref.ref(model), noise_w, noise_scale_w
+        self._model, self._noise_w, self._noise_scale_w, self._seeds = weakref.ref(model), noise_w, noise_scale_w, seeds
 
     def __missing__(self, key):
         m = self._model()
@@ -130,7 +181,8 @@ class _LastEncode(dict):
         else:
             B = self["x"].shape[0]
             scale, per_item = item_control("noise_scale_w", self._noise_scale_w, B, m.device)
-            zin = self._noise_w.to(m.device, torch.float32) * (scale if per_item is None else per_item.reshape(B, 1, 1))
+            nw = self._noise_w if self._seeds is None else seeded_noise(self._seeds, NOISE_W, 2, self["x"].shape[2], device=m.device)
+            zin = nw.to(m.device, torch.float32) * (scale if per_item is None else per_item.reshape(B, 1, 1))
             v = m.stage_sdp(self["x"], self["x_mask"], zin, self["g"])[:, 0]
         self[key] = v
         return v
@@ -421,6 +473,18 @@ class SynthesizerTrn(nn.Module):
         self._drop_graphs()
         self.flow_dtype = torch.float16 if code == L.F16 else torch.float32
 
+    @contextlib.contextmanager
+    def _seeded(self, seeds: Optional[torch.Tensor]):
+        """The library calls inside draw from ``seeds`` (int64 [B] on the device, ``bv2_set_noise_seeds``); None: nothing changes."""
+        if seeds is None:
+            yield
+            return
+        self._check(self._lib.bv2_set_noise_seeds(self._handle, _ptr(seeds), int(seeds.shape[0])), "bv2_set_noise_seeds")
+        try:
+            yield
+        finally:
+            self._lib.bv2_set_noise_seeds(self._handle, None, 0)
+
     def _workspace(self, B: int, T: int, Ty: int) -> torch.Tensor:
         n = self._lib.bv2_workspace_bytes(self._handle, B, T, Ty)
         if n < 0:
@@ -587,9 +651,12 @@ class SynthesizerTrn(nn.Module):
 
     # ------------------------------------------------------------------ the two phases
     @torch.no_grad()
-    def encode_durations(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w, noise_scale_w=0.8,
-                         sdp_ratio=0.0, length_scale=1.0, bert_index=None, g=None, lean=False) -> Dict[str, torch.Tensor]:
+    def encode_durations(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w=None, noise_scale_w=0.8,
+                         sdp_ratio=0.0, length_scale=1.0, bert_index=None, g=None, lean=False, seeds=None) -> Dict[str, torch.Tensor]:
         """Phase A = reference models.py:1045-1057.  ``noise_w`` [B,2,T] is the draw of models.py:248-251.
+
+        ``seeds`` (an int, B ints or an int64 tensor [B]; see ``infer``): the stochastic predictor's noise is computed on the device from
+        each utterance's seed instead (``bv2_set_noise_seeds``); ``noise_w`` must then be None.
 
         ``lean`` (what ``infer`` asks for): the output the mix ``logw = sdp * r + dp * (1 - r)`` cannot see is not asked for, which lets the
         library run only the other predictor (include/bv2.h, ``bv2_encode_out``): at a scalar ``sdp_ratio`` of exactly 0 there is no
@@ -633,7 +700,12 @@ class SynthesizerTrn(nn.Module):
                 ein.bert_index[i] = None if bidx[i] is None else ptr_of(i)
                 ein.bert_cols[i] = cols[i]
             return ein
-        if tuple(noise_w.shape) != (B, 2, T):
+        seeds = item_seeds(seeds, B, dev)
+        if seeds is not None and noise_w is not None:
+            raise ValueError("encode_durations: seeds and noise_w exclude each other (a seeded call reads no noise tensor)")
+        if seeds is None and noise_w is None:
+            raise ValueError("encode_durations needs noise_w [B,2,T] (draw_noise_w) or seeds")
+        if seeds is None and tuple(noise_w.shape) != (B, 2, T):
             raise ValueError("noise_w must be [B,2,T]")
         # per-utterance controls: if any of the three is a [B] tensor, all three go to the library as [B] arrays (rows 0-2 of a
         # [4, B] buffer, bv2_item_controls); otherwise the scalar call runs exactly as before
@@ -653,7 +725,7 @@ class SynthesizerTrn(nn.Module):
             noise_scale_w, sdp_ratio, length_scale = (v for v, _ in ctrl)
         # the library's rule for leaving the stochastic predictor out (bv2_exec.cpp run_encode), mirrored to know whether noise_w is read
         skip_sdp = bool(lean and ctl is None and sdp_ratio == 0.0 and not self._taps and self._options.get("lean_durations", 1))
-        noise_w = None if skip_sdp else f32(noise_w)
+        noise_w = None if (skip_sdp or seeds is not None) else f32(noise_w)
         hp = self.hp
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         okeys = ("g", "x", "m_p", "logs_p", "x_mask", "logw_sdp", "logw_dp", "logw", "w_ceil", "y_lengths")
@@ -677,9 +749,11 @@ class SynthesizerTrn(nn.Module):
                     ins[f"bert_index{i}"] = bidx[i]
             if ctl is not None:
                 ins["ctl"] = ctl                    # the graph owns a [4, B] copy: its values are refilled before every replay
+            if seeds is not None:
+                ins["seeds"] = seeds                # the graph owns an int64 [B] copy, read at replay time: the key says "seeded", not the values
 
             static = self._graphs_static
-            moving = ("noise_w", "ctl", "g")
+            moving = ("noise_w", "ctl", "g", "seeds")
 
             def build(own_inputs):
                 staged = tuple(ins) if own_inputs else tuple(k for k in moving if k in ins)   # static_io: the rest is read in place
@@ -691,7 +765,7 @@ class SynthesizerTrn(nn.Module):
                 with_index(ein, lambda i: sin[f"bert_index{i}"].data_ptr())
                 eout = L.EncodeOut(*[_ptr(sout.get(k)) for k in okeys])
                 icp = None if ctl is None else _controls_ptr(sin["ctl"], (0, 1, 2))
-                with torch.cuda.device(dev):
+                with torch.cuda.device(dev), self._seeded(sin.get("seeds")):
                     if g is not None:
                         gr = self._capture(self._lib.bv2_graph_capture_encode_g, C.byref(ein), C.byref(eout), icp, _ptr(sin["g"]),
                                            C.c_void_p(ws.data_ptr()), ws.numel())
@@ -721,7 +795,7 @@ class SynthesizerTrn(nn.Module):
         with_index(ein, lambda i: bidx[i].data_ptr())
         eout = L.EncodeOut(*[_ptr(out.get(k)) for k in okeys])
         ws = self._workspace(B, T, 1)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), self._seeded(seeds):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             if g is not None:
                 self._check(self._lib.bv2_encode_durations_g(self._handle, stream, C.byref(ein), C.byref(eout),
@@ -738,8 +812,10 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def decode(self, enc: Dict[str, torch.Tensor], noise_z: torch.Tensor, Ty: int, noise_scale=0.667, max_len=None,
-               want_attn: bool = True, exact_lengths: bool = False, ty_bucket: Optional[int] = None) -> Dict[str, torch.Tensor]:
+               want_attn: bool = True, exact_lengths: bool = False, ty_bucket: Optional[int] = None, seeds=None) -> Dict[str, torch.Tensor]:
         """Phase B = reference models.py:1058-1073.  ``noise_z`` [B,inter,>=Ty] replaces randn_like at :1071.
+        ``seeds`` (see ``infer``): the prior noise is computed inside the expanding kernel from each utterance's seed; ``noise_z`` must be
+        None, no noise tensor exists and nothing is drawn from torch's generator.
         ``ty_bucket``: run at T_y rounded up to a multiple of it and cut the outputs back (default: the ``enable_graphs`` bucket when a
         graph is replayed, none on the eager path; tests pass it to the eager path to compare like with like)."""
         if self._blob is None:
@@ -755,8 +831,11 @@ class SynthesizerTrn(nn.Module):
             ctl[3].copy_(ns_item)
             ctl = ctl.to(dev)
             noise_scale = 0.0
-        draw_z = noise_z is None                        # infer(): draw #2 straight into the graph's buffer (static_io)
-        if not draw_z:
+        seeds = item_seeds(seeds, B, dev)
+        if seeds is not None and noise_z is not None:
+            raise ValueError("decode: seeds and noise_z exclude each other (a seeded call reads no noise tensor)")
+        draw_z = noise_z is None and seeds is None      # infer(): draw #2 straight into the graph's buffer (static_io)
+        if noise_z is not None:
             assert noise_z.is_cuda and noise_z.dtype == torch.float32 and noise_z.shape[2] >= Ty and noise_z.shape[1] == Ci
         L_dec = Ty if (max_len is None or max_len <= 0 or max_len >= Ty) else int(max_len)
         S = L_dec * hp.total_upsample
@@ -809,15 +888,18 @@ class SynthesizerTrn(nn.Module):
             def build(own_inputs):
                 sin = {k: (torch.empty_like(enc[k]) if own_inputs else enc[k]) for k in ikeys}
                 # the reference's strides for the prior noise (draw_noise_z): an in-place normal_() on it IS randn_like(m_p)
-                sin["noise_z"] = torch.zeros(B, Ty, Ci, dtype=torch.float32, device=dev).transpose(1, 2)   # zeros: a bucket's tail is never drawn
+                if seeds is None:
+                    sin["noise_z"] = torch.zeros(B, Ty, Ci, dtype=torch.float32, device=dev).transpose(1, 2)   # zeros: a bucket's tail is never drawn
+                else:
+                    sin["seeds"] = torch.zeros_like(seeds)     # read at replay time; no noise buffer exists
                 if ctl is not None:
                     sin["ctl"] = torch.zeros_like(ctl)
                 sout = mk_out()
-                din = L.DecodeIn(B, T, int(Ty), int(L_dec), *[_ptr(sin[k]) for k in ikeys], _ptr(sin["noise_z"]),
-                                 sin["noise_z"].stride(0), sin["noise_z"].stride(1), sin["noise_z"].stride(2),
-                                 float(noise_scale), mode)
+                nzs = sin.get("noise_z")
+                din = L.DecodeIn(B, T, int(Ty), int(L_dec), *[_ptr(sin[k]) for k in ikeys], _ptr(nzs),
+                                 *((0, 0, 0) if nzs is None else nzs.stride()), float(noise_scale), mode)
                 dout = L.DecodeOut(*[_ptr(sout[k]) for k in okeys])
-                with torch.cuda.device(dev):
+                with torch.cuda.device(dev), self._seeded(sin.get("seeds")):
                     if ctl is None:
                         g = self._capture(self._lib.bv2_graph_capture_decode, C.byref(din), C.byref(dout),
                                           C.c_void_p(ws.data_ptr()), ws.numel())
@@ -828,13 +910,15 @@ class SynthesizerTrn(nn.Module):
 
             ptrs = tuple(enc[k].data_ptr() for k in ikeys) if static else ()
             scal = "item" if ctl is not None else float(noise_scale)   # per-utterance: the fact, not the values
-            ent = self._graph_entry(("B", B, T, int(Ty), int(L_dec), bool(want_attn), scal, mode), build, ptrs)
+            ent = self._graph_entry(("B", B, T, int(Ty), int(L_dec), bool(want_attn), scal, mode, seeds is not None), build, ptrs)
             if ent["own_inputs"]:
                 for k in ikeys:
                     ent["sin"][k].copy_(enc[k])
             if ctl is not None:
                 ent["sin"]["ctl"].copy_(ctl)
-            if draw_z and not bucketed:
+            if seeds is not None:
+                ent["sin"]["seeds"].copy_(seeds)
+            elif draw_z and not bucketed:
                 ent["sin"]["noise_z"].normal_()
             elif draw_z:                                # the reference draws exactly [B, C, T_y] in its memory order (draw_noise_z): keep the RNG contract
                 ent["sin"]["noise_z"][:, :, :Ty_true].copy_(draw_noise_z(B, Ci, Ty_true, dev))
@@ -848,17 +932,17 @@ class SynthesizerTrn(nn.Module):
             return {k: (None if v is None else v.clone()) for k, v in cut(ent["sout"]).items()}
         if draw_z:
             noise_z = draw_noise_z(B, Ci, Ty_true, dev)
-        if bucketed:                                    # eager run at a bucket (tests): zero tail, reference-strided like the graph's buffer
+        if bucketed and seeds is None:                  # eager run at a bucket (tests): zero tail, reference-strided like the graph's buffer
             nzb = torch.zeros(B, Ty, Ci, dtype=torch.float32, device=dev).transpose(1, 2)
             nzb[:, :, :Ty_true].copy_(noise_z[:, :, :Ty_true])
             noise_z = nzb
         out = mk_out()
         din = L.DecodeIn(B, T, int(Ty), int(L_dec), _ptr(enc["m_p"]), _ptr(enc["logs_p"]), _ptr(enc["x_mask"]),
                          _ptr(enc["w_ceil"]), _ptr(enc["y_lengths"]), _ptr(enc["g"]), _ptr(noise_z),
-                         noise_z.stride(0), noise_z.stride(1), noise_z.stride(2), float(noise_scale), mode)
+                         *((0, 0, 0) if noise_z is None else noise_z.stride()), float(noise_scale), mode)
         dout = L.DecodeOut(*[_ptr(out[k]) for k in okeys])
         ws = self._workspace(B, T, Ty)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), self._seeded(seeds):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             if ctl is None:
                 self._check(self._lib.bv2_decode(self._handle, stream, C.byref(din), C.byref(dout), C.c_void_p(ws.data_ptr()),
@@ -872,7 +956,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def infer(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_scale=0.667, length_scale=1,
               noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None, *, g=None, y_lengths=None, noise_w=None, noise_z=None,
-              w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, ty_bucket=None, w_ceil_items=None):
+              w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, ty_bucket=None, w_ceil_items=None, seeds=None):
         """reference models.py:1026-1074.  Keyword-only extras (not in the reference): ``noise_w`` [B,2,T] and
         ``noise_z`` [B,inter,>=T_y] inject the two N(0,1) draws (parity tests; the reference's ONNX export externalises
         them the same way), ``w_ceil`` substitutes the durations (``w_ceil_items`` [B] bool: only for the marked items), ``want_attn=False`` skips materialising the path,
@@ -890,20 +974,29 @@ class SynthesizerTrn(nn.Module):
         row, through the same kernel code (``g = stage_emb_g(s)`` is bit-identical to ``sid = s``), and ``sid`` may be None.  Otherwise a
         model with ``n_speakers=0`` encodes ``y`` [B, spec_channels, L] first (``reference_embedding(y, y_lengths)``; ``y_lengths`` [B] is
         this library's addition for padded reference batches), and a model with a speaker table looks ``sid`` up and ignores ``y``, as the
-        reference does.  With graphs on, ``g`` lives in a buffer the graph owns: one capture per shape serves every voice."""
+        reference does.  With graphs on, ``g`` lives in a buffer the graph owns: one capture per shape serves every voice.
+
+        ``seeds`` (an int for every item, B ints, or an int64 tensor [B]): per-utterance noise seeds.  Both draws then come from a
+        counter-based generator inside the kernels that consume them (``bv2_set_noise_seeds``, csrc/kernels/rng.h): utterance b's noise
+        at (draw, row, frame) depends on ``seeds[b]`` alone — not on the batch it rides in, its row, T, T_y or the bucket — torch's
+        generators are not touched, and no noise tensor is made.  It excludes ``noise_w`` / ``noise_z`` (``seeded_noise`` gives the same
+        values as tensors).  With graphs on the seeds live in a buffer the graph owns: one capture serves every seed."""
         if self.device.type != "cuda":
             raise RuntimeError("bert_vits2_amd.SynthesizerTrn.infer needs a GPU: no CPU fallback exists by design")
         dev = self.device
         B, T = x.shape
+        seeds = item_seeds(seeds, B, dev)
+        if seeds is not None and (noise_w is not None or noise_z is not None):
+            raise ValueError("infer: seeds and noise_w / noise_z exclude each other")
         if g is None and self.hp.n_speakers == 0:
             if y is None:
                 raise ValueError("this model has no speaker table (n_speakers=0): infer() needs y (the reference spectrogram) or g")
             g = self.reference_embedding(y, y_lengths)
-        if noise_w is None:
+        if noise_w is None and seeds is None:
             noise_w = draw_noise_w(B, T, None)         # drawn either way (the RNG stream stays the reference's); uploaded only if read
         enc = self.encode_durations(x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w,
                                     noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, length_scale=length_scale,
-                                    bert_index=bert_index, g=g, lean=True)
+                                    bert_index=bert_index, g=g, lean=True, seeds=seeds)
         if w_ceil is not None:
             _substitute_durations(enc, w_ceil, w_ceil_items, B, T, dev)
         # the reference's one host sync (commons.py:120-122).  One utterance: no reduction kernel in front of the copy.
@@ -911,15 +1004,15 @@ class SynthesizerTrn(nn.Module):
         if noise_z is not None:                        # None: decode() draws it (in place in the graph's buffer when replaying)
             noise_z = noise_z.to(dev, torch.float32)
         dec = self.decode(enc, noise_z, Ty, noise_scale=noise_scale, max_len=max_len, want_attn=want_attn,
-                          exact_lengths=exact_lengths, ty_bucket=ty_bucket)
-        self.last_encode = _LastEncode(enc, self, noise_w, noise_scale_w)
+                          exact_lengths=exact_lengths, ty_bucket=ty_bucket, seeds=seeds)
+        self.last_encode = _LastEncode(enc, self, noise_w, noise_scale_w, seeds)
         return dec["o"], dec["attn"], dec["y_mask"], (dec["z"], dec["z_p"], dec["m_p"], dec["logs_p"])
 
     @torch.no_grad()
     def infer_stream(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_scale=0.667, length_scale=1,
                      noise_scale_w=0.8, max_len=None, sdp_ratio=0, y=None, *, g=None, y_lengths=None, noise_w=None, noise_z=None,
                      w_ceil=None, want_attn=True, exact_lengths=False, bert_index=None, chunk_frames=64, first_chunk_frames=None,
-                     as_pcm16=False, pcm_gain=32767.0, output_rate=None, w_ceil_items=None) -> SynthesisStream:
+                     as_pcm16=False, pcm_gain=32767.0, output_rate=None, w_ceil_items=None, seeds=None) -> SynthesisStream:
         """``infer`` with the audio handed out chunk by chunk (``SynthesisStream``): phase A, the host sync and the flow run here
         (``bv2_stream_begin``), the Generator runs window by window as the caller iterates — ``chunk_frames`` kept frames per chunk
         (``first_chunk_frames`` for the first one: a short first chunk is on the host sooner), each window carrying ``generator_halo``
@@ -949,18 +1042,22 @@ class SynthesizerTrn(nn.Module):
             if y is None:
                 raise ValueError("this model has no speaker table (n_speakers=0): infer_stream() needs y (the reference spectrogram) or g")
             g = self.reference_embedding(y, y_lengths)
-        if noise_w is None:
+        seeds = item_seeds(seeds, B, dev)              # per-utterance noise seeds, as in infer: z_p does not depend on the chunking
+        if seeds is not None and (noise_w is not None or noise_z is not None):
+            raise ValueError("infer_stream: seeds and noise_w / noise_z exclude each other")
+        if noise_w is None and seeds is None:
             noise_w = draw_noise_w(B, T, None)         # drawn either way (the RNG stream stays the reference's); uploaded only if read
         enc = self.encode_durations(x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, noise_w,
                                     noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, length_scale=length_scale,
-                                    bert_index=bert_index, g=g, lean=True)
+                                    bert_index=bert_index, g=g, lean=True, seeds=seeds)
         if w_ceil is not None:
             _substitute_durations(enc, w_ceil, w_ceil_items, B, T, dev)
         yl_host = [int(v) for v in enc["y_lengths"].cpu()]           # the reference's one host sync; every length, for the consumer
         Ty = max(yl_host)
         Ci = hp.inter_channels
-        noise_z = draw_noise_z(B, Ci, Ty, dev) if noise_z is None else noise_z.to(dev, torch.float32)
-        assert noise_z.shape[2] >= Ty and noise_z.shape[1] == Ci
+        if seeds is None:
+            noise_z = draw_noise_z(B, Ci, Ty, dev) if noise_z is None else noise_z.to(dev, torch.float32)
+            assert noise_z.shape[2] >= Ty and noise_z.shape[1] == Ci
         noise_scale, ns_item = item_control("noise_scale", noise_scale, B, None)
         ctl = None
         if ns_item is not None:
@@ -978,10 +1075,10 @@ class SynthesizerTrn(nn.Module):
             raise RuntimeError("bv2_stream_workspace_bytes failed")
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)        # the stream's own: it must stay untouched until the last chunk
         din = L.DecodeIn(B, T, int(Ty), int(frames), _ptr(enc["m_p"]), _ptr(enc["logs_p"]), _ptr(enc["x_mask"]), _ptr(enc["w_ceil"]),
-                         _ptr(enc["y_lengths"]), _ptr(enc["g"]), _ptr(noise_z), noise_z.stride(0), noise_z.stride(1), noise_z.stride(2),
+                         _ptr(enc["y_lengths"]), _ptr(enc["g"]), _ptr(noise_z), *((0, 0, 0) if noise_z is None else noise_z.stride()),
                          float(noise_scale), int(bool(exact_lengths)))
         dout = L.DecodeOut(None, *[_ptr(aux[k]) for k in ("attn", "y_mask", "z", "z_p", "m_p", "logs_p")])
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), self._seeded(seeds):
             self._check(self._lib.bv2_stream_begin(self._handle, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(din),
                                                    C.byref(dout), _controls_ptr(ctl, (3,)), C.c_void_p(ws.data_ptr()), ws.numel()),
                         "bv2_stream_begin")
@@ -990,7 +1087,7 @@ class SynthesizerTrn(nn.Module):
             t1 = min(frames, t + (first if t == 0 else chunk_frames))
             bounds.append((t, t1))
             t = t1
-        self.last_encode = _LastEncode(enc, self, noise_w, noise_scale_w)
+        self.last_encode = _LastEncode(enc, self, noise_w, noise_scale_w, seeds)
         st = SynthesisStream(self, enc, ws, Ty, frames, bounds, window, exact_lengths, as_pcm16, pcm_gain, aux, output_rate)
         st.y_lengths_host = yl_host
         return st
@@ -1173,11 +1270,12 @@ class SynthesizerTrn(nn.Module):
             raise RuntimeError(f"{what}: the model moved to another device after load_posterior(); load it again")
 
     @torch.no_grad()
-    def posterior_encode(self, y, y_lengths, sid=None, g=None, noise_q=None, noise_scale_q=1.0) -> Dict[str, torch.Tensor]:
+    def posterior_encode(self, y, y_lengths, sid=None, g=None, noise_q=None, noise_scale_q=1.0, seeds=None) -> Dict[str, torch.Tensor]:
         """``enc_q(y, y_lengths, g=g)`` (reference models.py:957): ``y`` [B, spec_channels, Ty] the recording's linear spectrogram
         (``audio.spectrogram(wav, ..., net_g.stft_params)``), ``y_lengths`` [B]; the speaker is ``g`` [B, gin] or ``emb_g(sid)``.
         ``noise_q`` [B, inter, Ty] is the N(0, 1) draw of models.py:486, made by the caller like ``noise_w`` / ``noise_z``; ``None`` gives the
-        deterministic ``z = m_q * mask``.  Returns ``z``, ``m_q``, ``logs_q`` [B, inter, Ty], ``y_mask`` [B, 1, Ty] and ``g``."""
+        deterministic ``z = m_q * mask``; ``seeds`` (see ``infer``) computes the draw in the sampling kernel from each item's seed instead
+        (``seeded_noise(seeds, NOISE_Q, inter, Ty)`` as a tensor) and excludes ``noise_q``.  Returns ``z``, ``m_q``, ``logs_q`` [B, inter, Ty], ``y_mask`` [B, 1, Ty] and ``g``."""
         self._need_posterior("posterior_encode")
         if self._blob is None:
             self.repack()
@@ -1193,6 +1291,9 @@ class SynthesizerTrn(nn.Module):
         g = self._speaker_vector(g, B)
         yl = self._i64(y_lengths).reshape(B)
         nq = None
+        seeds = item_seeds(seeds, B, dev)
+        if seeds is not None and noise_q is not None:
+            raise ValueError("posterior_encode: seeds and noise_q exclude each other")
         if noise_q is not None:
             nq = self._f32(noise_q)
             if tuple(nq.shape) != (B, hp.inter_channels, Ty):
@@ -1201,7 +1302,7 @@ class SynthesizerTrn(nn.Module):
         out = dict(z=e(B, hp.inter_channels, Ty), m_q=e(B, hp.inter_channels, Ty), logs_q=e(B, hp.inter_channels, Ty), y_mask=e(B, 1, Ty))
         n = self._lib.bv2_posterior_workspace_bytes(self._handle, B, Ty)
         ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), self._seeded(seeds):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             self._check(self._lib.bv2_posterior_encode(self._handle, stream, B, Ty, _ptr(y), _ptr(yl), _ptr(g), _ptr(nq), float(noise_scale_q),
                                                        _ptr(out["z"]), _ptr(out["m_q"]), _ptr(out["logs_q"]), _ptr(out["y_mask"]),
@@ -1211,16 +1312,20 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def align(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, y, y_lengths, g=None, noise_q=None,
-              want_attn: bool = False, one_call: bool = False) -> Dict:
+              want_attn: bool = False, one_call: bool = False, seeds=None) -> Dict:
         """Text + recording -> frames per symbol, the reference's own aligner (models.py:950-991): phase A for the text's prior,
         ``posterior_encode`` and the forward flow for the recording's latent, ``neg_cent`` and ``maximum_path``.  ``y`` [B, spec_channels,
         Ty] may come straight from ``audio.spectrogram(wav, ..., net_g.stft_params)``.  ``y_lengths`` on the host (list, numpy, CPU
         tensor) are checked against ``x_lengths``.  Returns ``durations`` [B, T] int64, ``y_lengths``, ``score``, the encode dict ``enc``
         (``with_durations(out["enc"], out["durations"])`` is ready for ``decode``), the posterior dict ``posterior`` and, with
         ``want_attn``, ``attn`` and ``neg_cent``.  ``one_call``: everything behind phase A as ONE library call (``bv2_align``: same launches, one
-        workspace, the intermediates stay inside it — ``posterior``, ``z_p`` and ``neg_cent`` are then not returned)."""
+        workspace, the intermediates stay inside it — ``posterior``, ``z_p`` and ``neg_cent`` are then not returned).  ``seeds`` (see ``infer``): the
+        posterior draw comes from each item's seed (excludes ``noise_q``); the same seeds give the same durations."""
         self._need_posterior("align")
         B, T = x.shape
+        seeds = item_seeds(seeds, B, self.device)
+        if seeds is not None and noise_q is not None:
+            raise ValueError("align: seeds and noise_q exclude each other")
         xl_host = None if (isinstance(x_lengths, torch.Tensor) and x_lengths.is_cuda) else [int(v) for v in x_lengths]
         _align.check_lengths(xl_host, y_lengths, T, int(y.shape[2]))
         if g is None and self.hp.n_speakers == 0:
@@ -1236,13 +1341,13 @@ class SynthesizerTrn(nn.Module):
                        attn=torch.empty(B, 1, Ty, T, dtype=torch.float32, device=dev) if want_attn else None, y_lengths=yl, enc=enc)
             n = self._lib.bv2_align_workspace_bytes(self._handle, B, T, Ty)
             ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
+            with torch.cuda.device(dev), self._seeded(seeds):
                 self._check(self._lib.bv2_align(self._handle, C.c_void_p(torch.cuda.current_stream().cuda_stream), B, T, Ty, _ptr(enc["m_p"]),
                                                 _ptr(enc["logs_p"]), _ptr(xl), _ptr(yd), _ptr(yl), _ptr(enc["g"]), _ptr(nq),
                                                 _ptr(out["durations"]), _ptr(out["attn"]), _ptr(out["score"]), C.c_void_p(ws.data_ptr()),
                                                 ws.numel()), "bv2_align")
             return out
-        post = self.posterior_encode(y, torch.as_tensor(y_lengths), g=enc["g"], noise_q=noise_q)
+        post = self.posterior_encode(y, torch.as_tensor(y_lengths), g=enc["g"], noise_q=noise_q, seeds=seeds)
         z_p = self.stage_flow_forward(post["z"], torch.as_tensor(y_lengths), enc["g"])
         out = _align.align_latent(enc, z_p, y_lengths, want_attn=want_attn, x_lengths=x_lengths)
         out["enc"], out["posterior"], out["z_p"] = enc, post, z_p

@@ -31,7 +31,9 @@ class Utterance:
     per phone: what ``align.maximum_path`` returns for a recording of the same text) replaces the predicted durations after phase A — the
     utterance is spoken with that timing and comes back with exactly ``sum(durations) * hop`` samples; ``sdp_ratio``, ``noise_scale_w``
     and ``length_scale`` then change nothing for it.  Graph replay (``enable_graphs``) supports it: the substitution happens between the
-    two captured phases."""
+    two captured phases.  ``seed`` (an int in the int64 range) makes the utterance's noise its own: both draws come from the seeded
+    generator (``SynthesizerTrn.infer(seeds=...)``), so the same utterance with the same seed gets the same noise whatever it is batched
+    with, whichever bucket, lane or chunking serves it."""
     phones: torch.Tensor
     tones: torch.Tensor
     lang_ids: torch.Tensor
@@ -48,8 +50,14 @@ class Utterance:
     # np.ndarray or Tensor [T], whole non-negative numbers.  An init-only argument that __post_init__ validates and stores as an attribute:
     # the dataclass FIELDS still end with g, ref_spec (callers that build an Utterance positionally or walk its fields see what they saw)
     durations: InitVar[Optional[object]] = None
+    seed: InitVar[Optional[int]] = None                # init-only like durations: validated, then stored as an attribute (int or None)
 
-    def __post_init__(self, durations=None):
+    def __post_init__(self, durations=None, seed=None):
+        self.seed = None
+        if seed is not None:
+            if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not -2 ** 63 <= int(seed) < 2 ** 63:
+                raise ValueError("seed must be an int in the int64 range")
+            self.seed = int(seed)
         if self.g is not None and (not isinstance(self.g, torch.Tensor) or self.g.dim() != 1 or self.g.shape[0] < 1):
             raise ValueError("g must be a 1-D tensor [gin]")
         if self.ref_spec is not None and (not isinstance(self.ref_spec, torch.Tensor) or self.ref_spec.dim() != 2
@@ -228,6 +236,8 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     """Synthesise every utterance; returns one 1-D array per utterance in input order (float32 like reference
     infer.py:315-319, or int16 with ``as_pcm16``).  Defaults are the reference web UI's (webui.py:443-454).
     ``noise`` (tests): per utterance a pair ``(noise_w [2,T], noise_z [inter, >= T_y])`` to inject instead of drawing.
+    An utterance with a ``seed`` draws its noise from the seeded generator: its audio then does not depend on the other requests of the
+    call (up to the round-off between batch shapes, INTEGRATION.md "Seeds"); ``noise=`` together with a seeded utterance raises.
     ``requests_in_flight`` > 1: the buckets are dealt round-robin to that many ``replicas`` (own handle + HIP stream, shared
     weights), so one bucket's small-kernel phases overlap another's Generator; results do not depend on it.
     An utterance that carries its own ``sdp_ratio`` / ``noise_scale`` / ``noise_scale_w`` / ``length_scale`` gets it inside the
@@ -239,6 +249,8 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     with ``ceil(n L / M)``, and ``as_pcm16`` normalises by the peak of the resampled samples."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
+    if noise is not None and any(u.seed is not None for u in utts):
+        raise ValueError("noise= (injected tensors) and Utterance(seed=...) exclude each other")
     dev = model.device
     hop = model.hp.total_upsample
     output_rate = _output_rate(model, output_rate)
@@ -317,6 +329,12 @@ def _bucket_inputs(model, utts, idx, dev, noise, gvec):
         # the device (bit-identical to the lookup inside phase A, which reads the same row through the same code)
         rows = model.stage_emb_g(batch["sid"]) if any(gvec[i] is None for i in idx) else None
         kw["g"] = torch.stack([rows[r] if gvec[i] is None else gvec[i] for r, i in enumerate(idx)])
+    if any(utts[i].seed is not None for i in idx):
+        # a bucket with a seeded utterance runs the seeded path; the others get a seed from torch's CPU generator (torch.manual_seed governs them)
+        if noise is not None:
+            raise ValueError("noise= (injected tensors) and Utterance(seed=...) exclude each other")
+        kw["seeds"] = torch.tensor([utts[i].seed if utts[i].seed is not None else
+                                    int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64)) for i in idx], dtype=torch.int64)
     if noise is not None:
         T = batch["x"].shape[1]
         Tz = max(int(noise[i][1].shape[1]) for i in idx)
@@ -353,6 +371,8 @@ def synthesize_stream(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_
     PCM after the resampling); offsets and lengths then count output-rate samples."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
+    if noise is not None and any(u.seed is not None for u in utts):
+        raise ValueError("noise= (injected tensors) and Utterance(seed=...) exclude each other")
     dev = model.device
     hop = model.hp.total_upsample
     output_rate = _output_rate(model, output_rate)
@@ -433,16 +453,17 @@ def align(model, utts: Sequence[Utterance], specs: Optional[Sequence[torch.Tenso
         batch, kw = _bucket_inputs(model, utts, idx, dev, None, gvec)
         B, T = batch["x"].shape
         # the prior does not depend on the duration predictors: sdp_ratio 0 runs the deterministic one only, and its noise is not read
+        seeds = kw.get("seeds")                     # a seeded bucket: the posterior is SAMPLED from each utterance's seed (else z = m_q)
         enc = model.encode_durations(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"], batch["bert"],
-                                     batch["ja_bert"], batch["en_bert"], _models.draw_noise_w(B, T, None), sdp_ratio=0.0, lean=True,
-                                     g=kw.get("g"))
+                                     batch["ja_bert"], batch["en_bert"], None if seeds is not None else _models.draw_noise_w(B, T, None),
+                                     sdp_ratio=0.0, lean=True, g=kw.get("g"), seeds=seeds)
         y_len = [int(latents[i].shape[1]) for i in idx]
         z_p = torch.zeros(B, Ci, max(y_len), dtype=torch.float32, device=dev)
         for r, i in enumerate(idx):
             z_p[r, :, :y_len[r]] = latents[i].to(dev, torch.float32)
         if from_spec:
             yl = torch.tensor(y_len, dtype=torch.int64)
-            z_p = model.stage_flow_forward(model.posterior_encode(z_p, yl, g=enc["g"])["z"], yl, enc["g"])
+            z_p = model.stage_flow_forward(model.posterior_encode(z_p, yl, g=enc["g"], seeds=seeds)["z"], yl, enc["g"])
         out = _align.align_latent(enc, z_p, y_len, x_lengths=[utts[i].length for i in idx])
         dur = out["durations"].cpu().numpy()
         for r, i in enumerate(idx):

@@ -495,6 +495,25 @@ int64_t bv2_align_workspace_bytes(const bv2_handle* h, int B, int T, int Ty);
 int bv2_align(bv2_handle* h, bv2_stream stream, int B, int T, int Ty, const float* m_p, const float* logs_p, const int64_t* x_lengths,
               const float* y, const int64_t* y_lengths, const float* g, const float* noise_q, int64_t* durations, float* attn,
               float* score, void* workspace, int64_t workspace_bytes);
+
+/* ---- per-utterance noise seeds -----------------------------------------------------------------------------------------------
+ * bv2_set_noise_seeds: seeds_dev [B] DEVICE int64, one per batch item; NULL (B ignored) switches it off.  Until switched off every
+ * later call on this handle takes its N(0,1) numbers from a counter-based generator instead of a noise tensor — bv2_encode_durations*
+ * (noise_w), bv2_decode*, bv2_infer*, bv2_stream_begin (noise_z), bv2_posterior_encode, bv2_align (noise_q) and the graph captures —
+ * computed inside the kernels that consume them.  The value at (seed, draw, row, frame) is a pure function of those four numbers
+ * (Philox4x32-10 keyed by the seed, counter (frame, row >> 2, draw, 0), Box-Muller; DESIGN.md "Seeded noise"): it does not depend
+ * on the batch, the item's row in it, T, T_y, its bucket or the handle.  Frames of the prior draw at or past y_lengths[b] are 0.
+ * The noise pointers may then be NULL; a non-NULL noise_w / noise_z / noise_q together with active seeds is an error, and so is a call
+ * whose B differs from the seeds' B.  The array is read when a call RUNS: a captured graph reads it at every replay (a moving input,
+ * like the bv2_item_controls arrays), and it must stay valid until the work that reads it has finished.  Without seeds every call
+ * behaves exactly as before.  The setting belongs to the handle.
+ * bv2_seeded_noise: the same values as a tensor — out[b * bstride + r * rstride + t * tstride] = value(seeds[b], which, r, t) for
+ * r < rows, t < T; which: 0 = noise_w, 1 = noise_z, 2 = noise_q; lengths_dev [B] or NULL: frames at or past lengths[b] are written
+ * as 0.  Asynchronous on `stream`, graph-capturable, no handle (errors: bv2_last_error(NULL)). */
+int bv2_set_noise_seeds(bv2_handle* h, const int64_t* seeds_dev, int32_t B);
+int bv2_seeded_noise(bv2_stream stream, const int64_t* seeds_dev, int32_t B, int32_t which, int32_t rows, int32_t T,
+                     const int64_t* lengths_dev, float* out, int64_t bstride, int64_t rstride, int64_t tstride);
+
 int64_t bv2_maximum_path_workspace_bytes(int32_t B, int32_t T, int32_t Ty);
 int bv2_maximum_path(bv2_stream stream, int32_t B, int32_t T, int32_t Ty, const float* neg_cent, const int64_t* x_lengths,
                      const int64_t* y_lengths, int64_t* durations, float* attn, float* score, void* workspace, int64_t workspace_bytes);

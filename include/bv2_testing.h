@@ -248,6 +248,12 @@ int bv2_test_conv_timeline_report(long long* meta, int max_launches);
 int bv2_test_spline(void* stream, float* z, int src, int dst, const float* params, int prow, const float* mask,
                     float sqrt_fc, float tail, int B, int T);
 
+/* the HOST instantiations of kernels/rng.h (the seeded-noise generator of bv2_set_noise_seeds): Philox4x32-10 itself, and the N(0,1)
+ * value at (seed, which, row, t).  The integer core is the device's code; the host value differs from the device's only by the
+ * rounding of the host's log / sin / cos. */
+void bv2_test_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+float bv2_test_seeded_normal(int64_t seed, int which, int row, int t);
+
 #ifdef __cplusplus
 }
 #endif
