@@ -23,6 +23,7 @@
 
 #include "../../include/bv2_bert.h"
 #include "bv2_internal.h"
+#include "bv2_pack.h"
 
 using namespace bv2;
 
@@ -33,8 +34,6 @@ constexpr int kBertLayout = 1;
 
 // a Linear is a k = 1 ConvW (bv2_internal.h; the Generator-only stream offsets stay -1)
 struct LayerW { ConvW qkv, o, ffn1, ffn2; int64_t g1 = -1, b1 = -1, g2 = -1, b2 = -1, pk = -1, pq = -1; };   // pk / pq: DeBERTa [H][D][2 span]
-
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
 }  // namespace
 
@@ -57,8 +56,8 @@ struct bv2_bert {
 static thread_local std::string g_bert_create_err;
 
 static void lay_lin(ConvW& l, int cin, int cout, int64_t& off, int k = 1) {
-  l.cin = cin; l.cin_pad = rup(cin, 16); l.cout = cout; l.cout_pad = rup(cout, 32); l.w_ld = rup(cout, 128); l.k = k;
-  l.w_off = off; off += (int64_t)k * l.cin_pad * l.w_ld;
+  l = conv_desc(cin, cout, k);
+  l.w_off = off; off += conv_w_floats(l);
   l.b_off = off; off += l.w_ld;
 }
 
@@ -153,9 +152,7 @@ int64_t bv2_bert_packed_bytes(const bv2_bert* h) { return h ? h->total * 4 : -1;
 
 // place W [cout_src][cin] (PyTorch Linear) at output rows [row0, row0 + cout_src) of a fused projection, fragment order
 static void put_linear(float* blob, const ConvW& l, int row0, const float* w, int rows, float scale) {
-  for (int co = 0; co < rows; ++co)
-    for (int ci = 0; ci < l.cin; ++ci)
-      blob[l.w_off + conv_w_index(0, ci, row0 + co, l.cin_pad, 1)] = w[(size_t)co * l.cin + ci] * scale;
+  pack_f32(blob + l.w_off, l.cin, rows, 1, [&](int co, int ci, int) { return w[(size_t)co * l.cin + ci] * scale; }, row0);
 }
 
 int bv2_bert_pack_tensor(bv2_bert* h, void* host_blob, int64_t blob_bytes, const char* hf_key, const float* data,
@@ -200,10 +197,7 @@ int bv2_bert_pack_tensor(bv2_bert* h, void* host_blob, int64_t blob_bytes, const
     else if (k == "encoder.conv.conv.weight") {
       const int kk = c.conv_kernel_size;
       if (!(ndim == 3 && shape[0] == C && shape[1] == C && shape[2] == kk)) return bad();
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C; ++ci)
-          for (int j = 0; j < kk; ++j)
-            blob[h->conv.w_off + conv_w_index(j, ci, co, h->conv.cin_pad, kk)] = data[((size_t)co * C + ci) * kk + j];
+      pack_f32(blob + h->conv.w_off, C, C, kk, [&](int co, int ci, int j) { return data[((size_t)co * C + ci) * kk + j]; });
     }
     else if (k == "encoder.conv.conv.bias") { if (!is1(C)) return bad(); copy(h->conv.b_off, C); }
     else if (k == "encoder.conv.LayerNorm.weight") { if (!is1(C)) return bad(); copy(h->conv_g, C); }
@@ -280,7 +274,7 @@ static BertPlan plan(const bv2_bert* h, Arena& A, int B, int S) {
   const bv2_bert_config& c = h->cfg;
   BertPlan p;
   const int64_t C = c.hidden_size, BS = (int64_t)B * S;
-  p.ld = rup(S, 32);
+  p.ld = round_up(S, 32);
   p.slab = BS * C;
   p.x = A.get<float>(BS * C);
   p.x1 = A.get<float>(BS * C);

@@ -20,10 +20,9 @@
 #include <functional>
 
 #include "bv2_internal.h"
+#include "bv2_pack.h"
 
 namespace bv2 {
-
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 namespace {
 
@@ -37,6 +36,7 @@ struct Packer {
   bool emit_x6 = false;                                    // also write the three-plane bf16 split of the fp32 weights (conv_x6.hip)
 
   bool fill() const { return blob != nullptr; }
+  uint16_t* u16(int64_t off) const { return reinterpret_cast<uint16_t*>(blob + off); }   // a 16-bit stream at a float offset
 
   int64_t alloc(int64_t n) {
     const int64_t off = cursor;
@@ -96,70 +96,24 @@ struct Packer {
     return v;
   }
 
-  // generic conv packer: src(co, ci, j) gives the folded weight, bsrc(co) the bias
+  // generic conv packer: src(co, ci, j) gives the folded weight, bsrc(co) the bias; every stream through its writer in bv2_pack.h
   ConvW conv(int cout, int cin, int k, bool bias, const std::function<float(int, int, int)>& src,
              const std::function<float(int)>& bsrc, bool ok) {
-    ConvW c;
-    c.cin = cin; c.cout = cout; c.k = k;
-    c.cin_pad = round_up(cin, 16); c.cout_pad = round_up(cout, 32); c.w_ld = round_up(cout, 128);
-    c.w_off = alloc((int64_t)k * c.cin_pad * c.w_ld);
+    ConvW c = conv_desc(cin, cout, k);
+    c.w_off = alloc(conv_w_floats(c));
     c.b_off = bias ? alloc(c.cout_pad) : -1;
-    if (emit_bf16 && cin % 16 == 0) c.wb_off = alloc((cl_w_elems(cin, c.cout_pad, k) + 1) / 2);
-    if (emit_f16 && cin % 16 == 0) c.wh_off = alloc((cl_w_elems(cin, c.cout_pad, k) + 1) / 2);
-    if (emit_x6 && cin % 16 == 0) c.wx_off = alloc((x6_w_elems(cin, c.cout_pad, k) + 1) / 2);
+    if (emit_bf16 && cin % 16 == 0) c.wb_off = alloc(cl_w_floats(c));
+    if (emit_f16 && cin % 16 == 0) c.wh_off = alloc(cl_w_floats(c));
+    if (emit_x6 && cin % 16 == 0) c.wx_off = alloc(x6_w_floats(c));
     // ... and the two scaled fp16 planes of the "x3" form of conv_x6.hip / respair_x6.hip (1 / S_w in front)
-    if (emit_x6 && cin % 16 == 0) c.wy_off = alloc(X3_HDR_FLOATS + (x3_w_elems(cin, c.cout_pad, k) + 1) / 2);
+    if (emit_x6 && cin % 16 == 0) c.wy_off = alloc(x3_region_floats(c));
     if (fill() && ok) {
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co)
-            blob[c.w_off + conv_w_index(j, ci, co, c.cin_pad, k)] = src(co, ci, j);
-      if (bias)
-        for (int co = 0; co < cout; ++co) blob[c.b_off + co] = bsrc(co);
-      if (c.wb_off >= 0) {
-        uint16_t* wb = reinterpret_cast<uint16_t*>(blob + c.wb_off);
-        for (int j = 0; j < k; ++j)
-          for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co) wb[cl_w_index(j, ci, co, cin, k)] = f2bf(src(co, ci, j));
-      }
-      if (c.wx_off >= 0) {
-        // w = h1 + h2 + h3 exactly, one bf16 plane each (x6_split / x6_w_index, bv2_kernels.h)
-        uint16_t* wx = reinterpret_cast<uint16_t*>(blob + c.wx_off);
-        for (int j = 0; j < k; ++j)
-          for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co) {
-              uint16_t h[3];
-              x6_split(src(co, ci, j), h);
-              for (int pl = 0; pl < 3; ++pl) wx[x6_w_index(j, ci, co, cin, k, pl)] = h[pl];
-            }
-      }
-      if (c.wy_off >= 0) {
-        // w * S_w = g0 + g1 (x3_w_index, bv2_kernels.h); S_w from the tensor's largest magnitude
-        float wmax = 0.f;
-        for (int j = 0; j < k; ++j)
-          for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co) wmax = std::max(wmax, std::fabs(src(co, ci, j)));
-        uint32_t mb;
-        std::memcpy(&mb, &wmax, 4);
-        const unsigned e = x3_scale_exp(mb);
-        const float S = x3_scale(e);
-        blob[c.wy_off] = x3_scale_inv(e);
-        uint16_t* wy = reinterpret_cast<uint16_t*>(blob + c.wy_off + X3_HDR_FLOATS);
-        for (int j = 0; j < k; ++j)
-          for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co) {
-              const float v = src(co, ci, j) * S;                    // exact: S is a power of two, |v| < 2^15
-              const uint16_t g0 = f2h(v);
-              wy[x3_w_index(j, ci, co, cin, k, 0)] = g0;
-              wy[x3_w_index(j, ci, co, cin, k, 1)] = f2h(v - h2f(g0));
-            }
-      }
-      if (c.wh_off >= 0) {
-        uint16_t* wh = reinterpret_cast<uint16_t*>(blob + c.wh_off);
-        for (int j = 0; j < k; ++j)
-          for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co) wh[cl_w_index(j, ci, co, cin, k)] = f2h(src(co, ci, j));
-      }
+      pack_f32(blob + c.w_off, cin, cout, k, src);
+      if (bias) pack_bias(blob + c.b_off, cout, bsrc);
+      if (c.wb_off >= 0) pack_cl_bf16(u16(c.wb_off), cin, cout, k, src);
+      if (c.wx_off >= 0) pack_x6(u16(c.wx_off), cin, cout, k, src);
+      if (c.wy_off >= 0) blob[c.wy_off] = pack_x3(u16(c.wy_off + X3_HDR_FLOATS), cin, cout, k, src);
+      if (c.wh_off >= 0) pack_cl_f16(u16(c.wh_off), cin, cout, k, src);
     }
     return c;
   }
@@ -167,17 +121,12 @@ struct Packer {
   // bf16-only conv (no fp32 copy): weights as a channels-last fragment stream + fp32 bias
   ConvW conv_cl(int cout, int cin, int k, const std::function<float(int, int, int)>& src,
                 const std::function<float(int)>& bsrc, bool ok) {
-    ConvW c;
-    c.cin = cin; c.cout = cout; c.k = k;
-    c.cin_pad = cin; c.cout_pad = round_up(cout, 32); c.w_ld = c.cout_pad;
+    ConvW c = conv_cl_desc(cin, cout, k);
     c.b_off = alloc(c.cout_pad);
-    c.wb_off = alloc((cl_w_elems(cin, c.cout_pad, k) + 1) / 2);
+    c.wb_off = alloc(cl_w_floats(c));
     if (fill() && ok) {
-      uint16_t* wb = reinterpret_cast<uint16_t*>(blob + c.wb_off);
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co) wb[cl_w_index(j, ci, co, cin, k)] = f2bf(src(co, ci, j));
-      for (int co = 0; co < cout; ++co) blob[c.b_off + co] = bsrc(co);
+      pack_cl_bf16(u16(c.wb_off), cin, cout, k, src);
+      pack_bias(blob + c.b_off, cout, bsrc);
     }
     return c;
   }
@@ -504,55 +453,26 @@ int pack_all(Model& m, Packer& P) {
         }
       }
       P.emit_x6 = false;
-      if (rb2) {                                   // the fused / whole-ResBlock streams describe (conv, conv) pairs: ResBlock1 only
-        m.rbcl_w_off[i][j] = m.rbcl_b_off[i][j] = m.rb16_w_off[i][j] = m.rb16_b_off[i][j] = -1;
-        continue;
-      }
+      m.rbcl_w_off[i][j] = m.rbcl_b_off[i][j] = m.rb16_w_off[i][j] = m.rb16_b_off[i][j] = -1;
+      if (rb2) continue;                           // the fused / whole-ResBlock streams describe (conv, conv) pairs: ResBlock1 only
       // narrow stages: the 2*n_rbd convs of the block once more as ONE contiguous bf16 stream (+ one bias block) for the
-      // whole-ResBlock kernel; copied out of the per-conv streams just written (m-tile 0 = the whole channel dim)
-      m.rbcl_w_off[i][j] = m.rbcl_b_off[i][j] = -1;
-      if (m.n_rbd <= BV2_RBCL_MAX_D && resblock_cl_bf16_supported(ch, k, c.resblock_dilation_sizes[j], m.n_rbd)) {
-        const int U = (ch / 16) * k, Upad = resblock_cl_bf16_units(ch, k);
-        m.rbcl_w_off[i][j] = P.alloc(((int64_t)(2 * m.n_rbd * Upad + RBCL_PD) * 512 + 1) / 2);
-        m.rbcl_b_off[i][j] = P.alloc((int64_t)2 * m.n_rbd * 32);
-        if (P.fill()) {
-          uint16_t* dst = reinterpret_cast<uint16_t*>(P.blob + m.rbcl_w_off[i][j]);
-          for (int d = 0; d < m.n_rbd; ++d)
-            for (int e = 0; e < 2; ++e) {
-              const ConvW& cw = m.rb[i][j][d][e];
-              // TAP-MAJOR unit order (tap j outer, 16-channel group s inner): the kernel's LDS walk then needs one pointer add
-              // per tap and immediate offsets for the groups; the per-conv stream is group-major (unit = s*k + j)
-              const uint16_t* src = reinterpret_cast<const uint16_t*>(P.blob + cw.wb_off);
-              const int G = ch / 16;
-              for (int j2 = 0; j2 < k; ++j2)
-                for (int s2 = 0; s2 < G; ++s2)
-                  std::memcpy(dst + ((int64_t)(2 * d + e) * Upad + (int64_t)j2 * G + s2) * 512, src + ((int64_t)s2 * k + j2) * 512,
-                              sizeof(uint16_t) * 512);
-              (void)U;
-              std::memcpy(P.blob + m.rbcl_b_off[i][j] + (2 * d + e) * 32, P.blob + cw.b_off, sizeof(float) * (size_t)ch);
-            }
-        }
+      // whole-ResBlock kernel, and at C = 16 as the tap-pair stream of resblock_c16_bf16.hip; both rearranged from the per-conv
+      // bf16 streams just written (bv2_pack.h: same bf16 values)
+      const bool rbcl = m.n_rbd <= BV2_RBCL_MAX_D && resblock_cl_bf16_supported(ch, k, c.resblock_dilation_sizes[j], m.n_rbd);
+      if (rbcl) {
+        m.rbcl_w_off[i][j] = P.alloc((rbcl_stream_units(ch, k, m.n_rbd) * 512 + 1) / 2);
+        m.rbcl_b_off[i][j] = P.alloc((int64_t)2 * m.n_rbd * kRbclBiasRow);
       }
-      // C = 16: the tap-pair stream of resblock_c16_bf16.hip, rearranged from the per-conv bf16 stream just written (same bf16 values)
-      m.rb16_w_off[i][j] = m.rb16_b_off[i][j] = -1;
-      if (m.n_rbd <= BV2_RBCL_MAX_D && resblock_c16_bf16_supported(ch, k, c.resblock_dilation_sizes[j], m.n_rbd)) {
-        const int KU = rb16_units(k);
-        m.rb16_w_off[i][j] = P.alloc(((int64_t)2 * m.n_rbd * KU * 512 + 1) / 2);
-        m.rb16_b_off[i][j] = P.alloc((int64_t)2 * m.n_rbd * 16);
-        if (P.fill()) {
-          uint16_t* dst = reinterpret_cast<uint16_t*>(P.blob + m.rb16_w_off[i][j]);
-          std::memset(dst, 0, sizeof(uint16_t) * (size_t)2 * m.n_rbd * KU * 512);
-          for (int d = 0; d < m.n_rbd; ++d)
-            for (int e = 0; e < 2; ++e) {
-              const ConvW& cw = m.rb[i][j][d][e];
-              const uint16_t* src = reinterpret_cast<const uint16_t*>(P.blob + cw.wb_off);
-              uint16_t* cd = dst + (int64_t)(2 * d + e) * KU * 512;
-              for (int co = 0; co < 16; ++co)
-                for (int ci = 0; ci < 16; ++ci)
-                  for (int j2 = 0; j2 < k; ++j2) cd[rb16_w_index(j2, ci, co)] = src[cl_w_index(j2, ci, co, 16, k)];
-              std::memcpy(P.blob + m.rb16_b_off[i][j] + (2 * d + e) * 16, P.blob + cw.b_off, sizeof(float) * 16);
-            }
-        }
+      const bool rb16 = m.n_rbd <= BV2_RBCL_MAX_D && resblock_c16_bf16_supported(ch, k, c.resblock_dilation_sizes[j], m.n_rbd);
+      if (rb16) {
+        m.rb16_w_off[i][j] = P.alloc((rb16_stream_units(k, m.n_rbd) * 512 + 1) / 2);
+        m.rb16_b_off[i][j] = P.alloc((int64_t)2 * m.n_rbd * kRb16BiasRow);
+      }
+      if (!P.fill()) continue;
+      for (int s = 0; s < 2 * m.n_rbd; ++s) {
+        const ConvW& cw = m.rb[i][j][s / 2][s % 2];
+        if (rbcl) rbcl_put_conv(P.u16(m.rbcl_w_off[i][j]), P.blob + m.rbcl_b_off[i][j], s, P.u16(cw.wb_off), P.blob + cw.b_off, ch, k);
+        if (rb16) rb16_put_conv(P.u16(m.rb16_w_off[i][j]), P.blob + m.rb16_b_off[i][j], s, P.u16(cw.wb_off), P.blob + cw.b_off, k);
       }
     }
   }

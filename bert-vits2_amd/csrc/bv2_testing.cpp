@@ -6,22 +6,27 @@
 #include <vector>
 
 #include "bv2_internal.h"
+#include "bv2_pack.h"
 #include "../../include/bv2_testing.h"
 #include "kernels/rng.h"
 
 using namespace bv2;
 
+// a dense weight [cout][cin][k] / bias [cout] (null: zeros) as the sources the writers of bv2_pack.h take
+static auto t_dense(const float* w, int cin, int k) {
+  return [=](int co, int ci, int j) { return w[((size_t)co * cin + ci) * k + j]; };
+}
+static auto t_bias(const float* b) { return [=](int co) { return b ? b[co] : 0.f; }; }
+
 extern "C" {
 
-static inline int t_round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 int64_t bv2_test_conv_pack_floats(int cin, int cout, int k) {
+  const ConvW c = conv_desc(cin, cout, k);
   // + 2048 floats: the register-ring conv kernel prefetches up to 4 units (4 KB) past the last weight unit
   // + the three split-bf16 planes of conv_x6.hip (tile >= TILE_X6), 6 bytes per weight of the 32-row padded matrix
-  const int64_t base = (int64_t)k * t_round_up(cin, 16) * t_round_up(cout, 128) + t_round_up(cout, 32) + 2048;
-  // + the x3 form's region (tile == TILE_X3): two 64-float slots (max |x| in, max |out| back), 1 / S_w, the two fp16 planes
-  return base + (cin % 32 == 0 ? (x6_w_elems(cin, t_round_up(cout, 32), k) + 1) / 2 + 64 +
-                                 2 * X3_SLOT_WORDS + X3_HDR_FLOATS + (x3_w_elems(cin, t_round_up(cout, 32), k) + 1) / 2 + 64 : 0);
+  const int64_t base = conv_w_floats(c) + c.cout_pad + 2048;
+  // + the x3 form's region (tile == TILE_X3): two slots (max |x| in, max |out| back), 1 / S_w, the two fp16 planes
+  return base + (cin % 32 == 0 ? x6_w_floats(c) + 64 + 2 * X3_SLOT_WORDS + x3_region_floats(c) + 64 : 0);
 }
 void bv2_test_x6_split(float v, uint16_t* h3) { x6_split(v, h3); }
 int bv2_test_convert(int kind, const void* in, void* out, int64_t n) {
@@ -41,7 +46,7 @@ int bv2_test_x6_regions(const bv2_handle* h, int64_t* off_floats, int64_t* n_flo
   int n = 0;
   auto add = [&](const ConvW& w) {
     if (w.wx_off < 0) return;
-    if (n < max_regions) { off_floats[n] = w.wx_off; n_floats[n] = (x6_w_elems(w.cin, w.cout_pad, w.k) + 1) / 2; }
+    if (n < max_regions) { off_floats[n] = w.wx_off; n_floats[n] = x6_w_floats(w); }
     ++n;
   };
   for (int i = 0; i < m.n_ups; ++i)
@@ -60,64 +65,37 @@ int bv2_test_x3_regions(const bv2_handle* h, int64_t* off_floats, int64_t* n_flo
         for (int e = 0; e < 2; ++e) {
           const ConvW& w = m.rb[i][j][d][e];
           if (w.wy_off < 0 || w.wx_off < 0) continue;
-          if (n < max_regions) { off_floats[n] = w.wy_off; n_floats[n] = X3_HDR_FLOATS + (x3_w_elems(w.cin, w.cout_pad, w.k) + 1) / 2; }
+          if (n < max_regions) { off_floats[n] = w.wy_off; n_floats[n] = x3_region_floats(w); }
           ++n;
         }
   return n;
 }
 static int64_t t_x6_off(int cin, int cout, int k) {
-  return ((int64_t)k * t_round_up(cin, 16) * t_round_up(cout, 128) + t_round_up(cout, 32) + 2048 + 63) / 64 * 64;
+  const ConvW c = conv_desc(cin, cout, k);
+  return (conv_w_floats(c) + c.cout_pad + 2048 + 63) / 64 * 64;
 }
-
 static int64_t t_x3_off(int cin, int cout, int k) {                 // the x3 region: [slot in] [slot out] (X3_SLOT_WORDS each) [1 / S_w (64)] [planes]
-  return (t_x6_off(cin, cout, k) + (x6_w_elems(cin, t_round_up(cout, 32), k) + 1) / 2 + 64 + 63) / 64 * 64;
+  return (t_x6_off(cin, cout, k) + x6_w_floats(conv_desc(cin, cout, k)) + 64 + 63) / 64 * 64;
 }
 int64_t bv2_test_x3_omax_off(int cin, int cout, int k) { return t_x3_off(cin, cout, k) + X3_SLOT_WORDS; }
 
 // one conv w_host [cout][cin][k] + bias_host [cout] (or null) into a zeroed region of bv2_test_conv_pack_floats(cin, cout, k) floats: the
-// packed fp32 stream (conv_w_index), the bias behind it, with x6 the three bf16 planes at t_x6_off, and with x3 the region at t_x3_off:
+// packed fp32 stream, the bias behind it, with x6 the three bf16 planes at t_x6_off, and with x3 the region at t_x3_off:
 // [max |x| slot] [max |out| slot] (X3_SLOT_WORDS each, left zero) [1 / S_w] (X3_HDR_FLOATS) [the two scaled fp16 planes]
 static void t_pack_conv(float* pk, const float* w_host, const float* bias_host, int cin, int cout, int k, bool x6, bool x3 = false) {
-  const int cin_pad = t_round_up(cin, 16), ld = t_round_up(cout, 128);
-  for (int j = 0; j < k; ++j)
-    for (int ci = 0; ci < cin; ++ci)
-      for (int co = 0; co < cout; ++co)
-        pk[(size_t)conv_w_index(j, ci, co, cin_pad, k)] = w_host[((size_t)co * cin + ci) * k + j];
-  const size_t boff = (size_t)k * cin_pad * ld;
-  if (bias_host) for (int co = 0; co < cout; ++co) pk[boff + co] = bias_host[co];
+  const auto src = t_dense(w_host, cin, k);
+  pack_f32(pk, cin, cout, k, src);
+  if (bias_host) pack_bias(pk + conv_w_floats(conv_desc(cin, cout, k)), cout, t_bias(bias_host));
   if (!x6) return;
-  uint16_t* wx = reinterpret_cast<uint16_t*>(pk + t_x6_off(cin, cout, k));
-  for (int j = 0; j < k; ++j)
-    for (int ci = 0; ci < cin; ++ci)
-      for (int co = 0; co < cout; ++co) {
-        uint16_t hh[3];
-        x6_split(w_host[((size_t)co * cin + ci) * k + j], hh);
-        for (int pl = 0; pl < 3; ++pl) wx[x6_w_index(j, ci, co, cin, k, pl)] = hh[pl];
-      }
+  pack_x6(reinterpret_cast<uint16_t*>(pk + t_x6_off(cin, cout, k)), cin, cout, k, src);
   if (!x3) return;
-  float wmax = 0.f;
-  for (size_t i = 0; i < (size_t)cout * cin * k; ++i) wmax = std::max(wmax, std::fabs(w_host[i]));
-  uint32_t mb;
-  std::memcpy(&mb, &wmax, 4);
-  const unsigned e = x3_scale_exp(mb);
-  float* reg = pk + t_x3_off(cin, cout, k);
-  reg[2 * X3_SLOT_WORDS] = x3_scale_inv(e);
-  uint16_t* wy = reinterpret_cast<uint16_t*>(reg + 2 * X3_SLOT_WORDS + X3_HDR_FLOATS);
-  for (int j = 0; j < k; ++j)
-    for (int ci = 0; ci < cin; ++ci)
-      for (int co = 0; co < cout; ++co) {
-        const float v = w_host[((size_t)co * cin + ci) * k + j] * x3_scale(e);
-        const _Float16 g0 = (_Float16)v;
-        const _Float16 g1 = (_Float16)(v - (float)g0);
-        std::memcpy(&wy[x3_w_index(j, ci, co, cin, k, 0)], &g0, 2);
-        std::memcpy(&wy[x3_w_index(j, ci, co, cin, k, 1)], &g1, 2);
-      }
+  float* reg = pk + t_x3_off(cin, cout, k) + 2 * X3_SLOT_WORDS;
+  reg[0] = pack_x3(reinterpret_cast<uint16_t*>(reg + X3_HDR_FLOATS), cin, cout, k, src);
 }
 // the descriptor of a conv packed by t_pack_conv at float offset `off` of a scratch that plays the blob
 static ConvW t_conv_w(int64_t off, int cin, int cout, int k, bool bias, bool x6) {
-  ConvW w;
-  w.cin = cin; w.cin_pad = t_round_up(cin, 16); w.cout = cout; w.cout_pad = t_round_up(cout, 32); w.w_ld = t_round_up(cout, 128); w.k = k;
-  w.w_off = off; w.b_off = bias ? off + (int64_t)k * w.cin_pad * w.w_ld : -1;
+  ConvW w = conv_desc(cin, cout, k);
+  w.w_off = off; w.b_off = bias ? off + conv_w_floats(w) : -1;
   w.wx_off = x6 ? off + t_x6_off(cin, cout, k) : -1;
   return w;
 }
@@ -128,9 +106,9 @@ int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const flo
                     int mask_post, const float* bias2, int nsrc, const float* x1, const float* x2, float in_scale, int ksplit,
                     int64_t slab_stride) {
   try {
-    const int cin_pad = t_round_up(cin, 16), ld = t_round_up(cout, 128), cout_pad = t_round_up(cout, 32);
+    const ConvW c = conv_desc(cin, cout, k);
     std::vector<float> pk;
-    const size_t boff = (size_t)k * cin_pad * ld;
+    const size_t boff = (size_t)conv_w_floats(c);
     const bool x6 = tile >= TILE_X6 && cin % 32 == 0;
     const bool x3 = tile == TILE_X3 && x6;
     if (w_host) {                                 // w_host == NULL: wpack_dev already holds the packed weight (timing loops)
@@ -161,7 +139,7 @@ int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const flo
     p.bias2 = bias2; p.bias2_bstride = cout;
     p.out = out; p.out_bstride = (int64_t)cout * L; p.out_rstride = L; p.out_tstride = 1; p.out_toff = 0;
     p.res = res; p.res_bstride = p.out_bstride; p.res_mode = res_mode;
-    p.cin = cin; p.cin_pad = cin_pad; p.cout = cout; p.cout_pad = cout_pad; p.w_ld = ld; p.k = k; p.dil = dil;
+    p.cin = cin; p.cin_pad = c.cin_pad; p.cout = cout; p.cout_pad = c.cout_pad; p.w_ld = c.w_ld; p.k = k; p.dil = dil;
     p.pad_left = pad_left < 0 ? ((k - 1) / 2) * dil : pad_left;
     p.pre_act = lrelu_slope != 0.f ? PRE_LRELU : PRE_NONE; p.slope = lrelu_slope;
     p.act = relu ? ACT_RELU : ACT_NONE; p.mask_pre = mask_pre; p.mask_post = mask_post;
@@ -175,18 +153,10 @@ int bv2_test_resblock_fused(void* stream, const float* x, float* out, const floa
                             const float* w2_host, const float* b2_host, float* wpack_dev, int B, int C, int k, int dil, int L,
                             float slope) {
   try {
-    const int cin_pad = t_round_up(C, 16);
-    const size_t one = (size_t)bv2_test_conv_pack_floats(C, C, k), boff = (size_t)k * cin_pad * t_round_up(C, 128);
+    const size_t one = (size_t)bv2_test_conv_pack_floats(C, C, k), boff = (size_t)conv_w_floats(conv_desc(C, C, k));
     std::vector<float> pk(2 * one, 0.f);
-    const float* ws[2] = {w1_host, w2_host};
-    const float* bs[2] = {b1_host, b2_host};
-    for (int h = 0; h < 2; ++h) {
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < C; ++ci)
-          for (int co = 0; co < C; ++co)
-            pk[h * one + (size_t)conv_w_index(j, ci, co, cin_pad, k)] = ws[h][((size_t)co * C + ci) * k + j];
-      for (int co = 0; co < C; ++co) pk[h * one + boff + co] = bs[h][co];
-    }
+    t_pack_conv(pk.data(), w1_host, b1_host, C, C, k, false);
+    t_pack_conv(pk.data() + one, w2_host, b2_host, C, C, k, false);
     if (hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
     FusedLaunch F;
     std::memset(&F, 0, sizeof(F));
@@ -208,28 +178,16 @@ int bv2_test_resblock_cl(void* stream, const void* x, void* out, const float* w_
     if (nd < 1 || nd > BV2_RBCL_MAX_D) return -2;
     if (variant != 0 && variant != 1) return -2;
     if (variant == 1 ? !resblock_c16_bf16_supported(C, k, dil, nd) : !resblock_cl_bf16_supported(C, k, dil, nd)) return -2;
-    const int Upad = resblock_cl_bf16_units(C, k), KU = rb16_units(k), G = C / 16;
-    const int64_t wunits = variant == 1 ? (int64_t)2 * nd * KU : (int64_t)2 * nd * Upad + RBCL_PD;
-    const int brow = variant == 1 ? 16 : 32;
+    // as the packer (bv2_model.cpp): each conv's channels-last bf16 stream, then rearranged into the block's stream
+    const int64_t wunits = variant == 1 ? rb16_stream_units(k, nd) : rbcl_stream_units(C, k, nd);
     std::vector<uint16_t> pk((size_t)wunits * 512, 0);
-    std::vector<float> pb((size_t)2 * nd * brow, 0.f);
-    for (int d = 0; d < nd; ++d)
-      for (int e = 0; e < 2; ++e) {
-        const float* w = w_host + (size_t)(2 * d + e) * C * C * k;
-        for (int co = 0; co < C; ++co) {
-          pb[(size_t)(2 * d + e) * brow + co] = bias_host[(size_t)(2 * d + e) * C + co];
-          for (int ci = 0; ci < C; ++ci)
-            for (int j = 0; j < k; ++j) {
-              const uint16_t v = f2bf(w[((size_t)co * C + ci) * k + j]);
-              if (variant == 1) {
-                pk[(size_t)(2 * d + e) * KU * 512 + (size_t)rb16_w_index(j, ci, co)] = v;
-              } else {                                  // tap-major units of m-tile 0 (bv2_model.cpp): unit = tap * G + group
-                const int64_t in_unit = cl_w_index(j, ci, co, C, k) % 512;
-                pk[((size_t)(2 * d + e) * Upad + (size_t)j * G + ci / 16) * 512 + (size_t)in_unit] = v;
-              }
-            }
-        }
-      }
+    std::vector<float> pb((size_t)2 * nd * (variant == 1 ? kRb16BiasRow : kRbclBiasRow), 0.f);
+    for (int s = 0; s < 2 * nd; ++s) {
+      std::vector<uint16_t> cl((size_t)cl_w_elems(C, round_up(C, 32), k), 0);
+      pack_cl_bf16(cl.data(), C, C, k, t_dense(w_host + (size_t)s * C * C * k, C, k));
+      if (variant == 1) rb16_put_conv(pk.data(), pb.data(), s, cl.data(), bias_host + (size_t)s * C, k);
+      else rbcl_put_conv(pk.data(), pb.data(), s, cl.data(), bias_host + (size_t)s * C, C, k);
+    }
     char* base = static_cast<char*>(wpack_dev);
     const size_t wbytes = pk.size() * 2, boff = (wbytes + 255) / 256 * 256;
     if (hipMemcpy(base, pk.data(), wbytes, hipMemcpyHostToDevice) != hipSuccess) return -6;
@@ -253,11 +211,7 @@ int bv2_test_respair_cl(void* stream, const void* x, void* out, const float* w_h
     if (!respair_cl_bf16_supported(C, k, dil)) return -2;
     const int64_t ne = cl_w_elems(C, C, k);
     std::vector<uint16_t> pk((size_t)2 * ne, 0);
-    for (int e = 0; e < 2; ++e)
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C; ++ci)
-          for (int j = 0; j < k; ++j)
-            pk[(size_t)e * ne + (size_t)cl_w_index(j, ci, co, C, k)] = f2bf(w_host[(((size_t)e * C + co) * C + ci) * k + j]);
+    for (int e = 0; e < 2; ++e) pack_cl_bf16(pk.data() + e * ne, C, C, k, t_dense(w_host + (size_t)e * C * C * k, C, k));
     char* base = static_cast<char*>(wpack_dev);
     const size_t wbytes = pk.size() * 2 + 8192, boff = (wbytes + 255) / 256 * 256;     // + slack: the rings run a few units past a stream's end
     if (hipMemset(base, 0, boff + (size_t)2 * C * 4) != hipSuccess) return -6;
@@ -277,35 +231,22 @@ int bv2_test_respair_cl(void* stream, const void* x, void* out, const float* w_h
 int64_t bv2_test_respair_cl_pack_bytes(int C, int k) { return cl_w_elems(C, C, k) * 4 + 8192 + 256 + (int64_t)2 * C * 4; }
 
 int64_t bv2_test_respair_x6_pack_bytes(int C, int k) { return x6_w_elems(C, (C + 31) / 32 * 32, k) * 4 + 16384 + 256 + (int64_t)2 * 32 * 4 + (int64_t)2 * C * 4 + 1024; }
-static int t_respair_x3(void* stream, const float* x, float* out, const float* w_host, const float* bias_host, void* wpack_dev, int B,
-                        int C, int k, int dil, int L, float slope, const int64_t* lens) {
+// the C = 32 pair from the three bf16 planes of each conv (x3 = false) or from their two scaled fp16 planes.  Scratch: [planes of conv 1]
+// [of conv 2] [16 KB ring slack], then 256-byte aligned [b1] [b2] (cout_pad floats each) [1 / S_w of conv 1] [of conv 2] (64 floats each)
+static int t_respair_x(bool x3, void* stream, const float* x, float* out, const float* w_host, const float* bias_host, void* wpack_dev,
+                       int B, int C, int k, int dil, int L, float slope, const int64_t* lens) {
   try {
     if (!respair_x6_supported(C, k, dil)) return -2;
-    const int cout_pad = t_round_up(C, 32);
-    const int64_t ne = x3_w_elems(C, cout_pad, k);
+    const int cout_pad = round_up(C, 32);
+    const int64_t ne = x3 ? x3_w_elems(C, cout_pad, k) : x6_w_elems(C, cout_pad, k);
     std::vector<uint16_t> pk((size_t)2 * ne, 0);
-    float inv[2];
-    for (int e = 0; e < 2; ++e) {
-      float wmax = 0.f;
-      for (size_t i = 0; i < (size_t)C * C * k; ++i) wmax = std::max(wmax, std::fabs(w_host[(size_t)e * C * C * k + i]));
-      uint32_t mb;
-      std::memcpy(&mb, &wmax, 4);
-      const unsigned ex = x3_scale_exp(mb);
-      inv[e] = x3_scale_inv(ex);
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C; ++ci)
-          for (int j = 0; j < k; ++j) {
-            const float v = w_host[(((size_t)e * C + co) * C + ci) * k + j] * x3_scale(ex);
-            const _Float16 g0 = (_Float16)v;
-            const _Float16 g1 = (_Float16)(v - (float)g0);
-            std::memcpy(&pk[(size_t)e * ne + (size_t)x3_w_index(j, ci, co, C, k, 0)], &g0, 2);
-            std::memcpy(&pk[(size_t)e * ne + (size_t)x3_w_index(j, ci, co, C, k, 1)], &g1, 2);
-          }
-    }
     std::vector<float> pb((size_t)2 * cout_pad + 128, 0.f);
-    for (int e = 0; e < 2; ++e)
-      for (int co = 0; co < C; ++co) pb[(size_t)e * cout_pad + co] = bias_host[(size_t)e * C + co];
-    pb[(size_t)2 * cout_pad] = inv[0]; pb[(size_t)2 * cout_pad + 64] = inv[1];
+    for (int e = 0; e < 2; ++e) {
+      const auto src = t_dense(w_host + (size_t)e * C * C * k, C, k);
+      if (x3) pb[(size_t)2 * cout_pad + 64 * e] = pack_x3(pk.data() + e * ne, C, C, k, src);
+      else pack_x6(pk.data() + e * ne, C, C, k, src);
+      pack_bias(pb.data() + (size_t)e * cout_pad, C, t_bias(bias_host + (size_t)e * C));
+    }
     char* base = static_cast<char*>(wpack_dev);
     const size_t wbytes = pk.size() * 2 + 16384, boff = (wbytes + 255) / 256 * 256;
     if (hipMemset(base, 0, boff + pb.size() * 4) != hipSuccess) return -6;
@@ -316,51 +257,20 @@ static int t_respair_x3(void* stream, const float* x, float* out, const float* w
     F.nprob = 1; F.B = B; F.C = C; F.L = L; F.slope = slope; F.lens = lens; F.len_mul = 1;
     FusedProb& q = F.p[0];
     q.x = x; q.out = out; q.k = k; q.dil = dil;
-    q.w31 = reinterpret_cast<const uint16_t*>(base); q.w32 = q.w31 + ne;
-    q.w61 = q.w31; q.w62 = q.w32;                    // (the launcher insists on them; not read by the x3 form)
+    q.w61 = reinterpret_cast<const uint16_t*>(base); q.w62 = q.w61 + ne;      // (the launcher insists on them; not read by the x3 form)
     q.b1 = reinterpret_cast<const float*>(base + boff); q.b2 = q.b1 + cout_pad;
-    q.w3inv1 = q.b1 + 2 * cout_pad; q.w3inv2 = q.w3inv1 + 64;
-    q.w1 = q.b1; q.w2 = q.b1;
+    if (x3) { q.w31 = q.w61; q.w32 = q.w62; q.w3inv1 = q.b1 + 2 * cout_pad; q.w3inv2 = q.w3inv1 + 64; }
+    q.w1 = q.b1; q.w2 = q.b1;                        // the fp32 streams are not read by this kernel
     return launch_respair_x6(static_cast<hipStream_t>(stream), F);
   } catch (...) { return -100; }
 }
 int bv2_test_respair_x3(void* stream, const float* x, float* out, const float* w_host, const float* bias_host, void* wpack_dev, int B,
                         int C, int k, int dil, int L, float slope, const int64_t* lens) {
-  return t_respair_x3(stream, x, out, w_host, bias_host, wpack_dev, B, C, k, dil, L, slope, lens);
+  return t_respair_x(true, stream, x, out, w_host, bias_host, wpack_dev, B, C, k, dil, L, slope, lens);
 }
 int bv2_test_respair_x6(void* stream, const float* x, float* out, const float* w_host, const float* bias_host, void* wpack_dev, int B,
                         int C, int k, int dil, int L, float slope, const int64_t* lens) {
-  try {
-    if (!respair_x6_supported(C, k, dil)) return -2;
-    const int cout_pad = t_round_up(C, 32);
-    const int64_t ne = x6_w_elems(C, cout_pad, k);
-    std::vector<uint16_t> pk((size_t)2 * ne, 0);
-    for (int e = 0; e < 2; ++e)
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C; ++ci)
-          for (int j = 0; j < k; ++j) {
-            uint16_t h3[3];
-            x6_split(w_host[(((size_t)e * C + co) * C + ci) * k + j], h3);
-            for (int pl = 0; pl < 3; ++pl) pk[(size_t)e * ne + (size_t)x6_w_index(j, ci, co, C, k, pl)] = h3[pl];
-          }
-    std::vector<float> pb((size_t)2 * cout_pad, 0.f);
-    for (int e = 0; e < 2; ++e)
-      for (int co = 0; co < C; ++co) pb[(size_t)e * cout_pad + co] = bias_host[(size_t)e * C + co];
-    char* base = static_cast<char*>(wpack_dev);
-    const size_t wbytes = pk.size() * 2 + 16384, boff = (wbytes + 255) / 256 * 256;
-    if (hipMemset(base, 0, boff + pb.size() * 4) != hipSuccess) return -6;
-    if (hipMemcpy(base, pk.data(), pk.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    if (hipMemcpy(base + boff, pb.data(), pb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    FusedLaunch F;
-    std::memset(&F, 0, sizeof(F));
-    F.nprob = 1; F.B = B; F.C = C; F.L = L; F.slope = slope; F.lens = lens; F.len_mul = 1;
-    FusedProb& q = F.p[0];
-    q.x = x; q.out = out; q.k = k; q.dil = dil;
-    q.w61 = reinterpret_cast<const uint16_t*>(base); q.w62 = q.w61 + ne;
-    q.b1 = reinterpret_cast<const float*>(base + boff); q.b2 = q.b1 + cout_pad;
-    q.w1 = q.b1; q.w2 = q.b1;                        // the fp32 streams are not read by this kernel
-    return launch_respair_x6(static_cast<hipStream_t>(stream), F);
-  } catch (...) { return -100; }
+  return t_respair_x(false, stream, x, out, w_host, bias_host, wpack_dev, B, C, k, dil, L, slope, lens);
 }
 
 int bv2_test_flow_boundary(void* stream, const float* a, int nslab, int64_t slab_stride, const float* gamma, const float* beta,
@@ -369,16 +279,12 @@ int bv2_test_flow_boundary(void* stream, const float* a, int nslab, int64_t slab
   try {
     const int C1 = C / 2;
     // two 1x1 convs in the packed conv layout (conv_w_index, k = 1): post C -> C1, pre C1 -> C
-    const size_t npost = (size_t)t_round_up(C, 16) * t_round_up(C1, 128), npre = (size_t)t_round_up(C1, 16) * t_round_up(C, 128);
-    std::vector<float> pk(npost + npre + (size_t)C1 + (size_t)C + 64, 0.f);
-    for (int co = 0; co < C1; ++co)
-      for (int ci = 0; ci < C; ++ci) pk[(size_t)conv_w_index(0, ci, co, t_round_up(C, 16), 1)] = post_w_host[(size_t)co * C + ci];
-    if (pre_w_host)
-      for (int co = 0; co < C; ++co)
-        for (int ci = 0; ci < C1; ++ci) pk[npost + (size_t)conv_w_index(0, ci, co, t_round_up(C1, 16), 1)] = pre_w_host[(size_t)co * C1 + ci];
-    for (int co = 0; co < C1; ++co) pk[npost + npre + co] = post_b_host[co];
-    if (pre_b_host)
-      for (int co = 0; co < C; ++co) pk[npost + npre + C1 + co] = pre_b_host[co];
+    const size_t npost = (size_t)conv_w_floats(conv_desc(C, C1, 1)), npre = (size_t)conv_w_floats(conv_desc(C1, C, 1));
+    std::vector<float> pk((size_t)bv2_test_flow_boundary_pack_floats(C), 0.f);
+    pack_f32(pk.data(), C, C1, 1, t_dense(post_w_host, C, 1));
+    if (pre_w_host) pack_f32(pk.data() + npost, C1, C, 1, t_dense(pre_w_host, C1, 1));
+    pack_bias(pk.data() + npost + npre, C1, t_bias(post_b_host));
+    if (pre_b_host) pack_bias(pk.data() + npost + npre + C1, C, t_bias(pre_b_host));
     if (hipMemcpy(wpack_dev, pk.data(), pk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
     FbArgs F;
     std::memset(&F, 0, sizeof(F));
@@ -392,31 +298,37 @@ int bv2_test_flow_boundary(void* stream, const float* a, int nslab, int64_t slab
 }
 int64_t bv2_test_flow_boundary_pack_floats(int C) {
   const int C1 = C / 2;
-  return (int64_t)t_round_up(C, 16) * t_round_up(C1, 128) + (int64_t)t_round_up(C1, 16) * t_round_up(C, 128) + C1 + C + 64;
+  return conv_w_floats(conv_desc(C, C1, 1)) + conv_w_floats(conv_desc(C1, C, 1)) + C1 + C + 64;
 }
 
 int64_t bv2_test_conv_cl_pack_bytes(int cin, int cout, int k) {
-  return cl_w_elems(cin, t_round_up(cout, 32), k) * 2 + (int64_t)t_round_up(cout, 32) * 4;
+  return cl_w_elems(cin, round_up(cout, 32), k) * 2 + (int64_t)round_up(cout, 32) * 4;
 }
+}  // extern "C"
+// a conv's channels-last stream (bf16, or fp16) and, behind it, its zero-padded bias row to the device: bv2_test_conv_cl_pack_bytes bytes
+template <class Src, class BSrc>
+static bool t_upload_cl(void* dev, bool f16, int cin, int cout, int k, const Src& src, const BSrc& bsrc) {
+  const int cout_pad = round_up(cout, 32);
+  const int64_t ne = cl_w_elems(cin, cout_pad, k);
+  std::vector<uint16_t> pk((size_t)ne, 0);
+  if (f16) pack_cl_f16(pk.data(), cin, cout, k, src);
+  else pack_cl_bf16(pk.data(), cin, cout, k, src);
+  std::vector<float> bb((size_t)cout_pad, 0.f);
+  pack_bias(bb.data(), cout, bsrc);
+  return hipMemcpy(dev, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(static_cast<char*>(dev) + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) == hipSuccess;
+}
+extern "C" {
 
 int bv2_test_conv_cl_bf16(void* stream, const void* x0, const void* x1, const void* x2, int nsrc, const float* w_host,
                           const float* bias_host, void* wpack_dev, void* out, const void* res, const float* bias2, int B, int cin,
                           int cout, int k, int dil, int pad_left, int L, int pre_lrelu, float slope) {
   try {
     if (!conv_cl_bf16_supported(cin, cout, k, dil)) return -2;
-    const int cout_pad = t_round_up(cout, 32);
+    const int cout_pad = round_up(cout, 32);
     const int64_t ne = cl_w_elems(cin, cout_pad, k);
-    if (w_host) {
-      std::vector<uint16_t> pk((size_t)ne, 0);
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co)
-            pk[(size_t)cl_w_index(j, ci, co, cin, k)] = f2bf(w_host[((size_t)co * cin + ci) * k + j]);
-      std::vector<float> bb((size_t)cout_pad, 0.f);
-      if (bias_host) for (int co = 0; co < cout; ++co) bb[(size_t)co] = bias_host[co];
-      if (hipMemcpy(wpack_dev, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-      if (hipMemcpy(static_cast<char*>(wpack_dev) + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    }
+    // w_host == NULL: wpack_dev already holds the packed weight (timing loops)
+    if (w_host && !t_upload_cl(wpack_dev, false, cin, cout, k, t_dense(w_host, cin, k), t_bias(bias_host))) return -6;
     ClLaunch cl;
     std::memset(&cl, 0, sizeof(cl));
     ClProb& p = cl.p[0];
@@ -438,40 +350,9 @@ int bv2_test_conv_cl_bf16(void* stream, const void* x0, const void* x1, const vo
 int bv2_test_conv_f16(void* stream, const void* x, int in_ct, const float* in_mask, const float* w_host, const float* bias_host,
                       void* wpack_dev, void* out, int out_ct, const float* res, int res_mode, const float* out_mask, int mask_pre,
                       int mask_post, int act, int B, int cin, int cout, int k, int dil, int L, int out_rstride) {
-  try {
-    if (!conv_f16_supported(cin, cout, k, dil, !out_ct)) return -2;
-    const int cout_pad = t_round_up(cout, 32);
-    const int64_t ne = cl_w_elems(cin, cout_pad, k);
-    if (w_host) {
-      std::vector<uint16_t> pk((size_t)ne, 0);
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co) {
-            const _Float16 hv = (_Float16)w_host[((size_t)co * cin + ci) * k + j];
-            std::memcpy(&pk[(size_t)cl_w_index(j, ci, co, cin, k)], &hv, 2);
-          }
-      std::vector<float> bb((size_t)cout_pad, 0.f);
-      if (bias_host) for (int co = 0; co < cout; ++co) bb[(size_t)co] = bias_host[co];
-      if (hipMemcpy(wpack_dev, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-      if (hipMemcpy(static_cast<char*>(wpack_dev) + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    }
-    HcLaunch hl;
-    std::memset(&hl, 0, sizeof(hl));
-    hl.nprob = 1;
-    HcProb& p = hl.p[0];
-    p.x = x; p.in_ct = in_ct; p.x_bstride = (int64_t)cin * L; p.x_rstride = L; p.Lin = L;
-    p.in_mask = in_mask; p.in_mask_bstride = L;
-    p.w = static_cast<const uint16_t*>(wpack_dev);
-    p.bias = bias_host ? reinterpret_cast<const float*>(static_cast<char*>(wpack_dev) + ne * 2) : nullptr;
-    p.out = out; p.out_ct = out_ct;
-    p.out_rstride = out_ct ? (out_rstride > 0 ? out_rstride : L) : 0;
-    p.out_bstride = out_ct ? (int64_t)cout * p.out_rstride : (int64_t)cout * L;
-    p.res = res; p.res_bstride = p.out_bstride; p.res_mode = res_mode;
-    p.out_mask = out_mask; p.out_mask_bstride = L; p.mask_pre = mask_pre; p.mask_post = mask_post; p.act = act;
-    p.cin = cin; p.cout = cout; p.cout_pad = cout_pad; p.k = k; p.dil = dil; p.pad_left = ((k - 1) / 2) * dil;
-    hl.B = B; hl.L = L;
-    return launch_conv_f16(static_cast<hipStream_t>(stream), hl, nullptr);
-  } catch (...) { return -100; }
+  return bv2_test_conv_f16_ex(stream, x, in_ct, in_mask, w_host, bias_host, wpack_dev, out, out_ct, res, res_mode, out_mask, mask_pre,
+                              mask_post, act, B, cin, cout, k, dil, L, out_rstride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              0, 0, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
 int bv2_test_dump_cl_conv(bv2_handle* h, const void* host_blob, int kind, int i, int j, int d, int e, int32_t* dims,
@@ -530,9 +411,7 @@ int bv2_test_dump_cl_conv(bv2_handle* h, const void* host_blob, int kind, int i,
             }
             float f;
             if (half) {
-              _Float16 hv;
-              std::memcpy(&hv, &wb[idx], 2);
-              f = (float)hv;
+              f = h2f(wb[idx]);
             } else {
               const uint32_t u = (uint32_t)wb[idx] << 16;
               std::memcpy(&f, &u, 4);
@@ -548,27 +427,21 @@ int bv2_test_dump_cl_conv(bv2_handle* h, const void* host_blob, int kind, int i,
 
 int bv2_test_attention(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out,
                        int B, int H, int D, int T, int W) {
-  AttnArgs a;
-  a.qkv = qkv; a.ld = ld; a.mask = mask; a.erv = erv; a.out = out; a.B = B; a.H = H; a.D = D; a.T = T; a.W = W; a.f16 = 0;
-  return launch_attention(static_cast<hipStream_t>(stream), a);
+  return bv2_test_attention_q(stream, qkv, ld, mask, erv, out, B, H, D, T, W, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              0, 0, 1, nullptr, 0);
 }
 
 int bv2_test_attention_f16(void* stream, const float* qkv, int ld, const float* mask, const float* erv, float* out,
                            int B, int H, int D, int T, int W) {
-  AttnArgs a;
-  a.qkv = qkv; a.ld = ld; a.mask = mask; a.erv = erv; a.out = out; a.B = B; a.H = H; a.D = D; a.T = T; a.W = W; a.f16 = 1;
-  return launch_attention(static_cast<hipStream_t>(stream), a);
+  return bv2_test_attention_q(stream, qkv, ld, mask, erv, out, B, H, D, T, W, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              0, 0, 1, nullptr, 0);
 }
 
 int bv2_test_layernorm(void* stream, const float* a, const float* add, int mode, const float* dww, const float* dwb, int dil,
                        const float* in_mask, const float* gamma, const float* beta, int post_gelu, const float* res,
                        const float* vec, const float* mask, float* out, int B, int C, int T, int nslab, int64_t slab_stride) {
-  LnArgs l;
-  std::memset(&l, 0, sizeof(l));
-  l.a = a; l.add = add; l.nslab = nslab; l.slab_stride = slab_stride; l.mode = mode; l.dww = dww; l.dwb = dwb; l.dil = dil; l.in_mask = in_mask;
-  l.gamma = gamma; l.beta = beta; l.eps = 1e-5f; l.post_gelu = post_gelu; l.res = res; l.vec = vec; l.vec_bstride = C;
-  l.mask = mask; l.out = out; l.B = B; l.C = C; l.T = T;
-  return launch_layernorm(static_cast<hipStream_t>(stream), l);
+  return bv2_test_layernorm_ex(stream, a, add, mode, dww, dwb, dil, in_mask, gamma, beta, post_gelu, res, vec, mask, out, B, C, T, nslab,
+                               slab_stride, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
 // ---- the Encoder layer's fused launch forms (tests/test_encoder_forms_gpu.py): the three launchers above with every field of the
@@ -594,10 +467,9 @@ int bv2_test_attention_q(void* stream, const float* qkv, int ld, const float* ma
     a.kh = static_cast<const uint16_t*>(kh); a.vh = static_cast<const uint16_t*>(vh);
     if (wo_host) {
       if (!wo_pack_dev || Co < 1 || H < 1 || D < 1) return -1;
-      const int cin = H * D, cin_pad = t_round_up(cin, 16);
-      std::vector<float> pk((size_t)t_round_up(Co, 32) * cin_pad, 0.f);      // rows padded to whole 32-row tiles (zero)
-      for (int co = 0; co < Co; ++co)
-        for (int ci = 0; ci < cin; ++ci) pk[(size_t)conv_w_index(0, ci, co, cin_pad, 1)] = wo_host[(size_t)co * cin + ci];
+      const int cin = H * D, cin_pad = round_up(cin, 16);
+      std::vector<float> pk((size_t)round_up(Co, 32) * cin_pad, 0.f);        // rows padded to whole 32-row tiles (zero)
+      pack_f32(pk.data(), cin, Co, 1, t_dense(wo_host, cin, 1));
       if (hipMemcpy(wo_pack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
       a.wo = wo_pack_dev; a.wo_groups = cin_pad / 8;
     }
@@ -631,7 +503,7 @@ int bv2_test_conv_f16_ex(void* stream, const void* x, int in_ct, const float* in
                          const float* p1_w_host, const float* p1_bias_host, void* p1_out, const float* p1_res, int p1_res_mode) {
   try {
     if (!conv_f16_supported(cin, cout, k, dil, !out_ct)) return -2;
-    const int cout_pad = t_round_up(cout, 32);
+    const int cout_pad = round_up(cout, 32);
     const int64_t ne = cl_w_elems(cin, cout_pad, k);
     const int64_t one = bv2_test_conv_cl_pack_bytes(cin, cout, k);          // problem i's weights + bias at wpack_dev + i * one
     HcLaunch hl;
@@ -641,17 +513,8 @@ int bv2_test_conv_f16_ex(void* stream, const void* x, int in_ct, const float* in
     const float* bs[2] = {bias_host, p1_bias_host};
     for (int i = 0; i < hl.nprob; ++i) {
       char* base = static_cast<char*>(wpack_dev) + (size_t)i * one;
-      std::vector<uint16_t> pk((size_t)ne, 0);
-      for (int j = 0; j < k; ++j)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int co = 0; co < cout; ++co) {
-            const _Float16 hv = (_Float16)ws[i][((size_t)co * cin + ci) * k + j];
-            std::memcpy(&pk[(size_t)cl_w_index(j, ci, co, cin, k)], &hv, 2);
-          }
-      std::vector<float> bb((size_t)cout_pad, 0.f);
-      if (bs[i]) for (int co = 0; co < cout; ++co) bb[(size_t)co] = bs[i][co];
-      if (hipMemcpy(base, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-      if (hipMemcpy(base + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
+      // w_host == NULL (problem 0 only): wpack_dev already holds the packed weight (timing loops)
+      if (ws[i] && !t_upload_cl(base, true, cin, cout, k, t_dense(ws[i], cin, k), t_bias(bs[i]))) return -6;
       HcProb& p = hl.p[i];
       p.x = x; p.in_ct = in_ct; p.x_bstride = (int64_t)cin * L; p.x_rstride = L; p.Lin = L;
       p.in_mask = in_mask; p.in_mask_bstride = L;
@@ -706,16 +569,12 @@ int bv2_test_dds_layer(void* stream, const float* x, const float* pre_w_host, co
     auto put = [&](const float* src, size_t n) { size_t at = o; if (src) std::memcpy(&pk[o], src, n * sizeof(float)); o += n; return at; };
     const size_t o_dww = put(dww_host, 3 * (size_t)C), o_dwb = put(dwb_host, C), o_g1 = put(g1_host, C), o_b1 = put(b1_host, C),
                  o_g2 = put(g2_host, C), o_b2 = put(b2_host, C), o_pw = put(pre_w_host, C), o_pb = put(pre_b_host, C);
-    const int cin_pad = t_round_up(C, 16), ld = t_round_up(C, 128);
-    const size_t o_w = o, boff = (size_t)cin_pad * ld;
-    for (int ci = 0; ci < C; ++ci)
-      for (int co = 0; co < C; ++co) pk[o_w + (size_t)conv_w_index(0, ci, co, cin_pad, 1)] = w_host[(size_t)co * C + ci];
-    for (int co = 0; co < C; ++co) pk[o_w + boff + co] = bias_host[co];
+    const size_t o_w = o, boff = (size_t)conv_w_floats(conv_desc(C, C, 1));   // both convs keep their bias boff behind their weights
+    t_pack_conv(&pk[o_w], w_host, bias_host, C, C, 1, false);
     const size_t o_p = o_w + (size_t)one;
     if (post_w_host) {
-      for (int ci = 0; ci < C; ++ci)
-        for (int co = 0; co < post_cout; ++co) pk[o_p + (size_t)conv_w_index(0, ci, co, cin_pad, 1)] = post_w_host[(size_t)co * C + ci];
-      if (post_b_host) for (int co = 0; co < post_cout; ++co) pk[o_p + boff + co] = post_b_host[co];
+      pack_f32(&pk[o_p], C, post_cout, 1, t_dense(post_w_host, C, 1));
+      if (post_b_host) pack_bias(&pk[o_p + boff], post_cout, t_bias(post_b_host));
     }
     if (hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
     DdsArgs a;
@@ -726,7 +585,7 @@ int bv2_test_dds_layer(void* stream, const float* x, const float* pre_w_host, co
     a.g2 = wpack_dev + o_g2; a.b2 = wpack_dev + o_b2; a.w = wpack_dev + o_w; a.bias = wpack_dev + o_w + boff;
     a.out = out; a.dil = dil; a.last_mask = last_mask; a.eps = 1e-5f;
     if (post_w_host) {
-      a.post_w = wpack_dev + o_p; a.post_b = wpack_dev + o_p + boff; a.post_cout = post_cout; a.post_cout_pad = t_round_up(post_cout, 32);
+      a.post_w = wpack_dev + o_p; a.post_b = wpack_dev + o_p + boff; a.post_cout = post_cout; a.post_cout_pad = round_up(post_cout, 32);
       a.post_out = post_out; a.zio = zio; a.z_src = z_src; a.z_dst = z_dst; a.sqrt_fc = std::sqrt((float)C); a.tail = 5.0f;
     }
     a.B = B; a.C = C; a.T = T;
@@ -853,8 +712,7 @@ int bv2_test_conv_transpose(void* stream, const float* w_host, const float* bias
 int64_t bv2_test_conv_transpose_cl_pack_bytes(int u, int k, int cin, int cout) {
   UpsGeom G;
   if (!ups_geometry(u, k, G) || cin % 16) return -2;
-  const int cout_pad = t_round_up(u * cout, 32);
-  return cl_w_elems(cin, cout_pad, G.cl_k) * 2 + (int64_t)cout_pad * 4;
+  return bv2_test_conv_cl_pack_bytes(cin, u * cout, G.cl_k);
 }
 int bv2_test_conv_transpose_cl(void* stream, const float* w_host, const float* bias_host, int u, int k, int cin, int cout, const void* x0,
                                const void* x1, const void* x2, int nsrc, void* out, const int64_t* lens, int len_mul, int B, int L,
@@ -863,24 +721,15 @@ int bv2_test_conv_transpose_cl(void* stream, const float* w_host, const float* b
     UpsGeom G;
     if (!ups_geometry(u, k, G) || !w_host || !bias_host || nsrc < 1 || nsrc > 3) return -2;
     if (!conv_cl_bf16_supported(cin, u * cout, G.cl_k, 1)) return -2;
-    const int cout_pad = t_round_up(u * cout, 32);
-    const int64_t ne = cl_w_elems(cin, cout_pad, G.cl_k);
     std::vector<float> dense((size_t)u * cout * cin * G.cl_k);
     t_ups_cl_dense(G, cin, cout, w_host, dense.data());
-    std::vector<uint16_t> pk((size_t)ne, 0);
-    for (int j = 0; j < G.cl_k; ++j)
-      for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < u * cout; ++co)
-          pk[(size_t)cl_w_index(j, ci, co, cin, G.cl_k)] = f2bf(dense[((size_t)co * cin + ci) * G.cl_k + j]);
-    std::vector<float> bb((size_t)cout_pad, 0.f);
-    for (int co = 0; co < u * cout; ++co) bb[(size_t)co] = bias_host[co % cout];
-    if (hipMemcpy(wpack_dev, pk.data(), (size_t)ne * 2, hipMemcpyHostToDevice) != hipSuccess) return -6;
-    if (hipMemcpy(static_cast<char*>(wpack_dev) + ne * 2, bb.data(), (size_t)cout_pad * 4, hipMemcpyHostToDevice) != hipSuccess) return -6;
+    if (!t_upload_cl(wpack_dev, false, cin, u * cout, G.cl_k, t_dense(dense.data(), cin, G.cl_k), [&](int co) { return bias_host[co % cout]; }))
+      return -6;
     UpW U;
     U.u = u; U.k = k; U.cin = cin; U.cout = cout; U.ntaps = G.ntaps; U.cl_pad_left = G.cl_pad_left;
     for (int ph = 0; ph < u; ++ph) U.pad_left[ph] = G.pad_left[ph];
-    U.cl.cin = cin; U.cl.cin_pad = cin; U.cl.cout = u * cout; U.cl.cout_pad = cout_pad; U.cl.k = G.cl_k;
-    U.cl.wb_off = 0; U.cl.b_off = ne / 2;                        // float offsets from wpack_dev, which plays the blob
+    U.cl = conv_cl_desc(cin, u * cout, G.cl_k);
+    U.cl.wb_off = 0; U.cl.b_off = cl_w_elems(cin, U.cl.cout_pad, G.cl_k) / 2;   // float offsets from wpack_dev, which plays the blob
     const uint16_t* src[3] = {static_cast<const uint16_t*>(x0), nsrc > 1 ? static_cast<const uint16_t*>(x1) : nullptr,
                               nsrc > 2 ? static_cast<const uint16_t*>(x2) : nullptr};
     const ClLaunch cl = ups_cl_launch(U, static_cast<const float*>(wpack_dev), src, nsrc, static_cast<uint16_t*>(out), B, L, lens,
