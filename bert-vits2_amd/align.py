@@ -3,6 +3,7 @@
 ``neg_cent``       the negative cross-entropy between every latent frame of a recording and every symbol's prior (``bv2_neg_cent``)
 ``maximum_path``   ``monotonic_align.maximum_path`` over it: frames per symbol, the one-hot path, the path's score (``bv2_maximum_path``)
 ``align_latent``   both, from a phase-A encode dict and the recording's latent ``z_p``
+``kl_path``        the KL between the recording's posterior and the text's prior along a path, per frame and per item (``bv2_kl_path``)
 ``with_durations`` an encode dict with its durations replaced, ready for ``decode`` — timing transfer is
                    ``align_latent`` -> ``with_durations`` -> ``decode``
 
@@ -121,6 +122,37 @@ def align_latent(enc: Dict[str, torch.Tensor], z_p: torch.Tensor, y_lengths, wan
     out = maximum_path(nc, xl_d, yl_d, want_attn)
     out["y_lengths"] = yl_d
     out["neg_cent"] = nc if want_attn else None
+    return out
+
+
+@torch.no_grad()
+def kl_path(z_p: torch.Tensor, logs_q: torch.Tensor, m_p: torch.Tensor, logs_p: torch.Tensor, durations, x_lengths=None,
+            y_lengths=None) -> Dict[str, torch.Tensor]:
+    """The KL term of the reference's ``forward()`` (losses.py:45-61) along the path, per frame (``bv2_kl_path``): ``z_p`` / ``logs_q``
+    [B, inter, Ty] the recording's latent in the prior's space and its posterior log-std, ``m_p`` / ``logs_p`` [B, inter, T] the text's
+    prior, ``durations`` [B, T] frames per symbol (frame j reads the prior of the symbol whose interval holds it: a gather).  Returns
+    ``kl_frame`` [B, Ty] (0 at and past ``y_lengths``) and ``kl`` [B], the fixed-order sum of each row; ``kl.sum() / y_lengths.sum()``
+    is the reference's ``kl_loss``."""
+    if not z_p.is_cuda:
+        raise RuntimeError("bert_vits2_amd.align.kl_path needs device tensors: there is no CPU fallback")
+    lib = L.load()
+    dev = z_p.device
+    B, D, Ty = z_p.shape
+    T = m_p.shape[2]
+    if tuple(logs_q.shape) != (B, D, Ty) or tuple(m_p.shape) != (B, D, T) or tuple(logs_p.shape) != (B, D, T):
+        raise ValueError("logs_q must be [B, inter, Ty] and m_p / logs_p [B, inter, T] with z_p's B and inter")
+    w = torch.as_tensor(durations)
+    if w.numel() != B * T:
+        raise ValueError(f"durations must be [B, T] = [{B}, {T}], got {tuple(w.shape)}")
+    f32 = lambda t: t.to(dev, torch.float32).contiguous()
+    i64 = lambda t: None if t is None else torch.as_tensor(t).to(dev, torch.int64).contiguous()
+    z_p, logs_q, m_p, logs_p, w, xl, yl = f32(z_p), f32(logs_q), f32(m_p), f32(logs_p), f32(w.reshape(B, T)), i64(x_lengths), i64(y_lengths)
+    out = dict(kl_frame=torch.empty(B, Ty, dtype=torch.float32, device=dev), kl=torch.empty(B, dtype=torch.float32, device=dev))
+    with torch.cuda.device(dev):
+        rc = lib.bv2_kl_path(_stream(), B, D, T, Ty, _ptr(z_p), _ptr(logs_q), _ptr(m_p), _ptr(logs_p), _ptr(w), _ptr(xl), _ptr(yl),
+                             _ptr(out["kl_frame"]), _ptr(out["kl"]))
+    if rc:
+        _fail(lib, "bv2_kl_path", rc)
     return out
 
 

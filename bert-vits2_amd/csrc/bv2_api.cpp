@@ -6,6 +6,7 @@
 #include <new>
 
 #include "bv2_internal.h"
+#include "bv2_pack.h"
 
 using namespace bv2;
 
@@ -233,6 +234,124 @@ int bv2_posterior_encode(bv2_handle* h, bv2_stream stream, int B, int Ty, const 
   return run_posterior_encode(h, static_cast<hipStream_t>(stream), B, Ty, y, y_lengths, g, noise_q, noise_scale_q, z, m_q, logs_q, y_mask,
                               ws, wsb);
   BV2_CATCH(h)
+}
+
+// ---- the forward duration predictor's own blob (sdp.post_*, sdp.flows.1.*; the other two blobs are untouched) ----------------------
+static int sdp_forward_layout(bv2_handle* h, const char* what) {
+  if (h->sdpf.total_floats > 0) return 0;
+  SdpForwardW w;
+  std::string e;
+  if (int rc = build_sdp_forward_layout(h->model.cfg, w, e)) { h->err = std::string(what) + ": " + e; return rc; }
+  h->sdpf = w;
+  return 0;
+}
+
+int64_t bv2_sdp_forward_packed_bytes(bv2_handle* h) {
+  if (!h) return -1;
+  BV2_TRY
+  if (sdp_forward_layout(h, "bv2_sdp_forward_packed_bytes")) return -1;
+  return h->sdpf.total_floats * (int64_t)sizeof(float);
+  BV2_CATCH(h)
+}
+
+int bv2_sdp_forward_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
+  if (!h) return -1;
+  BV2_TRY
+  if (!key || !host_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { h->err = "bv2_sdp_forward_load_tensor: bad argument"; return -1; }
+  if (!sdp_forward_key(key)) return 1;                             // not one of this blob's tensors: ignored
+  HostTensor t;
+  int64_t n = 1;
+  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= shape[i]; }
+  t.data.resize((size_t)n);
+  if (dtype == BV2_F32) std::memcpy(t.data.data(), host_ptr, sizeof(float) * (size_t)n);
+  else if (dtype == BV2_F16) {
+    const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
+    for (int64_t i = 0; i < n; ++i) t.data[(size_t)i] = h2f(s[i]);
+  } else if (dtype == BV2_BF16) {
+    const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
+    for (int64_t i = 0; i < n; ++i) { uint32_t b = (uint32_t)s[i] << 16; std::memcpy(&t.data[(size_t)i], &b, 4); }
+  } else { h->err = "bv2_sdp_forward_load_tensor: unknown dtype"; return -1; }
+  h->sdpf_tensors[key] = std::move(t);
+  return 0;
+  BV2_CATCH(h)
+}
+
+int bv2_sdp_forward_pack(bv2_handle* h, void* host_blob, int64_t bytes) {
+  if (!h) return -1;
+  BV2_TRY
+  if (int rc = sdp_forward_layout(h, "bv2_sdp_forward_pack")) return rc;
+  if (!host_blob || bytes < h->sdpf.total_floats * (int64_t)sizeof(float)) { h->err = "bv2_sdp_forward_pack: buffer too small"; return -1; }
+  return pack_sdp_forward_blob(h->model.cfg, h->sdpf, h->sdpf_tensors, static_cast<float*>(host_blob), h->err);
+  BV2_CATCH(h)
+}
+
+int bv2_sdp_forward_attach(bv2_handle* h, const void* dev_blob, int64_t bytes) {
+  if (!h) return -1;
+  BV2_TRY
+  if (int rc = sdp_forward_layout(h, "bv2_sdp_forward_attach")) return rc;
+  if (!dev_blob || bytes < h->sdpf.total_floats * (int64_t)sizeof(float)) { h->err = "bv2_sdp_forward_attach: blob too small for this config"; return -1; }
+  uint32_t hdr[8];
+  if (hipMemcpy(hdr, dev_blob, sizeof(hdr), hipMemcpyDeviceToHost) != hipSuccess) {
+    h->err = "bv2_sdp_forward_attach: cannot read the blob header (is this a device pointer on the current GPU?)";
+    return -6;
+  }
+  if (!blob_header_matches(hdr, kSdpForwardMagic, BV2_SDP_FORWARD_LAYOUT, h->sdpf.cfg_hash, h->sdpf.total_floats)) {
+    h->err = "bv2_sdp_forward_attach: blob header does not match this handle's config (not a forward duration predictor blob, or packed for another model)";
+    return -7;
+  }
+  h->sdpf_blob = static_cast<const float*>(dev_blob);
+  return 0;
+  BV2_CATCH(h)
+}
+
+int bv2_sdp_forward_detach(bv2_handle* h) {
+  if (!h) return -1;
+  h->sdpf_blob = nullptr;
+  return 0;
+}
+
+int64_t bv2_duration_nll_workspace_bytes(const bv2_handle* h, int B, int T) {
+  if (!h || B < 1 || B > 65535 || T < 1) return -1;
+  return duration_nll_workspace_bytes(h->model, B, T);
+}
+
+int bv2_duration_nll(bv2_handle* h, bv2_stream stream, int B, int T, const float* x, const float* x_mask, const float* w, const float* g,
+                     const float* noise_e, float* nll_sym, float* nll, void* ws, int64_t wsb) {
+  if (!h) return -1;
+  BV2_TRY
+  if (B < 1 || B > 65535 || T < 1 || !x || !x_mask || !w || !g || !nll_sym || !nll) {
+    h->err = "bv2_duration_nll: bad argument (B in [1, 65535], T >= 1; x, x_mask, w, g, nll_sym and nll must not be null)";
+    return -1;
+  }
+  if ((int64_t)h->model.cfg.hidden_channels * T >= (1ll << 31)) { h->err = "bv2_duration_nll: hidden_channels * T must stay below 2^31"; return -1; }
+  if (!ws) { h->err = "bv2_duration_nll: workspace is null"; return -5; }
+  if (wsb < duration_nll_workspace_bytes(h->model, B, T)) { h->err = "workspace too small for bv2_duration_nll"; return -5; }
+  if (!h->blob) { h->err = "bv2_duration_nll: no weights attached (call bv2_pack_weights + bv2_attach_weights first)"; return -8; }
+  if (!h->sdpf_blob) {
+    h->err = "bv2_duration_nll: no forward duration predictor weights attached (bv2_sdp_forward_pack + bv2_sdp_forward_attach; release "
+             "checkpoints written by compress_model.py are stripped of sdp.post_*)";
+    return -8;
+  }
+  return run_duration_nll(h, static_cast<hipStream_t>(stream), B, T, x, x_mask, w, g, noise_e, nll_sym, nll, ws, wsb);
+  BV2_CATCH(h)
+}
+
+int bv2_kl_path(bv2_stream stream, int32_t B, int32_t inter, int32_t T, int32_t Ty, const float* z_p, const float* logs_q, const float* m_p,
+                const float* logs_p, const float* w_ceil, const int64_t* x_lengths, const int64_t* y_lengths, float* kl_frame, float* kl) {
+  auto fail = [&](const std::string& m, int rc) { g_create_err = "bv2_kl_path: " + m; return rc; };
+  if (!z_p || !logs_q || !m_p || !logs_p || !w_ceil || !kl_frame || !kl)
+    return fail("z_p, logs_q, m_p, logs_p, w_ceil, kl_frame and kl must not be null", -1);
+  if (B < 1 || B > 65535) return fail("B must be in [1, 65535]", -1);
+  if (inter < 1 || inter > 65535) return fail("inter must be in [1, 65535]", -1);
+  if (T < 1 || T > MP_MAX_T) return fail("T must be in [1, " + std::to_string(MP_MAX_T) + "]", -1);
+  if (Ty < 1 || (int64_t)inter * Ty >= (1ll << 31)) return fail("Ty must be >= 1 with inter * Ty below 2^31", -1);
+  try {
+    KlPathArgs a;
+    a.z_p = z_p; a.logs_q = logs_q; a.m_p = m_p; a.logs_p = logs_p; a.w_ceil = w_ceil; a.x_lengths = x_lengths; a.y_lengths = y_lengths;
+    a.kl_frame = kl_frame; a.kl = kl; a.B = B; a.D = inter; a.T = T; a.Ty = Ty;
+    if (launch_kl_path(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
 }
 
 int bv2_set_generator_dtype(bv2_handle* h, int dtype) {

@@ -795,6 +795,135 @@ int run_stage_sdp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, co
   return c.rc;
 }
 
+// ---- the duration likelihood: StochasticDurationPredictor.forward on given durations (models.py:197-244) ----------------------
+// 35 launches: cond GEMV, pre, the trunk (3), the h_w trunk (3), begin, 4 post ConvFlows (12), mid, 4 ConvFlows (12), end.
+namespace {
+struct PlanNll { float *gv, *h, *x, *xh, *y1, *y2, *zq, *z, *acc; };
+PlanNll plan_nll(Arena& A, const Model& m, int B, int T) {
+  const int64_t H = m.cfg.hidden_channels, BT = (int64_t)B * T;
+  PlanNll p;
+  p.gv = A.get<float>((int64_t)B * H);
+  p.h = A.get<float>(BT * H);
+  p.x = A.get<float>(BT * H);
+  p.xh = A.get<float>(BT * H);
+  p.y1 = A.get<float>(BT * H);
+  p.y2 = A.get<float>(BT * H);
+  p.zq = A.get<float>(BT * 2);
+  p.z = A.get<float>(BT * 2);
+  p.acc = A.get<float>(BT);
+  return p;
+}
+
+// one DDSConv, forward kernels: the layers ping-pong between ha and hb like run_dds_fused; `blob` is the blob `d` and `post.proj` live in
+struct DdsFwdPre { const float* w = nullptr; const float* b = nullptr; const float* z = nullptr; int z_rows = 2, z_src = 0; const float* g = nullptr; };
+struct DdsFwdPost {
+  const ConvW* proj = nullptr;
+  float* post_out = nullptr; const float* post_add = nullptr;
+  float* zio = nullptr; int z_src = 0, z_dst = 0; float* acc = nullptr;
+};
+void run_dds_fwd(Ctx& c, const float* blob, const DDSW& d, const DdsFwdPre& pre, float* ha, float* hb, const float* mask,
+                 const DdsFwdPost& post, int B, int C, int T, float sqrt_fc) {
+  auto W = [blob](int64_t off) { return off < 0 ? nullptr : blob + off; };
+  const float* cur = nullptr;
+  for (int i = 0; i < kSdpLayers; ++i) {
+    const DDSLayerW& L = d.l[i];
+    const bool last = i + 1 == kSdpLayers;
+    DdsFwdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    if (i == 0) { a.pre_w = pre.w; a.pre_b = pre.b; a.z = pre.z; a.z_rows = pre.z_rows; a.z_src = pre.z_src; a.g = pre.g; }
+    else a.x = cur;
+    a.mask = mask;
+    a.dww = W(L.dww.off); a.dwb = W(L.dwb.off); a.g1 = W(L.g1.off); a.b1 = W(L.b1.off); a.g2 = W(L.g2.off); a.b2 = W(L.b2.off);
+    a.w = W(L.c1x1.w_off); a.bias = W(L.c1x1.b_off);
+    float* out = (cur == ha) ? hb : ha;
+    a.out = out; a.dil = L.dil; a.last_mask = last ? 1 : 0; a.eps = 1e-5f;
+    a.B = B; a.C = C; a.T = T;
+    if (last) {
+      a.post_w = W(post.proj->w_off); a.post_b = W(post.proj->b_off);
+      a.post_cout = post.proj->cout; a.post_cout_pad = post.proj->cout_pad;
+      a.post_out = post.post_out; a.post_add = post.post_add;
+      a.zio = post.zio; a.z_src = post.z_src; a.z_dst = post.z_dst; a.acc = post.acc;
+      a.sqrt_fc = sqrt_fc; a.tail = 5.0f;
+      a.out = nullptr;
+    }
+    if (!c.rc) { if (int r = launch_dds_fwd_layer(c.s, a)) c.fail("sdp.forward.layer", r); }
+    cur = out;
+  }
+}
+}  // namespace
+
+int64_t duration_nll_workspace_bytes(const Model& m, int B, int T) {
+  Arena a(nullptr, 0);
+  plan_nll(a, m, B, T);
+  return a.off + 256;
+}
+
+int run_duration_nll(bv2_handle* h, hipStream_t s, int B, int T, const float* x, const float* x_mask, const float* w, const float* g,
+                     const float* noise_e, float* nll_sym, float* nll, void* ws, int64_t wsb) {
+  const Model& m = h->model;
+  const SdpForwardW& F = h->sdpf;
+  const float* fb = h->sdpf_blob;
+  const int H = m.cfg.hidden_channels;
+  if (!dds_fused_supported(H)) { h->err = "bv2_duration_nll: hidden_channels must be 128, 192 or 256"; return -1; }
+  if (int e = check_seeds(h, B, noise_e, "bv2_duration_nll", "noise_e")) return e;
+  if (!noise_e && !h->seeds) { h->err = "bv2_duration_nll: noise_e is NULL and no noise seeds are set (bv2_set_noise_seeds)"; return -1; }
+  Arena A(ws, wsb);
+  PlanNll P = plan_nll(A, m, B, T);
+  if (int e = ws_short(h, A, "bv2_duration_nll")) return e;
+  Ctx c{h, s, m, h->blob};
+  const float sqrt_fc = (float)std::sqrt((double)H);
+  // the trunk x = proj(convs(pre(x) + cond(g))) * mask: the launches of phase A (sdp_core)
+  const GemvW* gw[1] = {&m.sdp_cond};
+  float* go[1] = {P.gv};
+  run_front(c, nullptr, g, nullptr, gw, go, 1, H, nullptr, nullptr, B, T, nullptr, nullptr, 0.f);
+  ConvProb p = c.prob(m.sdp_pre, x, P.h, T);
+  p.bias2 = P.gv; p.bias2_bstride = H;
+  c.conv1(p, B, T, "sdp.pre");
+  {
+    DdsPost post;
+    post.proj = &m.sdp_proj; post.post_out = P.x;
+    run_dds_fused(c, m.sdp_convs, P.h, DdsPre(), P.y1, P.y2, x_mask, post, B, H, T, sqrt_fc);
+  }
+  // h_w = post_proj(post_convs(post_pre(w))) * mask, written as x + h_w: the post flows' conditioning
+  {
+    DdsFwdPre pre;
+    pre.w = fb + F.post_pre_w.off; pre.b = fb + F.post_pre_b.off; pre.z = w; pre.z_rows = 1; pre.z_src = 0;
+    DdsFwdPost post;
+    post.proj = &F.post_proj; post.post_out = P.xh; post.post_add = P.x;
+    run_dds_fwd(c, fb, F.post_convs, pre, P.y1, P.y2, x_mask, post, B, H, T, sqrt_fc);
+  }
+  SdpFwdPointArgs q;
+  std::memset(&q, 0, sizeof(q));
+  q.noise = noise_e; q.seeds = noise_e ? nullptr : h->seeds; q.w = w; q.mask = x_mask; q.zq = P.zq; q.z = P.z; q.acc = P.acc;
+  q.nll_sym = nll_sym; q.nll = nll; q.B = B; q.T = T;
+  q.ea_m = fb + F.post_ea_m.off; q.ea_logs = fb + F.post_ea_logs.off;
+  c.chk(launch_sdp_fwd_point(s, 0, q), "sdp.forward.begin");
+  // ConvFlow, Flip, ...: the 2-channel flips are index swaps, and an even number of them leaves z_q in its own order
+  for (int i = 0; i < kSdpFlows; ++i) {
+    const int src = i % 2, dst = 1 - src;
+    const ConvFlowW& cf = F.post_cf[i];
+    DdsFwdPre pre;
+    pre.w = fb + cf.pre_w.off; pre.b = fb + cf.pre_b.off; pre.z = P.zq; pre.z_src = src; pre.g = P.xh;
+    DdsFwdPost post;
+    post.proj = &cf.proj; post.zio = P.zq; post.z_src = src; post.z_dst = dst; post.acc = P.acc;
+    run_dds_fwd(c, fb, cf.convs, pre, P.y1, P.y2, x_mask, post, B, H, T, sqrt_fc);
+  }
+  q.ea_m = c.W(m.ea_m.off); q.ea_logs = c.W(m.ea_logs.off);
+  c.chk(launch_sdp_fwd_point(s, 1, q), "sdp.forward.mid");
+  for (int i = 0; i < kSdpFlows; ++i) {
+    const int src = i % 2, dst = 1 - src;
+    const ConvFlowW& cf = i == 0 ? F.cf_first : m.cf[kSdpFlowsUsed - i];     // flows.1, then .3 / .5 / .7 = cf[2] / [1] / [0]
+    const float* blob = i == 0 ? fb : h->blob;
+    DdsFwdPre pre;
+    pre.w = blob + cf.pre_w.off; pre.b = blob + cf.pre_b.off; pre.z = P.z; pre.z_src = src; pre.g = P.x;
+    DdsFwdPost post;
+    post.proj = &cf.proj; post.zio = P.z; post.z_src = src; post.z_dst = dst; post.acc = P.acc;
+    run_dds_fwd(c, blob, cf.convs, pre, P.y1, P.y2, x_mask, post, B, H, T, sqrt_fc);
+  }
+  c.chk(launch_sdp_fwd_point(s, 2, q), "sdp.forward.end");
+  return c.rc;
+}
+
 int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, const float* x_mask, const float* g, float* logw,
                  void* ws, int64_t wsb) {
   const Model& m = h->model;

@@ -134,6 +134,21 @@ struct PosteriorW {
   uint32_t cfg_hash = 0;
 };
 
+// What the StochasticDurationPredictor needs in its FORWARD direction and the inference blob does not hold (models.py:176-187, 206-244):
+// post_pre / post_convs / post_proj / post_flows and the ConvFlow sdp.flows.1 that inference drops — a third, optional blob
+constexpr uint32_t kSdpForwardMagic = 0x66765642u;  // "BVvf"
+constexpr int kSdpFlows = 4;                        // ConvFlows per side (models.py:155, 183)
+struct SdpForwardW {
+  VecW post_pre_w, post_pre_b;       // Conv1d(1 -> C, k = 1)
+  DDSW post_convs;
+  ConvW post_proj;
+  VecW post_ea_m, post_ea_logs;      // post_flows.0
+  ConvFlowW post_cf[kSdpFlows];      // post_flows.1, .3, .5, .7 in forward order
+  ConvFlowW cf_first;                // flows.1; flows.3 / .5 / .7 are Model::cf[2] / [1] / [0] of the inference blob
+  int64_t total_floats = 0;
+  uint32_t cfg_hash = 0;
+};
+
 struct Model {
   bv2_config cfg;
   bool flow_flip_first = false;      // odd number of couplings: the reverse pass starts with a real channel Flip of z (bv2_model.cpp)
@@ -240,6 +255,10 @@ struct bv2_handle {
   bv2::PosteriorW post;
   std::map<std::string, bv2::HostTensor> post_tensors;
   const float* post_blob = nullptr;  // device
+  // the forward duration predictor's own weights (bv2_sdp_forward_*): the same three parts
+  bv2::SdpForwardW sdpf;
+  std::map<std::string, bv2::HostTensor> sdpf_tensors;
+  const float* sdpf_blob = nullptr;  // device
   std::string err;
   std::map<std::string, bv2::Tap> taps;
   int gen_dtype = BV2_F32;           // Generator arithmetic: BV2_F32 (conv_mfma.hip) or BV2_BF16 (gen_bf16.hip)
@@ -303,6 +322,9 @@ int pack_blob(const Model& m, const std::map<std::string, HostTensor>& t, float*
 bool key_in_schema(const Model& m, const std::string& key);
 int build_posterior_layout(const bv2_config& cfg, int spec_channels, PosteriorW& w, std::string& err);
 int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w, const std::map<std::string, HostTensor>& t, float* blob, std::string& err);
+bool sdp_forward_key(const std::string& key);                      // sdp.post_* and sdp.flows.1.*
+int build_sdp_forward_layout(const bv2_config& cfg, SdpForwardW& w, std::string& err);
+int pack_sdp_forward_blob(const bv2_config& cfg, const SdpForwardW& w, const std::map<std::string, HostTensor>& t, float* blob, std::string& err);
 
 // bv2_exec.cpp
 // active seeds (bv2_set_noise_seeds) against a call's batch and its noise pointer: non-zero with h->err set on a mismatch
@@ -330,6 +352,10 @@ int run_stage_sdp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, co
                   const float* g, float* logw, void* ws, int64_t wsb);
 int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, const float* x_mask, const float* g, float* logw,
                  void* ws, int64_t wsb);
+// sdp(x, x_mask, w, g) forward (models.py:206-244): nll_sym [B][T], nll [B]; noise_e [B][2][T] or null with the handle's seeds
+int64_t duration_nll_workspace_bytes(const Model& m, int B, int T);
+int run_duration_nll(bv2_handle* h, hipStream_t s, int B, int T, const float* x, const float* x_mask, const float* w, const float* g,
+                     const float* noise_e, float* nll_sym, float* nll, void* ws, int64_t wsb);
 int run_generator(bv2_handle* h, hipStream_t s, int B, int Ty, int L, const float* z, const int64_t* y_lengths,
                   const float* g, float* o, void* ws, int64_t wsb);
 // The Generator's ConvTranspose1d launches, built in one place for the executors and for the tests' entry points (bv2_testing.cpp): x =

@@ -676,6 +676,59 @@ struct DdsArgs {
 bool dds_fused_supported(int C);
 int launch_dds_layer(hipStream_t stream, const DdsArgs& a);
 
+// --- the stochastic duration predictor FORWARD: the likelihood of given durations (kernels/sdp_forward.hip; models.py:206-244) ---
+// One DDSConv layer per launch as above, with what the forward direction needs:
+//   first layer   xin = pre_w[c]*z[b][z_src][t] + pre_b[c] (+ g[b][c][t] when g != null); z has z_rows rows per item (1: post_pre on w)
+//   post_out      post_out = (Wp out + bp) * mask (+ post_add, same shape: x + h_w)
+//   zio           params as above; z[b][z_dst] = mask * rq_spline_forward(z[b][z_dst]; params); z[b][z_src] *= mask;
+//                 acc[b][t] -= logabsdet * mask            (one owner per position: no atomics)
+struct DdsFwdArgs {
+  const float* x; const float* pre_w; const float* pre_b; const float* z; int z_rows, z_src; const float* g;
+  const float* mask;
+  const float* dww; const float* dwb; const float* g1; const float* b1; const float* g2; const float* b2;
+  const float* w; const float* bias;
+  float* out;
+  int dil, last_mask; float eps;
+  const float* post_w; const float* post_b; int post_cout, post_cout_pad;
+  float* post_out; const float* post_add;
+  float* zio; int z_dst; float sqrt_fc, tail;
+  float* acc;                           // [B][T]
+  float cst, wscale;                    // filled by launch_dds_fwd_layer
+  int B, C, T;
+};
+int launch_dds_fwd_layer(hipStream_t stream, const DdsFwdArgs& a);
+// the pointwise launches between the flows.  step 0: zq = EA_post(e_q * mask), acc = the e_q Gaussian term - EA_post's log-determinant
+// (noise [B][2][T], or seeds [B]: seeded_normal(seeds[b], RNG_NOISE_E, row, t)); step 1: u, z0, the logsigmoid terms, the Log flow and
+// the main ElementwiseAffine: zq, w -> z, acc; step 2 (one wave per item): the z Gaussian term, nll_sym [B][T] (0 where masked) and
+// nll [B] = the fixed-order sum of its row (lane l adds t = l, l + 64, ... in sequence; butterfly over xor 32 .. 1; fp64 accumulators, rounded to fp32 once)
+struct SdpFwdPointArgs {
+  const float* noise; const int64_t* seeds;
+  const float* w;                       // [B][T] durations
+  const float* mask;                    // [B][T]
+  const float* ea_m; const float* ea_logs;   // [2] each: post_flows.0 (step 0) / flows.0 (step 1)
+  float* zq; float* z;                  // [B][2][T]
+  float* acc; float* nll_sym; float* nll;
+  int B, T;
+};
+int launch_sdp_fwd_point(hipStream_t stream, int step, const SdpFwdPointArgs& a);
+int launch_row_sum(hipStream_t stream, const float* x, float* out, int B, int n);   // out[b] = that same fixed-order sum of x[b][0..n)
+// the forward RQ spline alone (tests): x, y, lad [N]; uw / uh [N][10] (already divided by sqrt(filter_channels)), ud [N][9]
+int launch_spline_forward(hipStream_t stream, const float* x, const float* uw, const float* uh, const float* ud, float tail, int64_t N,
+                          float* y, float* lad);
+// KL between the posterior and the prior along the path (kernels/align.hip; losses.py:45-61): frame j of item b belongs to the symbol s
+// whose duration interval holds j (w_ceil [B][T], integer-valued; the last symbol takes frames past the durations' sum);
+//   kl_frame[b][j] = sum_c (logs_p[c][s] - logs_q[c][j] - 0.5 + 0.5 (z_p[c][j] - m_p[c][s])^2 exp(-2 logs_p[c][s]))   for j < y_lengths[b], else 0
+// channel c adds into fp64 accumulator c & 3 in sequence, (a0 + a1) + (a2 + a3) at the end; kl[b] = the fixed-order row sum (launch_row_sum)
+struct KlPathArgs {
+  const float *z_p, *logs_q;            // [B][D][Ty]
+  const float *m_p, *logs_p;            // [B][D][T]
+  const float* w_ceil;                  // [B][T]
+  const int64_t *x_lengths, *y_lengths; // [B] or null = T / Ty
+  float* kl_frame; float* kl;           // [B][Ty], [B]
+  int B, D, T, Ty;
+};
+int launch_kl_path(hipStream_t stream, const KlPathArgs& a);
+
 // --- length regulation (reference models.py:1058-1071, commons.py:126-140) ---
 struct ExpandArgs {
   const float* w_ceil; const float* x_mask; const int64_t* y_lengths;

@@ -586,10 +586,65 @@ int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w_in, const std
     return -2;
   }
   if (w.total_floats != w_in.total_floats) { err = "internal: posterior layout drift between passes"; return -4; }
-  uint32_t* hdr = reinterpret_cast<uint32_t*>(blob);
-  hdr[0] = kPosteriorMagic; hdr[1] = BV2_ABI_VERSION; hdr[2] = w_in.cfg_hash; hdr[3] = BV2_POSTERIOR_LAYOUT;
-  int64_t tf = w.total_floats;
-  std::memcpy(hdr + 4, &tf, sizeof(tf));
+  write_blob_header(blob, kPosteriorMagic, BV2_POSTERIOR_LAYOUT, w_in.cfg_hash, w.total_floats);
+  return 0;
+}
+
+// ---- the forward duration predictor's blob: every DDSConv and ConvFlow through pack_dds / conv1d, as the inference blob's
+namespace {
+ConvFlowW pack_convflow(Packer& P, const std::string& p, int hid) {
+  ConvFlowW f;
+  f.pre_w = P.vec(p + ".pre.weight", {hid, 1, 1});
+  f.pre_b = P.vec(p + ".pre.bias", {hid});
+  f.convs = pack_dds(P, p + ".convs", hid);
+  f.proj = P.conv1d(p + ".proj", 3 * kSdpBins - 1, hid, 1);
+  return f;
+}
+void pack_sdp_forward(const bv2_config& c, SdpForwardW& W, Packer& P) {
+  const int hid = c.hidden_channels;               // models.py:159: the predictor's filter_channels is its in_channels
+  W.post_pre_w = P.vec("sdp.post_pre.weight", {hid, 1, 1});
+  W.post_pre_b = P.vec("sdp.post_pre.bias", {hid});
+  W.post_convs = pack_dds(P, "sdp.post_convs", hid);
+  W.post_proj = P.conv1d("sdp.post_proj", hid, hid, 1);
+  W.post_ea_m = P.vec("sdp.post_flows.0.m", {2, 1});
+  W.post_ea_logs = P.vec("sdp.post_flows.0.logs", {2, 1});
+  for (int i = 0; i < kSdpFlows; ++i) W.post_cf[i] = pack_convflow(P, "sdp.post_flows." + std::to_string(2 * i + 1), hid);
+  W.cf_first = pack_convflow(P, "sdp.flows.1", hid);
+  P.alloc(2048);                                  // slack, as the inference blob's
+  W.total_floats = P.cursor;
+}
+}  // namespace
+
+bool sdp_forward_key(const std::string& key) {
+  return key.compare(0, 9, "sdp.post_") == 0 || key.compare(0, 12, "sdp.flows.1.") == 0;
+}
+
+int build_sdp_forward_layout(const bv2_config& cfg, SdpForwardW& w, std::string& err) {
+  if (!dds_fused_supported(cfg.hidden_channels)) {
+    err = "forward duration predictor: hidden_channels must be 128, 192 or 256 (the whole-layer DDSConv kernel)";
+    return -1;
+  }
+  w = SdpForwardW();
+  Packer P;
+  pack_sdp_forward(cfg, w, P);
+  w.cfg_hash = hash_cfg(cfg) * 16777619u ^ kSdpForwardMagic;
+  return 0;
+}
+
+int pack_sdp_forward_blob(const bv2_config& cfg, const SdpForwardW& w_in, const std::map<std::string, HostTensor>& t, float* blob, std::string& err) {
+  SdpForwardW w = w_in;
+  Packer P;
+  P.T = &t;
+  P.blob = blob;
+  std::memset(blob, 0, sizeof(float) * kBlobHeaderFloats);
+  pack_sdp_forward(cfg, w, P);
+  if (!P.missing.empty()) {
+    err = "forward duration predictor: missing/invalid tensors (" + std::to_string(P.missing.size()) + "): ";
+    for (size_t i = 0; i < P.missing.size() && i < 12; ++i) err += P.missing[i] + "; ";
+    return -2;
+  }
+  if (w.total_floats != w_in.total_floats) { err = "internal: forward duration predictor layout drift between passes"; return -4; }
+  write_blob_header(blob, kSdpForwardMagic, BV2_SDP_FORWARD_LAYOUT, w_in.cfg_hash, w.total_floats);
   return 0;
 }
 
@@ -614,10 +669,7 @@ int pack_blob(const Model& m_in, const std::map<std::string, HostTensor>& t, flo
     return -2;
   }
   if (m.total_floats != m_in.total_floats) { err = "internal: layout drift between passes"; return -4; }
-  uint32_t* hdr = reinterpret_cast<uint32_t*>(blob);
-  hdr[0] = kBlobMagic; hdr[1] = BV2_ABI_VERSION; hdr[2] = m_in.cfg_hash; hdr[3] = BV2_PACK_LAYOUT;
-  int64_t tf = m.total_floats;
-  std::memcpy(hdr + 4, &tf, sizeof(tf));
+  write_blob_header(blob, kBlobMagic, BV2_PACK_LAYOUT, m_in.cfg_hash, m.total_floats);
   return 0;
 }
 

@@ -16,6 +16,21 @@ namespace bv2 {
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// ---- the header every packed blob opens with (kBlobHeaderFloats floats, zeroed by the caller): magic, ABI version, config hash, the
+// blob's own layout number, then its length in floats.  The inference blob (kBlobMagic, BV2_PACK_LAYOUT), the posterior encoder's
+// (kPosteriorMagic, BV2_POSTERIOR_LAYOUT) and the forward duration predictor's (kSdpForwardMagic, BV2_SDP_FORWARD_LAYOUT) differ in the
+// two numbers only; the attach calls read it back with blob_header_matches.
+inline void write_blob_header(float* blob, uint32_t magic, uint32_t layout, uint32_t cfg_hash, int64_t total_floats) {
+  uint32_t* hdr = reinterpret_cast<uint32_t*>(blob);
+  hdr[0] = magic; hdr[1] = BV2_ABI_VERSION; hdr[2] = cfg_hash; hdr[3] = layout;
+  std::memcpy(hdr + 4, &total_floats, sizeof(total_floats));
+}
+inline bool blob_header_matches(const uint32_t hdr[8], uint32_t magic, uint32_t layout, uint32_t cfg_hash, int64_t total_floats) {
+  int64_t tf;
+  std::memcpy(&tf, hdr + 4, sizeof(tf));
+  return hdr[0] == magic && hdr[1] == BV2_ABI_VERSION && hdr[2] == cfg_hash && hdr[3] == layout && tf == total_floats;
+}
+
 // ---- descriptors (offsets left unset)
 inline ConvW conv_desc(int cin, int cout, int k) {               // fp32 stream, with its optional bf16 / fp16 / x6 / x3 companions
   ConvW c;

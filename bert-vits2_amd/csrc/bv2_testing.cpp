@@ -760,6 +760,10 @@ int bv2_test_spline(void* stream, float* z, int src, int dst, const float* param
                     float sqrt_fc, float tail, int B, int T) {
   return launch_spline(static_cast<hipStream_t>(stream), z, src, dst, params, prow, mask, sqrt_fc, tail, B, T);
 }
+int bv2_test_spline_forward(void* stream, const float* x, const float* uw, const float* uh, const float* ud, float tail, long long N,
+                            float* y, float* logabsdet) {
+  return launch_spline_forward(static_cast<hipStream_t>(stream), x, uw, uh, ud, tail, N, y, logabsdet);
+}
 
 
 // kernels/rng.h on the host

@@ -260,6 +260,74 @@ int launch_posterior_sample(hipStream_t stream, const float* m, const float* log
   return BV2_CHECK_LAUNCH();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The KL term of SynthesizerTrn.forward() along the path (losses.py:45-61), per frame.  A workgroup owns 256 frames of one item: it
+// forms the inclusive cumulative durations of the item's symbols in LDS (wave 0, 64 symbols per step, integer adds: exact), every thread
+// then finds its frame's symbol by bisection — the gather `expand` does, no [Ty x T] product — and walks the channels.
+constexpr int KL_THREADS = 256;
+
+__global__ void __launch_bounds__(KL_THREADS) kl_path_kernel(const KlPathArgs A) {
+  __shared__ int cum[MP_MAX_T];                                      // cum[s] = frames of symbols 0 .. s
+  const int tid = threadIdx.x, b = blockIdx.y, T = A.T, Ty = A.Ty, D = A.D;
+  int tx = A.x_lengths ? (int)A.x_lengths[b] : T, ty = A.y_lengths ? (int)A.y_lengths[b] : Ty;
+  tx = tx < 0 ? 0 : (tx > T ? T : tx);
+  ty = ty < 0 ? 0 : (ty > Ty ? Ty : ty);
+  if (tid < 64) {
+    int carry = 0;
+    for (int s0 = 0; s0 < tx; s0 += 64) {
+      const int s = s0 + tid;
+      float wf = s < tx ? A.w_ceil[(int64_t)b * T + s] : 0.f;
+      wf = wf > 0.f ? (wf < 16777216.f ? wf : 16777216.f) : 0.f;   // negative / NaN durations count as 0
+      int v = (int)wf;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int u = __shfl_up(v, off);
+        if (tid >= off) v += u;
+      }
+      v += carry;
+      if (s < tx) cum[s] = v;
+      carry = __shfl(v, 63);
+    }
+  }
+  __syncthreads();
+  const int j = blockIdx.x * KL_THREADS + tid;
+  if (j >= Ty) return;
+  float* out = A.kl_frame + (int64_t)b * Ty + j;
+  if (j >= ty || tx < 1) { *out = 0.f; return; }
+  int lo = 0, hi = tx - 1;                                           // the first symbol whose cumulative duration exceeds j; the last one otherwise
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cum[mid] > j) hi = mid; else lo = mid + 1;
+  }
+  const int s = lo;
+  const float* zp = A.z_p + ((int64_t)b * D) * Ty + j;
+  const float* lq = A.logs_q + ((int64_t)b * D) * Ty + j;
+  const float* mp = A.m_p + ((int64_t)b * D) * T + s;
+  const float* lp = A.logs_p + ((int64_t)b * D) * T + s;
+  double a[4] = {0.0, 0.0, 0.0, 0.0};                                  // fp32 terms as the reference forms them, fp64 sums
+  for (int c0 = 0; c0 < D; c0 += 4) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int c = c0 + q;
+      if (c < D) {
+        const float l = lp[(int64_t)c * T], d = zp[(int64_t)c * Ty] - mp[(int64_t)c * T];
+        float k = (l - lq[(int64_t)c * Ty]) - 0.5f;
+        k = k + (0.5f * (d * d)) * expf(-2.f * l);
+        a[q] = a[q] + (double)k;
+      }
+    }
+  }
+  *out = (float)((a[0] + a[1]) + (a[2] + a[3]));
+}
+
+int launch_kl_path(hipStream_t stream, const KlPathArgs& a) {
+  if (a.B < 1 || a.B > 65535 || a.T < 1 || a.T > MP_MAX_T || a.Ty < 1 || a.D < 1) return -1;
+  if (!a.z_p || !a.logs_q || !a.m_p || !a.logs_p || !a.w_ceil || !a.kl_frame || !a.kl) return -1;
+  hipLaunchKernelGGL(kl_path_kernel, dim3((unsigned)((a.Ty + KL_THREADS - 1) / KL_THREADS), (unsigned)a.B), dim3(KL_THREADS), 0, stream, a);
+  if (BV2_CHECK_LAUNCH()) return -1;
+  return launch_row_sum(stream, a.kl_frame, a.kl, a.B, a.Ty);
+}
+
 int64_t maximum_path_workspace_bytes(int B, int T, int Ty) { return (int64_t)B * Ty * mp_words(T) * 8; }
 
 int64_t maximum_path_lds_bytes(int T) {

@@ -17,6 +17,7 @@
 namespace bv2 {
 
 enum { RNG_NOISE_W = 0, RNG_NOISE_Z = 1, RNG_NOISE_Q = 2 };   // `which`: the SDP draw, the prior draw, the posterior draw
+enum { RNG_NOISE_E = 3 };                                     // e_q of the duration likelihood (models.py:214-217); 0-2 and their values do not move
 
 struct Philox4 { uint32_t x, y, z, w; };
 

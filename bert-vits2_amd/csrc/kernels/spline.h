@@ -1,7 +1,8 @@
 // spline.h — inverse piecewise rational-quadratic spline with linear tails (K = 10 bins), one element per call; always fp32.
 // reference transforms.py:49-96 (tails) and :99-187 (inverse branch :160-173); op order kept (softmax, min-width affine,
 // sequential cumsum, knots forced to +-tail, widths as knot differences, searchsorted with +1e-6 on the last knot).
-// Shared by spline_kernel (misc.hip) and the ConvFlow epilogue of dds_layer_kernel (dds_fused.hip).
+// Shared by spline_kernel (misc.hip) and the ConvFlow epilogue of dds_layer_kernel (dds_fused.hip).  The forward direction with its
+// log-determinant (transforms.py:188-208) serves the duration likelihood (sdp_forward.hip); it shares spline_knots and the bin search.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -60,6 +61,37 @@ __device__ __forceinline__ float rq_spline_inverse_one(float y, const float* uw,
   const float disc = bq * bq - 4.f * a * cq;
   const float root = (2.f * cq) / (-bq - sqrtf(disc));
   return root * iw + icw;
+}
+
+// x -> y and log|dy/dx| for one element (transforms.py:188-208, the non-inverse branch); arguments as rq_spline_inverse_one.  The bin is
+// searched among the WIDTH knots; outside [-tail, tail] the transform is the identity with log-determinant 0 (transforms.py:73-74).
+__device__ __forceinline__ float rq_spline_forward_one(float x, const float* uw, const float* uh, const float* ud, float tail,
+                                                       float wscale, float* logabsdet) {
+  *logabsdet = 0.f;
+  if (!(x >= -tail && x <= tail)) return x;
+  float cw[SPK + 1], w[SPK], ch[SPK + 1], hh[SPK];
+  spline_knots(uw, -tail, tail, 1e-3f, wscale, cw, w);
+  spline_knots(uh, -tail, tail, 1e-3f, wscale, ch, hh);
+  int bin = -1;
+#pragma unroll
+  for (int i = 0; i <= SPK; ++i) {
+    const float kn = (i == SPK) ? cw[i] + 1e-6f : cw[i];
+    bin += (x >= kn) ? 1 : 0;
+  }
+  bin = bin < 0 ? 0 : (bin > SPK - 1 ? SPK - 1 : bin);
+  float icw = 0, iw = 0, ich = 0, ih = 0, d0 = 0, d1 = 0;
+#pragma unroll
+  for (int i = 0; i < SPK; ++i)
+    if (i == bin) { icw = cw[i]; iw = w[i]; ich = ch[i]; ih = hh[i]; d0 = 1e-3f + softplus_f(ud[i]); d1 = 1e-3f + softplus_f(ud[i + 1]); }
+  const float idl = ih / iw;
+  const float th = (x - icw) / iw;
+  const float tomt = th * (1.f - th);
+  const float num = ih * (idl * (th * th) + d0 * tomt);
+  const float den = idl + ((d0 + d1 - 2.f * idl) * tomt);
+  const float omt = 1.f - th;
+  const float dnum = (idl * idl) * (d1 * (th * th) + 2.f * idl * tomt + d0 * (omt * omt));
+  *logabsdet = logf(dnum) - 2.f * logf(den);
+  return ich + num / den;
 }
 
 }  // namespace bv2

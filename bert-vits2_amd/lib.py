@@ -184,6 +184,14 @@ SYMBOLS = [
     ("bv2_posterior_detach", C.c_int, [_P]),
     ("bv2_posterior_workspace_bytes", C.c_int64, [_P, C.c_int, C.c_int]),
     ("bv2_posterior_encode", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, C.c_int64]),
+    ("bv2_sdp_forward_packed_bytes", C.c_int64, [_P]),
+    ("bv2_sdp_forward_load_tensor", C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int, C.c_int]),
+    ("bv2_sdp_forward_pack", C.c_int, [_P, _P, C.c_int64]),
+    ("bv2_sdp_forward_attach", C.c_int, [_P, _P, C.c_int64]),
+    ("bv2_sdp_forward_detach", C.c_int, [_P]),
+    ("bv2_duration_nll_workspace_bytes", C.c_int64, [_P, C.c_int, C.c_int]),
+    ("bv2_duration_nll", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64]),
+    ("bv2_kl_path", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("bv2_graph_capture_encode", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_decode", C.c_int, [_P, _P, C.POINTER(DecodeIn), C.POINTER(DecodeOut), _P, C.c_int64, C.POINTER(_P)]),
     ("bv2_graph_capture_encode_ex", C.c_int, [_P, _P, C.POINTER(EncodeIn), C.POINTER(EncodeOut), C.POINTER(ItemControls), _P,

@@ -52,6 +52,7 @@ def draw_noise_z(B: int, C: int, Ty: int, device) -> torch.Tensor:
 
 
 NOISE_W, NOISE_Z, NOISE_Q = 0, 1, 2     # ``which`` of the seeded generator (csrc/kernels/rng.h): the SDP draw, the prior draw, the posterior draw
+NOISE_E = 3                             # e_q of the duration likelihood (``duration_nll``); computed in its kernel only, ``seeded_noise`` offers 0-2
 
 
 def item_seeds(seeds, B: int, device) -> Optional[torch.Tensor]:
@@ -1364,6 +1365,150 @@ class SynthesizerTrn(nn.Module):
         if tuple(z_p.shape[:2]) != (enc["m_p"].shape[0], self.hp.inter_channels):
             raise ValueError(f"z_p must be [B, {self.hp.inter_channels}, Ty] with the encode dict's B")
         return _align.align_latent(enc, z_p.to(self.device), y_lengths, want_attn=want_attn, x_lengths=x_lengths)
+
+    # ------------------------------------------------------------------ scoring a take (reference models.py:993-1002, losses.py:45-61)
+    SDP_FORWARD_HINT = ("no sdp.post_* tensors: the posterior side of the stochastic duration predictor is only in TRAINING checkpoints "
+                        "(G_*.pth as utils.save_checkpoint writes them); release checkpoints written by compress_model.py are stripped of it")
+
+    @property
+    def has_sdp_forward(self) -> bool:
+        return getattr(self, "_sdpf_blob", None) is not None
+
+    def pack_sdp_forward_host_blob(self, state_dict) -> torch.Tensor:
+        """``sdp.post_*`` and ``sdp.flows.1.*`` packed into the forward duration predictor's own blob (host, uint8).  ``sdp.flows.1.*`` is
+        part of the inference schema (inference just never applies it): where ``state_dict`` does not carry it, the model's own
+        parameters are packed.  CPU-only."""
+        lib = self._ensure_handle()
+        if not any(k.startswith("sdp.post_") for k in state_dict):
+            raise ValueError(self.SDP_FORWARD_HINT)
+        own = {k: v for k, v in self.state_dict().items() if k.startswith("sdp.flows.1.")}
+        tensors = dict(own)
+        tensors.update({k: v for k, v in state_dict.items() if k.startswith("sdp.post_") or k.startswith("sdp.flows.1.")})
+        n = lib.bv2_sdp_forward_packed_bytes(self._handle)
+        if n < 0:
+            self._check(-1, "bv2_sdp_forward_packed_bytes")
+        for key, v in tensors.items():
+            t = v.detach().to("cpu", torch.float32).contiguous()
+            shape = (C.c_int64 * t.dim())(*t.shape)
+            rc = lib.bv2_sdp_forward_load_tensor(self._handle, key.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), L.F32)
+            if rc < 0:
+                self._check(rc, "bv2_sdp_forward_load_tensor(" + key + ")")
+        blob = torch.empty(n, dtype=torch.uint8)
+        self._check(lib.bv2_sdp_forward_pack(self._handle, C.c_void_p(blob.data_ptr()), n), "bv2_sdp_forward_pack")
+        return blob
+
+    def load_sdp_forward(self, path_or_state_dict) -> None:
+        """Load what the stochastic duration predictor needs to run FORWARD on observed durations (``duration_nll``, ``score``) from a
+        training checkpoint (a path to a ``G_*.pth``, its dict, or a plain state dict): ``sdp.post_pre / post_convs / post_proj /
+        post_flows.*`` and ``sdp.flows.1.*`` go into a blob of their own; the inference and posterior blobs are untouched.  Raises
+        ``ValueError`` with a hint at ``compress_model.py`` when the checkpoint has no ``sdp.post_*``."""
+        sd = path_or_state_dict
+        if isinstance(sd, (str, bytes)) or hasattr(sd, "__fspath__"):
+            sd = torch.load(sd, map_location="cpu")
+        if isinstance(sd, dict) and "model" in sd and isinstance(sd["model"], dict):
+            sd = sd["model"]
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+        blob = self.pack_sdp_forward_host_blob(sd)
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("load_sdp_forward needs the model on a GPU (model.to('cuda')); there is no CPU fallback")
+        with torch.cuda.device(dev):
+            dblob = blob.to(dev)
+            self._check(self._lib.bv2_sdp_forward_attach(self._handle, C.c_void_p(dblob.data_ptr()), dblob.numel()), "bv2_sdp_forward_attach")
+        self._sdpf_blob = dblob
+
+    def _need_sdp_forward(self, what: str) -> None:
+        if not self.has_sdp_forward:
+            raise RuntimeError(f"{what}: the forward duration predictor is not loaded (load_sdp_forward(checkpoint)); " + self.SDP_FORWARD_HINT)
+        if self._sdpf_blob.device != self.device:
+            raise RuntimeError(f"{what}: the model moved to another device after load_sdp_forward(); load it again")
+
+    @torch.no_grad()
+    def duration_nll(self, enc: Dict[str, torch.Tensor], durations, noise_e=None, seeds=None) -> Dict[str, torch.Tensor]:
+        """``sdp(x, x_mask, w, g=g)`` of the reference's ``forward()`` (models.py:993, 197-244): the negative log-likelihood of
+        ``durations`` [B, T] (frames per symbol: what ``align`` returns, or a caller's) under the stochastic duration predictor, given the
+        text of ``enc`` (an ``encode_durations`` dict: ``x``, ``x_mask``, ``g``).  Returns ``nll`` [B] and its exact per-symbol
+        decomposition ``nll_sym`` [B, T] (0 at masked positions; ``nll[b]`` is the fixed-order sum of row b).  ``noise_e`` [B, 2, T] is the
+        N(0, 1) draw of models.py:214-217; ``seeds`` (see ``infer``) takes it from each item's seed instead (draw ``NOISE_E``) and excludes
+        ``noise_e``; with neither it is drawn with ``torch.randn`` like ``draw_noise_w``.  Always fp32."""
+        self._need_sdp_forward("duration_nll")
+        if self._blob is None:
+            self.repack()
+        dev = self.device
+        x = self._f32(enc["x"])
+        B, Hc, T = x.shape
+        mask, g = self._f32(enc["x_mask"], B, T), self._f32(enc["g"], B, -1)
+        if Hc != self.hp.hidden_channels or g.shape[1] != self.hp.gin_channels:
+            raise ValueError(f"enc must hold x [B, {self.hp.hidden_channels}, T] and g [B, {self.hp.gin_channels}] (an encode_durations dict)")
+        w = torch.as_tensor(durations)
+        if w.numel() != B * T:
+            raise ValueError(f"durations must be [B, T] = [{B}, {T}], got {tuple(w.shape)}")
+        w = self._f32(w, B, T)
+        seeds = item_seeds(seeds, B, dev)
+        if seeds is not None and noise_e is not None:
+            raise ValueError("duration_nll: seeds and noise_e exclude each other")
+        ne = None
+        if seeds is None:
+            ne = self._f32(draw_noise_w(B, T, None) if noise_e is None else noise_e)
+            if tuple(ne.shape) != (B, 2, T):
+                raise ValueError("noise_e must be [B, 2, T]")
+        out = dict(nll=torch.empty(B, dtype=torch.float32, device=dev), nll_sym=torch.empty(B, T, dtype=torch.float32, device=dev))
+        n = self._lib.bv2_duration_nll_workspace_bytes(self._handle, B, T)
+        ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev), self._seeded(seeds):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self._check(self._lib.bv2_duration_nll(self._handle, stream, B, T, _ptr(x), _ptr(mask), _ptr(w), _ptr(g), _ptr(ne),
+                                                   _ptr(out["nll_sym"]), _ptr(out["nll"]), C.c_void_p(ws.data_ptr()), ws.numel()),
+                        "bv2_duration_nll")
+        return out
+
+    @torch.no_grad()
+    def score(self, x, x_lengths, sid, tone, language, bert, ja_bert, en_bert, y, y_lengths, g=None, durations=None, seeds=None,
+              noise_q=None, noise_e=None) -> Dict:
+        """How well the model explains a recording of a text: the two quantities the reference's ``forward()`` computes for it
+        (models.py:993-1002, losses.py:45-61), decomposed.  Phase A for the text, ``posterior_encode`` and the forward flow for the
+        recording ``y`` [B, spec_channels, Ty], the aligner (or the given ``durations`` [B, T]), then ``duration_nll`` and
+        ``align.kl_path``.  Returns ``nll`` [B] / ``nll_sym`` [B, T] (duration likelihood per item / per symbol), ``kl`` [B] / ``kl_frame``
+        [B, Ty] (the reference's ``kl_loss`` is ``kl.sum() / y_lengths.sum()``), ``durations``, ``y_lengths``, the aligner's ``score`` (None
+        with given durations), and the two MSE terms of models.py:996-1002 per item, ``l_length_dp`` and ``l_length_sdp_mse``: the sum over
+        the item's symbols of ``(logw - log(w + 1e-6))^2`` for the deterministic predictor and for the stochastic one run in reverse at
+        noise scale 1, divided by the ITEM's symbol count (the reference divides by the batch's; at B = 1 they coincide).  Also ``enc``,
+        ``posterior`` and ``z_p``.  ``seeds`` (see ``infer``) fixes all three draws (the reverse predictor's, the posterior's, ``e_q``) per
+        item, so a take's score does not depend on its batch; it excludes ``noise_q`` / ``noise_e``.  Needs ``load_posterior`` and
+        ``load_sdp_forward``."""
+        self._need_posterior("score")
+        self._need_sdp_forward("score")
+        B, T = x.shape
+        dev = self.device
+        seeds = item_seeds(seeds, B, dev)
+        if seeds is not None and (noise_q is not None or noise_e is not None):
+            raise ValueError("score: seeds exclude noise_q and noise_e")
+        xl_host = None if (isinstance(x_lengths, torch.Tensor) and x_lengths.is_cuda) else [int(v) for v in x_lengths]
+        _align.check_lengths(xl_host, y_lengths, T, int(y.shape[2]))
+        if g is None and self.hp.n_speakers == 0:
+            g = self.reference_embedding(y, torch.as_tensor(y_lengths))
+        # both predictors run (sdp_ratio strictly between 0 and 1, the full output set); the reverse predictor at noise scale 1 (models.py:998)
+        enc = self.encode_durations(x, torch.as_tensor(x_lengths), sid, tone, language, bert, ja_bert, en_bert,
+                                    None if seeds is not None else draw_noise_w(B, T, None), noise_scale_w=1.0, sdp_ratio=0.5, g=g, seeds=seeds)
+        yl = torch.as_tensor(y_lengths)
+        post = self.posterior_encode(y, yl, g=enc["g"], noise_q=noise_q, seeds=seeds)
+        z_p = self.stage_flow_forward(post["z"], yl, enc["g"])
+        xl_d = self._i64(torch.as_tensor(x_lengths)).reshape(B)
+        yl_d = self._i64(yl).reshape(B)
+        if durations is None:
+            al = _align.align_latent(enc, z_p, y_lengths, x_lengths=x_lengths)
+            dur, path_score = al["durations"], al["score"]
+        else:
+            dur, path_score = torch.as_tensor(durations).to(dev).reshape(B, T), None
+        out = self.duration_nll(enc, dur, noise_e=noise_e, seeds=seeds)
+        out.update(_align.kl_path(z_p, post["logs_q"], enc["m_p"], enc["logs_p"], dur, xl_d, yl_d))
+        mask = enc["x_mask"].reshape(B, T)
+        logw_ = torch.log(dur.to(torch.float32) + 1e-6) * mask
+        n_sym = mask.sum(1)
+        out["l_length_dp"] = ((enc["logw_dp"].reshape(B, T) - logw_) ** 2).sum(1) / n_sym
+        out["l_length_sdp_mse"] = ((enc["logw_sdp"].reshape(B, T) - logw_) ** 2).sum(1) / n_sym
+        out.update(durations=dur, y_lengths=yl_d, score=path_score, enc=enc, posterior=post, z_p=z_p)
+        return out
 
     def set_option(self, key: str, value: int) -> None:
         """Kernel-selection switches of ``bv2_set_option`` ("fused_resblock", "fused_dds", "lean_durations"); tests and A/B runs."""

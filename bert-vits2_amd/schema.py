@@ -218,3 +218,24 @@ def posterior_param_shapes(hp) -> "OrderedDict[str, tuple]":
     d["enc_q.proj.weight"] = (2 * C, H, 1)
     d["enc_q.proj.bias"] = (2 * C,)
     return d
+
+
+def sdp_forward_param_shapes(hp) -> "OrderedDict[str, tuple]":
+    """The ``sdp.post_*`` tensors of a training checkpoint: the posterior side of the StochasticDurationPredictor (reference
+    models.py:176-187), needed only when it runs FORWARD on observed durations (``SynthesizerTrn.duration_nll``).  Like ``enc_q.*`` they are
+    NOT part of ``param_shapes``; together with ``sdp.flows.1.*`` (which is, although inference never applies it) they fill a blob of their
+    own (``SynthesizerTrn.load_sdp_forward``)."""
+    from collections import OrderedDict
+    fc = hp.hidden_channels
+    d = OrderedDict()
+    _conv(d, "sdp.post_pre", fc, 1, 1)
+    _conv(d, "sdp.post_proj", fc, fc, 1)
+    _ddsconv(d, "sdp.post_convs", fc, H.SDP_KERNEL, H.SDP_DDS_LAYERS)
+    d["sdp.post_flows.0.m"] = (2, 1)
+    d["sdp.post_flows.0.logs"] = (2, 1)
+    for f in range(4):                   # models.py:183
+        p = f"sdp.post_flows.{2 * f + 1}"
+        _conv(d, p + ".pre", fc, 1, 1)
+        _ddsconv(d, p + ".convs", fc, H.SDP_KERNEL, H.SDP_DDS_LAYERS)
+        _conv(d, p + ".proj", 3 * H.SDP_NUM_BINS - 1, fc, 1)
+    return d

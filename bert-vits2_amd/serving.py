@@ -469,3 +469,52 @@ def align(model, utts: Sequence[Utterance], specs: Optional[Sequence[torch.Tenso
         for r, i in enumerate(idx):
             results[i] = dur[r, :utts[i].length].copy()
     return results
+
+
+@torch.no_grad()
+def score(model, utts: Sequence[Utterance], specs: Sequence[torch.Tensor], *, use_durations: bool = False, max_batch: int = 32,
+          max_pad_ratio: float = 1.25) -> List[dict]:
+    """How well the model explains each utterance's recording (``SynthesizerTrn.score``; ``model.load_posterior`` and
+    ``model.load_sdp_forward`` first).  ``specs[i]`` is the recording's linear spectrogram ``[spec_channels, Ty_i]``.  Utterances are
+    bucketed by length like ``align``; a bucket is ONE ragged batch.  ``use_durations``: every utterance carries ``durations`` and is
+    scored with them (a timing transfer judged before it is spoken) instead of being aligned.  ``Utterance(seed=...)`` fixes the
+    utterance's three draws, so its numbers do not depend on the bucket it lands in; unseeded utterances draw from torch's CPU generator.
+    Returns one dict of numpy arrays per utterance, in input order, cut to the utterance's own ``T`` and ``T_y``: ``nll`` (scalar),
+    ``nll_sym`` [T], ``kl`` (scalar), ``kl_frame`` [Ty], ``durations`` [T], ``score`` (the aligner's, absent with ``use_durations``),
+    ``l_length_dp`` and ``l_length_sdp_mse``."""
+    if model.device.type != "cuda":
+        raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
+    model._need_posterior("serving.score")
+    model._need_sdp_forward("serving.score")
+    if len(specs) != len(utts):
+        raise ValueError("one recording per utterance")
+    dev, S = model.device, model.hp.spec_channels
+    for i, (u, y) in enumerate(zip(utts, specs)):
+        if y.dim() != 2 or y.shape[0] != S:
+            raise ValueError(f"utterance {i}: the spectrogram must be [{S}, Ty], got {tuple(y.shape)}")
+        if u.length > y.shape[1]:
+            raise ValueError(f"utterance {i}: {u.length} phones cannot be aligned to {y.shape[1]} frames")
+        if use_durations and u.durations is None:
+            raise ValueError(f"utterance {i}: use_durations needs Utterance(durations=...)")
+    gvec = speaker_vectors(model, utts)
+    results: List[Optional[dict]] = [None] * len(utts)
+    for idx in plan_batches([u.length for u in utts], max_batch, max_pad_ratio):
+        batch, kw = _bucket_inputs(model, utts, idx, dev, None, gvec)
+        y_len = [int(specs[i].shape[1]) for i in idx]
+        y = torch.zeros(len(idx), S, max(y_len), dtype=torch.float32, device=dev)
+        for r, i in enumerate(idx):
+            y[r, :, :y_len[r]] = specs[i].to(dev, torch.float32)
+        out = model.score(batch["x"], [utts[i].length for i in idx], batch["sid"], batch["tone"], batch["language"], batch["bert"],
+                          batch["ja_bert"], batch["en_bert"], y, y_len, g=kw.get("g"), seeds=kw.get("seeds"),
+                          durations=kw["w_ceil"] if use_durations else None)
+        host = {k: out[k].cpu().numpy() for k in ("nll", "nll_sym", "kl", "kl_frame", "durations", "l_length_dp", "l_length_sdp_mse")}
+        path = None if out["score"] is None else out["score"].cpu().numpy()
+        for r, i in enumerate(idx):
+            n = utts[i].length
+            res = dict(nll=host["nll"][r], nll_sym=host["nll_sym"][r, :n].copy(), kl=host["kl"][r], kl_frame=host["kl_frame"][r, :y_len[r]].copy(),
+                       durations=host["durations"][r, :n].astype(np.int64), l_length_dp=host["l_length_dp"][r],
+                       l_length_sdp_mse=host["l_length_sdp_mse"][r])
+            if path is not None:
+                res["score"] = path[r]
+            results[i] = res
+    return results

@@ -253,3 +253,31 @@ def synthetic_posterior_state_dict(hp: H.HParams, seed: int = 0) -> "OrderedDict
     sd["enc_q.proj.weight"][C:] *= 0.3           # posterior log-std rows: keep exp(logs_q) moderate, as trained models do
     sd["enc_q.proj.bias"][C:] -= 0.5
     return sd
+
+
+def synthetic_sdp_forward_state_dict(hp: H.HParams, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded synthetic ``sdp.post_*`` tensors (``schema.sdp_forward_param_shapes``), drawn like their inference-side twins in
+    ``synthetic_state_dict`` (the zero-initialised ``ConvFlow.proj`` re-randomised to O(1) spline parameters).  A function of its own with
+    generators of its own: the stream of ``synthetic_state_dict`` does not move.  ``sdp.flows.1.*`` is already in that dict."""
+    from .schema import sdp_forward_param_shapes
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for key, shape in sdp_forward_param_shapes(hp).items():
+        leaf = key.rsplit(".", 1)[-1]
+        if leaf == "gamma":
+            t = _normal(key, seed, shape, 0.1, 1.0)
+        elif leaf == "beta":
+            t = _normal(key, seed, shape, 0.1)
+        elif leaf == "bias":
+            t = _normal(key, seed, shape, 0.02)
+        elif leaf in ("m", "logs"):
+            t = _normal(key, seed, shape, 0.1)
+        else:
+            fan_in = shape[1] * shape[2]
+            std = 1.0 / math.sqrt(fan_in)
+            if key.endswith(".proj.weight") and key.startswith("sdp.post_flows"):
+                std = 3.0 / math.sqrt(fan_in)
+            elif ".convs_sep." in key:
+                std = 1.0 / math.sqrt(shape[2])
+            t = _normal(key, seed, shape, std)
+        sd[key] = t.contiguous()
+    return sd

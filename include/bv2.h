@@ -33,6 +33,7 @@ extern "C" {
 #define BV2_PACK_LAYOUT 16   /* bumped whenever bv2_model.cpp changes the order / format of anything inside the packed blob:
                                a blob cached on disk by an older packer is rejected by bv2_attach_weights */
 #define BV2_POSTERIOR_LAYOUT 1   /* the same for the posterior encoder's own blob (bv2_posterior_pack) */
+#define BV2_SDP_FORWARD_LAYOUT 1 /* ... and for the forward duration predictor's (bv2_sdp_forward_pack) */
 #define BV2_MAX_UPS 8
 #define BV2_MAX_RESBLOCK_KERNELS 4
 #define BV2_MAX_RESBLOCK_DILATIONS 4
@@ -545,6 +546,43 @@ int64_t bv2_posterior_workspace_bytes(const bv2_handle* h, int B, int Ty);
 int bv2_posterior_encode(bv2_handle* h, bv2_stream stream, int B, int Ty, const float* y, const int64_t* y_lengths, const float* g,
                          const float* noise_q, float noise_scale_q, float* z, float* m_q, float* logs_q, float* y_mask,
                          void* workspace, int64_t workspace_bytes);
+
+/* ---- scoring a take against its text: the duration likelihood and the KL term of SynthesizerTrn.forward() -------------------------
+ * forward() computes two quantities that say how well the model explains a recording (models.py:993, losses.py:45-61): the negative
+ * log-likelihood of the aligned durations under the StochasticDurationPredictor run FORWARD, and the KL between the recording's posterior
+ * and the text's prior along the path.  Every term of both is a per-position sum, so both come back decomposed: per symbol and per frame.
+ *
+ * Weights.  The forward predictor needs what inference drops: sdp.post_pre / post_convs / post_proj / post_flows.* and the ConvFlow
+ * sdp.flows.1.  They live in a THIRD, optional blob, handled exactly like the posterior encoder's: bv2_load_tensor keeps ignoring them
+ * (returns 1), bv2_sdp_forward_load_tensor takes exactly those keys (others: 1); pack on the host, upload, attach; detach forgets the blob.
+ * Nothing here changes bv2_packed_bytes, the inference blob, the posterior blob or their headers.  hidden_channels must be 128, 192 or 256.
+ *
+ * bv2_duration_nll: x [B, hidden, T] and x_mask [B, T] of phase A (bv2_encode_out), w [B, T] fp32 frames per symbol (bv2_align's durations
+ * or a caller's; 0 past x_lengths), g [B, gin] -> nll_sym [B, T], nll [B] = sdp(x, x_mask, w, g) of models.py:197-244, that is nll + logq.
+ * nll_sym is the exact decomposition (every term of the reference's sums over [1, 2] at its position; 0 at masked positions), nll[b] the
+ * sum of row b in a fixed order (lane l of one wave adds positions l, l + 64, ... in sequence, then a butterfly over xor 32 .. 1; fp64 accumulators, rounded to fp32 once): it
+ * depends neither on a tiling nor on the item's batch neighbours, and no floating-point atomic is used.  noise_e [B, 2, T] is the caller's
+ * N(0, 1) draw e_q of models.py:214-217; NULL takes it from the seeds of bv2_set_noise_seeds as draw 3 (RNG_NOISE_E; the draws 0-2 and
+ * their values are untouched; bv2_seeded_noise keeps offering 0-2 only) and is an error without seeds.  Always fp32.  35 launches (the
+ * trunk's five are phase A's), asynchronous on `stream`, no allocation.  -1 for a bad argument, -5 for a null or short workspace
+ * (bv2_duration_nll_workspace_bytes), -8 while a blob is missing; every argument is checked before anything touches the device.
+ *
+ * bv2_kl_path (no handle; errors in bv2_last_error(NULL)): z_p, logs_q [B, inter, Ty], m_p, logs_p [B, inter, T], w_ceil [B, T] fp32
+ * frames per symbol, x_lengths / y_lengths [B] int64 DEVICE or NULL (= T / Ty) ->
+ *   kl_frame[b, j] = sum_c (logs_p[c, s] - logs_q[c, j] - 0.5 + 0.5 (z_p[c, j] - m_p[c, s])^2 exp(-2 logs_p[c, s]))   for j < y_lengths[b], else 0
+ * with s the symbol whose duration interval holds frame j (a gather, as the length regulator's; frames past the durations' sum take the
+ * last symbol), channel c added into fp64 accumulator c & 3, and kl[b] the fixed-order sum of row b (as nll).  The reference's kl_loss is
+ * sum(kl) / sum(y_lengths), formed by the caller.  T <= 4096.  Two launches. */
+int64_t bv2_sdp_forward_packed_bytes(bv2_handle* h);
+int bv2_sdp_forward_load_tensor(bv2_handle* h, const char* ref_key, const void* host_ptr, const int64_t* shape, int ndim, int dtype);
+int bv2_sdp_forward_pack(bv2_handle* h, void* host_blob, int64_t bytes);
+int bv2_sdp_forward_attach(bv2_handle* h, const void* dev_blob, int64_t bytes);
+int bv2_sdp_forward_detach(bv2_handle* h);
+int64_t bv2_duration_nll_workspace_bytes(const bv2_handle* h, int B, int T);
+int bv2_duration_nll(bv2_handle* h, bv2_stream stream, int B, int T, const float* x, const float* x_mask, const float* w, const float* g,
+                     const float* noise_e, float* nll_sym, float* nll, void* workspace, int64_t workspace_bytes);
+int bv2_kl_path(bv2_stream stream, int32_t B, int32_t inter, int32_t T, int32_t Ty, const float* z_p, const float* logs_q, const float* m_p,
+                const float* logs_p, const float* w_ceil, const int64_t* x_lengths, const int64_t* y_lengths, float* kl_frame, float* kl);
 
 /* ---- hipGraph capture (BASELINE config 3: "hipGraph-captured decode") ----------------------------------------- */
 /* Both phases are fixed launch sequences on the caller's stream with no allocation, host sync or device->host copy,

@@ -248,6 +248,12 @@ int bv2_test_conv_timeline_report(long long* meta, int max_launches);
 int bv2_test_spline(void* stream, float* z, int src, int dst, const float* params, int prow, const float* mask,
                     float sqrt_fc, float tail, int B, int T);
 
+/* forward RQ spline with linear tails alone (kernels/spline.h rq_spline_forward_one), N elements, all DEVICE: x [N]; uw / uh [N][10]
+ * unnormalised widths / heights as the spline takes them (already divided by sqrt(filter_channels)); ud [N][9] raw interior derivatives
+ * -> y [N], logabsdet [N] */
+int bv2_test_spline_forward(void* stream, const float* x, const float* uw, const float* uh, const float* ud, float tail, long long N,
+                            float* y, float* logabsdet);
+
 /* the HOST instantiations of kernels/rng.h (the seeded-noise generator of bv2_set_noise_seeds): Philox4x32-10 itself, and the N(0,1)
  * value at (seed, which, row, t).  The integer core is the device's code; the host value differs from the device's only by the
  * rounding of the host's log / sin / cos. */
