@@ -50,7 +50,7 @@ int bv2_create(const bv2_config* cfg, bv2_handle** out) {
     }
     if (h->model.cfg.n_speakers >= 1) h->model.cfg.spec_channels = 0;     // not read: the layout and the blob do not depend on it
     std::string err;
-    if (int rc = build_layout(h->model, err)) {
+    if (int rc = build_layout(h->model, h->blob[kInference], err)) {
       g_create_err = "bv2_create: " + err;
       delete h;
       return rc;
@@ -75,11 +75,31 @@ void bv2_destroy(bv2_handle* h) {
 
 const char* bv2_last_error(const bv2_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
-int bv2_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
+// ---- the packed weight blobs: the inference blob, the posterior encoder's (enc_q.*) and the forward duration predictor's (sdp.post_*,
+// sdp.flows.1.*).  Each is its own allocation with its own header; they share one lifecycle — host tensors in, size, pack, attach, detach —
+// written once below for a BlobKind (bv2_internal.h kBlobDesc); the exported entry points name the kind and themselves.
+// The inference layout is bv2_create's; the posterior's is built once spec_channels is known (and again, dropping the attached blob, when
+// it changes), the forward duration predictor's on first use.
+static int blob_layout(bv2_handle* h, BlobKind k, int spec_channels, const char* what) {
+  WeightBlob& b = h->blob[k];
+  std::string e;
+  int rc = 0;
+  if (k == kPosterior && !(h->post.spec == spec_channels && b.total_floats > 0)) {
+    rc = build_posterior_layout(h->model.cfg, spec_channels, h->post, b, e);
+    if (!rc) b.dev = nullptr;          // a blob attached for another width no longer fits
+  } else if (k == kSdpForward && b.total_floats == 0) {
+    rc = build_sdp_forward_layout(h->model.cfg, h->sdpf, b, e);
+  }
+  if (rc) h->err = std::string(what) + ": " + e;
+  return rc;
+}
+
+static int blob_load_tensor(bv2_handle* h, BlobKind k, const char* what, const char* key, const void* host_ptr, const int64_t* shape,
+                            int ndim, int dtype) {
   if (!h) return -1;
   BV2_TRY
-  if (!key || !host_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { h->err = "bv2_load_tensor: bad argument"; return -1; }
-  if (!key_in_schema(h->model, key)) return 1;     // training-only tensors (enc_q.*, sdp.post_*): ignored
+  if (!key || !host_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { h->err = std::string(what) + ": bad argument"; return -1; }
+  if (!kBlobDesc[k].mine(key)) return 1;           // another blob's tensor (the inference blob: enc_q.*, sdp.post_*, sdp.flows.1.*): ignored
   HostTensor t;
   int64_t n = 1;
   for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= shape[i]; }
@@ -91,129 +111,101 @@ int bv2_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const 
   } else if (dtype == BV2_BF16) {
     const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
     for (int64_t i = 0; i < n; ++i) { uint32_t b = (uint32_t)s[i] << 16; std::memcpy(&t.data[(size_t)i], &b, 4); }
-  } else { h->err = "bv2_load_tensor: unknown dtype"; return -1; }
-  h->tensors[key] = std::move(t);
+  } else { h->err = std::string(what) + ": unknown dtype"; return -1; }
+  h->blob[k].tensors[key] = std::move(t);
   return 0;
   BV2_CATCH(h)
 }
 
-int64_t bv2_packed_bytes(const bv2_handle* h) { return h ? h->model.total_floats * (int64_t)sizeof(float) : -1; }
+static int64_t blob_bytes(const bv2_handle* h, BlobKind k) { return h->blob[k].total_floats * (int64_t)sizeof(float); }
 
-int bv2_pack_weights(bv2_handle* h, void* host_blob, int64_t bytes) {
+static int64_t blob_packed_bytes(bv2_handle* h, BlobKind k, int spec_channels, const char* what) {
   if (!h) return -1;
   BV2_TRY
-  if (!host_blob || bytes < bv2_packed_bytes(h)) { h->err = "bv2_pack_weights: buffer too small"; return -1; }
-  return pack_blob(h->model, h->tensors, static_cast<float*>(host_blob), h->err);
+  if (blob_layout(h, k, spec_channels, what)) return -1;
+  return blob_bytes(h, k);
   BV2_CATCH(h)
 }
 
-int bv2_attach_weights(bv2_handle* h, const void* dev_blob, int64_t bytes) {
+static int blob_pack(bv2_handle* h, BlobKind k, int spec_channels, const char* what, void* host_blob, int64_t bytes) {
   if (!h) return -1;
   BV2_TRY
-  if (!dev_blob || bytes < bv2_packed_bytes(h)) { h->err = "bv2_attach_weights: blob too small for this config"; return -1; }
+  if (int rc = blob_layout(h, k, spec_channels, what)) return rc;
+  if (!host_blob || bytes < blob_bytes(h, k)) { h->err = std::string(what) + ": buffer too small"; return -1; }
+  float* out = static_cast<float*>(host_blob);
+  const WeightBlob& b = h->blob[k];
+  if (k == kPosterior) return pack_posterior_blob(h->model.cfg, h->post, b, out, h->err);
+  if (k == kSdpForward) return pack_sdp_forward_blob(h->model.cfg, h->sdpf, b, out, h->err);
+  return pack_blob(h->model, b, out, h->err);
+  BV2_CATCH(h)
+}
+
+static int blob_attach(bv2_handle* h, BlobKind k, int spec_channels, const char* what, const void* dev_blob, int64_t bytes) {
+  if (!h) return -1;
+  BV2_TRY
+  const std::string w(what);
+  if (int rc = blob_layout(h, k, spec_channels, what)) return rc;
+  if (!dev_blob || bytes < blob_bytes(h, k)) { h->err = w + ": blob too small for this config"; return -1; }
   uint32_t hdr[8];
   if (hipMemcpy(hdr, dev_blob, sizeof(hdr), hipMemcpyDeviceToHost) != hipSuccess) {
-    h->err = "bv2_attach_weights: cannot read the blob header (is this a device pointer on the current GPU?)";
+    h->err = w + ": cannot read the blob header (is this a device pointer on the current GPU?)";
     return -6;
   }
-  int64_t tf;
-  std::memcpy(&tf, hdr + 4, sizeof(tf));
-  if (hdr[0] != kBlobMagic || hdr[1] != BV2_ABI_VERSION || hdr[2] != h->model.cfg_hash || tf != h->model.total_floats) {
-    h->err = "bv2_attach_weights: blob header does not match this handle's config (not packed, or packed for another model)";
+  const BlobDesc& d = kBlobDesc[k];
+  WeightBlob& b = h->blob[k];
+  if (!blob_header_matches(hdr, d.magic, d.layout, b.cfg_hash, b.total_floats)) {
+    if (k == kInference && blob_header_matches(hdr, d.magic, hdr[3], b.cfg_hash, b.total_floats))
+      h->err = w + ": blob was packed with another pack layout (a cache written by an older library build): repack";
+    else
+      h->err = w + ": blob header does not match this handle's " + d.noun + " layout (not packed, another kind of blob, or packed for another model)";
     return -7;
   }
-  if (hdr[3] != BV2_PACK_LAYOUT) {
-    h->err = "bv2_attach_weights: blob was packed with another pack layout (a cache written by an older library build): repack";
-    return -7;
-  }
-  h->blob = static_cast<const float*>(dev_blob);
+  b.dev = static_cast<const float*>(dev_blob);
   return 0;
   BV2_CATCH(h)
 }
 
-int bv2_detach_weights(bv2_handle* h) {
+static int blob_detach(bv2_handle* h, BlobKind k) {
   if (!h) return -1;
-  h->blob = nullptr;
+  h->blob[k].dev = nullptr;
   return 0;
 }
 
-// ---- the posterior encoder's own blob (enc_q.*; the inference blob, its size and its header are untouched) ---------------------
-static int posterior_layout(bv2_handle* h, int spec_channels, const char* what) {
-  if (h->post.spec == spec_channels && h->post.total_floats > 0) return 0;
-  PosteriorW w;
-  std::string e;
-  if (int rc = build_posterior_layout(h->model.cfg, spec_channels, w, e)) { h->err = std::string(what) + ": " + e; return rc; }
-  h->post = w;
-  h->post_blob = nullptr;              // a blob attached for another width no longer fits
-  return 0;
+int bv2_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
+  return blob_load_tensor(h, kInference, "bv2_load_tensor", key, host_ptr, shape, ndim, dtype);
 }
-
-int64_t bv2_posterior_packed_bytes(bv2_handle* h, int spec_channels) {
-  if (!h) return -1;
-  BV2_TRY
-  if (posterior_layout(h, spec_channels, "bv2_posterior_packed_bytes")) return -1;
-  return h->post.total_floats * (int64_t)sizeof(float);
-  BV2_CATCH(h)
+int64_t bv2_packed_bytes(const bv2_handle* h) { return h ? blob_bytes(h, kInference) : -1; }
+int bv2_pack_weights(bv2_handle* h, void* host_blob, int64_t bytes) { return blob_pack(h, kInference, 0, "bv2_pack_weights", host_blob, bytes); }
+int bv2_attach_weights(bv2_handle* h, const void* dev_blob, int64_t bytes) {
+  return blob_attach(h, kInference, 0, "bv2_attach_weights", dev_blob, bytes);
 }
+int bv2_detach_weights(bv2_handle* h) { return blob_detach(h, kInference); }
 
 int bv2_posterior_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
-  if (!h) return -1;
-  BV2_TRY
-  if (!key || !host_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { h->err = "bv2_posterior_load_tensor: bad argument"; return -1; }
-  if (std::strncmp(key, "enc_q.", 6) != 0) return 1;            // not a posterior-encoder tensor: ignored
-  HostTensor t;
-  int64_t n = 1;
-  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= shape[i]; }
-  t.data.resize((size_t)n);
-  if (dtype == BV2_F32) std::memcpy(t.data.data(), host_ptr, sizeof(float) * (size_t)n);
-  else if (dtype == BV2_F16) {
-    const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
-    for (int64_t i = 0; i < n; ++i) t.data[(size_t)i] = h2f(s[i]);
-  } else if (dtype == BV2_BF16) {
-    const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
-    for (int64_t i = 0; i < n; ++i) { uint32_t b = (uint32_t)s[i] << 16; std::memcpy(&t.data[(size_t)i], &b, 4); }
-  } else { h->err = "bv2_posterior_load_tensor: unknown dtype"; return -1; }
-  h->post_tensors[key] = std::move(t);
-  return 0;
-  BV2_CATCH(h)
+  return blob_load_tensor(h, kPosterior, "bv2_posterior_load_tensor", key, host_ptr, shape, ndim, dtype);
 }
-
+int64_t bv2_posterior_packed_bytes(bv2_handle* h, int spec_channels) {
+  return blob_packed_bytes(h, kPosterior, spec_channels, "bv2_posterior_packed_bytes");
+}
 int bv2_posterior_pack(bv2_handle* h, int spec_channels, void* host_blob, int64_t bytes) {
-  if (!h) return -1;
-  BV2_TRY
-  if (int rc = posterior_layout(h, spec_channels, "bv2_posterior_pack")) return rc;
-  if (!host_blob || bytes < h->post.total_floats * (int64_t)sizeof(float)) { h->err = "bv2_posterior_pack: buffer too small"; return -1; }
-  return pack_posterior_blob(h->model.cfg, h->post, h->post_tensors, static_cast<float*>(host_blob), h->err);
-  BV2_CATCH(h)
+  return blob_pack(h, kPosterior, spec_channels, "bv2_posterior_pack", host_blob, bytes);
 }
-
 int bv2_posterior_attach(bv2_handle* h, int spec_channels, const void* dev_blob, int64_t bytes) {
-  if (!h) return -1;
-  BV2_TRY
-  if (int rc = posterior_layout(h, spec_channels, "bv2_posterior_attach")) return rc;
-  if (!dev_blob || bytes < h->post.total_floats * (int64_t)sizeof(float)) { h->err = "bv2_posterior_attach: blob too small for this config"; return -1; }
-  uint32_t hdr[8];
-  if (hipMemcpy(hdr, dev_blob, sizeof(hdr), hipMemcpyDeviceToHost) != hipSuccess) {
-    h->err = "bv2_posterior_attach: cannot read the blob header (is this a device pointer on the current GPU?)";
-    return -6;
-  }
-  int64_t tf;
-  std::memcpy(&tf, hdr + 4, sizeof(tf));
-  if (hdr[0] != kPosteriorMagic || hdr[1] != BV2_ABI_VERSION || hdr[2] != h->post.cfg_hash || hdr[3] != BV2_POSTERIOR_LAYOUT ||
-      tf != h->post.total_floats) {
-    h->err = "bv2_posterior_attach: blob header does not match this handle's config and spec_channels (not a posterior blob, or packed for another model)";
-    return -7;
-  }
-  h->post_blob = static_cast<const float*>(dev_blob);
-  return 0;
-  BV2_CATCH(h)
+  return blob_attach(h, kPosterior, spec_channels, "bv2_posterior_attach", dev_blob, bytes);
 }
+int bv2_posterior_detach(bv2_handle* h) { return blob_detach(h, kPosterior); }
 
-int bv2_posterior_detach(bv2_handle* h) {
-  if (!h) return -1;
-  h->post_blob = nullptr;
-  return 0;
+int bv2_sdp_forward_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
+  return blob_load_tensor(h, kSdpForward, "bv2_sdp_forward_load_tensor", key, host_ptr, shape, ndim, dtype);
 }
+int64_t bv2_sdp_forward_packed_bytes(bv2_handle* h) { return blob_packed_bytes(h, kSdpForward, 0, "bv2_sdp_forward_packed_bytes"); }
+int bv2_sdp_forward_pack(bv2_handle* h, void* host_blob, int64_t bytes) {
+  return blob_pack(h, kSdpForward, 0, "bv2_sdp_forward_pack", host_blob, bytes);
+}
+int bv2_sdp_forward_attach(bv2_handle* h, const void* dev_blob, int64_t bytes) {
+  return blob_attach(h, kSdpForward, 0, "bv2_sdp_forward_attach", dev_blob, bytes);
+}
+int bv2_sdp_forward_detach(bv2_handle* h) { return blob_detach(h, kSdpForward); }
 
 int64_t bv2_posterior_workspace_bytes(const bv2_handle* h, int B, int Ty) {
   if (!h || B < 1 || Ty < 1) return -1;
@@ -225,7 +217,7 @@ int bv2_posterior_encode(bv2_handle* h, bv2_stream stream, int B, int Ty, const 
                          void* ws, int64_t wsb) {
   if (!h) return -1;
   BV2_TRY
-  if (!h->post_blob) {
+  if (!h->blob[kPosterior].dev) {
     h->err = "bv2_posterior_encode: no posterior weights attached (bv2_posterior_pack + bv2_posterior_attach; release checkpoints "
              "written by compress_model.py are stripped of enc_q.*)";
     return -8;
@@ -234,80 +226,6 @@ int bv2_posterior_encode(bv2_handle* h, bv2_stream stream, int B, int Ty, const 
   return run_posterior_encode(h, static_cast<hipStream_t>(stream), B, Ty, y, y_lengths, g, noise_q, noise_scale_q, z, m_q, logs_q, y_mask,
                               ws, wsb);
   BV2_CATCH(h)
-}
-
-// ---- the forward duration predictor's own blob (sdp.post_*, sdp.flows.1.*; the other two blobs are untouched) ----------------------
-static int sdp_forward_layout(bv2_handle* h, const char* what) {
-  if (h->sdpf.total_floats > 0) return 0;
-  SdpForwardW w;
-  std::string e;
-  if (int rc = build_sdp_forward_layout(h->model.cfg, w, e)) { h->err = std::string(what) + ": " + e; return rc; }
-  h->sdpf = w;
-  return 0;
-}
-
-int64_t bv2_sdp_forward_packed_bytes(bv2_handle* h) {
-  if (!h) return -1;
-  BV2_TRY
-  if (sdp_forward_layout(h, "bv2_sdp_forward_packed_bytes")) return -1;
-  return h->sdpf.total_floats * (int64_t)sizeof(float);
-  BV2_CATCH(h)
-}
-
-int bv2_sdp_forward_load_tensor(bv2_handle* h, const char* key, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
-  if (!h) return -1;
-  BV2_TRY
-  if (!key || !host_ptr || ndim < 0 || ndim > 8 || (ndim && !shape)) { h->err = "bv2_sdp_forward_load_tensor: bad argument"; return -1; }
-  if (!sdp_forward_key(key)) return 1;                             // not one of this blob's tensors: ignored
-  HostTensor t;
-  int64_t n = 1;
-  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= shape[i]; }
-  t.data.resize((size_t)n);
-  if (dtype == BV2_F32) std::memcpy(t.data.data(), host_ptr, sizeof(float) * (size_t)n);
-  else if (dtype == BV2_F16) {
-    const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
-    for (int64_t i = 0; i < n; ++i) t.data[(size_t)i] = h2f(s[i]);
-  } else if (dtype == BV2_BF16) {
-    const uint16_t* s = static_cast<const uint16_t*>(host_ptr);
-    for (int64_t i = 0; i < n; ++i) { uint32_t b = (uint32_t)s[i] << 16; std::memcpy(&t.data[(size_t)i], &b, 4); }
-  } else { h->err = "bv2_sdp_forward_load_tensor: unknown dtype"; return -1; }
-  h->sdpf_tensors[key] = std::move(t);
-  return 0;
-  BV2_CATCH(h)
-}
-
-int bv2_sdp_forward_pack(bv2_handle* h, void* host_blob, int64_t bytes) {
-  if (!h) return -1;
-  BV2_TRY
-  if (int rc = sdp_forward_layout(h, "bv2_sdp_forward_pack")) return rc;
-  if (!host_blob || bytes < h->sdpf.total_floats * (int64_t)sizeof(float)) { h->err = "bv2_sdp_forward_pack: buffer too small"; return -1; }
-  return pack_sdp_forward_blob(h->model.cfg, h->sdpf, h->sdpf_tensors, static_cast<float*>(host_blob), h->err);
-  BV2_CATCH(h)
-}
-
-int bv2_sdp_forward_attach(bv2_handle* h, const void* dev_blob, int64_t bytes) {
-  if (!h) return -1;
-  BV2_TRY
-  if (int rc = sdp_forward_layout(h, "bv2_sdp_forward_attach")) return rc;
-  if (!dev_blob || bytes < h->sdpf.total_floats * (int64_t)sizeof(float)) { h->err = "bv2_sdp_forward_attach: blob too small for this config"; return -1; }
-  uint32_t hdr[8];
-  if (hipMemcpy(hdr, dev_blob, sizeof(hdr), hipMemcpyDeviceToHost) != hipSuccess) {
-    h->err = "bv2_sdp_forward_attach: cannot read the blob header (is this a device pointer on the current GPU?)";
-    return -6;
-  }
-  if (!blob_header_matches(hdr, kSdpForwardMagic, BV2_SDP_FORWARD_LAYOUT, h->sdpf.cfg_hash, h->sdpf.total_floats)) {
-    h->err = "bv2_sdp_forward_attach: blob header does not match this handle's config (not a forward duration predictor blob, or packed for another model)";
-    return -7;
-  }
-  h->sdpf_blob = static_cast<const float*>(dev_blob);
-  return 0;
-  BV2_CATCH(h)
-}
-
-int bv2_sdp_forward_detach(bv2_handle* h) {
-  if (!h) return -1;
-  h->sdpf_blob = nullptr;
-  return 0;
 }
 
 int64_t bv2_duration_nll_workspace_bytes(const bv2_handle* h, int B, int T) {
@@ -326,8 +244,8 @@ int bv2_duration_nll(bv2_handle* h, bv2_stream stream, int B, int T, const float
   if ((int64_t)h->model.cfg.hidden_channels * T >= (1ll << 31)) { h->err = "bv2_duration_nll: hidden_channels * T must stay below 2^31"; return -1; }
   if (!ws) { h->err = "bv2_duration_nll: workspace is null"; return -5; }
   if (wsb < duration_nll_workspace_bytes(h->model, B, T)) { h->err = "workspace too small for bv2_duration_nll"; return -5; }
-  if (!h->blob) { h->err = "bv2_duration_nll: no weights attached (call bv2_pack_weights + bv2_attach_weights first)"; return -8; }
-  if (!h->sdpf_blob) {
+  if (!h->blob[kInference].dev) { h->err = "bv2_duration_nll: no weights attached (call bv2_pack_weights + bv2_attach_weights first)"; return -8; }
+  if (!h->blob[kSdpForward].dev) {
     h->err = "bv2_duration_nll: no forward duration predictor weights attached (bv2_sdp_forward_pack + bv2_sdp_forward_attach; release "
              "checkpoints written by compress_model.py are stripped of sdp.post_*)";
     return -8;
@@ -382,12 +300,12 @@ int bv2_set_flow_dtype(bv2_handle* h, int dtype) {
     const Model& m = h->model;
     bool ok = m.cfg.hidden_channels % 32 == 0;
     for (int a = 0; a < m.n_coupling && ok; ++a)
-      for (int i = 0; i < m.coupling[a].wn_layers && ok; ++i) {
-        const CouplingW& K = m.coupling[a];
-        const bool last = i + 1 == K.wn_layers;
-        ok = K.wn_in[i].wh_off >= 0 && K.wn_skip[i].wh_off >= 0 && (last || K.wn_res[i].wh_off >= 0) &&
-             conv_f16_supported(K.wn_in[i].cin, K.wn_in[i].cout, K.wn_in[i].k, 1, true) &&
-             conv_f16_supported(K.wn_skip[i].cin, K.wn_skip[i].cout, 1, 1, false);
+      for (int i = 0; i < m.coupling[a].wn.layers && ok; ++i) {
+        const WnW& K = m.coupling[a].wn;
+        const bool last = i + 1 == K.layers;
+        ok = K.in[i].wh_off >= 0 && K.skip[i].wh_off >= 0 && (last || K.res[i].wh_off >= 0) &&
+             conv_f16_supported(K.in[i].cin, K.in[i].cout, K.in[i].k, 1, true) &&
+             conv_f16_supported(K.skip[i].cin, K.skip[i].cout, 1, 1, false);
       }
     if (!ok) { h->err = "bv2_set_flow_dtype: the fp16 WN flow needs hidden_channels % 32 == 0"; return -2; }
   } else if (dtype == BV2_F16) {
@@ -413,7 +331,7 @@ int64_t bv2_workspace_bytes(const bv2_handle* h, int B, int T, int Ty_max) {
 
 static int ready(bv2_handle* h, const void* ws) {
   if (!h) return -1;
-  if (!h->blob) { h->err = "no weights attached (call bv2_pack_weights + bv2_attach_weights first)"; return -8; }
+  if (!h->blob[kInference].dev) { h->err = "no weights attached (call bv2_pack_weights + bv2_attach_weights first)"; return -8; }
   if (!ws) { h->err = "workspace is null"; return -5; }
   return 0;
 }
@@ -508,7 +426,7 @@ int bv2_decode_ex(bv2_handle* h, bv2_stream stream, const bv2_decode_in* in, con
 
 int bv2_stage_emb_g(bv2_handle* h, bv2_stream stream, int B, const int64_t* sid, float* g) {
   if (!h) return -1;
-  if (!h->blob) { h->err = "no weights attached (call bv2_pack_weights + bv2_attach_weights first)"; return -8; }
+  if (!h->blob[kInference].dev) { h->err = "no weights attached (call bv2_pack_weights + bv2_attach_weights first)"; return -8; }
   BV2_TRY
   if (B < 1 || !sid || !g) { h->err = "bv2_stage_emb_g: bad argument"; return -1; }
   if (h->model.cfg.n_speakers == 0) { h->err = "bv2_stage_emb_g: this model has no speaker table (n_speakers == 0); g comes from bv2_ref_encode"; return -2; }
@@ -1050,7 +968,7 @@ int bv2_align(bv2_handle* h, bv2_stream stream, int B, int T, int Ty, const floa
               float* score, void* ws, int64_t wsb) {
   if (int rc = ready(h, ws)) return rc;
   BV2_TRY
-  if (!h->post_blob) {
+  if (!h->blob[kPosterior].dev) {
     h->err = "bv2_align: no posterior weights attached (bv2_posterior_pack + bv2_posterior_attach; release checkpoints written by "
              "compress_model.py are stripped of enc_q.*)";
     return -8;
@@ -1088,7 +1006,7 @@ static int capture_phase(bv2_handle* h, bv2_stream stream, bv2_graph** graph, co
                          const std::function<int(hipStream_t)>& run) {
   if (!graph) { h->err = std::string(what) + ": graph is null"; return -1; }
   *graph = nullptr;
-  if (!h->blob) { h->err = std::string(what) + ": no weights attached"; return -4; }
+  if (!h->blob[kInference].dev) { h->err = std::string(what) + ": no weights attached"; return -4; }
   if (h->prof_on || !h->taps.empty()) { h->err = std::string(what) + ": switch profiling and taps off before capturing"; return -1; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (!s) { h->err = std::string(what) + ": capture needs a non-default stream"; return -1; }

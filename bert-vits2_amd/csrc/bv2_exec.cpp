@@ -677,7 +677,7 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
   Arena A(ws, wsb);
   PlanA P = plan_a(A, m, B, T);
   if (int e = ws_short(h, A, "bv2_encode_durations")) return e;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const float* mask = out.x_mask;
 
   // Run only the predictor the mix can see (include/bv2.h, bv2_encode_out): logw = sdp * r + dp * (1 - r), so at r == 0 the stochastic
@@ -718,7 +718,7 @@ int run_encode(bv2_handle* h, hipStream_t s, const bv2_encode_in& in, const bv2_
     }
     if (!h->no_overlap_dp && hipEventRecord(h->ev_fork, s) == hipSuccess &&
         hipStreamWaitEvent(h->side_stream, h->ev_fork, 0) == hipSuccess) {
-      Ctx c2{h, h->side_stream, m, h->blob};
+      Ctx c2{h, h->side_stream, m, h->blob[kInference].dev};
       dp_core(c2, P, P.dp0, mask, B, T, logw_dp);
       if (c2.rc && !c.rc) c.rc = c2.rc;
       if (hipEventRecord(h->ev_join, h->side_stream) != hipSuccess) c.fail("dp join", -6);
@@ -739,7 +739,7 @@ int run_ref_encode(bv2_handle* h, hipStream_t s, const float* y, const int64_t* 
   const Model& m = h->model;
   const int spec = m.cfg.spec_channels;
   if (wsb < (int64_t)sizeof(float) * ref_enc_workspace_floats(B, L, spec)) { h->err = "workspace too small for bv2_ref_encode"; return -5; }
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const RefEncW& R = m.ref_enc;
   RefEncArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -757,7 +757,7 @@ int run_ref_encode(bv2_handle* h, hipStream_t s, const float* y, const int64_t* 
 // ---- the reference's ONNX stages of phase A (include/bv2.h) --------------------------------------------------------
 int run_stage_emb_g(bv2_handle* h, hipStream_t s, int B, const int64_t* sid, float* g) {
   const Model& m = h->model;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   c.chk(launch_gather_rows(s, c.W(m.emb_g.off), sid, g, B, m.cfg.gin_channels, m.cfg.n_speakers), "emb_g");
   return c.rc;
 }
@@ -770,7 +770,7 @@ int run_stage_enc_p(bv2_handle* h, hipStream_t s, int B, int T, const int64_t* x
   Arena A(ws, wsb);
   PlanA P = plan_a(A, m, B, T);
   if (int e = ws_short(h, A, "bv2_stage_enc_p")) return e;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const GemvW* gw[1] = {&m.enc.spk};
   float* go[1] = {P.gv};
   run_front(c, nullptr, g, nullptr, gw, go, 1, 3 * H, x_lengths, x_mask, B, T, nullptr, nullptr, 0.f);
@@ -786,7 +786,7 @@ int run_stage_sdp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, co
   Arena A(ws, wsb);
   PlanA P = plan_a(A, m, B, T);
   if (int e = ws_short(h, A, "bv2_stage_sdp")) return e;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const GemvW* gw[1] = {&m.sdp_cond};
   float* go[1] = {P.gv + H};
   run_front(c, nullptr, g, nullptr, gw, go, 1, 3 * H, nullptr, nullptr, B, T, zin, P.z, 1.0f);   // zin is already scaled
@@ -862,7 +862,7 @@ int run_duration_nll(bv2_handle* h, hipStream_t s, int B, int T, const float* x,
                      const float* noise_e, float* nll_sym, float* nll, void* ws, int64_t wsb) {
   const Model& m = h->model;
   const SdpForwardW& F = h->sdpf;
-  const float* fb = h->sdpf_blob;
+  const float* fb = h->blob[kSdpForward].dev;
   const int H = m.cfg.hidden_channels;
   if (!dds_fused_supported(H)) { h->err = "bv2_duration_nll: hidden_channels must be 128, 192 or 256"; return -1; }
   if (int e = check_seeds(h, B, noise_e, "bv2_duration_nll", "noise_e")) return e;
@@ -870,7 +870,7 @@ int run_duration_nll(bv2_handle* h, hipStream_t s, int B, int T, const float* x,
   Arena A(ws, wsb);
   PlanNll P = plan_nll(A, m, B, T);
   if (int e = ws_short(h, A, "bv2_duration_nll")) return e;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const float sqrt_fc = (float)std::sqrt((double)H);
   // the trunk x = proj(convs(pre(x) + cond(g))) * mask: the launches of phase A (sdp_core)
   const GemvW* gw[1] = {&m.sdp_cond};
@@ -913,7 +913,7 @@ int run_duration_nll(bv2_handle* h, hipStream_t s, int B, int T, const float* x,
   for (int i = 0; i < kSdpFlows; ++i) {
     const int src = i % 2, dst = 1 - src;
     const ConvFlowW& cf = i == 0 ? F.cf_first : m.cf[kSdpFlowsUsed - i];     // flows.1, then .3 / .5 / .7 = cf[2] / [1] / [0]
-    const float* blob = i == 0 ? fb : h->blob;
+    const float* blob = i == 0 ? fb : h->blob[kInference].dev;
     DdsFwdPre pre;
     pre.w = blob + cf.pre_w.off; pre.b = blob + cf.pre_b.off; pre.z = P.z; pre.z_src = src; pre.g = P.x;
     DdsFwdPost post;
@@ -931,7 +931,7 @@ int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, con
   Arena A(ws, wsb);
   PlanA P = plan_a(A, m, B, T);
   if (int e = ws_short(h, A, "bv2_stage_dp")) return e;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const GemvW* gw[1] = {&m.dp_cond};
   float* go[1] = {P.gv + 2 * H};
   run_front(c, nullptr, g, nullptr, gw, go, 1, 3 * H, nullptr, nullptr, B, T, nullptr, nullptr, 0.f);
@@ -943,22 +943,23 @@ int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, con
 // WN.forward (modules.py:185-210) in fp32, 2 launches per layer: in_layer + g_l + gate (ACT_GATE epilogue), then res_skip as two
 // problems of one launch — x = (x + rs[:H]) * mask in place, output += rs[H:] (first layer: =; last layer: all H rows, * mask).
 // The residual flow's couplings and the posterior encoder (16 layers) run on it; gl: the layers' conditioning rows [nl][2H] per item.
-static void run_wn(Ctx& c, const ConvW* wn_in, const ConvW* wn_res, const ConvW* wn_skip, int nl, const float* gl, int gl_bstride,
-                   float* x, float* acts, float* outacc, const float* mask, int B, int H, int Ty) {
+static void run_wn(Ctx& c, const WnW& W, const float* gl, int gl_bstride, float* x, float* acts, float* outacc, const float* mask, int B,
+                   int H, int Ty) {
+  const int nl = W.layers;
   for (int i = 0; i < nl; ++i) {
     const bool last = i == nl - 1;
-    ConvProb p = c.prob(wn_in[i], x, acts, Ty);
+    ConvProb p = c.prob(W.in[i], x, acts, Ty);
     p.bias2 = gl + (int64_t)i * 2 * H; p.bias2_bstride = gl_bstride;
     p.act = ACT_GATE; p.out_bstride = (int64_t)H * Ty;
     c.conv1(p, B, Ty, "wn.in+gate");
     ConvLaunch cl;
     cl.B = B; cl.L = Ty; cl.nprob = 0;
     if (!last) {
-      ConvProb r = c.prob(wn_res[i], acts, x, Ty);
+      ConvProb r = c.prob(W.res[i], acts, x, Ty);
       r.res = x; r.res_mode = RES_ADD; r.out_mask = mask; r.mask_post = 1;
       cl.p[cl.nprob++] = r;
     }
-    ConvProb sk = c.prob(wn_skip[i], acts, outacc, Ty);
+    ConvProb sk = c.prob(W.skip[i], acts, outacc, Ty);
     if (i > 0) { sk.res = outacc; sk.res_mode = RES_ADD; }
     if (last) { sk.out_mask = mask; sk.mask_post = 1; }
     cl.p[cl.nprob++] = sk;
@@ -1022,20 +1023,20 @@ static void flow_core(Ctx& c, const PlanB& P, float* z, const float* ymask, cons
       // bias + g_l and gates in fp32, writes the gate output as fp16 channels-last — it is only ever res_skip's input; res_skip
       // runs as two problems of one launch on that tensor with the fp32 epilogues of the fp32 path (x update in place with the
       // mask, skip sum).  x, the skip sum, pre / post stay fp32.
-      const int nl = K.wn_layers;
+      const int nl = K.wn.layers;
       const float* gl = gv_flow + (int64_t)a * 2 * H * nl;
       uint16_t* actsh = reinterpret_cast<uint16_t*>(P.acts);
       for (int i = 0; i < nl; ++i) {
         const bool last = i == nl - 1;
-        HcProb q = c.hprob(K.wn_in[i], P.h, true, actsh, false, Ty);
+        HcProb q = c.hprob(K.wn.in[i], P.h, true, actsh, false, Ty);
         q.bias2 = gl + (int64_t)i * 2 * H; q.bias2_bstride = P.gv_stride;
         q.act = ACT_GATE; q.out_bstride = (int64_t)H * Ty;
         c.conv_h(q, B, Ty, "wn.in+gate");
-        HcProb sk = c.hprob(K.wn_skip[i], actsh, false, P.outacc, true, Ty);
+        HcProb sk = c.hprob(K.wn.skip[i], actsh, false, P.outacc, true, Ty);
         if (i > 0) { sk.res = P.outacc; sk.res_mode = RES_ADD; }
         if (last) { sk.out_mask = ymask; sk.mask_post = 1; }
         if (!last) {
-          HcProb r = c.hprob(K.wn_res[i], actsh, false, P.h, true, Ty);
+          HcProb r = c.hprob(K.wn.res[i], actsh, false, P.h, true, Ty);
           r.res = P.h; r.res_mode = RES_ADD; r.out_mask = ymask; r.mask_post = 1;
           c.conv_h(r, B, Ty, "wn.res_skip", &sk);
         } else {
@@ -1044,8 +1045,7 @@ static void flow_core(Ctx& c, const PlanB& P, float* z, const float* ymask, cons
       }
       hres = P.outacc;
     } else {
-      run_wn(c, K.wn_in, K.wn_res, K.wn_skip, K.wn_layers, gv_flow + (int64_t)a * 2 * H * K.wn_layers, P.gv_stride, P.h, P.acts, P.outacc,
-             ymask, B, H, Ty);
+      run_wn(c, K.wn, gv_flow + (int64_t)a * 2 * H * K.wn.layers, P.gv_stride, P.h, P.acts, P.outacc, ymask, B, H, Ty);
       hres = P.outacc;
     }
     c.tap(hres, (int64_t)B * H * Ty, "flow.", a, ".enc");
@@ -1475,7 +1475,7 @@ static GemvLaunch phase_b_gemv_args(Ctx& c, const PlanB& P, const float* g, int 
   float* gf = P.gv + cf.upsample_initial_channel;
   for (int a = 0; a < m.n_coupling; ++a) {
     if (cf.use_transformer_flow) add(m.coupling[a].enc.spk, gf + a * cf.hidden_channels);
-    else add(m.coupling[a].wn_cond, gf + (int64_t)a * 2 * cf.hidden_channels * cf.n_flow_layer);
+    else add(m.coupling[a].wn.cond, gf + (int64_t)a * 2 * cf.hidden_channels * cf.n_flow_layer);
   }
   G.nprob = n; G.B = B; G.g = g; G.g_bstride = cf.gin_channels;
   return G;
@@ -1534,7 +1534,7 @@ int run_decode(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, const bv2_
   Arena A(ws, wsb);
   PlanB P = plan_b(A, m, B, Ty);
   if (int e = ws_short(h, A, "bv2_decode")) return e;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   float* z = out.z ? out.z : P.z;
   float* ymask = out.y_mask ? out.y_mask : P.ymask;
   const bool slots_clear = expand_and_flow(c, P, in, out, ic, z, ymask, true);
@@ -1554,7 +1554,7 @@ int run_flow(bv2_handle* h, hipStream_t s, int B, int Ty, const float* z_p, cons
   Arena A(ws, wsb);
   PlanB P = plan_b(A, m, B, Ty);
   if (int e = ws_short(h, A, forward ? "bv2_stage_flow_forward" : "bv2_stage_flow")) return e;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const float* ymask = y_mask;
   if (!ymask) {
     c.chk(launch_seq_mask(s, y_lengths, P.ymask, B, Ty), "y_mask");
@@ -1602,7 +1602,7 @@ int run_posterior_encode(bv2_handle* h, hipStream_t s, int B, int Ty, const floa
   Arena A(ws, wsb);
   PlanQ P = plan_q(A, m, B, Ty);
   if (int e = ws_short(h, A, "bv2_posterior_encode")) return e;
-  Ctx c{h, s, m, h->post_blob};
+  Ctx c{h, s, m, h->blob[kPosterior].dev};
   float* ymask = y_mask ? y_mask : P.ymask;
   float* mq = m_q ? m_q : P.m;
   float* lq = logs_q ? logs_q : P.logs;
@@ -1610,8 +1610,8 @@ int run_posterior_encode(bv2_handle* h, hipStream_t s, int B, int Ty, const floa
   {
     GemvLaunch G;                                    // cond_layer(g): every layer's conditioning rows, as phase B computes the flow's
     std::memset(&G, 0, sizeof(G));
-    G.p[0].w = c.W(Q.cond.w_off); G.p[0].bias = c.W(Q.cond.b_off); G.p[0].out = P.gv; G.p[0].cout = Q.cond.cout; G.p[0].cin = Q.cond.cin;
-    G.p[0].out_bstride = Q.cond.cout;
+    G.p[0].w = c.W(Q.wn.cond.w_off); G.p[0].bias = c.W(Q.wn.cond.b_off); G.p[0].out = P.gv; G.p[0].cout = Q.wn.cond.cout; G.p[0].cin = Q.wn.cond.cin;
+    G.p[0].out_bstride = Q.wn.cond.cout;
     G.nprob = 1; G.B = B; G.g = g; G.g_bstride = m.cfg.gin_channels;
     c.chk(launch_gemv(s, G), "enc_q.cond");
   }
@@ -1619,7 +1619,7 @@ int run_posterior_encode(bv2_handle* h, hipStream_t s, int B, int Ty, const floa
   p.out_mask = ymask; p.mask_post = 1;
   c.conv1(p, B, Ty, "enc_q.pre");
   c.tap(P.h, (int64_t)B * H * Ty, "enc_q.pre");
-  run_wn(c, Q.wn_in, Q.wn_res, Q.wn_skip, kPosteriorLayers, P.gv, Q.cond.cout, P.h, P.acts, P.outacc, ymask, B, H, Ty);
+  run_wn(c, Q.wn, P.gv, Q.wn.cond.cout, P.h, P.acts, P.outacc, ymask, B, H, Ty);
   c.tap(P.outacc, (int64_t)B * H * Ty, "enc_q.enc");
   {
     ConvLaunch cl;
@@ -1640,7 +1640,7 @@ int run_generator(bv2_handle* h, hipStream_t s, int B, int Ty, int L, const floa
   Arena A(ws, wsb);
   PlanB P = plan_b(A, m, B, Ty);
   if (int e = ws_short(h, A, "bv2_stage_generator")) return e;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const float* ymask = nullptr;                    // y_lengths == null: z_in is taken as it is (the exported dec graph)
   if (y_lengths) {
     c.chk(launch_seq_mask(s, y_lengths, P.ymask, B, Ty), "y_mask");
@@ -1711,7 +1711,7 @@ int run_stream_begin(bv2_handle* h, hipStream_t s, const bv2_decode_in& in, cons
   PlanS S = plan_stream(A, m, B, Ty, 1, 1);
   if (int e = ws_short(h, A, "bv2_stream_begin")) return e;
   const PlanB& P = S.b;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   expand_and_flow(c, P, in, out, ic, P.z, P.ymask, false);   // the windows' Generator runs zero their own x3 slots
   if (c.rc) return c.rc;
   // the caller's copies (bv2_decode writes them in place; here the workspace's are the ones the windows read)
@@ -1732,7 +1732,7 @@ int run_stream_chunk(bv2_handle* h, hipStream_t s, const bv2_stream_chunk_args& 
   PlanS S = plan_stream(A, m, B, Ty, W, 2);
   if (int e = ws_short(h, A, "bv2_stream_chunk")) return e;
   const PlanB& P = S.b;
-  Ctx c{h, s, m, h->blob};
+  Ctx c{h, s, m, h->blob[kInference].dev};
   const int64_t* lens = nullptr;
   if (a.exact_lengths) {
     c.chk(launch_stream_window_lens(s, a.y_lengths, S.wlens, w0, W, B), "stream.window_lens");

@@ -52,14 +52,19 @@ struct DDSLayerW { VecW dww, dwb; ConvW c1x1; VecW g1, b1, g2, b2; int dil = 1; 
 struct DDSW { DDSLayerW l[kSdpLayers]; };
 struct ConvFlowW { VecW pre_w, pre_b; DDSW convs; ConvW proj; };
 
+// modules.WN (modules.py:160-210), the stack of the residual flow's couplings and of the posterior encoder
+struct WnW {
+  GemvW cond;                        // cond_layer: 2 * hidden * layers rows, each layer's slice in the gate order of `in`
+  ConvW in[kMaxLayers];              // rows in gate order (ACT_GATE): per 32-row tile 16 tanh rows then their 16 sigmoid rows
+  ConvW res[kMaxLayers], skip[kMaxLayers];   // res_skip_layers split into its x-update rows and its output rows
+  int layers = 0;
+};
+
 struct CouplingW {
   bool flipped = false;              // channel Flip folded into pre/post weight permutations
   ConvW pre, post;
   EncoderW enc;                      // transformer flow
-  GemvW wn_cond;                     // residual (WN) flow
-  ConvW wn_in[kMaxLayers];             // rows in gate order (ACT_GATE): per 32-row tile 16 tanh rows then their 16 sigmoid rows
-  ConvW wn_res[kMaxLayers], wn_skip[kMaxLayers];   // res_skip_layers split into its x-update rows and its output rows
-  int wn_layers = 0;
+  WnW wn;                            // residual (WN) flow
 };
 
 struct UpW {
@@ -127,11 +132,8 @@ constexpr int kPosteriorLayers = 16;               // modules.WN(hidden, 5, 1, 1
 struct PosteriorW {
   int spec = 0;                      // spec_channels: pre's input rows (odd widths ride on cin_pad, rows >= cin read as zero)
   ConvW pre;                         // Conv1d(spec -> hidden, 1)
-  GemvW cond;                        // enc.cond_layer: 2 * hidden * 16 rows, in gate order like CouplingW::wn_cond
-  ConvW wn_in[kMaxLayers], wn_res[kMaxLayers], wn_skip[kMaxLayers];   // as CouplingW's
+  WnW wn;                            // enc: kPosteriorLayers layers
   ConvW proj_m, proj_logs;           // proj (hidden -> 2 inter, 1) split into its halves
-  int64_t total_floats = 0;
-  uint32_t cfg_hash = 0;
 };
 
 // What the StochasticDurationPredictor needs in its FORWARD direction and the inference blob does not hold (models.py:176-187, 206-244):
@@ -145,8 +147,6 @@ struct SdpForwardW {
   VecW post_ea_m, post_ea_logs;      // post_flows.0
   ConvFlowW post_cf[kSdpFlows];      // post_flows.1, .3, .5, .7 in forward order
   ConvFlowW cf_first;                // flows.1; flows.3 / .5 / .7 are Model::cf[2] / [1] / [0] of the inference blob
-  int64_t total_floats = 0;
-  uint32_t cfg_hash = 0;
 };
 
 struct Model {
@@ -187,8 +187,6 @@ struct Model {
   VecW conv_post;
   int post_c = 0, post_k = 7;
   int total_up = 1;
-  int64_t total_floats = 0;
-  uint32_t cfg_hash = 0;
 };
 
 // ---- shared by the two host executors (bv2_exec.cpp, bv2_bert.cpp) ----
@@ -241,6 +239,31 @@ inline Prefetch weight_prefetch(const ConvW* w, const float* blob, bool on) {
 
 struct HostTensor { std::vector<float> data; std::vector<int64_t> shape; };
 
+// A packed weight blob as the handle holds it, whatever it packs: the host tensors its load call took, its length and config hash once its
+// layout is built (total_floats == 0: not yet), the attached device copy.  The typed descriptor of its contents (Model, PosteriorW,
+// SdpForwardW) stands beside it on the handle.
+struct WeightBlob {
+  std::map<std::string, HostTensor> tensors;
+  const float* dev = nullptr;
+  int64_t total_floats = 0;
+  uint32_t cfg_hash = 0;
+};
+// ... and what tells the three kinds apart: the two header numbers (bv2_pack.h write_blob_header), the keys it takes, its name in messages
+enum BlobKind { kInference = 0, kPosterior, kSdpForward, kBlobKinds };
+struct BlobDesc {
+  uint32_t magic, layout;
+  bool (*mine)(const std::string& key);
+  const char* noun;
+};
+bool inference_key(const std::string& key);                        // everything but the other two kinds' (training-only) tensors
+bool posterior_key(const std::string& key);                        // enc_q.*
+bool sdp_forward_key(const std::string& key);                      // sdp.post_* and sdp.flows.1.*
+constexpr BlobDesc kBlobDesc[kBlobKinds] = {
+    {kBlobMagic, BV2_PACK_LAYOUT, inference_key, "inference"},
+    {kPosteriorMagic, BV2_POSTERIOR_LAYOUT, posterior_key, "posterior encoder"},
+    {kSdpForwardMagic, BV2_SDP_FORWARD_LAYOUT, sdp_forward_key, "forward duration predictor"},
+};
+
 struct ProfileRec { hipEvent_t e0, e1; int fam; double flops, bytes; };
 
 struct Tap { float* dst; int64_t cap; };
@@ -248,17 +271,10 @@ struct Tap { float* dst; int64_t cap; };
 }  // namespace bv2
 
 struct bv2_handle {
-  bv2::Model model;
-  std::map<std::string, bv2::HostTensor> tensors;
-  const float* blob = nullptr;       // device
-  // the posterior encoder's own weights (bv2_posterior_*): layout once spec_channels is known, host tensors, attached device blob
-  bv2::PosteriorW post;
-  std::map<std::string, bv2::HostTensor> post_tensors;
-  const float* post_blob = nullptr;  // device
-  // the forward duration predictor's own weights (bv2_sdp_forward_*): the same three parts
-  bv2::SdpForwardW sdpf;
-  std::map<std::string, bv2::HostTensor> sdpf_tensors;
-  const float* sdpf_blob = nullptr;  // device
+  bv2::Model model;                  // laid out by bv2_create
+  bv2::PosteriorW post;              // laid out once spec_channels is known (bv2_posterior_*), again when it changes
+  bv2::SdpForwardW sdpf;             // laid out on first use (bv2_sdp_forward_*)
+  bv2::WeightBlob blob[bv2::kBlobKinds];
   std::string err;
   std::map<std::string, bv2::Tap> taps;
   int gen_dtype = BV2_F32;           // Generator arithmetic: BV2_F32 (conv_mfma.hip) or BV2_BF16 (gen_bf16.hip)
@@ -317,14 +333,14 @@ struct bv2_handle {
 namespace bv2 {
 
 // bv2_model.cpp
-int build_layout(Model& m, std::string& err);                       // fills every descriptor + total_floats
-int pack_blob(const Model& m, const std::map<std::string, HostTensor>& t, float* blob, std::string& err);
-bool key_in_schema(const Model& m, const std::string& key);
-int build_posterior_layout(const bv2_config& cfg, int spec_channels, PosteriorW& w, std::string& err);
-int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w, const std::map<std::string, HostTensor>& t, float* blob, std::string& err);
-bool sdp_forward_key(const std::string& key);                      // sdp.post_* and sdp.flows.1.*
-int build_sdp_forward_layout(const bv2_config& cfg, SdpForwardW& w, std::string& err);
-int pack_sdp_forward_blob(const bv2_config& cfg, const SdpForwardW& w, const std::map<std::string, HostTensor>& t, float* blob, std::string& err);
+// first pass: every descriptor, b.total_floats and b.cfg_hash; on an error nothing is touched
+int build_layout(Model& m, WeightBlob& b, std::string& err);
+int build_posterior_layout(const bv2_config& cfg, int spec_channels, PosteriorW& w, WeightBlob& b, std::string& err);
+int build_sdp_forward_layout(const bv2_config& cfg, SdpForwardW& w, WeightBlob& b, std::string& err);
+// second pass: b.tensors into `blob` (b.total_floats floats), header included
+int pack_blob(const Model& m, const WeightBlob& b, float* blob, std::string& err);
+int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w, const WeightBlob& b, float* blob, std::string& err);
+int pack_sdp_forward_blob(const bv2_config& cfg, const SdpForwardW& w, const WeightBlob& b, float* blob, std::string& err);
 
 // bv2_exec.cpp
 // active seeds (bv2_set_noise_seeds) against a call's batch and its noise pointer: non-zero with h->err set on a mismatch

@@ -26,6 +26,19 @@ namespace bv2 {
 
 namespace {
 
+// weight_norm fold w = g * v / ||v|| over all dims but 0: v is [d0][inner], g is [d0]
+void fold_weight_norm(const std::vector<float>& v, const std::vector<float>& g, int64_t d0, int64_t inner, std::vector<float>& w) {
+  w.resize(v.size());
+  for (int64_t a = 0; a < d0; ++a) {
+    double ss = 0;
+    for (int64_t i = 0; i < inner; ++i) { const double x = v[a * inner + i]; ss += x * x; }
+    // torch computes the norm in fp32; a double sqrt rounded to fp32 agrees to <= 1 ulp
+    const float nrm = (float)std::sqrt(ss);
+    const float sc = g[a] / nrm;
+    for (int64_t i = 0; i < inner; ++i) w[a * inner + i] = v[a * inner + i] * sc;
+  }
+}
+
 struct Packer {
   const std::map<std::string, HostTensor>* T = nullptr;   // null => layout only
   float* blob = nullptr;
@@ -45,11 +58,10 @@ struct Packer {
     return off;
   }
 
-  const HostTensor* get(const std::string& key, std::initializer_list<int64_t> shape) {
+  const HostTensor* get(const std::string& key, const std::vector<int64_t>& want) {
     if (!fill()) return nullptr;
     auto it = T->find(key);
     if (it == T->end()) { missing.push_back(key); return nullptr; }
-    std::vector<int64_t> want(shape);
     if (it->second.shape != want) {
       std::string s = key + " (shape mismatch: got [";
       for (auto d : it->second.shape) s += std::to_string(d) + ",";
@@ -63,32 +75,26 @@ struct Packer {
   }
   bool has(const std::string& key) const { return fill() && T->count(key); }
 
-  // folded weight [d0][d1][k] of a (possibly weight-normed) conv; norm over all dims but 0
-  bool folded(const std::string& p, int d0, int d1, int k, std::vector<float>& w) {
+  // folded weight of a (possibly weight-normed) conv of any rank, shape = [d0][...]; norm over all dims but 0
+  bool folded(const std::string& p, const std::vector<int64_t>& shape, std::vector<float>& w) {
     if (!fill()) return false;
     if (has(p + ".weight_v") || !has(p + ".weight")) {
-      const HostTensor* v = get(p + ".weight_v", {d0, d1, k});
-      const HostTensor* g = get(p + ".weight_g", {d0, 1, 1});
+      std::vector<int64_t> gshape(shape.size(), 1);
+      gshape[0] = shape[0];
+      const HostTensor* v = get(p + ".weight_v", shape);
+      const HostTensor* g = get(p + ".weight_g", gshape);
       if (!v || !g) return false;
-      w.resize(v->data.size());
-      const int64_t inner = (int64_t)d1 * k;
-      for (int a = 0; a < d0; ++a) {
-        double ss = 0;
-        for (int64_t i = 0; i < inner; ++i) { const double x = v->data[a * inner + i]; ss += x * x; }
-        // torch computes the norm in fp32; a double sqrt rounded to fp32 agrees to <= 1 ulp
-        const float nrm = (float)std::sqrt(ss);
-        const float sc = g->data[a] / nrm;
-        for (int64_t i = 0; i < inner; ++i) w[a * inner + i] = v->data[a * inner + i] * sc;
-      }
+      fold_weight_norm(v->data, g->data, shape[0], (int64_t)v->data.size() / shape[0], w);
       return true;
     }
-    const HostTensor* t = get(p + ".weight", {d0, d1, k});
+    const HostTensor* t = get(p + ".weight", shape);
     if (!t) return false;
     w = t->data;
     return true;
   }
+  bool folded(const std::string& p, int d0, int d1, int k, std::vector<float>& w) { return folded(p, {d0, d1, k}, w); }
 
-  VecW vec(const std::string& key, std::initializer_list<int64_t> shape) {
+  VecW vec(const std::string& key, const std::vector<int64_t>& shape) {
     int64_t n = 1;
     for (auto d : shape) n *= d;
     VecW v; v.n = n; v.off = alloc(n);
@@ -246,6 +252,42 @@ DDSW pack_dds(Packer& P, const std::string& p, int c) {
   return d;
 }
 
+ConvFlowW pack_convflow(Packer& P, const std::string& p, int hid) {
+  ConvFlowW f;
+  f.pre_w = P.vec(p + ".pre.weight", {hid, 1, 1});
+  f.pre_b = P.vec(p + ".pre.bias", {hid});
+  f.convs = pack_dds(P, p + ".convs", hid);
+  f.proj = P.conv1d(p + ".proj", 3 * kSdpBins - 1, hid, 1);
+  return f;
+}
+
+// modules.WN `p` (the residual flow's couplings, enc_q.enc).  The gate (commons.py:98-105: tanh(first half) * sigmoid(second half)) is fused
+// into in_layer's epilogue (ACT_GATE): rows are packed so that every 32-row tile holds the tanh rows of 16 channels followed by their
+// sigmoid rows; the conditioning slice g_l (cond_layer rows [2H*i, 2H*(i+1)), modules.py:189-197) is permuted the same way.
+// f16: in_layers / res_skip_layers also as fp16 streams in the same row order ("fp16 flow"); cond_layer never is.
+WnW pack_wn(Packer& P, const std::string& p, int hid, int nl, int gin, bool f16) {
+  WnW W;
+  W.layers = nl;
+  const std::function<int(int)> gate_row = [hid](int n) { const int mt = n / 32, j = n % 32; return j < 16 ? 16 * mt + j : hid + 16 * mt + (j - 16); };
+  const std::function<int(int)> cond_row = [hid, &gate_row](int n) { return (n / (2 * hid)) * 2 * hid + gate_row(n % (2 * hid)); };
+  W.cond = P.gemv(p + ".cond_layer", 2 * hid * nl, gin, true, /*wn=*/true, &cond_row);
+  P.emit_f16 = f16;
+  for (int i = 0; i < nl; ++i) {
+    const std::string rsn = p + ".res_skip_layers." + std::to_string(i);
+    W.in[i] = P.conv1d(p + ".in_layers." + std::to_string(i), 2 * hid, hid, kFlowKernel, true, true, 0, -1, false, false, &gate_row);
+    // res_skip (modules.py:203-210): rows [0,H) update x, rows [H,2H) accumulate into the output; the last layer has H rows,
+    // all of them output.  Two problems of ONE launch, each with its own residual target (no separate res/skip kernel).
+    if (i < nl - 1) {
+      W.res[i] = P.conv1d(rsn, 2 * hid, hid, 1, true, true, 0, hid);
+      W.skip[i] = P.conv1d(rsn, 2 * hid, hid, 1, true, true, hid, hid);
+    } else {
+      W.skip[i] = P.conv1d(rsn, hid, hid, 1, true, true);
+    }
+  }
+  P.emit_f16 = false;
+  return W;
+}
+
 uint32_t hash_cfg(const bv2_config& c_in) {
   // A model with a speaker table hashes the struct as it was before spec_channels was appended (the field is not read there), so its blob —
   // header included — is byte for byte what the earlier packer wrote; a ReferenceEncoder model hashes the whole struct.
@@ -275,23 +317,7 @@ void pack_ref_enc(Model& m, Packer& P) {
     R.cb[i] = P.vec(p + ".bias", {cout});
     if (!P.fill()) continue;
     std::vector<float> w;
-    if (P.has(p + ".weight_v") || !P.has(p + ".weight")) {
-      const HostTensor* v = P.get(p + ".weight_v", {cout, cin, 3, 3});
-      const HostTensor* g = P.get(p + ".weight_g", {cout, 1, 1, 1});
-      if (!v || !g) continue;
-      w.resize(v->data.size());
-      const int64_t inner = (int64_t)cin * 9;
-      for (int a = 0; a < cout; ++a) {
-        double ss = 0;
-        for (int64_t q = 0; q < inner; ++q) { const double x = v->data[a * inner + q]; ss += x * x; }
-        const float sc = g->data[a] / (float)std::sqrt(ss);      // as Packer::folded
-        for (int64_t q = 0; q < inner; ++q) w[a * inner + q] = v->data[a * inner + q] * sc;
-      }
-    } else {
-      const HostTensor* t = P.get(p + ".weight", {cout, cin, 3, 3});
-      if (!t) continue;
-      w = t->data;
-    }
+    if (!P.folded(p, {cout, cin, 3, 3}, w)) continue;
     float* dst = P.blob + R.cw[i].off;
     for (int co = 0; co < cout; ++co)
       for (int ci = 0; ci < cin; ++ci)
@@ -334,13 +360,7 @@ int pack_all(Model& m, Packer& P) {
   m.sdp_cond = P.gemv("sdp.cond", hid, gin, true);
   m.sdp_convs = pack_dds(P, "sdp.convs", hid);
   const int cf_idx[kSdpFlowsUsed] = {7, 5, 3};      // reversed(flows) minus the "useless vflow" (models.py:246-247)
-  for (int i = 0; i < kSdpFlowsUsed; ++i) {
-    const std::string p = "sdp.flows." + std::to_string(cf_idx[i]);
-    m.cf[i].pre_w = P.vec(p + ".pre.weight", {hid, 1, 1});
-    m.cf[i].pre_b = P.vec(p + ".pre.bias", {hid});
-    m.cf[i].convs = pack_dds(P, p + ".convs", hid);
-    m.cf[i].proj = P.conv1d(p + ".proj", 3 * kSdpBins - 1, hid, 1);
-  }
+  for (int i = 0; i < kSdpFlowsUsed; ++i) m.cf[i] = pack_convflow(P, "sdp.flows." + std::to_string(cf_idx[i]), hid);
   m.ea_m = P.vec("sdp.flows.0.m", {2, 1});
   m.ea_logs = P.vec("sdp.flows.0.logs", {2, 1});
 
@@ -374,28 +394,7 @@ int pack_all(Model& m, Packer& P) {
       C.enc = pack_encoder(P, p + ".enc", hid, filt, c.n_heads, c.n_layers_trans_flow, kFlowKernel, gin);
       P.emit_f16 = false;
     } else {
-      const int nl = c.n_flow_layer;
-      C.wn_layers = nl;
-      // WN gate (commons.py:98-105: tanh(first half) * sigmoid(second half)) fused into in_layer's epilogue (ACT_GATE): rows are
-      // packed so that every 32-row tile holds the tanh rows of 16 channels followed by their sigmoid rows; the conditioning
-      // slice g_l (cond_layer rows [2H*i, 2H*(i+1)), modules.py:189-197) is permuted the same way
-      const std::function<int(int)> gate_row = [hid](int n) { const int mt = n / 32, j = n % 32; return j < 16 ? 16 * mt + j : hid + 16 * mt + (j - 16); };
-      const std::function<int(int)> cond_row = [hid, &gate_row](int n) { return (n / (2 * hid)) * 2 * hid + gate_row(n % (2 * hid)); };
-      C.wn_cond = P.gemv(p + ".enc.cond_layer", 2 * hid * nl, gin, true, /*wn=*/true, &cond_row);
-      P.emit_f16 = true;                           // "fp16 flow": in_layers / res_skip_layers also as fp16 streams (same row order)
-      for (int i = 0; i < nl; ++i) {
-        const std::string rsn = p + ".enc.res_skip_layers." + std::to_string(i);
-        C.wn_in[i] = P.conv1d(p + ".enc.in_layers." + std::to_string(i), 2 * hid, hid, kFlowKernel, true, true, 0, -1, false, false, &gate_row);
-        // res_skip (modules.py:203-210): rows [0,H) update x, rows [H,2H) accumulate into the output; the last layer has H rows,
-        // all of them output.  Two problems of ONE launch, each with its own residual target (no separate res/skip kernel).
-        if (i < nl - 1) {
-          C.wn_res[i] = P.conv1d(rsn, 2 * hid, hid, 1, true, true, 0, hid);
-          C.wn_skip[i] = P.conv1d(rsn, 2 * hid, hid, 1, true, true, hid, hid);
-        } else {
-          C.wn_skip[i] = P.conv1d(rsn, hid, hid, 1, true, true);
-        }
-      }
-      P.emit_f16 = false;
+      C.wn = pack_wn(P, p + ".enc", hid, c.n_flow_layer, gin, /*f16=*/true);
     }
     C.post = P.conv1d(p + ".post", half, hid, 1, true, false, 0, -1, false, /*rev_out=*/C.flipped);
   }
@@ -480,7 +479,6 @@ int pack_all(Model& m, Packer& P) {
   m.post_c = ch;
   m.conv_post = P.vec("dec.conv_post.weight", {1, ch, m.post_k});
   P.alloc(2048);                                  // slack: weight prefetch rings run up to 4 units (4 KB) past a stream's end
-  m.total_floats = P.cursor;
   return 0;
 }
 
@@ -533,73 +531,18 @@ int validate(const bv2_config& c, std::string& err) {
   return 0;
 }
 
-// enc_q (models.py:448-487) into its own blob: the WN stack exactly as the residual flow's (gate-ordered in_layers, res_skip split into its
-// x-update and output rows, cond_layer permuted the same way), pre with an odd cin on the cin_pad route, proj split into m / logs
+// enc_q (models.py:448-487) into its own blob: the WN stack exactly as the residual flow's (without fp16 streams), pre with an odd cin on
+// the cin_pad route, proj split into m / logs
 void pack_posterior(const bv2_config& c, PosteriorW& W, Packer& P) {
-  const int hid = c.hidden_channels, inter = c.inter_channels, gin = c.gin_channels, nl = kPosteriorLayers;
+  const int hid = c.hidden_channels, inter = c.inter_channels;
   W.pre = P.conv1d("enc_q.pre", hid, W.spec, 1);
-  const std::function<int(int)> gate_row = [hid](int n) { const int mt = n / 32, j = n % 32; return j < 16 ? 16 * mt + j : hid + 16 * mt + (j - 16); };
-  const std::function<int(int)> cond_row = [hid, &gate_row](int n) { return (n / (2 * hid)) * 2 * hid + gate_row(n % (2 * hid)); };
-  W.cond = P.gemv("enc_q.enc.cond_layer", 2 * hid * nl, gin, true, /*wn=*/true, &cond_row);
-  for (int i = 0; i < nl; ++i) {
-    const std::string rsn = "enc_q.enc.res_skip_layers." + std::to_string(i);
-    W.wn_in[i] = P.conv1d("enc_q.enc.in_layers." + std::to_string(i), 2 * hid, hid, kFlowKernel, true, true, 0, -1, false, false, &gate_row);
-    if (i < nl - 1) {
-      W.wn_res[i] = P.conv1d(rsn, 2 * hid, hid, 1, true, true, 0, hid);
-      W.wn_skip[i] = P.conv1d(rsn, 2 * hid, hid, 1, true, true, hid, hid);
-    } else {
-      W.wn_skip[i] = P.conv1d(rsn, hid, hid, 1, true, true);
-    }
-  }
+  W.wn = pack_wn(P, "enc_q.enc", hid, kPosteriorLayers, c.gin_channels, /*f16=*/false);
   W.proj_m = P.conv1d("enc_q.proj", 2 * inter, hid, 1, true, false, 0, inter);
   W.proj_logs = P.conv1d("enc_q.proj", 2 * inter, hid, 1, true, false, inter, inter);
   P.alloc(2048);                                  // slack, as the inference blob's
-  W.total_floats = P.cursor;
 }
 
-}  // namespace
-
-int build_posterior_layout(const bv2_config& cfg, int spec_channels, PosteriorW& w, std::string& err) {
-  // the widths pinned against the reference (hparams.ENVELOPE["spec_channels"]), for models with a speaker table too
-  if (spec_channels != 1025 && spec_channels != 513 && spec_channels != 80) {
-    err = "posterior encoder: spec_channels must be 1025, 513 or 80";
-    return -1;
-  }
-  w = PosteriorW();
-  w.spec = spec_channels;
-  Packer P;
-  pack_posterior(cfg, w, P);
-  w.cfg_hash = hash_cfg(cfg) * 16777619u ^ (uint32_t)spec_channels;
-  return 0;
-}
-
-int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w_in, const std::map<std::string, HostTensor>& t, float* blob, std::string& err) {
-  PosteriorW w = w_in;
-  Packer P;
-  P.T = &t;
-  P.blob = blob;
-  std::memset(blob, 0, sizeof(float) * kBlobHeaderFloats);
-  pack_posterior(cfg, w, P);
-  if (!P.missing.empty()) {
-    err = "posterior encoder: missing/invalid tensors (" + std::to_string(P.missing.size()) + "): ";
-    for (size_t i = 0; i < P.missing.size() && i < 12; ++i) err += P.missing[i] + "; ";
-    return -2;
-  }
-  if (w.total_floats != w_in.total_floats) { err = "internal: posterior layout drift between passes"; return -4; }
-  write_blob_header(blob, kPosteriorMagic, BV2_POSTERIOR_LAYOUT, w_in.cfg_hash, w.total_floats);
-  return 0;
-}
-
-// ---- the forward duration predictor's blob: every DDSConv and ConvFlow through pack_dds / conv1d, as the inference blob's
-namespace {
-ConvFlowW pack_convflow(Packer& P, const std::string& p, int hid) {
-  ConvFlowW f;
-  f.pre_w = P.vec(p + ".pre.weight", {hid, 1, 1});
-  f.pre_b = P.vec(p + ".pre.bias", {hid});
-  f.convs = pack_dds(P, p + ".convs", hid);
-  f.proj = P.conv1d(p + ".proj", 3 * kSdpBins - 1, hid, 1);
-  return f;
-}
+// the forward duration predictor's blob: every DDSConv and ConvFlow through pack_dds / pack_convflow, as the inference blob's
 void pack_sdp_forward(const bv2_config& c, SdpForwardW& W, Packer& P) {
   const int hid = c.hidden_channels;               // models.py:159: the predictor's filter_channels is its in_channels
   W.post_pre_w = P.vec("sdp.post_pre.weight", {hid, 1, 1});
@@ -611,74 +554,79 @@ void pack_sdp_forward(const bv2_config& c, SdpForwardW& W, Packer& P) {
   for (int i = 0; i < kSdpFlows; ++i) W.post_cf[i] = pack_convflow(P, "sdp.post_flows." + std::to_string(2 * i + 1), hid);
   W.cf_first = pack_convflow(P, "sdp.flows.1", hid);
   P.alloc(2048);                                  // slack, as the inference blob's
-  W.total_floats = P.cursor;
 }
+
+// The two passes every blob takes.  First: `pack` on a Packer without tensors walks the layout, which gives the blob's length.  Second: the
+// same walk with the tensors writes `blob`; what it could not find or fit is reported, and the header goes in last.
+template <class Pack>
+void lay_out(WeightBlob& b, uint32_t cfg_hash, const Pack& pack) {
+  Packer P;
+  pack(P);
+  b.total_floats = P.cursor;
+  b.cfg_hash = cfg_hash;
+}
+template <class Pack>
+int fill_blob(BlobKind kind, const WeightBlob& b, float* blob, std::string& err, const Pack& pack) {
+  const BlobDesc& d = kBlobDesc[kind];
+  Packer P;
+  P.T = &b.tensors;
+  P.blob = blob;
+  std::memset(blob, 0, sizeof(float) * kBlobHeaderFloats);
+  pack(P);
+  if (!P.missing.empty()) {
+    err = std::string(d.noun) + ": missing/invalid tensors (" + std::to_string(P.missing.size()) + "): ";
+    for (size_t i = 0; i < P.missing.size() && i < 12; ++i) err += P.missing[i] + "; ";
+    return -2;
+  }
+  if (P.cursor != b.total_floats) { err = std::string(d.noun) + ": internal: layout drift between passes"; return -4; }
+  write_blob_header(blob, d.magic, d.layout, b.cfg_hash, b.total_floats);
+  return 0;
+}
+
 }  // namespace
 
-bool sdp_forward_key(const std::string& key) {
-  return key.compare(0, 9, "sdp.post_") == 0 || key.compare(0, 12, "sdp.flows.1.") == 0;
+bool posterior_key(const std::string& key) { return key.compare(0, 6, "enc_q.") == 0; }
+bool sdp_forward_key(const std::string& key) { return key.compare(0, 9, "sdp.post_") == 0 || key.compare(0, 12, "sdp.flows.1.") == 0; }
+bool inference_key(const std::string& key) { return !posterior_key(key) && !sdp_forward_key(key); }
+
+int build_layout(Model& m, WeightBlob& b, std::string& err) {
+  if (int rc = validate(m.cfg, err)) return rc;
+  lay_out(b, hash_cfg(m.cfg), [&](Packer& P) { pack_all(m, P); });
+  return 0;
+}
+int pack_blob(const Model& m_in, const WeightBlob& b, float* blob, std::string& err) {
+  Model m = m_in;
+  return fill_blob(kInference, b, blob, err, [&](Packer& P) { pack_all(m, P); });
 }
 
-int build_sdp_forward_layout(const bv2_config& cfg, SdpForwardW& w, std::string& err) {
+int build_posterior_layout(const bv2_config& cfg, int spec_channels, PosteriorW& w, WeightBlob& b, std::string& err) {
+  // the widths pinned against the reference (hparams.ENVELOPE["spec_channels"]), for models with a speaker table too
+  if (spec_channels != 1025 && spec_channels != 513 && spec_channels != 80) {
+    err = "posterior encoder: spec_channels must be 1025, 513 or 80";
+    return -1;
+  }
+  w = PosteriorW();
+  w.spec = spec_channels;
+  lay_out(b, hash_cfg(cfg) * 16777619u ^ (uint32_t)spec_channels, [&](Packer& P) { pack_posterior(cfg, w, P); });
+  return 0;
+}
+int pack_posterior_blob(const bv2_config& cfg, const PosteriorW& w_in, const WeightBlob& b, float* blob, std::string& err) {
+  PosteriorW w = w_in;
+  return fill_blob(kPosterior, b, blob, err, [&](Packer& P) { pack_posterior(cfg, w, P); });
+}
+
+int build_sdp_forward_layout(const bv2_config& cfg, SdpForwardW& w, WeightBlob& b, std::string& err) {
   if (!dds_fused_supported(cfg.hidden_channels)) {
     err = "forward duration predictor: hidden_channels must be 128, 192 or 256 (the whole-layer DDSConv kernel)";
     return -1;
   }
   w = SdpForwardW();
-  Packer P;
-  pack_sdp_forward(cfg, w, P);
-  w.cfg_hash = hash_cfg(cfg) * 16777619u ^ kSdpForwardMagic;
+  lay_out(b, hash_cfg(cfg) * 16777619u ^ kSdpForwardMagic, [&](Packer& P) { pack_sdp_forward(cfg, w, P); });
   return 0;
 }
-
-int pack_sdp_forward_blob(const bv2_config& cfg, const SdpForwardW& w_in, const std::map<std::string, HostTensor>& t, float* blob, std::string& err) {
+int pack_sdp_forward_blob(const bv2_config& cfg, const SdpForwardW& w_in, const WeightBlob& b, float* blob, std::string& err) {
   SdpForwardW w = w_in;
-  Packer P;
-  P.T = &t;
-  P.blob = blob;
-  std::memset(blob, 0, sizeof(float) * kBlobHeaderFloats);
-  pack_sdp_forward(cfg, w, P);
-  if (!P.missing.empty()) {
-    err = "forward duration predictor: missing/invalid tensors (" + std::to_string(P.missing.size()) + "): ";
-    for (size_t i = 0; i < P.missing.size() && i < 12; ++i) err += P.missing[i] + "; ";
-    return -2;
-  }
-  if (w.total_floats != w_in.total_floats) { err = "internal: forward duration predictor layout drift between passes"; return -4; }
-  write_blob_header(blob, kSdpForwardMagic, BV2_SDP_FORWARD_LAYOUT, w_in.cfg_hash, w.total_floats);
-  return 0;
-}
-
-int build_layout(Model& m, std::string& err) {
-  if (int rc = validate(m.cfg, err)) return rc;
-  Packer P;
-  pack_all(m, P);
-  m.cfg_hash = hash_cfg(m.cfg);
-  return 0;
-}
-
-int pack_blob(const Model& m_in, const std::map<std::string, HostTensor>& t, float* blob, std::string& err) {
-  Model m = m_in;
-  Packer P;
-  P.T = &t;
-  P.blob = blob;
-  std::memset(blob, 0, sizeof(float) * kBlobHeaderFloats);
-  pack_all(m, P);
-  if (!P.missing.empty()) {
-    err = "missing/invalid tensors (" + std::to_string(P.missing.size()) + "): ";
-    for (size_t i = 0; i < P.missing.size() && i < 12; ++i) err += P.missing[i] + "; ";
-    return -2;
-  }
-  if (m.total_floats != m_in.total_floats) { err = "internal: layout drift between passes"; return -4; }
-  write_blob_header(blob, kBlobMagic, BV2_PACK_LAYOUT, m_in.cfg_hash, m.total_floats);
-  return 0;
-}
-
-bool key_in_schema(const Model& m, const std::string& key) {
-  (void)m;
-  static const char* ignored[] = {"enc_q.", "sdp.post_", "sdp.flows.1."};
-  for (const char* p : ignored)
-    if (key.compare(0, std::strlen(p), p) == 0) return false;
-  return true;
+  return fill_blob(kSdpForward, b, blob, err, [&](Packer& P) { pack_sdp_forward(cfg, w, P); });
 }
 
 }  // namespace bv2

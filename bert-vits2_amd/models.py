@@ -23,7 +23,7 @@ import ctypes as C
 import math
 import numbers
 import weakref
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -49,6 +49,39 @@ def draw_noise_z(B: int, C: int, Ty: int, device) -> torch.Tensor:
     with those strides reproduces the reference's values (plain ``torch.randn(B, C, T_y)`` does not); the
     C ABI takes the strides (``bv2_decode_in.nz_*stride``), so the tensor is handed over as it is."""
     return torch.randn_like(torch.empty(B, Ty, C, device=device, dtype=torch.float32).transpose(1, 2))
+
+
+class _BlobKind(NamedTuple):
+    """One of the model's packed weight blobs: its C entry points, the keys offered to it, where the attached device copy is remembered."""
+    c: str                    # the family of C calls: <c>load_tensor, <c>packed_bytes, <c>pack<suffix>, <c>attach<suffix>
+    attr: str                 # the attribute that keeps the attached device blob
+    prefixes: tuple           # the state-dict keys offered to it (the library itself answers 1 to a key that is not its own)
+    suffix: str = ""
+    takes_spec: bool = False  # the C calls take spec_channels
+    noun: str = "inference weights"
+    loader: str = "repack"    # the public method that loads it
+    hint: str = ""            # why a checkpoint may not have it
+
+
+_TRAINING_ONLY = ("is only in TRAINING checkpoints (G_*.pth as utils.save_checkpoint writes them); release checkpoints written by "
+                  "compress_model.py are stripped of ")
+_INFERENCE = _BlobKind(c="bv2_", suffix="_weights", attr="_blob", prefixes=("",))
+_POSTERIOR = _BlobKind(c="bv2_posterior_", attr="_post_blob", prefixes=("enc_q.",), takes_spec=True,
+                       noun="posterior encoder", loader="load_posterior",
+                       hint="no enc_q.* tensors: the posterior encoder " + _TRAINING_ONLY + "enc_q")
+_SDP_FORWARD = _BlobKind(c="bv2_sdp_forward_", attr="_sdpf_blob", prefixes=("sdp.post_", "sdp.flows.1."),
+                         noun="forward duration predictor", loader="load_sdp_forward",
+                         hint="no sdp.post_* tensors: the posterior side of the stochastic duration predictor " + _TRAINING_ONLY + "it")
+
+
+def _plain_state_dict(path_or_state_dict) -> Dict[str, torch.Tensor]:
+    """A path to a ``G_*.pth``, its dict, or a plain state dict -> a plain state dict without DDP's ``module.`` prefix."""
+    sd = path_or_state_dict
+    if isinstance(sd, (str, bytes)) or hasattr(sd, "__fspath__"):
+        sd = torch.load(sd, map_location="cpu")
+    if isinstance(sd, dict) and "model" in sd and isinstance(sd["model"], dict):
+        sd = sd["model"]
+    return {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
 
 
 NOISE_W, NOISE_Z, NOISE_Q = 0, 1, 2     # ``which`` of the seeded generator (csrc/kernels/rng.h): the SDP draw, the prior draw, the posterior draw
@@ -413,28 +446,55 @@ class SynthesizerTrn(nn.Module):
         except Exception:
             pass
 
+    # ---- the packed weight blobs (_BlobKind): host tensors -> packed host blob; device blob -> attached and remembered
+    def _pack_kind(self, kind: _BlobKind, tensors) -> torch.Tensor:
+        lib = self._ensure_handle()
+        spec = (int(self.hp.spec_channels),) if kind.takes_spec else ()
+        n = getattr(lib, kind.c + "packed_bytes")(self._handle, *spec)
+        if n < 0:
+            self._check(-1, kind.c + "packed_bytes")
+        for key, v in tensors:
+            if not key.startswith(kind.prefixes):
+                continue
+            t = v.detach().to("cpu", torch.float32).contiguous()
+            shape = (C.c_int64 * t.dim())(*t.shape)
+            rc = getattr(lib, kind.c + "load_tensor")(self._handle, key.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), L.F32)
+            if rc < 0:                         # rc == 1: a key this blob ignores (the inference blob: sdp.flows.1.*)
+                self._check(rc, kind.c + "load_tensor(" + key + ")")
+        blob = torch.empty(n, dtype=torch.uint8)
+        pack = kind.c + "pack" + kind.suffix
+        self._check(getattr(lib, pack)(self._handle, *spec, C.c_void_p(blob.data_ptr()), n), pack)
+        return blob
+
+    def _attach_kind(self, kind: _BlobKind, dev_blob: torch.Tensor) -> None:
+        spec = (int(self.hp.spec_channels),) if kind.takes_spec else ()
+        attach = kind.c + "attach" + kind.suffix
+        self._check(getattr(self._ensure_handle(), attach)(self._handle, *spec, C.c_void_p(dev_blob.data_ptr()), dev_blob.numel()), attach)
+        setattr(self, kind.attr, dev_blob)
+
+    def _load_kind(self, kind: _BlobKind, host_blob: torch.Tensor) -> None:
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"{kind.loader} needs the model on a GPU (model.to('cuda')); there is no CPU fallback")
+        with torch.cuda.device(dev):
+            self._attach_kind(kind, host_blob.to(dev))
+
+    def _need_kind(self, kind: _BlobKind, what: str) -> None:
+        blob = getattr(self, kind.attr, None)
+        if blob is None:
+            raise RuntimeError(f"{what}: the {kind.noun} is not loaded ({kind.loader}(checkpoint)); " + kind.hint)
+        if blob.device != self.device:
+            raise RuntimeError(f"{what}: the model moved to another device after {kind.loader}(); load it again")
+
     def pack_host_blob(self) -> torch.Tensor:
         """Fold weight-norm / repack every tensor into the library's blob (host, uint8).  CPU-only: usable without a GPU."""
-        lib = self._ensure_handle()
-        for key, p in self.named_parameters():
-            t = p.detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            rc = lib.bv2_load_tensor(self._handle, key.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), L.F32)
-            if rc < 0:                         # rc == 1: a key the inference path ignores (e.g. sdp.flows.1.*)
-                self._check(rc, "bv2_load_tensor(" + key + ")")
-        n = lib.bv2_packed_bytes(self._handle)
-        blob = torch.empty(n, dtype=torch.uint8)
-        self._check(lib.bv2_pack_weights(self._handle, C.c_void_p(blob.data_ptr()), n), "bv2_pack_weights")
-        return blob
+        return self._pack_kind(_INFERENCE, self.named_parameters())
 
     def attach_blob(self, dev_blob: torch.Tensor) -> None:
         """Use an already packed blob resident on this GPU (e.g. received through an RCCL broadcast)."""
-        lib = self._ensure_handle()
         assert dev_blob.is_cuda and dev_blob.dtype == torch.uint8 and dev_blob.is_contiguous()
         self._drop_graphs()
-        self._check(lib.bv2_attach_weights(self._handle, C.c_void_p(dev_blob.data_ptr()), dev_blob.numel()),
-                    "bv2_attach_weights")
-        self._blob = dev_blob
+        self._attach_kind(_INFERENCE, dev_blob)
 
     def repack(self) -> None:
         """(Re)build the packed device weights from the current parameters (call after editing parameters in place)."""
@@ -1217,8 +1277,7 @@ class SynthesizerTrn(nn.Module):
         return o
 
     # ------------------------------------------------------------------ posterior encoder (reference models.py:448-487)
-    POSTERIOR_HINT = ("no enc_q.* tensors: the posterior encoder is only in TRAINING checkpoints (G_*.pth as utils.save_checkpoint writes "
-                      "them); release checkpoints written by compress_model.py are stripped of enc_q")
+    POSTERIOR_HINT = _POSTERIOR.hint
 
     @property
     def has_posterior(self) -> bool:
@@ -1226,49 +1285,18 @@ class SynthesizerTrn(nn.Module):
 
     def pack_posterior_host_blob(self, state_dict) -> torch.Tensor:
         """The ``enc_q.*`` tensors of ``state_dict`` packed into the posterior encoder's own blob (host, uint8).  CPU-only."""
-        lib = self._ensure_handle()
-        keys = [k for k in state_dict if k.startswith("enc_q.")]
-        if not keys:
+        if not any(k.startswith("enc_q.") for k in state_dict):
             raise ValueError(self.POSTERIOR_HINT)
-        spec = int(self.hp.spec_channels)
-        n = lib.bv2_posterior_packed_bytes(self._handle, spec)
-        if n < 0:
-            self._check(-1, "bv2_posterior_packed_bytes")
-        for key in keys:
-            t = state_dict[key].detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            rc = lib.bv2_posterior_load_tensor(self._handle, key.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), L.F32)
-            if rc < 0:
-                self._check(rc, "bv2_posterior_load_tensor(" + key + ")")
-        blob = torch.empty(n, dtype=torch.uint8)
-        self._check(lib.bv2_posterior_pack(self._handle, spec, C.c_void_p(blob.data_ptr()), n), "bv2_posterior_pack")
-        return blob
+        return self._pack_kind(_POSTERIOR, state_dict.items())
 
     def load_posterior(self, path_or_state_dict) -> None:
         """Load the posterior encoder ``enc_q`` from a training checkpoint (a path to a ``G_*.pth``, its dict, or a plain state dict): the
         ``enc_q.*`` keys are packed into a blob of their own and attached; the inference blob is untouched.  Raises ``ValueError`` with a
         hint at ``compress_model.py`` when the checkpoint has none."""
-        sd = path_or_state_dict
-        if isinstance(sd, (str, bytes)) or hasattr(sd, "__fspath__"):
-            sd = torch.load(sd, map_location="cpu")
-        if isinstance(sd, dict) and "model" in sd and isinstance(sd["model"], dict):
-            sd = sd["model"]
-        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
-        blob = self.pack_posterior_host_blob(sd)
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("load_posterior needs the model on a GPU (model.to('cuda')); there is no CPU fallback")
-        with torch.cuda.device(dev):
-            dblob = blob.to(dev)
-            self._check(self._lib.bv2_posterior_attach(self._handle, int(self.hp.spec_channels), C.c_void_p(dblob.data_ptr()), dblob.numel()),
-                        "bv2_posterior_attach")
-        self._post_blob = dblob
+        self._load_kind(_POSTERIOR, self.pack_posterior_host_blob(_plain_state_dict(path_or_state_dict)))
 
     def _need_posterior(self, what: str) -> None:
-        if not self.has_posterior:
-            raise RuntimeError(f"{what}: the posterior encoder is not loaded (load_posterior(checkpoint)); " + self.POSTERIOR_HINT)
-        if self._post_blob.device != self.device:
-            raise RuntimeError(f"{what}: the model moved to another device after load_posterior(); load it again")
+        self._need_kind(_POSTERIOR, what)
 
     @torch.no_grad()
     def posterior_encode(self, y, y_lengths, sid=None, g=None, noise_q=None, noise_scale_q=1.0, seeds=None) -> Dict[str, torch.Tensor]:
@@ -1367,8 +1395,7 @@ class SynthesizerTrn(nn.Module):
         return _align.align_latent(enc, z_p.to(self.device), y_lengths, want_attn=want_attn, x_lengths=x_lengths)
 
     # ------------------------------------------------------------------ scoring a take (reference models.py:993-1002, losses.py:45-61)
-    SDP_FORWARD_HINT = ("no sdp.post_* tensors: the posterior side of the stochastic duration predictor is only in TRAINING checkpoints "
-                        "(G_*.pth as utils.save_checkpoint writes them); release checkpoints written by compress_model.py are stripped of it")
+    SDP_FORWARD_HINT = _SDP_FORWARD.hint
 
     @property
     def has_sdp_forward(self) -> bool:
@@ -1378,50 +1405,21 @@ class SynthesizerTrn(nn.Module):
         """``sdp.post_*`` and ``sdp.flows.1.*`` packed into the forward duration predictor's own blob (host, uint8).  ``sdp.flows.1.*`` is
         part of the inference schema (inference just never applies it): where ``state_dict`` does not carry it, the model's own
         parameters are packed.  CPU-only."""
-        lib = self._ensure_handle()
         if not any(k.startswith("sdp.post_") for k in state_dict):
             raise ValueError(self.SDP_FORWARD_HINT)
-        own = {k: v for k, v in self.state_dict().items() if k.startswith("sdp.flows.1.")}
-        tensors = dict(own)
-        tensors.update({k: v for k, v in state_dict.items() if k.startswith("sdp.post_") or k.startswith("sdp.flows.1.")})
-        n = lib.bv2_sdp_forward_packed_bytes(self._handle)
-        if n < 0:
-            self._check(-1, "bv2_sdp_forward_packed_bytes")
-        for key, v in tensors.items():
-            t = v.detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            rc = lib.bv2_sdp_forward_load_tensor(self._handle, key.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), L.F32)
-            if rc < 0:
-                self._check(rc, "bv2_sdp_forward_load_tensor(" + key + ")")
-        blob = torch.empty(n, dtype=torch.uint8)
-        self._check(lib.bv2_sdp_forward_pack(self._handle, C.c_void_p(blob.data_ptr()), n), "bv2_sdp_forward_pack")
-        return blob
+        tensors = {k: v for k, v in self.state_dict().items() if k.startswith("sdp.flows.1.")}
+        tensors.update(state_dict)
+        return self._pack_kind(_SDP_FORWARD, tensors.items())
 
     def load_sdp_forward(self, path_or_state_dict) -> None:
         """Load what the stochastic duration predictor needs to run FORWARD on observed durations (``duration_nll``, ``score``) from a
         training checkpoint (a path to a ``G_*.pth``, its dict, or a plain state dict): ``sdp.post_pre / post_convs / post_proj /
         post_flows.*`` and ``sdp.flows.1.*`` go into a blob of their own; the inference and posterior blobs are untouched.  Raises
         ``ValueError`` with a hint at ``compress_model.py`` when the checkpoint has no ``sdp.post_*``."""
-        sd = path_or_state_dict
-        if isinstance(sd, (str, bytes)) or hasattr(sd, "__fspath__"):
-            sd = torch.load(sd, map_location="cpu")
-        if isinstance(sd, dict) and "model" in sd and isinstance(sd["model"], dict):
-            sd = sd["model"]
-        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
-        blob = self.pack_sdp_forward_host_blob(sd)
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("load_sdp_forward needs the model on a GPU (model.to('cuda')); there is no CPU fallback")
-        with torch.cuda.device(dev):
-            dblob = blob.to(dev)
-            self._check(self._lib.bv2_sdp_forward_attach(self._handle, C.c_void_p(dblob.data_ptr()), dblob.numel()), "bv2_sdp_forward_attach")
-        self._sdpf_blob = dblob
+        self._load_kind(_SDP_FORWARD, self.pack_sdp_forward_host_blob(_plain_state_dict(path_or_state_dict)))
 
     def _need_sdp_forward(self, what: str) -> None:
-        if not self.has_sdp_forward:
-            raise RuntimeError(f"{what}: the forward duration predictor is not loaded (load_sdp_forward(checkpoint)); " + self.SDP_FORWARD_HINT)
-        if self._sdpf_blob.device != self.device:
-            raise RuntimeError(f"{what}: the model moved to another device after load_sdp_forward(); load it again")
+        self._need_kind(_SDP_FORWARD, what)
 
     @torch.no_grad()
     def duration_nll(self, enc: Dict[str, torch.Tensor], durations, noise_e=None, seeds=None) -> Dict[str, torch.Tensor]:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""sha256 of the packed weight blobs (``pack_host_blob`` and ``pack_posterior_host_blob``) of a fixed set of models with seeded synthetic
-weights.  Packing is CPU-only, so this runs without a GPU.  A change that is meant to leave the blob alone (a refactor of the packer, a new
-writer for an old format) must print the same listing before and after:
+"""sha256 of the packed weight blobs (``pack_host_blob``, ``pack_posterior_host_blob`` and ``pack_sdp_forward_host_blob``) of a fixed set of
+models with seeded synthetic weights.  Packing is CPU-only, so this runs without a GPU.  A change that is meant to leave the blob alone (a
+refactor of the packer, a new writer for an old format) must print the same listing before and after:
 
     python tools/blob_digest.py > after.txt        # and the same in a checkout of the parent commit; diff the two
 
@@ -47,6 +47,11 @@ def main():
         print(f"{name:14s} inference {blob.numel():>11d} bytes {sha(blob)}")
         post = m.pack_posterior_host_blob(synth.synthetic_posterior_state_dict(hp, SEED))
         print(f"{name:14s} posterior {post.numel():>11d} bytes {sha(post)}")
+        try:
+            sdpf = m.pack_sdp_forward_host_blob(synth.synthetic_sdp_forward_state_dict(hp, SEED))
+            print(f"{name:14s} sdp_forward {sdpf.numel():>9d} bytes {sha(sdpf)}")
+        except RuntimeError as e:                                  # hidden_channels the whole-layer DDSConv kernel does not support
+            print(f"{name:14s} sdp_forward refused: {str(e).split(': ', 1)[-1]}")
         if name == "v23_full":
             for _ in range(args.time):
                 t0 = time.perf_counter()

@@ -5,7 +5,8 @@
 //         tools/probe/posterior_pack_check.cpp bert-vits2_amd/csrc/bv2_model.cpp -Wl,--unresolved-symbols=ignore-all -o /tmp/posterior_pack_check
 //   /tmp/posterior_pack_check
 //
-// (bv2_model.cpp's inference packer refers to helpers of other translation units; this program never reaches them, hence the linker flag.)
+// (bv2_model.cpp's inference packer refers to helpers of other translation units; this program never reaches them, hence the linker flag —
+// with it a newly reached helper is a jump to address 0 at run time, not a link error.)
 // It packs seeded tensors for the three accepted spectrogram widths in both weight-norm forms, checks the header, that every weight landed
 // exactly once (sum of squares), that a missing and a misshapen tensor are reported, and that a bad width is refused.
 #include <cmath>
@@ -42,7 +43,8 @@ int main() {
   for (int spec : {1025, 513, 80}) {
     for (int folded = 0; folded < 2; ++folded) {
       std::mt19937 rng(7u + (unsigned)spec);
-      std::map<std::string, HostTensor> T;
+      WeightBlob b;                                               // the handle's record of this blob: tensors in, length and hash out
+      std::map<std::string, HostTensor>& T = b.tensors;
       double want = 0;                                            // sum of squares of every packed weight and bias
       auto plain = [&](const std::string& k, std::vector<int64_t> s, float sd) {
         T[k] = tensor(rng, s, sd);
@@ -73,28 +75,29 @@ int main() {
 
       PosteriorW W;
       std::string err;
-      expect(build_posterior_layout(c, spec, W, err) == 0 && W.total_floats > 0, "layout");
-      std::vector<float> blob((size_t)W.total_floats, -1.f);      // exactly the advertised size: a write past it is the sanitizer's to find
-      expect(pack_posterior_blob(c, W, T, blob.data(), err) == 0, err.c_str());
+      expect(build_posterior_layout(c, spec, W, b, err) == 0 && b.total_floats > 0, "layout");
+      std::vector<float> blob((size_t)b.total_floats, -1.f);      // exactly the advertised size: a write past it is the sanitizer's to find
+      expect(pack_posterior_blob(c, W, b, blob.data(), err) == 0, err.c_str());
       uint32_t hdr[4];
       std::memcpy(hdr, blob.data(), sizeof(hdr));
-      expect(hdr[0] == kPosteriorMagic && hdr[1] == BV2_ABI_VERSION && hdr[2] == W.cfg_hash && hdr[3] == BV2_POSTERIOR_LAYOUT, "header");
+      expect(hdr[0] == kPosteriorMagic && hdr[1] == BV2_ABI_VERSION && hdr[2] == b.cfg_hash && hdr[3] == BV2_POSTERIOR_LAYOUT, "header");
       double got = 0;
       for (size_t i = kBlobHeaderFloats; i < blob.size(); ++i) got += (double)blob[i] * blob[i];
       expect(std::fabs(got - want) <= 1e-6 * want, "every weight exactly once, padding zero");
-      std::printf("spec %4d %s: %lld floats, sum of squares %.6f / %.6f\n", spec, folded ? "folded  " : "weight_g/v", (long long)W.total_floats, got, want);
+      std::printf("spec %4d %s: %lld floats, sum of squares %.6f / %.6f\n", spec, folded ? "folded  " : "weight_g/v", (long long)b.total_floats, got, want);
 
-      auto T2 = T;
-      T2.erase("enc_q.proj.bias");
-      expect(pack_posterior_blob(c, W, T2, blob.data(), err) == -2 && err.find("enc_q.proj.bias") != std::string::npos, "missing tensor named");
-      T2 = T;
-      T2["enc_q.pre.bias"].shape = {H + 1};
-      expect(pack_posterior_blob(c, W, T2, blob.data(), err) == -2 && err.find("shape mismatch") != std::string::npos, "misshapen tensor named");
+      WeightBlob b2 = b;
+      b2.tensors.erase("enc_q.proj.bias");
+      expect(pack_posterior_blob(c, W, b2, blob.data(), err) == -2 && err.find("enc_q.proj.bias") != std::string::npos, "missing tensor named");
+      b2 = b;
+      b2.tensors["enc_q.pre.bias"].shape = {H + 1};
+      expect(pack_posterior_blob(c, W, b2, blob.data(), err) == -2 && err.find("shape mismatch") != std::string::npos, "misshapen tensor named");
     }
   }
   PosteriorW W;
+  WeightBlob b;
   std::string err;
-  expect(build_posterior_layout(c, 1024, W, err) != 0 && err.find("1025, 513 or 80") != std::string::npos, "bad width refused");
+  expect(build_posterior_layout(c, 1024, W, b, err) != 0 && b.total_floats == 0 && err.find("1025, 513 or 80") != std::string::npos, "bad width refused");
   std::printf(fails ? "%d check(s) failed\n" : "posterior_pack_check: all checks passed\n", fails);
   return fails ? 1 : 0;
 }
