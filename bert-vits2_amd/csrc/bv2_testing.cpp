@@ -106,6 +106,7 @@ int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const flo
                     int mask_post, const float* bias2, int nsrc, const float* x1, const float* x2, float in_scale, int ksplit,
                     int64_t slab_stride) {
   try {
+    if (relu != ACT_NONE && relu != ACT_RELU && relu != ACT_GELU) return -1;
     const ConvW c = conv_desc(cin, cout, k);
     std::vector<float> pk;
     const size_t boff = (size_t)conv_w_floats(c);
@@ -142,7 +143,7 @@ int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const flo
     p.cin = cin; p.cin_pad = c.cin_pad; p.cout = cout; p.cout_pad = c.cout_pad; p.w_ld = c.w_ld; p.k = k; p.dil = dil;
     p.pad_left = pad_left < 0 ? ((k - 1) / 2) * dil : pad_left;
     p.pre_act = lrelu_slope != 0.f ? PRE_LRELU : PRE_NONE; p.slope = lrelu_slope;
-    p.act = relu ? ACT_RELU : ACT_NONE; p.mask_pre = mask_pre; p.mask_post = mask_post;
+    p.act = relu; p.mask_pre = mask_pre; p.mask_post = mask_post;
     cl.nprob = 1; cl.B = B; cl.L = L; cl.ksplit = ksplit < 1 ? 1 : ksplit; cl.slab_stride = slab_stride;
     const char* vn = nullptr;
     return launch_conv1d(static_cast<hipStream_t>(stream), cl, tile, &vn);
@@ -536,6 +537,36 @@ int bv2_test_conv_f16_ex(void* stream, const void* x, int in_ct, const float* in
     hl.B = B; hl.L = L; hl.no_ksplit = no_ksplit;
     return launch_conv_f16(static_cast<hipStream_t>(stream), hl, nullptr);
   } catch (...) { return -100; }
+}
+
+// ---- the BERT / DeBERTa-v2 feature extractor's own kernels (tests/test_bert_kernels_gpu.py): the launchers of kernels/deberta_attn.hip
+// and kernels/bert.hip, status passed through unchanged
+int bv2_test_deberta_attn(void* stream, const float* qkv, int ld, const float* mask, const float* pk, const float* pq, const float* tab,
+                          float* out, int B, int H, int D, int T, int P, int span) {
+  DebertaAttnArgs a;
+  a.qkv = qkv; a.ld = ld; a.mask = mask; a.pk = pk; a.pq = pq; a.tab = tab; a.out = out;
+  a.B = B; a.H = H; a.D = D; a.T = T; a.P = P; a.span = span;
+  return launch_deberta_attn(static_cast<hipStream_t>(stream), a);
+}
+
+int bv2_test_bert_ln(void* stream, const float* a, int nslab, int64_t slab_stride, const float* gamma, const float* beta, float eps,
+                     const float* mask, float* out, int B, int C, int T, const void* pf_ptr, unsigned pf_bytes) {
+  BertLnArgs l;
+  l.a = a; l.nslab = nslab; l.slab_stride = slab_stride; l.gamma = gamma; l.beta = beta; l.eps = eps; l.mask = mask; l.out = out;
+  l.B = B; l.C = C; l.T = T;
+  l.pf = Prefetch{pf_ptr, pf_bytes};
+  return launch_bert_ln(static_cast<hipStream_t>(stream), l);
+}
+
+int bv2_test_bert_embed_ln(void* stream, const int64_t* input_ids, const int64_t* token_type_ids, const float* word, const float* pos,
+                           const float* type, const int64_t* lengths, const float* gamma, const float* beta, float eps, float* out,
+                           int B, int S, int C, int vocab, int max_pos, int type_vocab, const void* pf_ptr, unsigned pf_bytes) {
+  BertEmbedArgs e;
+  e.input_ids = input_ids; e.token_type_ids = token_type_ids; e.word = word; e.pos = pos; e.type = type; e.lengths = lengths;
+  e.gamma = gamma; e.beta = beta; e.eps = eps; e.out = out;
+  e.B = B; e.S = S; e.C = C; e.vocab = vocab; e.max_pos = max_pos; e.type_vocab = type_vocab;
+  e.pf = Prefetch{pf_ptr, pf_bytes};
+  return launch_bert_embed_ln(static_cast<hipStream_t>(stream), e);
 }
 
 void bv2_test_conv_timeline(void* dev_buf, long long capacity_u64) {

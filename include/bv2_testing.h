@@ -19,7 +19,8 @@ int64_t bv2_test_conv_pack_floats(int cin, int cout, int k);
  * shapes, 6 = split-K kernel; see bv2_kernels.h TILE_*).  With tile 6 and ksplit > 1 the output is `ksplit` partial
  * slabs, `slab_stride` floats apart, whose SUM is the result (bias / residual ride on slab 0).  w_host [cout][cin][k] / bias_host [cout] are HOST pointers (packed + uploaded
  * synchronously into wpack_dev); every other pointer is DEVICE.  x [B][cin][L], out/res [B][cout][L*out_tstride],
- * masks [B][L].  pad_left < 0 means "same" padding ((k-1)/2*dil). */
+ * masks [B][L].  pad_left < 0 means "same" padding ((k-1)/2*dil).  `relu` is the activation code: 0 = none, 1 = ReLU, 3 = exact erf
+ * GELU (ACT_GELU); any other value is refused with -1 before anything is packed or launched. */
 int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const float* bias_host, float* out, float* wpack_dev,
                     int B, int cin, int cout, int k, int dil, int pad_left, int L, int tile, float lrelu_slope, int relu,
                     const float* res, int res_mode, const float* in_mask, const float* out_mask, int mask_pre,
@@ -159,6 +160,24 @@ int bv2_test_conv_f16_ex(void* stream, const void* x, int in_ct, const float* in
                          const float* ln_gamma, const float* ln_beta, const float* ln_vec, const float* ln_mask, void* k16, void* v16,
                          int kv_row0, int kv_rows, int k16_ld, const float* bias2, int bias2_bstride, int no_ksplit,
                          const float* p1_w_host, const float* p1_bias_host, void* p1_out, const float* p1_res, int p1_res_mode);
+
+/* ---- the BERT / DeBERTa-v2 feature extractor's own kernels (tests/test_bert_kernels_gpu.py); all DEVICE pointers, the launcher's status
+ * returned unchanged (-1 = refused arguments, -2 = a shape the kernel cannot serve; both before any device call).
+ *
+ * DeBERTa-v2 disentangled attention (kernels/deberta_attn.hip, DebertaAttnArgs): qkv [B][3*H*D][ld] (q rows pre-divided by sqrt(3 D)),
+ * mask [B][T], pk / pq [H][D][2*span] (pq pre-divided by sqrt(3 D)), tab [2*P - 1] floats, out [B][H*D][T]. */
+int bv2_test_deberta_attn(void* stream, const float* qkv, int ld, const float* mask, const float* pk, const float* pq, const float* tab,
+                          float* out, int B, int H, int D, int T, int P, int span);
+/* out [B][C][T] = LayerNorm_C(sum of nslab slabs a, slab_stride floats apart; eps) * mask [B][T] (null: none) (kernels/bert.hip,
+ * BertLnArgs); pf_ptr / pf_bytes: the B == 1 weight prefetch (DEVICE memory that is only read) */
+int bv2_test_bert_ln(void* stream, const float* a, int nslab, int64_t slab_stride, const float* gamma, const float* beta, float eps,
+                     const float* mask, float* out, int B, int C, int T, const void* pf_ptr, unsigned pf_bytes);
+/* out [B][C][S] = LayerNorm_C(word[id] + type[tt] + pos[s]) (kernels/bert.hip, BertEmbedArgs): input_ids / token_type_ids (null: 0) int64
+ * [B][S], word [vocab][C], pos [max_pos][C] and type [type_vocab][C] (either may be null), lengths null or int64 [B] (columns s >=
+ * lengths[b] are zeroed) */
+int bv2_test_bert_embed_ln(void* stream, const int64_t* input_ids, const int64_t* token_type_ids, const float* word, const float* pos,
+                           const float* type, const int64_t* lengths, const float* gamma, const float* beta, float eps, float* out,
+                           int B, int S, int C, int vocab, int max_pos, int type_vocab, const void* pf_ptr, unsigned pf_bytes);
 
 /* one fused DDSConv layer (kernels/dds_fused.hip) on x [B][C][T] -> out [B][C][T] (out != x): depthwise k=3 conv (dww_host [C][3],
  * dwb_host [C], dilation dil) + LN1 (g1/b1) + GELU + 1x1 conv (w_host [C][C], bias_host [C]) + LN2 (g2/b2) + GELU + residual,

@@ -189,15 +189,19 @@ def test_attention_relpos_every_head_dim(H, D, B, T, lens, f16):
     _attention_case(B, T, lens, f16, H, D)
 
 
-def _attention_case(B, T, lens, f16, H, D):
+def _attention_case(B, T, lens, f16, H, D, W=4, inputs=None):
+    """inputs: (qkv with unscaled q rows, erk, erv [2W + 1][D], mask, fp64 reference) of a case that brings its own (the W = 0 cases of
+    tests/test_bert_kernels_gpu.py); None = the random ones below."""
     lib = _lib()
-    W = 4
-    g = torch.Generator().manual_seed(T + 7 * H + D)
-    qkv = torch.randn(B, 3 * H * D, T, generator=g)
-    qkv[:, : H * D] *= 3.0                      # sharpen the softmax a little
-    erk, erv = torch.randn(2 * W + 1, D, generator=g) * D ** -0.5, torch.randn(2 * W + 1, D, generator=g) * D ** -0.5
-    mask = (torch.arange(T)[None, :] < torch.tensor(lens)[:, None]).float()
-    ref = _ref_attention(qkv, mask, erk, erv, H, W)
+    if inputs is None:
+        g = torch.Generator().manual_seed(T + 7 * H + D)
+        qkv = torch.randn(B, 3 * H * D, T, generator=g)
+        qkv[:, : H * D] *= 3.0                      # sharpen the softmax a little
+        erk, erv = torch.randn(2 * W + 1, D, generator=g) * D ** -0.5, torch.randn(2 * W + 1, D, generator=g) * D ** -0.5
+        mask = (torch.arange(T)[None, :] < torch.tensor(lens)[:, None]).float()
+        ref = _ref_attention(qkv, mask, erk, erv, H, W)
+    else:
+        qkv, erk, erv, mask, ref = inputs
     out = torch.full((B, H * D, T), float("nan"), device="cuda")
     # kernel input layout: rows [q/sqrt(D) | k | v | per head the 2W+1 relative-key logits], row stride ld (32-aligned),
     # padding columns filled with NaN to prove they are never consumed
