@@ -6,10 +6,12 @@ Hann window, ``torch.stft(center=False)``, ``sqrt(re^2 + im^2 + 1e-6)``; mel_pro
 below is that step: samples at the model's sampling rate go in (fp32 in [-1, 1], or 16-bit PCM read as ``x / 32768``), ``[B, C, L]`` comes
 out.  A recording at another rate goes through ``resample`` first (the reference resamples offline with librosa, resample.py): a polyphase
 Kaiser-windowed sinc on the device (``bv2_resample``, kernels/resample.hip), the same call that brings synthesised audio to the rate a
-consumer wants.  Not done here: decoding of audio files.
+consumer wants.  ``loudness`` / ``normalize_loudness`` measure integrated loudness (ITU-R BS.1770-4, mono) and bring audio to a target level
+on the device (``bv2_loudness_*``, kernels/loudness.hip).  Not done here: decoding of audio files.
 
 Nothing in here computes: the filterbank comes from ``bv2_mel_basis`` and the resampler's table from ``bv2_resample_taps`` (fp64 on the
-host, rounded to fp32), everything else runs in the two launches of ``bv2_spectrogram`` / the one of ``bv2_resample`` on the current stream.
+host, rounded to fp32), everything else runs in the two launches of ``bv2_spectrogram`` / the one of ``bv2_resample`` / the four of
+``bv2_loudness_measure`` and the one of ``bv2_loudness_apply`` on the current stream.
 """
 from __future__ import annotations
 
@@ -313,6 +315,232 @@ def resample(wav: torch.Tensor, wav_lengths=None, rate_in: Optional[int] = None,
     with torch.cuda.device(dev):
         out = resample_range(wav, 0, wl, rate_in, rate_out, 0, N, None, lengths)
     return out, lengths
+
+
+# ---- loudness (include/bv2.h bv2_loudness_*) ----------------------------------------------------------------------------------------------
+LOUDNESS_RATES = (8000, 192000)
+
+
+def loudness_config(rate: int, input_format: int = L.WAV_F32) -> L.LoudnessConfig:
+    c = L.LoudnessConfig()
+    c.struct_bytes = C.sizeof(L.LoudnessConfig)
+    c.sample_rate, c.input_format = int(rate), int(input_format)
+    return c
+
+
+def loudness_plan(rate: int) -> Tuple[int, int, int]:
+    """``(step, block, tile)`` at a sampling rate (``bv2_loudness_plan``): ``round(rate / 10)`` samples, four steps, and the samples one
+    workgroup owns.  ``ValueError`` outside 8 000 .. 192 000 Hz, with the library's message."""
+    lib = L.load()
+    v = [C.c_int32() for _ in range(3)]
+    if lib.bv2_loudness_plan(C.byref(loudness_config(rate)), *[C.byref(x) for x in v]) != 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return tuple(int(x.value) for x in v)
+
+
+def loudness_coeffs(rate: int) -> np.ndarray:
+    """The K-weighting's two biquads at ``rate``: ``b0 b1 b2 a1 a2`` of the high shelf, then of the high pass (fp64, ``a0 = 1``)."""
+    lib = L.load()
+    out = np.empty(10, np.float64)
+    if lib.bv2_loudness_coeffs(C.byref(loudness_config(rate)), C.c_void_p(out.ctypes.data)) != 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return out
+
+
+def loudness_blocks(rate: int, n: int) -> int:
+    """Blocks of an item of ``n`` samples (``bv2_loudness_blocks``): 0 for none, 1 below a block, else ``(n - block) // step + 1``."""
+    lib = L.load()
+    r = lib.bv2_loudness_blocks(C.byref(loudness_config(rate)), int(n))
+    if r < 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return int(r)
+
+
+def _host_groups(groups, B: int) -> Tuple[Optional[list], int]:
+    """Group ids given on the host, checked there: ``[B]`` integers in ``[0, G)`` with ``G = max + 1``."""
+    if groups is None:
+        return None, B
+    ids = [int(v) for v in torch.as_tensor(groups).reshape(-1).tolist()]
+    if len(ids) != B:
+        raise ValueError("groups must be [B]")
+    G = max(ids) + 1
+    if min(ids) < 0 or G > B:
+        raise ValueError(f"group ids must lie in [0, n_groups) with n_groups <= B = {B}, got {min(ids)} .. {max(ids)}")
+    return ids, G
+
+
+def _loudness_input(wav, wav_lengths, rate, device):
+    """The input conventions and host-side checks of ``resample``, before anything touches the device."""
+    if rate is None:
+        raise ValueError("loudness needs the sampling rate")
+    rate = int(rate)
+    if not isinstance(wav, torch.Tensor):
+        wav = torch.as_tensor(wav)
+    if wav.dim() == 1:
+        wav = wav[None]
+    if wav.dim() != 2 or wav.shape[1] < 1 or wav.shape[0] < 1:
+        raise ValueError(f"wav must be [B, S] or [S], got {tuple(wav.shape)}")
+    if wav.dtype not in (torch.int16, torch.float32):
+        raise ValueError(f"wav must be float32 in [-1, 1] or int16 PCM, got {wav.dtype}")
+    B, S = wav.shape
+    loudness_plan(rate)                                            # ValueError naming the envelope
+    if B > 4096:
+        raise ValueError(f"loudness takes at most 4096 items per call, got {B}")
+    if wav_lengths is not None and (not isinstance(wav_lengths, torch.Tensor) or not wav_lengths.is_cuda):
+        host = [int(v) for v in torch.as_tensor(wav_lengths).reshape(-1).tolist()]
+        if len(host) != B:
+            raise ValueError("wav_lengths must be [B]")
+        for b, n in enumerate(host):
+            if not 1 <= n <= S:
+                raise ValueError(f"wav_lengths[{b}] = {n} is outside [1, {S}], the samples of the batch")
+    elif wav_lengths is not None and tuple(wav_lengths.reshape(-1).shape) != (B,):
+        raise ValueError("wav_lengths must be [B]")
+
+    def move():
+        dev = torch.device(device if device is not None else
+                           (wav.device if wav.is_cuda else torch.device("cuda", torch.cuda.current_device())))
+        w = wav.detach().to(dev)
+        if w.stride(1) != 1:
+            w = w.contiguous()
+        wl = None if wav_lengths is None else torch.as_tensor(wav_lengths).to(dev, torch.int64).reshape(-1).contiguous()
+        return dev, w, wl
+    return rate, B, S, L.WAV_I16 if wav.dtype == torch.int16 else L.WAV_F32, move
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def loudness_measure(wav: torch.Tensor, wl: Optional[torch.Tensor], rate: int, groups: Optional[torch.Tensor] = None,
+                     n_groups: Optional[int] = None, target_lufs: float = -23.0, peak_ceiling_db: float = -1.0, want_blocks: bool = False,
+                     gate: bool = True) -> Dict[str, torch.Tensor]:
+    """``bv2_loudness_measure`` on the current stream: ``wav`` [B, S] (device, fp32 or int16, unit sample stride), ``wl`` [B] device int64
+    or ``None``, ``groups`` [B] device int32 in ``[0, n_groups)`` or ``None``.  Returns device tensors ``lufs`` fp64 [G], ``gain`` fp32
+    [G], ``flags`` int32 [G], ``peak`` fp32 [B] and, if asked, ``block_ms`` fp64 [B, blocks(S)].  ``gate=False``: ``peak`` and
+    ``block_ms`` only, for ``loudness_gate`` over several calls."""
+    if not wav.is_cuda or wav.dim() != 2 or wav.stride(1) != 1 or wav.dtype not in (torch.float32, torch.int16):
+        raise ValueError("wav must be a device tensor [B, S], float32 or int16, with unit sample stride")
+    B, S = wav.shape
+    dev = wav.device
+    G = B if groups is None else int(n_groups)
+    cfg = loudness_config(rate, L.WAV_I16 if wav.dtype == torch.int16 else L.WAV_F32)
+    lib = L.load()
+    n = lib.bv2_loudness_workspace_bytes(C.byref(cfg), B, S)
+    if n < 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    out = {"peak": torch.empty(B, dtype=torch.float32, device=dev)}
+    if gate:
+        out.update(lufs=torch.empty(G, dtype=torch.float64, device=dev), gain=torch.empty(G, dtype=torch.float32, device=dev),
+                   flags=torch.empty(G, dtype=torch.int32, device=dev))
+    if want_blocks or not gate:
+        out["block_ms"] = torch.empty(B, loudness_blocks(rate, S), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.bv2_loudness_measure(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), _ptr(wav),
+                                      wav.stride(0) if B > 1 else S, _ptr(wl), B, S, _ptr(groups) if gate else None, G if gate else B,
+                                      float(target_lufs), float(peak_ceiling_db), _ptr(out.get("lufs")), _ptr(out.get("gain")),
+                                      _ptr(out["peak"]), _ptr(out.get("flags")), _ptr(out.get("block_ms")), _ptr(ws), ws.numel())
+    if rc != 0:
+        raise RuntimeError(f"bv2_loudness_measure failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return out
+
+
+def loudness_gate(block_ms: torch.Tensor, wl: torch.Tensor, S: int, peak: torch.Tensor, rate: int, groups: Optional[torch.Tensor],
+                  n_groups: int, target_lufs: float = -23.0, peak_ceiling_db: float = -1.0) -> Dict[str, torch.Tensor]:
+    """``bv2_loudness_gate`` on the current stream: gates and gains from block mean squares [B, >= blocks(S)] and peaks [B] that
+    ``loudness_measure(gate=False)`` produced, possibly in several calls (rows padded to one width); ``wl`` [B] device int64."""
+    B = block_ms.shape[0]
+    dev = block_ms.device
+    block_ms = block_ms.contiguous()
+    cfg = loudness_config(rate)
+    lib = L.load()
+    ws = torch.empty(32 * B + 8, dtype=torch.uint8, device=dev)
+    out = dict(lufs=torch.empty(n_groups, dtype=torch.float64, device=dev), gain=torch.empty(n_groups, dtype=torch.float32, device=dev),
+               flags=torch.empty(n_groups, dtype=torch.int32, device=dev), peak=peak)
+    with torch.cuda.device(dev):
+        rc = lib.bv2_loudness_gate(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), _ptr(block_ms), block_ms.shape[1],
+                                   _ptr(wl), B, int(S), _ptr(peak), _ptr(groups), int(n_groups), float(target_lufs),
+                                   float(peak_ceiling_db), _ptr(out["lufs"]), _ptr(out["gain"]), _ptr(out["flags"]), _ptr(ws), ws.numel())
+    if rc != 0:
+        raise RuntimeError(f"bv2_loudness_gate failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return out
+
+
+def loudness_apply(wav: torch.Tensor, wl: Optional[torch.Tensor], rate: int, gain: torch.Tensor, groups: Optional[torch.Tensor] = None,
+                   as_pcm16: bool = False) -> torch.Tensor:
+    """``bv2_loudness_apply`` on the current stream: ``wav * gain[group]`` as fp32, or as 16-bit PCM with the fixed-gain rounding rule;
+    zeros behind each item's length."""
+    B, S = wav.shape
+    cfg = loudness_config(rate, L.WAV_I16 if wav.dtype == torch.int16 else L.WAV_F32)
+    out = torch.empty(B, S, dtype=torch.int16 if as_pcm16 else torch.float32, device=wav.device)
+    lib = L.load()
+    with torch.cuda.device(wav.device):
+        rc = lib.bv2_loudness_apply(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), _ptr(wav),
+                                    wav.stride(0) if B > 1 else S, _ptr(wl), B, S, _ptr(groups), gain.numel(), _ptr(gain),
+                                    None if as_pcm16 else _ptr(out), _ptr(out) if as_pcm16 else None, S)
+    if rc != 0:
+        raise RuntimeError(f"bv2_loudness_apply failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return out
+
+
+def _device_groups(groups, ids, dev) -> Optional[torch.Tensor]:
+    if groups is None:
+        return None
+    if ids is not None:
+        return torch.tensor(ids, dtype=torch.int32, device=dev)
+    return groups.to(dev, torch.int32).reshape(-1).contiguous()
+
+
+def _groups_arg(groups, B):
+    """Host ids are checked here; ids on the device are the caller's word (``n_groups = B`` is then the safe size of the outputs)."""
+    if isinstance(groups, torch.Tensor) and groups.is_cuda:
+        if tuple(groups.reshape(-1).shape) != (B,):
+            raise ValueError("groups must be [B]")
+        return None, B
+    return _host_groups(groups, B)
+
+
+@torch.no_grad()
+def loudness(wav, wav_lengths=None, rate: Optional[int] = None, groups=None, want_blocks: bool = False, device=None
+             ) -> Dict[str, torch.Tensor]:
+    """Integrated loudness (ITU-R BS.1770-4, mono) of ``wav`` [B, S] or [S] at ``rate`` — fp32, or int16 PCM read as ``x / 32768``; host
+    or device, any batch stride; ``wav_lengths`` as in ``resample`` (the padding is never read).  Returns device tensors: ``lufs`` fp64
+    [G] (``-inf`` for a group with no block above -70 LUFS), ``peak`` fp32 [B] (sample peak), ``silent`` bool [G] and, with
+    ``want_blocks``, ``block_ms`` fp64 [B, blocks(S)] (the block mean squares, ``-0.691 + 10 log10`` of which is the momentary curve).
+    ``groups`` [B]: items with one id are the pieces of one programme and are measured together; ``None``: every item on its own, G = B.
+    An item shorter than 400 ms is one block of its own length."""
+    rate, B, S, _, move = _loudness_input(wav, wav_lengths, rate, device)
+    ids, G = _groups_arg(groups, B)
+    dev, w, wl = move()
+    m = loudness_measure(w, wl, rate, _device_groups(groups, ids, dev), G, want_blocks=want_blocks)
+    out = {"lufs": m["lufs"], "peak": m["peak"], "silent": (m["flags"] & L.LOUDNESS_SILENT) != 0}
+    if want_blocks:
+        out["block_ms"] = m["block_ms"]
+    return out
+
+
+@torch.no_grad()
+def normalize_loudness(wav, wav_lengths=None, rate: Optional[int] = None, target_lufs: float = -23.0, peak_ceiling_db: float = -1.0,
+                       groups=None, as_pcm16: bool = False, device=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """``wav`` brought to ``target_lufs``: ``(out [B, S], info)`` on the device.  Every group gets ONE static gain ``10^((target - L) /
+    20)``, lowered to ``ceiling / peak`` where the group's sample peak would pass ``peak_ceiling_db`` (``info["limited"]``); a silent
+    group keeps gain 1.  ``out = wav * gain`` is one fp32 multiply (zeros behind each item's length); ``as_pcm16``: int16
+    ``trunc(clamp(v * 32767))`` of that product, the fixed-gain rule of streamed PCM.  ``info``: ``lufs`` fp64 [G], ``gain_db`` fp64 [G],
+    ``gain`` fp32 [G] (the factor that was applied), ``peak`` fp32 [B], ``limited`` and ``silent`` bool [G]."""
+    rate, B, S, _, move = _loudness_input(wav, wav_lengths, rate, device)
+    ids, G = _groups_arg(groups, B)
+    if not (np.isfinite(target_lufs) and np.isfinite(peak_ceiling_db)):
+        raise ValueError("target_lufs and peak_ceiling_db must be finite")
+    dev, w, wl = move()
+    g = _device_groups(groups, ids, dev)
+    m = loudness_measure(w, wl, rate, g, G, target_lufs, peak_ceiling_db)
+    out = loudness_apply(w, wl, rate, m["gain"], g, as_pcm16)
+    return out, loudness_info(m)
+
+
+def loudness_info(m: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    return {"lufs": m["lufs"], "gain_db": 20.0 * torch.log10(m["gain"].to(torch.float64)), "gain": m["gain"], "peak": m["peak"],
+            "limited": (m["flags"] & L.LOUDNESS_LIMITED) != 0, "silent": (m["flags"] & L.LOUDNESS_SILENT) != 0}
 
 
 def to_rate(wav, wav_lengths, sampling_rate: Optional[int], model_rate: int, params: StftParams, device):

@@ -869,6 +869,240 @@ int bv2_resample(bv2_stream stream, const bv2_resample_config* cfg, const float*
   } catch (...) { return fail("exception", -100); }
 }
 
+// ---- BS.1770 loudness (kernels/loudness.hip) -------------------------------------------------------------------------
+static const int LD_MIN_RATE = 8000, LD_MAX_RATE = 192000, LD_MAX_B = 4096;
+static const int64_t LD_MAX_S = ((int64_t)1 << 31) - 4096;
+
+static int loudness_check(const bv2_loudness_config* c, const char* what) {
+  auto fail = [&](const std::string& m) { g_create_err = std::string(what) + ": " + m; return -1; };
+  if (!c) return fail("cfg is null");
+  if (c->struct_bytes != (int32_t)sizeof(bv2_loudness_config)) return fail("bv2_loudness_config.struct_bytes mismatch (ABI drift)");
+  if (c->sample_rate < LD_MIN_RATE || c->sample_rate > LD_MAX_RATE)
+    return fail("sample_rate must be in [" + std::to_string(LD_MIN_RATE) + ", " + std::to_string(LD_MAX_RATE) + "], got " +
+                std::to_string(c->sample_rate));
+  if (c->input_format != BV2_WAV_F32 && c->input_format != BV2_WAV_I16) return fail("input_format must be BV2_WAV_F32 or BV2_WAV_I16");
+  return 0;
+}
+
+static int loudness_step(const bv2_loudness_config* c) { return (c->sample_rate + 5) / 10; }   // round(fs / 10)
+
+static void loudness_coeffs(int rate, double out[10]) {
+  const double pi = 3.14159265358979323846;
+  {
+    const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+    const double K = std::tan(pi * f0 / rate), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+    const double a0 = 1.0 + K / Q + K * K;
+    out[0] = (Vh + Vb * K / Q + K * K) / a0;
+    out[1] = 2.0 * (K * K - Vh) / a0;
+    out[2] = (Vh - Vb * K / Q + K * K) / a0;
+    out[3] = 2.0 * (K * K - 1.0) / a0;
+    out[4] = (1.0 - K / Q + K * K) / a0;
+  }
+  {
+    const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+    const double K = std::tan(pi * f0 / rate), a0 = 1.0 + K / Q + K * K;
+    out[5] = 1.0; out[6] = -2.0; out[7] = 1.0;
+    out[8] = 2.0 * (K * K - 1.0) / a0;
+    out[9] = (1.0 - K / Q + K * K) / a0;
+  }
+}
+
+// The cascade in transposed direct form II has the state (s1, s2, t1, t2) and, for a zero input, s' = A s.  P, Q, R = A^16, A^256, A^4096
+// by repeated squaring in fp64 (the spectral radius is below 1: the powers only shrink).
+static void loudness_filter(int rate, LoudnessFilter* f) {
+  loudness_coeffs(rate, f->c);
+  const double *c = f->c;
+  double M[16] = {-c[3], 1, 0, 0,
+                  -c[4], 0, 0, 0,
+                  c[6] - c[8] * c[5], 0, -c[8], 1,
+                  c[7] - c[9] * c[5], 0, -c[9], 0};
+  for (int sq = 1; sq <= 12; ++sq) {                                          // M = A^(2^sq)
+    double N[16];
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 4; ++j) {
+        double s = 0;
+        for (int k = 0; k < 4; ++k) s += M[i * 4 + k] * M[k * 4 + j];
+        N[i * 4 + j] = s;
+      }
+    std::memcpy(M, N, sizeof(M));
+    if (sq == 4) std::memcpy(f->P, M, sizeof(M));
+    if (sq == 8) std::memcpy(f->Q, M, sizeof(M));
+    if (sq == 12) std::memcpy(f->R, M, sizeof(M));
+  }
+  static_assert(LD_SEG == 16 && LD_TILE == 4096, "the powers above are A^LD_SEG, A^(LD_SEG^2) and A^LD_TILE");
+}
+
+static int64_t loudness_blocks(int64_t n, int step) {
+  const int64_t block = 4 * (int64_t)step;
+  return n <= 0 ? 0 : (n < block ? 1 : (n - block) / step + 1);
+}
+
+struct LoudnessWs { int64_t tile_z, tile_s, part, item, block_ms, tile_peak, total; };
+static LoudnessWs loudness_ws(int step, int64_t B, int64_t S) {
+  const int64_t nt = (S + LD_TILE - 1) / LD_TILE;
+  LoudnessWs w;
+  int64_t o = 0;
+  w.tile_z = o; o += B * nt * 4 * 8;
+  w.tile_s = o; o += B * nt * 4 * 8;
+  w.part = o; o += B * nt * LD_MAX_PARTS * 8;
+  w.item = o; o += B * 4 * 8;
+  w.block_ms = o; o += B * loudness_blocks(S, step) * 8;
+  w.tile_peak = o; o += B * nt * 4;
+  w.total = o;
+  return w;
+}
+
+int bv2_loudness_plan(const bv2_loudness_config* cfg, int32_t* step, int32_t* block, int32_t* tile) {
+  if (int rc = loudness_check(cfg, "bv2_loudness_plan")) return rc;
+  if (step) *step = loudness_step(cfg);
+  if (block) *block = 4 * loudness_step(cfg);
+  if (tile) *tile = LD_TILE;
+  return 0;
+}
+
+int bv2_loudness_coeffs(const bv2_loudness_config* cfg, double out[10]) {
+  if (int rc = loudness_check(cfg, "bv2_loudness_coeffs")) return rc;
+  if (!out) { g_create_err = "bv2_loudness_coeffs: out is null"; return -1; }
+  loudness_coeffs(cfg->sample_rate, out);
+  return 0;
+}
+
+int64_t bv2_loudness_blocks(const bv2_loudness_config* cfg, int64_t n) {
+  if (loudness_check(cfg, "bv2_loudness_blocks")) return -1;
+  if (n < 0 || n > LD_MAX_S) { g_create_err = "bv2_loudness_blocks: n must be in [0, 2^31 - 4096]"; return -1; }
+  return loudness_blocks(n, loudness_step(cfg));
+}
+
+int64_t bv2_loudness_workspace_bytes(const bv2_loudness_config* cfg, int32_t B, int64_t S) {
+  if (loudness_check(cfg, "bv2_loudness_workspace_bytes")) return -1;
+  if (B < 1 || B > LD_MAX_B || S < 1 || S > LD_MAX_S) {
+    g_create_err = "bv2_loudness_workspace_bytes: B must be in [1, " + std::to_string(LD_MAX_B) + "] and S in [1, 2^31 - 4096]";
+    return -1;
+  }
+  return loudness_ws(loudness_step(cfg), B, S).total + 256;
+}
+
+// the checks bv2_loudness_measure and bv2_loudness_gate share; returns the 8-byte aligned workspace through *ws
+static int loudness_common(const char* what, const bv2_loudness_config* cfg, int32_t B, int64_t S, const int32_t* groups, int32_t n_groups,
+                           void* workspace, int64_t workspace_bytes, int64_t need, unsigned char** ws) {
+  if (int rc = loudness_check(cfg, what)) return rc;
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (B < 1 || B > LD_MAX_B) return fail("B must be in [1, " + std::to_string(LD_MAX_B) + "]", -1);
+  if (S < 1 || S > LD_MAX_S) return fail("S must be in [1, 2^31 - 4096]", -1);
+  if (groups ? (n_groups < 1 || n_groups > B) : n_groups != B)
+    return fail("n_groups must be in [1, B] with groups, and equal to B without", -1);
+  if (!workspace || workspace_bytes < need) return fail("workspace too small (bv2_loudness_workspace_bytes)", -5);
+  *ws = static_cast<unsigned char*>(workspace);
+  const uintptr_t mis = reinterpret_cast<uintptr_t>(*ws) & 7u;
+  if (mis) {
+    if (workspace_bytes < need + 8) return fail("workspace too small (bv2_loudness_workspace_bytes)", -5);
+    *ws += 8 - mis;
+  }
+  return 0;
+}
+
+static void loudness_gate_args(const bv2_loudness_config* cfg, LoudnessGateArgs* g, unsigned char* item_ws, const int64_t* lengths,
+                               int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, double target_lufs, double peak_ceiling_db) {
+  g->lengths = lengths; g->S = S; g->B = B; g->groups = groups; g->n_groups = n_groups;
+  g->step = loudness_step(cfg);
+  g->ms_width = loudness_blocks(S, g->step);
+  g->abs_ms = std::pow(10.0, (-70.0 + 0.691) / 10.0);
+  g->target_lufs = target_lufs;
+  g->ceiling = std::pow(10.0, peak_ceiling_db / 20.0);
+  g->item_s = reinterpret_cast<double*>(item_ws);
+  g->item_c = reinterpret_cast<int64_t*>(item_ws + (size_t)B * 8);
+  g->sort_s = reinterpret_cast<double*>(item_ws + (size_t)B * 16);
+  g->sort_c = reinterpret_cast<int64_t*>(item_ws + (size_t)B * 24);
+}
+
+int bv2_loudness_measure(bv2_stream stream, const bv2_loudness_config* cfg, const void* wav, int64_t wav_bstride, const int64_t* lengths,
+                         int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, double target_lufs, double peak_ceiling_db,
+                         double* lufs, float* gain, float* peak, int32_t* flags, double* block_ms, void* workspace,
+                         int64_t workspace_bytes) {
+  const char* what = "bv2_loudness_measure";
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (int rc = loudness_check(cfg, what)) return rc;
+  if (!wav) return fail("wav is null", -1);
+  if (!peak) return fail("peak is null", -1);
+  if (wav_bstride < 0) return fail("wav_bstride must not be negative", -1);
+  const bool gate = lufs || gain || flags;
+  if (gate && (!lufs || !gain || !flags)) return fail("lufs, gain and flags go together: all three, or none (block_ms and peak only)", -1);
+  if (!gate && !block_ms) return fail("block_ms is null in a call without lufs, gain and flags: nothing to produce", -1);
+  if (!(target_lufs == target_lufs) || !(peak_ceiling_db == peak_ceiling_db) || std::isinf(target_lufs) || std::isinf(peak_ceiling_db))
+    return fail("target_lufs and peak_ceiling_db must be finite", -1);
+  if (!gate) { groups = nullptr; n_groups = B; }
+  unsigned char* ws = nullptr;
+  const LoudnessWs lay = (B >= 1 && B <= LD_MAX_B && S >= 1 && S <= LD_MAX_S) ? loudness_ws(loudness_step(cfg), B, S) : LoudnessWs{};
+  if (int rc = loudness_common(what, cfg, B, S, groups, n_groups, workspace, workspace_bytes, lay.total ? lay.total : 1, &ws)) return rc;
+  try {
+    LoudnessArgs a;
+    a.wav = wav; a.bstride = wav_bstride; a.lengths = lengths; a.B = B; a.S = S; a.step = loudness_step(cfg);
+    a.input_format = cfg->input_format;
+    loudness_filter(cfg->sample_rate, &a.filter);
+    a.tile_z = reinterpret_cast<double*>(ws + lay.tile_z);
+    a.tile_s = reinterpret_cast<double*>(ws + lay.tile_s);
+    a.part = reinterpret_cast<double*>(ws + lay.part);
+    a.tile_peak = reinterpret_cast<float*>(ws + lay.tile_peak);
+    LoudnessGateArgs& g = a.gate;
+    loudness_gate_args(cfg, &g, ws + lay.item, lengths, B, S, groups, n_groups, target_lufs, peak_ceiling_db);
+    g.part = a.part; g.tile_peak = a.tile_peak; g.nt = (int)((S + LD_TILE - 1) / LD_TILE);
+    g.block_ms = block_ms ? block_ms : reinterpret_cast<double*>(ws + lay.block_ms);
+    g.ms_bstride = g.ms_width;
+    g.gate = gate ? 1 : 0;
+    g.lufs = lufs; g.gain = gain; g.peak = peak; g.flags = flags;
+    if (launch_loudness_measure(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
+int bv2_loudness_gate(bv2_stream stream, const bv2_loudness_config* cfg, const double* block_ms, int64_t ms_bstride, const int64_t* lengths,
+                      int32_t B, int64_t S, const float* peak, const int32_t* groups, int32_t n_groups, double target_lufs,
+                      double peak_ceiling_db, double* lufs, float* gain, int32_t* flags, void* workspace, int64_t workspace_bytes) {
+  const char* what = "bv2_loudness_gate";
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (int rc = loudness_check(cfg, what)) return rc;
+  if (!block_ms || !peak || !lufs || !gain || !flags) return fail("block_ms, peak, lufs, gain and flags must not be null", -1);
+  if (!(target_lufs == target_lufs) || !(peak_ceiling_db == peak_ceiling_db) || std::isinf(target_lufs) || std::isinf(peak_ceiling_db))
+    return fail("target_lufs and peak_ceiling_db must be finite", -1);
+  unsigned char* ws = nullptr;
+  if (int rc = loudness_common(what, cfg, B, S, groups, n_groups, workspace, workspace_bytes, (int64_t)(B > 0 ? B : 1) * 32, &ws)) return rc;
+  if (ms_bstride < loudness_blocks(S, loudness_step(cfg))) return fail("ms_bstride is shorter than bv2_loudness_blocks(S)", -1);
+  try {
+    LoudnessGateArgs g;
+    loudness_gate_args(cfg, &g, ws, lengths, B, S, groups, n_groups, target_lufs, peak_ceiling_db);
+    g.part = nullptr; g.tile_peak = nullptr; g.nt = 0;
+    g.block_ms = const_cast<double*>(block_ms); g.ms_bstride = ms_bstride;
+    g.gate = 1;
+    g.lufs = lufs; g.gain = gain; g.peak = const_cast<float*>(peak); g.flags = flags;
+    if (launch_loudness_gate(static_cast<hipStream_t>(stream), g)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
+int bv2_loudness_apply(bv2_stream stream, const bv2_loudness_config* cfg, const void* src, int64_t src_bstride, const int64_t* lengths,
+                       int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, const float* gain, float* dst_f32, int16_t* dst_i16,
+                       int64_t dst_bstride) {
+  const char* what = "bv2_loudness_apply";
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (int rc = loudness_check(cfg, what)) return rc;
+  if (!src) return fail("src is null", -1);
+  if (!gain) return fail("gain is null", -1);
+  if ((dst_f32 != nullptr) == (dst_i16 != nullptr)) return fail("exactly one of dst_f32 / dst_i16 must be given", -1);
+  if (src_bstride < 0) return fail("src_bstride must not be negative", -1);
+  if (B < 1 || B > 65535) return fail("B must be in [1, 65535]", -1);
+  if (S < 1 || S > LD_MAX_S) return fail("S must be in [1, 2^31 - 4096]", -1);
+  if (groups ? n_groups < 1 : n_groups != B)                  // with groups the gain table may be longer than B: groups can span calls
+    return fail("n_groups (the length of gain) must be at least 1 with groups, and equal to B without", -1);
+  if (dst_bstride < S) return fail("dst_bstride is shorter than S", -1);
+  try {
+    LoudnessApplyArgs a;
+    a.src = src; a.src_bstride = src_bstride; a.lengths = lengths; a.B = B; a.S = S; a.input_format = cfg->input_format;
+    a.groups = groups; a.n_gain = n_groups; a.gain = gain; a.dst = dst_f32; a.dst16 = dst_i16; a.dst_bstride = dst_bstride;
+    if (launch_loudness_apply(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
 // ---- forced alignment (kernels/align.hip) ----------------------------------------------------------------------
 int bv2_neg_cent(bv2_stream stream, int32_t B, int32_t inter, int32_t T, int32_t Ty, const float* z_p, const float* m_p,
                  const float* logs_p, const int64_t* x_lengths, const int64_t* y_lengths, float* neg_cent) {

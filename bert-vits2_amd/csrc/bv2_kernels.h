@@ -834,4 +834,38 @@ int launch_posterior_sample(hipStream_t stream, const float* m, const float* log
 int64_t maximum_path_workspace_bytes(int B, int T, int Ty);
 int launch_maximum_path(hipStream_t stream, const MaxPathArgs& a);
 
+// --- BS.1770 loudness (kernels/loudness.hip): K-weighting in fp64, block energies, gates, one gain per group; the multiply that applies it ---
+constexpr int LD_THREADS = 256, LD_SEG = 16;         // a thread filters LD_SEG samples; a workgroup owns LD_TILE samples of one item
+constexpr int LD_TILE = LD_THREADS * LD_SEG;
+constexpr int LD_MAX_PARTS = 8;                      // 100 ms steps a tile can touch: (LD_TILE - 1) / step + 2 with step >= 800 (8 kHz)
+constexpr int LD_FLAG_SILENT = 1, LD_FLAG_LIMITED = 2;   // include/bv2.h BV2_LOUDNESS_SILENT / BV2_LOUDNESS_LIMITED
+struct LoudnessFilter {
+  double c[10];                                      // b0 b1 b2 a1 a2 of the shelf, then of the high pass
+  double P[16], Q[16], R[16];                        // A^LD_SEG, A^(LD_SEG^2), A^LD_TILE of the cascade's state matrix, row-major
+};
+struct LoudnessGateArgs {
+  const double* part; const float* tile_peak; int nt;   // [B][nt][LD_MAX_PARTS], [B][nt]; part null = block_ms and peak are inputs
+  double* block_ms; int64_t ms_bstride, ms_width;    // [B][ms_bstride >= ms_width]; ms_width = blocks of S
+  const int64_t* lengths; int64_t S; int B;          // [B] or null = S
+  const int* groups; int n_groups;                   // [B] in [0, n_groups), or null = the item's row (n_groups == B)
+  int step, gate;                                    // gate 0: block_ms and peak only
+  double abs_ms, target_lufs, ceiling;               // the absolute gate as a mean square; the ceiling as an amplitude
+  double* lufs; float* gain; float* peak; int* flags;   // [n_groups], [n_groups], [B], [n_groups]
+  double* item_s; int64_t* item_c; double* sort_s; int64_t* sort_c;   // [B] each
+};
+struct LoudnessArgs {
+  const void* wav; int64_t bstride; const int64_t* lengths; int B; int64_t S; int step, input_format;
+  LoudnessFilter filter;
+  double *tile_z, *tile_s, *part; float* tile_peak;  // [B][nt][4] twice, [B][nt][LD_MAX_PARTS], [B][nt]
+  LoudnessGateArgs gate;
+};
+struct LoudnessApplyArgs {
+  const void* src; int64_t src_bstride; const int64_t* lengths; int B; int64_t S; int input_format;
+  const int* groups; int n_gain; const float* gain;  // gain [n_gain]; item b takes gain[groups ? groups[b] : b]
+  float* dst; int16_t* dst16; int64_t dst_bstride;   // exactly one of the two
+};
+int launch_loudness_measure(hipStream_t stream, const LoudnessArgs& a);   // four launches
+int launch_loudness_gate(hipStream_t stream, const LoudnessGateArgs& a);
+int launch_loudness_apply(hipStream_t stream, const LoudnessApplyArgs& a);
+
 }  // namespace bv2

@@ -105,6 +105,14 @@ class ResampleConfig(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("rate_in", C.c_int32), ("rate_out", C.c_int32), ("input_format", C.c_int32)]
 
 
+class LoudnessConfig(C.Structure):
+    """include/bv2.h bv2_loudness_config"""
+    _fields_ = [("struct_bytes", C.c_int32), ("sample_rate", C.c_int32), ("input_format", C.c_int32)]
+
+
+LOUDNESS_SILENT, LOUDNESS_LIMITED = 1, 2
+
+
 class ProfileRow(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -170,6 +178,16 @@ SYMBOLS = [
     ("bv2_resample_taps_f64", C.c_int, [C.POINTER(ResampleConfig), _P]),
     ("bv2_resample", C.c_int, [_P, C.POINTER(ResampleConfig), _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int64, C.c_int64,
                                _P, C.c_int64, _P]),
+    ("bv2_loudness_plan", C.c_int, [C.POINTER(LoudnessConfig), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("bv2_loudness_coeffs", C.c_int, [C.POINTER(LoudnessConfig), _P]),
+    ("bv2_loudness_blocks", C.c_int64, [C.POINTER(LoudnessConfig), C.c_int64]),
+    ("bv2_loudness_workspace_bytes", C.c_int64, [C.POINTER(LoudnessConfig), C.c_int32, C.c_int64]),
+    ("bv2_loudness_measure", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, C.c_double,
+                                       C.c_double, _P, _P, _P, _P, _P, _P, C.c_int64]),
+    ("bv2_loudness_gate", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, C.c_double,
+                                    C.c_double, _P, _P, _P, _P, C.c_int64]),
+    ("bv2_loudness_apply", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P, _P,
+                                     C.c_int64]),
     ("bv2_neg_cent", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("bv2_maximum_path_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     ("bv2_maximum_path", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int64]),

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from dataclasses import InitVar, dataclass
 from typing import List, Optional, Sequence
 
@@ -232,7 +233,9 @@ def replicas(model, n: int) -> list:
 @torch.no_grad()
 def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0.6, noise_scale_w=0.9, length_scale=1.0,
                max_batch: int = 32, max_pad_ratio: float = 1.25, as_pcm16: bool = False,
-               noise: Optional[Sequence] = None, requests_in_flight: int = 1, output_rate: Optional[int] = None) -> List[np.ndarray]:
+               noise: Optional[Sequence] = None, requests_in_flight: int = 1, output_rate: Optional[int] = None,
+               target_lufs: Optional[float] = None, peak_ceiling_db: float = -1.0, loudness_groups: Optional[Sequence] = None,
+               return_levels: bool = False) -> List[np.ndarray]:
     """Synthesise every utterance; returns one 1-D array per utterance in input order (float32 like reference
     infer.py:315-319, or int16 with ``as_pcm16``).  Defaults are the reference web UI's (webui.py:443-454).
     ``noise`` (tests): per utterance a pair ``(noise_w [2,T], noise_z [inter, >= T_y])`` to inject instead of drawing.
@@ -246,7 +249,17 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     others on their ``sid`` row, all in the same buckets (``speaker_vectors``).
     ``output_rate``: audio at that sampling rate instead of the model's — every bucket is resampled on the device (``audio.resample`` over
     each utterance's own ``y_lengths * hop`` samples) before its one device-to-host copy; an utterance of n model-rate samples comes back
-    with ``ceil(n L / M)``, and ``as_pcm16`` normalises by the peak of the resampled samples."""
+    with ``ceil(n L / M)``, and ``as_pcm16`` normalises by the peak of the resampled samples.
+    ``target_lufs``: every utterance leaves at that integrated loudness (ITU-R BS.1770-4, ``audio.normalize_loudness``): each bucket is
+    measured and scaled on the device before its one copy — after the resampling, at the output rate — by one static gain per utterance,
+    lowered where the sample peak would pass ``peak_ceiling_db``; ``as_pcm16`` is then the fixed-gain 16-bit form of the normalised audio
+    (``trunc(clamp(x * 32767))``), not the peak-normalised one.  ``None``: no levelling, today's output to the bit.
+    ``loudness_groups``: one hashable per utterance; the utterances of a group (the sentences of one document) are measured as one
+    programme and share ONE gain, whichever buckets they fall into — the buckets' block energies and peaks stay on the device until the
+    last bucket has run, then one gating launch and one multiply per bucket follow (ungrouped calls keep the overlap of a bucket's copy
+    with the next bucket's kernels).  ``return_levels``: ``(audio, levels)`` with one dict per utterance — ``lufs`` (measured, of its
+    group), ``gain_db`` and ``gain`` (the fp32 factor that was applied), ``peak`` (its own sample peak before the gain), ``limited``,
+    ``silent``."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
     if noise is not None and any(u.seed is not None for u in utts):
@@ -256,6 +269,7 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     output_rate = _output_rate(model, output_rate)
     if output_rate is not None:
         hop = 1                                            # the buckets' lengths then count output-rate samples
+    level = _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels)
     results: List[Optional[np.ndarray]] = [None] * len(utts)
     pending = []
     lanes = replicas(model, requests_in_flight) if requests_in_flight > 1 else [(model, None)]
@@ -275,12 +289,89 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
         else:
             ctl = call
         with torch.cuda.stream(lane_stream) if lane_stream is not None else contextlib.nullcontext():
-            _run_bucket(lane, utts, idx, dev, noise, pending, as_pcm16, gvec, output_rate=output_rate, **ctl)
-    for idx, host, y_len, ev in pending:
+            _run_bucket(lane, utts, idx, dev, noise, pending, as_pcm16, gvec, output_rate=output_rate, level=level, **ctl)
+    if level is not None and level["ids"] is not None:
+        _level_groups(level, pending, as_pcm16, dev)
+    levels: List[Optional[dict]] = [None] * len(utts)
+    for idx, host, y_len, ev, *lv in pending:
         ev.synchronize()
         for r, i in enumerate(idx):
             results[i] = host[r, :int(y_len[r]) * hop].numpy().copy()
-    return results
+            if lv:
+                lufs, gain, peak, flags = (float(v) for v in lv[0][:, r])
+                levels[i] = dict(lufs=lufs, gain_db=20.0 * math.log10(gain), gain=gain, peak=peak, limited=bool(int(flags) & 2),
+                                 silent=bool(int(flags) & 1))
+    return (results, levels) if return_levels else results
+
+
+def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels) -> Optional[dict]:
+    """The loudness arguments of ``synthesize``, checked before any work: ``None`` without a target."""
+    if target_lufs is None:
+        if loudness_groups is not None or return_levels:
+            raise ValueError("loudness_groups and return_levels need target_lufs")
+        return None
+    if not (math.isfinite(float(target_lufs)) and math.isfinite(float(peak_ceiling_db))):
+        raise ValueError("target_lufs and peak_ceiling_db must be finite")
+    from . import audio
+    rate = int(output_rate if output_rate is not None else model.hp.sampling_rate)
+    audio.loudness_plan(rate)                               # ValueError naming the envelope
+    ids = None
+    if loudness_groups is not None:
+        keys = list(loudness_groups)
+        if len(keys) != len(utts):
+            raise ValueError("loudness_groups takes one hashable per utterance")
+        dense = {}
+        ids = [dense.setdefault(k, len(dense)) for k in keys]
+    return dict(rate=rate, target=float(target_lufs), ceiling=float(peak_ceiling_db), ids=ids, held=[])
+
+
+def _level_groups(level, pending, as_pcm16, dev):
+    """Groups that span buckets: every bucket has left its audio, block mean squares and peaks on the device (``level["held"]``).  One
+    gating launch over all of them on the caller's stream, ordered behind every bucket by its event; then, on each bucket's own stream
+    and behind the gate's event, one multiply and the bucket's copy."""
+    from . import audio
+    held = level["held"]
+    main = torch.cuda.current_stream(dev)
+    for h in held:
+        main.wait_event(h["ev"])
+    width = max(h["block_ms"].shape[1] for h in held)
+    S = max(h["wave"].shape[1] for h in held)
+    ms = torch.cat([torch.nn.functional.pad(h["block_ms"], (0, width - h["block_ms"].shape[1])) for h in held])
+    rows = [i for h in held for i in h["idx"]]
+    groups = torch.tensor([level["ids"][i] for i in rows], dtype=torch.int32).to(dev)
+    n_groups = max(level["ids"]) + 1
+    m = audio.loudness_gate(ms, torch.cat([h["lens"] for h in held]), S, torch.cat([h["peak"] for h in held]), level["rate"], groups,
+                            n_groups, level["target"], level["ceiling"])
+    gated = torch.cuda.Event()
+    gated.record(main)
+    o = 0
+    for h in held:
+        B = len(h["idx"])
+        g = groups[o:o + B]
+        with torch.cuda.stream(h["stream"]) if h["stream"] is not None else contextlib.nullcontext():
+            torch.cuda.current_stream(dev).wait_event(gated)
+            out = audio.loudness_apply(h["wave"], h["lens"], level["rate"], m["gain"], g, as_pcm16)
+            gl = g.long()
+            lv = torch.stack([m["lufs"][gl], m["gain"][gl].double(), h["peak"].double(), m["flags"][gl].double()])
+            _enqueue_copy(pending, h["idx"], out, h["y_len"], lv)
+        o += B
+
+
+def _enqueue_copy(pending, idx, audio, y_len, levels=None):
+    """One async D2H per bucket into pinned memory (audio AND lengths, levels if any): nothing here blocks the host, so the next bucket's
+    kernels are enqueued while this copy runs; the drain loop of ``synthesize`` waits on the bucket's event."""
+    host = torch.empty(audio.shape, dtype=audio.dtype, pin_memory=True)
+    host.copy_(audio, non_blocking=True)
+    host_len = torch.empty(y_len.shape, dtype=torch.int64, pin_memory=True)
+    host_len.copy_(y_len, non_blocking=True)
+    extra = []
+    if levels is not None:
+        host_lv = torch.empty(levels.shape, dtype=torch.float64, pin_memory=True)
+        host_lv.copy_(levels, non_blocking=True)
+        extra.append(host_lv)
+    ev = torch.cuda.Event()
+    ev.record()
+    pending.append((idx, host, host_len, ev, *extra))
 
 
 def _output_rate(model, output_rate) -> Optional[int]:
@@ -293,30 +384,34 @@ def _output_rate(model, output_rate) -> Optional[int]:
 
 
 def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio, noise_scale, noise_scale_w, length_scale,
-                output_rate=None):
-    """One bucket on the CURRENT stream: collate, infer (exact lengths), optional resampling, optional PCM16, async D2H into pinned
-    memory.  The lengths that travel with it count frames, or samples after a resampling."""
+                output_rate=None, level=None):
+    """One bucket on the CURRENT stream: collate, infer (exact lengths), optional resampling, optional levelling or PCM16, async D2H into
+    pinned memory.  The lengths that travel with it count frames, or samples after a resampling."""
     batch, kw = _bucket_inputs(model, utts, idx, dev, noise, gvec)
     o, _attn, y_mask, _ = model.infer(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"],
                                       batch["bert"], batch["ja_bert"], batch["en_bert"], sdp_ratio=sdp_ratio,
                                       noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale,
                                       want_attn=False, exact_lengths=True, **kw)
     y_len = model.last_encode["y_lengths"]             # int64 [B], already on the device (phase A output)
+    from . import audio as _audio
     if output_rate is None:
-        audio = pcm16(model, o, y_len) if as_pcm16 else o[:, 0]
+        wave, lens = o[:, 0], None if level is None else y_len * model.hp.total_upsample
     else:
-        from . import audio as _audio
-        res, y_len = _audio.resample(o[:, 0], y_len * model.hp.total_upsample, model.hp.sampling_rate, output_rate)
-        audio = pcm16(model, res[:, None], y_len, hop=1) if as_pcm16 else res
-    # one async D2H per bucket into pinned memory (audio AND lengths): nothing here blocks the host, so the next bucket's
-    # kernels are enqueued while this copy runs; the drain loop below waits on the bucket's event
-    host = torch.empty(audio.shape, dtype=audio.dtype, pin_memory=True)
-    host.copy_(audio, non_blocking=True)
-    host_len = torch.empty(y_len.shape, dtype=torch.int64, pin_memory=True)
-    host_len.copy_(y_len, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record()
-    pending.append((idx, host, host_len, ev))
+        wave, y_len = _audio.resample(o[:, 0], y_len * model.hp.total_upsample, model.hp.sampling_rate, output_rate)
+        lens = y_len
+    if level is None:
+        audio = pcm16(model, wave[:, None], y_len, hop=None if output_rate is None else 1) if as_pcm16 else wave
+        _enqueue_copy(pending, idx, audio, y_len)
+    elif level["ids"] is None:                         # every utterance its own programme: measure, scale, copy
+        m = _audio.loudness_measure(wave, lens, level["rate"], None, None, level["target"], level["ceiling"])
+        audio = _audio.loudness_apply(wave, lens, level["rate"], m["gain"], None, as_pcm16)
+        _enqueue_copy(pending, idx, audio, y_len, torch.stack([m["lufs"], m["gain"].double(), m["peak"].double(), m["flags"].double()]))
+    else:                                              # groups may span buckets: energies and peaks wait on the device (_level_groups)
+        m = _audio.loudness_measure(wave, lens, level["rate"], gate=False)
+        ev = torch.cuda.Event()
+        ev.record()
+        level["held"].append(dict(idx=idx, wave=wave, lens=lens, y_len=y_len, block_ms=m["block_ms"], peak=m["peak"], ev=ev,
+                                  stream=torch.cuda.current_stream(dev)))
 
 
 def _bucket_inputs(model, utts, idx, dev, noise, gvec):

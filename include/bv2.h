@@ -460,6 +460,67 @@ int bv2_resample(bv2_stream stream, const bv2_resample_config* cfg, const float*
                  int64_t src_start, int64_t src_n, const int64_t* src_lengths, int32_t B, int64_t n0, int64_t n1, float* dst,
                  int64_t dst_bstride, int64_t* dst_lengths_out);
 
+/* ---- loudness: ITU-R BS.1770-4 meter (mono) and a gain to a target level (handle-free; kernels/loudness.hip) -------------
+ * K-weighting at sampling rate fs: two biquads whose coefficients come from the bilinear forms below, in fp64 on the host
+ * (bv2_loudness_coeffs; at 48 kHz they are the standard's table to 1e-15).
+ *   stage 1, high shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / fs), Vh = 10^(G/20),
+ *     Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2; b = [Vh + Vb K/Q + K^2, 2 (K^2 - Vh), Vh - Vb K/Q + K^2] / a0,
+ *     a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0];
+ *   stage 2, high pass: f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1], a as above with its own K and a0.
+ * Blocks: step = round(fs / 10) samples, block = 4 step; block j of an item covers its samples [j step, j step + block), only whole blocks
+ * count, and an item shorter than a block is ONE block of its own length.  z_j = mean square of the K-weighted samples of block j,
+ * l_j = -0.691 + 10 log10 z_j.  Gating: the blocks with l_j > -70; of those, the blocks with l_j > -0.691 + 10 log10(mean z) - 10; the
+ * integrated loudness is -0.691 + 10 log10(mean z of what is left).  No block above -70: the loudness is -inf and the group is flagged
+ * BV2_LOUDNESS_SILENT.  Items that share a group id are the pieces of one programme: their blocks are pooled (blocks never span two items)
+ * and the group gets one loudness and one gain.  groups == NULL: every item is its own group (n_groups == B).
+ * Gain of a group: 10^((target_lufs - L) / 20); if peak * gain > 10^(peak_ceiling_db / 20), with peak the group's largest |sample|, the gain
+ * is ceiling / peak and the group is flagged BV2_LOUDNESS_LIMITED (a static gain: nothing is distorted); a silent group gets gain 1.  The
+ * gain is formed in fp64 on the device and rounded once to fp32.
+ * Arithmetic: the recurrence and every energy sum are fp64; each sum has one fixed order that depends on the item's own samples only, so an
+ * item's block mean squares (and an ungrouped item's lufs and gain) are the same bits alone and in any batch, at any row, batch stride or
+ * S, and a group's numbers do not depend on the order of its items.  Samples at or behind lengths[b] are never loaded (the padding of a
+ * batch may hold anything); int16 input is read as x / 32768.
+ * Envelope: 8000 <= sample_rate <= 192000, 1 <= B <= 4096, 1 <= S < 2^31 - 4096.  Every argument is checked before anything touches the
+ * device: -1 with a message in bv2_last_error(NULL) (the size queries a negative value), -5 for a null or short workspace.  The device
+ * calls are asynchronous on `stream`, allocate nothing and do not sync (capture in a hipGraph has not been tested). */
+enum { BV2_LOUDNESS_SILENT = 1, BV2_LOUDNESS_LIMITED = 2 };
+typedef struct bv2_loudness_config {
+  int32_t struct_bytes;            /* = sizeof(bv2_loudness_config) */
+  int32_t sample_rate;
+  int32_t input_format;            /* BV2_WAV_F32 / BV2_WAV_I16 */
+} bv2_loudness_config;
+/* HOST: step, block and tile (the samples one workgroup owns, counted from the item's first sample); each pointer may be NULL. */
+int bv2_loudness_plan(const bv2_loudness_config* cfg, int32_t* step, int32_t* block, int32_t* tile);
+/* HOST: b0 b1 b2 a1 a2 of stage 1, then of stage 2 (a0 = 1). */
+int bv2_loudness_coeffs(const bv2_loudness_config* cfg, double out[10]);
+/* HOST: blocks of an item of n samples: 0 for n = 0, 1 for n < block, else (n - block) / step + 1; negative for a bad config or n < 0. */
+int64_t bv2_loudness_blocks(const bv2_loudness_config* cfg, int64_t n);
+/* Bytes of DEVICE workspace of bv2_loudness_measure at (B, S); it covers bv2_loudness_gate at B as well. */
+int64_t bv2_loudness_workspace_bytes(const bv2_loudness_config* cfg, int32_t B, int64_t S);
+/* Four launches.  wav [B][wav_bstride] fp32 or int16 (DEVICE), item b's samples [0, lengths[b]) (lengths int64 [B] DEVICE, clamped to
+ * [0, S]; NULL = S); groups int32 [B] DEVICE with values in [0, n_groups) — the CALLER guarantees the range (an item with another id
+ * belongs to no group and its outputs are not written) — or NULL with n_groups == B.  Outputs, all DEVICE: lufs fp64 [n_groups], gain fp32
+ * [n_groups], peak fp32 [B] (sample peak per item), flags int32 [n_groups], block_ms fp64 [B][bv2_loudness_blocks(S)] or NULL (z_j per
+ * item; zeros behind the item's last block).  lufs, gain and flags all NULL: only peak and block_ms are produced (block_ms is then
+ * required) — the first half of a measurement whose groups span several calls; bv2_loudness_gate is the second half. */
+int bv2_loudness_measure(bv2_stream stream, const bv2_loudness_config* cfg, const void* wav, int64_t wav_bstride, const int64_t* lengths,
+                         int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, double target_lufs, double peak_ceiling_db,
+                         double* lufs, float* gain, float* peak, int32_t* flags, double* block_ms, void* workspace,
+                         int64_t workspace_bytes);
+/* One launch: the gates and gains from block mean squares and peaks that bv2_loudness_measure produced, possibly in several calls:
+ * block_ms [B][ms_bstride >= bv2_loudness_blocks(S)] and peak [B] are inputs, item b has bv2_loudness_blocks(lengths[b]) blocks. */
+int bv2_loudness_gate(bv2_stream stream, const bv2_loudness_config* cfg, const double* block_ms, int64_t ms_bstride, const int64_t* lengths,
+                      int32_t B, int64_t S, const float* peak, const int32_t* groups, int32_t n_groups, double target_lufs,
+                      double peak_ceiling_db, double* lufs, float* gain, int32_t* flags, void* workspace, int64_t workspace_bytes);
+/* One launch: dst[b][i] = src[b][i] * gain[groups ? groups[b] : b] for i < lengths[b] — ONE fp32 multiply — and zeros behind the length up
+ * to S.  Exactly one of dst_f32 / dst_i16 is non-NULL; the 16-bit form is (int16) trunc(clamp(v * 32767.0f, -32768, 32767)) of the fp32
+ * product v, bv2_emit's rule, no contraction into an FMA: given the gain, numpy reproduces both outputs bit for bit.  gain [n_groups]:
+ * n_groups == B when groups is NULL; with groups it is the length of the gain table, which may exceed B (groups that span several calls;
+ * an item whose id lies outside the table keeps gain 1).  B <= 65535; cfg gives the input format. */
+int bv2_loudness_apply(bv2_stream stream, const bv2_loudness_config* cfg, const void* src, int64_t src_bstride, const int64_t* lengths,
+                       int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, const float* gain, float* dst_f32, int16_t* dst_i16,
+                       int64_t dst_bstride);
+
 /* ---- forced alignment: the reference's own aligner (handle-free; kernels/align.hip) --------------------------------------
  * SynthesizerTrn.forward() aligns a recording to its text with two steps that need no weights (models.py:960-991): the negative
  * cross-entropy between every latent frame z_p[:, y] of the recording and every symbol's prior N(m_p[:, x], exp(logs_p[:, x])), and
