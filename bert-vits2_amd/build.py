@@ -27,7 +27,10 @@ SOURCES = [
 EXPORTS = "libbv2.map"     # linker version script: export bv2_* only
 HEADERS = [EXPORTS, "bv2_internal.h", "bv2_kernels.h", "bv2_pack.h", "kernels/spline.h", "kernels/dds_tile.h", "kernels/cl_bf16.h", "kernels/device_helpers.h", "kernels/rng.h", os.path.join(ROOT, "include", "bv2.h"),
            os.path.join(ROOT, "include", "bv2_testing.h"), os.path.join(ROOT, "include", "bv2_bert.h")]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-x", "hip"]
+# -amdgpu-kernarg-preload-count: up to 16 dwords of a kernel's LEADING SCALAR arguments arrive in SGPRs at wave launch (kernels whose
+# first argument is a by-value struct are unaffected: preload length 0; tools/kernel_resources.py prints the length per kernel)
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16",
+         "-x", "hip"]
 
 
 def _hipcc() -> str:

@@ -1353,6 +1353,7 @@ int bv2_set_option(bv2_handle* h, const char* key, int value) {
   else if (k == "overlap_dp") h->no_overlap_dp = value == 0;
   else if (k == "lean_durations") h->no_lean_durations = value == 0;
   else if (k == "phase_b_front") h->no_phase_b_front = value == 0;
+  else if (k == "kernarg_head") h->no_kernarg_head = value == 0;
   else { h->err = "bv2_set_option: unknown key '" + k + "'"; return -1; }
   return 0;
   BV2_CATCH(h)

@@ -100,7 +100,7 @@ struct Ctx {
   // across workgroups: max_split > 1 means the CONSUMER sums `slab_stride`-spaced slabs).
   int conv(ConvLaunch& L, const char* tag, int max_split = 1, int64_t slab_stride = 0) {
     if (rc) return 1;
-    L.ksplit = 1; L.slab_stride = slab_stride;
+    L.ksplit = 1; L.slab_stride = slab_stride; L.no_head = h->no_kernarg_head ? 1 : 0;
     if (max_split > 1 && conv_use_splitk(L)) L.ksplit = conv_pick_ksplit(L, max_split);
     const char* vn = "conv1d_mfma";
     timed(tag, &vn, [&] { return conv_shape(L.nprob, L.p[0].cin, L.p[0].cout, L.p[0].k, L.L, L.B) + " s" + std::to_string(L.ksplit); },
@@ -139,8 +139,10 @@ struct Ctx {
     timed(tag, &vn, [&] { return conv_shape(1, p.cin, p.cout, p.k, L, B); },      // "n1" also with p2: the row keys stay as they are
           [&] { return conv_f16_flops(hl); }, [&] { return conv_f16_bytes(hl); }, [&] { return launch_conv_f16(s, hl, &vn); });
   }
-  void ln(const LnArgs& a, const char* tag) {
+  void ln(const LnArgs& a0, const char* tag) {
     if (rc) return;
+    LnArgs a = a0;
+    a.no_head = h->no_kernarg_head ? 1 : 0;
     if (int r = launch_layernorm(s, a)) fail(tag, r);
   }
   void chk(int r, const char* tag) { if (r && !rc) fail(tag, r); }
@@ -189,6 +191,7 @@ void run_encoder(Ctx& c, const EncoderW& e, const EncBufs& b, const float* mask,
     a.B = B; a.H = e.heads; a.D = H / e.heads; a.T = T; a.W = kAttnWindow; a.f16 = f16 ? 1 : 0; a.xcd_b = xcd ? 1 : 0;
     if (kv16) { a.kh = b.k16; a.vh = b.v16; }
     if (!f16) a.qtile = c.h->attn_qtile;
+    a.no_head = c.h->no_kernarg_head ? 1 : 0;
     // small-N regime (the one where `s` holds partial slabs): conv_o runs inside the attention kernel, head h -> slab h
     const bool fuse_o = !f16 && !c.h->no_fused_attn_o && n_slabs(B, T) >= e.heads && L.o.k == 1 && L.o.cin == H;
     // key split (batch 1, long sequences): the key tiles of a (head, query tile) go to `ks` workgroups, each writing its own partial
@@ -268,7 +271,7 @@ void run_encoder(Ctx& c, const EncoderW& e, const EncBufs& b, const float* mask,
     if (fb && i + 1 == e.n_layers) {
       // the flow: this LayerNorm, the coupling's post and the next coupling's pre in one launch (flow_boundary.hip)
       fb->a = l.a; fb->nslab = l.nslab; fb->slab_stride = l.slab_stride; fb->gamma = l.gamma; fb->beta = l.beta; fb->eps = l.eps;
-      fb->mask = mask; fb->B = B; fb->C = H; fb->T = T;
+      fb->mask = mask; fb->B = B; fb->C = H; fb->T = T; fb->no_head = c.h->no_kernarg_head ? 1 : 0;
       fb->launched = flow_boundary_supported(*fb) ? 1 : 0;
     }
     if (fb && i + 1 == e.n_layers && fb->launched)

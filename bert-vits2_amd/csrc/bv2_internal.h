@@ -309,6 +309,7 @@ struct bv2_handle {
   bool no_fused_respair = false;     // "fused_respair" = 0: the wide bf16 Generator stages one conv per launch (gen_bf16.hip) instead of one pair per launch
   bool no_fused_attn_o = false;      // "fused_attn_o" = 0: conv_o as its own launch after the attention kernel
   int attn_ksplit = -1;              // "attn_ksplit": key ranges per (head, query tile) of the fused attention; -1 = picked per shape, 0 / 1 = off
+  bool no_kernarg_head = false;      // "kernarg_head" = 0: the split-K conv, LayerNorm, fp32 attention and flow boundary launches take their generic kernels (bv2_kernels.h SkHead)
   int attn_qtile = 0;                // "attn_qtile": queries per workgroup of the fp32 attention; 0 = picked per shape (attention_pick_qtile), 16, 32
   bool no_fused_dds = false;         // "fused_dds" = 0: DDSConv layers as 3 launches each
   bool no_overlap_dp = true;         // "overlap_dp" = 1: the (independent) DurationPredictor on an internal side stream, forked from and

@@ -138,7 +138,46 @@ struct ConvLaunch {
   int64_t slab_stride;      // floats between the partial slabs of one output (slab z is written at out + z*slab_stride)
   unsigned long long* dbg = nullptr;   // tools/timeline.py only: 8 u64 per workgroup (s_memtime stamps + HW ids); null in the product
   Prefetch pf = {nullptr, 0};          // split-K kernel only: the NEXT launch's weight stream, touched by PF_BLOCKS spare workgroups
+  int no_head = 0;                     // host only ("kernarg_head" = 0): the split-K launcher never takes the head form below
 };
+
+// The split-K kernel's HEAD form (one problem, B = 1, no `lens`).  Everything a workgroup needs to decode its tile and to form the
+// addresses of its first global loads (X tile, mask row, weight ring) travels as LEADING SCALAR kernel arguments — 13 dwords, which
+// gfx950 preloads into SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count=16; only leading scalars are eligible, a by-value
+// struct is a `byref` argument) — and the rest of the one problem follows in a ConvLaunch1 at static offsets: no computed index into
+// p[], and a kernarg segment of one ConvProb instead of BV2_MAX_PROBS.  The small fields are packed: pk0 = k | dil << 8 |
+// pad_left << 16 | ksplit << 24 (8 bits each), pk1 = cin | cin_pad << 16.
+struct ConvLaunch1 {
+  ConvProb p;
+  int L; int64_t slab_stride; unsigned long long* dbg;
+};
+struct SkHead {
+  const float* x; const float* w; const float* in_mask;
+  int x_rstride, Lin, ntiles, per_xcd, total;          // the row tile is what remains of the virtual id: one problem, mtiles = cout_pad / 32
+  unsigned pk0, pk1;
+};
+struct SkSmall { int k, dil, pad_left, ksplit, cin, cin_pad; };
+#if defined(__HIPCC__)
+#define BV2_HD __host__ __device__
+#else
+#define BV2_HD
+#endif
+BV2_HD inline SkSmall sk_head_unpack(unsigned pk0, unsigned pk1) {
+  return SkSmall{(int)(pk0 & 255u), (int)((pk0 >> 8) & 255u), (int)((pk0 >> 16) & 255u), (int)(pk0 >> 24), (int)(pk1 & 65535u), (int)(pk1 >> 16)};
+}
+// false: a value does not fit its packed field, or the launch is not the head form's (several problems, a batch, `lens`, several
+// sources, a prefetch tail: its spare workgroups would read `pf` from the struct first) — the launcher takes the generic kernel
+inline bool sk_head_pack(const ConvLaunch& L, int ntiles, int per_xcd, int total, SkHead* h) {
+  const ConvProb& p = L.p[0];
+  if (L.no_head || L.nprob != 1 || L.B != 1 || L.lens || p.nsrc != 1 || (L.pf.ptr && L.pf.bytes)) return false;
+  if (p.k < 1 || p.k > 255 || p.dil < 1 || p.dil > 255 || p.pad_left < 0 || p.pad_left > 255 || L.ksplit < 1 || L.ksplit > 255) return false;
+  if (p.cin < 1 || p.cin > 65535 || p.cin_pad < 1 || p.cin_pad > 65535) return false;
+  h->x = p.x[0]; h->w = p.w; h->in_mask = p.in_mask;
+  h->x_rstride = p.x_rstride; h->Lin = p.Lin; h->ntiles = ntiles; h->per_xcd = per_xcd; h->total = total;
+  h->pk0 = (unsigned)p.k | (unsigned)p.dil << 8 | (unsigned)p.pad_left << 16 | (unsigned)L.ksplit << 24;
+  h->pk1 = (unsigned)p.cin | (unsigned)p.cin_pad << 16;
+  return true;
+}
 // tools/timeline.py: while a device buffer is set, every conv launch records per-workgroup timestamps into its own slice of it
 void conv_set_timeline(unsigned long long* dev_buf, long long capacity_u64);
 int conv_timeline_report(long long* meta, int max_launches);
@@ -490,6 +529,7 @@ struct LnArgs {
   const float* ml; int ml_H, ml_ks; const float* bias;
   int xcd_b; int xcd_per;             // batch item -> XCD affinity (HcLaunch::xcd_b); xcd_per: filled by the launcher
   Prefetch pf;                        // B == 1 only: the next launch's weight stream (Prefetch above); ptr null = none
+  int no_head;                        // host only ("kernarg_head" = 0): never the head form (layernorm.hip: a, add, ml, slab_stride, C, T as leading scalars)
 };
 int launch_layernorm(hipStream_t stream, const LnArgs& a);
 
@@ -508,6 +548,7 @@ struct FbArgs {
   int B, C, T;
   int launched;                                        // set by the executor: the fused launch was taken (else LayerNorm + post + pre)
   int C1;                                              // rows of x1 (= post's outputs = pre's inputs); the kernel is built for C1 == C/2
+  int no_head;                                         // host only ("kernarg_head" = 0): never the head form (flow_boundary.hip: post_w, a, slab_stride, T as leading scalars)
 };
 bool flow_boundary_supported(const FbArgs& a);
 int launch_flow_boundary(hipStream_t stream, const FbArgs& a);
@@ -574,6 +615,7 @@ struct AttnArgs {
   int qtile = 0;            // queries per workgroup: 0 = attention_pick_qtile, 16 (fp32 only) or 32 forced ("attn_qtile", tests)
   unsigned long long* dbg = nullptr;   // tools/timeline.py only
   int xcd_b = 0; int xcd_gx = 0, xcd_per = 0;   // batch item -> XCD affinity (HcLaunch::xcd_b); xcd_gx / xcd_per: filled by the launcher
+  int no_head = 0;          // host only ("kernarg_head" = 0): never the head form (attention.hip: qkv, mask, erv, ld, T, H, W, ksplit as leading scalars)
 };
 int attention_pick_ksplit(int B, int H, int T, int max_slabs);   // key ranges per (head, query tile) that fill the chip at small batch
 int attention_pick_qtile(int B, int H, int T, int D, int ksplit, bool f16);   // 16 or 32 queries per workgroup, from the shape and dtype alone

@@ -100,6 +100,25 @@ static ConvW t_conv_w(int64_t off, int cin, int cout, int k, bool bias, bool x6)
   return w;
 }
 
+// "kernarg_head" for the launch entries of this file (they have no handle): 0 = every launch below takes its generic kernel
+static int g_test_no_head = 0;
+void bv2_test_set_kernarg_head(int on) { g_test_no_head = on ? 0 : 1; }
+// host only: the split-K head's packed fields (bv2_kernels.h sk_head_pack / sk_head_unpack).  Returns 1 and the six unpacked fields
+// {k, dil, pad_left, ksplit, cin, cin_pad} when a one-problem launch with these values takes the head form, 0 when it falls back
+int bv2_test_splitk_head(int k, int dil, int pad_left, int ksplit, int cin, int cin_pad, int B, int has_lens, int nprob, int32_t* out6) {
+  ConvLaunch cl;
+  std::memset(&cl, 0, sizeof(cl));
+  static const int64_t one_len = 1;
+  ConvProb& p = cl.p[0];
+  p.nsrc = 1; p.k = k; p.dil = dil; p.pad_left = pad_left; p.cin = cin; p.cin_pad = cin_pad;
+  cl.nprob = nprob; cl.B = B; cl.L = 1; cl.ksplit = ksplit; cl.lens = has_lens ? &one_len : nullptr;
+  SkHead h;
+  if (!sk_head_pack(cl, 1, 1, 1, &h)) return 0;
+  const SkSmall q = sk_head_unpack(h.pk0, h.pk1);
+  if (out6) { out6[0] = q.k; out6[1] = q.dil; out6[2] = q.pad_left; out6[3] = q.ksplit; out6[4] = q.cin; out6[5] = q.cin_pad; }
+  return 1;
+}
+
 int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const float* bias_host, float* out, float* wpack_dev,
                     int B, int cin, int cout, int k, int dil, int pad_left, int L, int tile, float lrelu_slope, int relu,
                     const float* res, int res_mode, const float* in_mask, const float* out_mask, int mask_pre,
@@ -144,7 +163,7 @@ int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const flo
     p.pad_left = pad_left < 0 ? ((k - 1) / 2) * dil : pad_left;
     p.pre_act = lrelu_slope != 0.f ? PRE_LRELU : PRE_NONE; p.slope = lrelu_slope;
     p.act = relu; p.mask_pre = mask_pre; p.mask_post = mask_post;
-    cl.nprob = 1; cl.B = B; cl.L = L; cl.ksplit = ksplit < 1 ? 1 : ksplit; cl.slab_stride = slab_stride;
+    cl.nprob = 1; cl.B = B; cl.L = L; cl.ksplit = ksplit < 1 ? 1 : ksplit; cl.slab_stride = slab_stride; cl.no_head = g_test_no_head;
     const char* vn = nullptr;
     return launch_conv1d(static_cast<hipStream_t>(stream), cl, tile, &vn);
   } catch (...) { return -100; }
@@ -292,7 +311,7 @@ int bv2_test_flow_boundary(void* stream, const float* a, int nslab, int64_t slab
     F.a = a; F.nslab = nslab; F.slab_stride = slab_stride; F.gamma = gamma; F.beta = beta; F.eps = 1e-5f; F.mask = mask;
     F.x1 = x1; F.x1_out = x1; F.z_bstride = z_bstride; F.post_w = wpack_dev; F.post_b = wpack_dev + npost + npre;
     if (pre_w_host) { F.pre_w = wpack_dev + npost; F.pre_b = wpack_dev + npost + npre + C1; F.pre_out = pre_out; }
-    F.B = B; F.C = C; F.T = T; F.C1 = C1;
+    F.B = B; F.C = C; F.T = T; F.C1 = C1; F.no_head = g_test_no_head;
     if (!flow_boundary_supported(F)) return -2;
     return launch_flow_boundary(static_cast<hipStream_t>(stream), F);
   } catch (...) { return -100; }
@@ -475,7 +494,7 @@ int bv2_test_attention_q(void* stream, const float* qkv, int ld, const float* ma
       a.wo = wo_pack_dev; a.wo_groups = cin_pad / 8;
     }
     a.bo = bo; a.res = res; a.o_out = o_out; a.o_slab_stride = o_slab_stride; a.Co = Co;
-    a.ksplit = ksplit; a.ml_out = ml_out;
+    a.ksplit = ksplit; a.ml_out = ml_out; a.no_head = g_test_no_head;
     return launch_attention(static_cast<hipStream_t>(stream), a);
   } catch (...) { return -100; }
 }
@@ -492,7 +511,7 @@ int bv2_test_layernorm_ex(void* stream, const float* a, const float* add, int mo
   l.mask = mask; l.out = out; l.B = B; l.C = C; l.T = T;
   l.ml = ml; l.ml_H = ml_H; l.ml_ks = ml_ks; l.bias = bias;
   l.out2 = out2; l.vec2 = vec2; l.vec2_bstride = C;
-  l.pf = Prefetch{pf_ptr, pf_bytes};
+  l.pf = Prefetch{pf_ptr, pf_bytes}; l.no_head = g_test_no_head;
   return launch_layernorm(static_cast<hipStream_t>(stream), l);
 }
 
@@ -701,7 +720,7 @@ int bv2_test_conv_multi(void* stream, const bv2_test_conv_prob* probs, int nprob
     }
     cl.nprob = nprob; cl.B = B; cl.L = L; cl.lens = lens; cl.len_mul = len_mul < 1 ? 1 : len_mul;
     cl.ksplit = ksplit >= 1 ? ksplit : conv_pick_ksplit(cl, BV2_MAX_KSPLIT);      // ksplit 0: the split the executor would take (Ctx::conv)
-    cl.slab_stride = slab_stride;
+    cl.slab_stride = slab_stride; cl.no_head = g_test_no_head;
     const char* vn = nullptr;
     const int rc = launch_conv1d(static_cast<hipStream_t>(stream), cl, tile, &vn);
     if (info) { info[0] = conv_last_placement(); info[1] = cl.ksplit; }

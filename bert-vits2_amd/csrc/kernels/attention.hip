@@ -64,8 +64,15 @@ constexpr int ANS = 4;          // merge slots
 //         operand is its own probability register and its A operands v[c][16 bk + 4g .. + 3] are one aligned float4.
 //   conv_o  C_out / 16 row blocks dealt over the waves, D/4 MFMAs each; K-step (t, q) takes channel 16t + 8 (g >> 1) + (g & 1) + 2q from
 //         group g, which is component q of ONE float4 of the 32-row fragment order (conv_w_index): no second packed view.
-template <int DT, int NW, bool F16, bool ONE, bool KV16 = false, int QT = AQ_WIDE>   // D = 32*DT head channels, NW waves; ONE: at most one key tile per wave (no loop); QT queries per workgroup
-__global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
+
+// What a workgroup needs in front of its first global loads (K tile, key / query mask, query tile, relative-value table, relative-key
+// logit rows): the generic kernel fills it from AttnArgs, the head form from its leading scalar arguments.
+struct AttnHead { const float* qkv; const float* mask; const float* erv; int ld, T, H, W, ksplit; };
+
+// One (batch item b, head h, query tile / key range bx) workgroup.  Of A only fields the first loads do NOT need are read.
+template <int DT, int NW, bool F16, bool ONE, bool KV16, int QT>   // D = 32*DT head channels, NW waves; ONE: at most one key tile per wave (no loop); QT queries per workgroup
+__device__ __forceinline__ void attention_tile(const AttnHead Hd, const AttnArgs& A, const int b, const int h, const int bx,
+                                               const unsigned long long ts0) {
   static_assert(!KV16 || F16, "fp16 K / V only feed the fp16 matrix products");
   static_assert(QT == AQ_WIDE || (QT == AQ_NARROW && !F16), "the fp16 forms stay on 32 queries");
   constexpr int D = 32 * DT;
@@ -78,20 +85,13 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: keeps everything derived from it in SGPRs
   const int l31 = lane & 31, lh = lane >> 5;
   const int lq = lane & (AQ - 1), lg = lane >> QSH; // query column and lane group of the MFMA layouts (QT = 32: l31, lh)
-  const int KS = A.ksplit > 1 ? A.ksplit : 1;
-  int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
-  if (A.xcd_b) {                                             // batch item -> XCD affinity (bv2_kernels.h xcd_decode)
-    int r;
-    if (!xcd_decode(blockIdx.x, A.xcd_per, A.B, b, r)) return;
-    bx = r % A.xcd_gx; h = r / A.xcd_gx;
-  }
+  const int KS = Hd.ksplit > 1 ? Hd.ksplit : 1;
   const int kr = KS > 1 ? bx % KS : 0;                       // this workgroup's key range
   const int i0 = (KS > 1 ? bx / KS : bx) * AQ;
-  unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0;  // timeline stamps (tools/timeline.py; A.dbg is null in the product)
-  if (A.dbg) ts0 = __builtin_amdgcn_s_memtime();
-  const int T = A.T, W = A.W, NR = 2 * W + 1, ld = A.ld;
-  const int HD = A.H * D;
-  const int R = 3 * HD + A.H * NR;
+  unsigned long long ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0;     // timeline stamps (tools/timeline.py; A.dbg is null in the product)
+  const int T = Hd.T, W = Hd.W, NR = 2 * W + 1, ld = Hd.ld;
+  const int HD = Hd.H * D;
+  const int R = 3 * HD + Hd.H * NR;
 
   float* Os = smem;                                 // [ANS][D][AQ] partial outputs
   float* Qs = Os + ANS * D * AQ;                    // [D][AQ] query tile (pre-scaled by the projection)
@@ -101,12 +101,12 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   float* Lw = Mw + NW * AQ;                         // [NW][AQ]
   float* Qe = Lw + NW * AQ;                         // [NR][AQ] relative-key logits q_i.Ek[r]/sqrt(d) of this query tile
 
-  const float* base = A.qkv + (int64_t)b * R * ld;
+  const float* base = Hd.qkv + (int64_t)b * R * ld;
   const float* qp = base + (int64_t)(h * D) * ld;
   const float* kp = qp + (int64_t)HD * ld;
   const float* vp = kp + (int64_t)HD * ld;
   const float* qe = base + (int64_t)(3 * HD + h * NR) * ld;
-  const float* mp = A.mask + (int64_t)b * T;
+  const float* mp = Hd.mask + (int64_t)b * T;
 
   const int iq = i0 + lq;                           // this lane's query
   const bool iok = iq < T;
@@ -196,7 +196,7 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
     for (int q = 0; q < EVPT; ++q) {
       int e = tid + q * NT;
       e = e < NR * D ? e : NR * D - 1;
-      evv[q] = A.erv[e];
+      evv[q] = Hd.erv[e];
     }
 #pragma unroll
     for (int q = 0; q < QEPT; ++q) {
@@ -475,7 +475,7 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   }
   if (KS > 1 && tid < AQ && i0 + tid < T) {
     // (m_r, l_r) of this key range for the merge in the LayerNorm: [b][h][kr][2][T]
-    float* ml = A.ml_out + ((((int64_t)b * A.H + h) * KS + kr) * 2) * T + i0 + tid;
+    float* ml = A.ml_out + ((((int64_t)b * Hd.H + h) * KS + kr) * 2) * T + i0 + tid;
     ml[0] = m_tot;                                 // tid < AQ: lane lq == tid, so m_tot / l_tot are query tid's
     ml[T] = l_tot;
   }
@@ -668,6 +668,32 @@ __global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
   }
 }
 
+// the generic form: every dtype, batch item -> XCD affinity
+template <int DT, int NW, bool F16, bool ONE, bool KV16 = false, int QT = AQ_WIDE>
+__global__ void __launch_bounds__(64 * NW) attention_kernel(const AttnArgs A) {
+  int b = blockIdx.z, h = blockIdx.y, bx = blockIdx.x;
+  if (A.xcd_b) {                                             // batch item -> XCD affinity (bv2_kernels.h xcd_decode)
+    int r;
+    if (!xcd_decode(blockIdx.x, A.xcd_per, A.B, b, r)) return;
+    bx = r % A.xcd_gx; h = r / A.xcd_gx;
+  }
+  unsigned long long ts0 = 0;
+  if (A.dbg) ts0 = __builtin_amdgcn_s_memtime();
+  attention_tile<DT, NW, F16, ONE, KV16, QT>(AttnHead{A.qkv, A.mask, A.erv, A.ld, A.T, A.H, A.W, A.ksplit}, A, b, h, bx, ts0);
+}
+
+// The head form (batch 1, fp32 with the fused conv_o): the 11 leading scalar dwords are preloaded into SGPRs at wave launch, so the K
+// tile, the masks, the query tile and the relative-position rows are addressed without a trip to the kernarg segment; A's other fields
+// (conv_o's weights and outputs, the key split's (max, sum) rows) follow at static offsets and are needed only behind the first barrier.
+template <int DT, int NW, bool ONE, int QT>
+__global__ void __launch_bounds__(64 * NW) attention_head_kernel(const float* const qkv, const float* const mask, const float* const erv,
+                                                                 const int ld, const int T, const int H, const int W, const int ksplit,
+                                                                 const AttnArgs A) {
+  const unsigned long long ts0 = __builtin_amdgcn_s_memtime();     // unconditional: `if (A.dbg)` would wait for the struct first
+  attention_tile<DT, NW, false, ONE, false, QT>(AttnHead{qkv, mask, erv, ld, T, H, W, ksplit}, A, (int)blockIdx.z, (int)blockIdx.y,
+                                                (int)blockIdx.x, ts0);
+}
+
 static size_t attn_lds_bytes(int D, int NW, int AQ) {
   return sizeof(float) * (size_t)(ANS * D * AQ + D * AQ + (2 * AMAXW + 1) * D + 2 * (2 * AMAXW + 1) * AQ + 2 * NW * AQ);
 }
@@ -675,14 +701,22 @@ static size_t attn_lds_bytes(int D, int NW, int AQ) {
 template <int DT, int NW, bool F16, bool ONE, bool KV16 = false, int QT = AQ_WIDE>
 static int launch_attn_variant2(hipStream_t stream, const AttnArgs& a, dim3 grid) {
   const size_t lds = attn_lds_bytes(32 * DT, NW, QT);
-  auto kern = attention_kernel<DT, NW, F16, ONE, KV16, QT>;
-  ensure_dyn_lds((const void*)kern, lds);
   AttnArgs at = a;
   if (a.xcd_b) {
     at.xcd_gx = (int)grid.x; at.xcd_per = (int)(grid.x * grid.y);
     grid = dim3(xcd_grid(a.B, at.xcd_per), 1, 1);
   }
   at.dbg = timeline_slice(grid.x, grid.y, grid.z, 77000 + (QT == AQ_NARROW ? 100 : 0) + 10 * DT + NW, 0, a.D, a.T);    // tile id 77xxx: attention (771xx: 16 queries)
+  if constexpr (!F16) {
+    if (!a.no_head && a.B == 1 && a.wo && !a.xcd_b) {      // batch 1 only, as the other head forms (layernorm.hip launch_ln_form)
+      auto kern = attention_head_kernel<DT, NW, ONE, QT>;
+      ensure_dyn_lds((const void*)kern, lds);
+      hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, stream, at.qkv, at.mask, at.erv, at.ld, at.T, at.H, at.W, at.ksplit, at);
+      return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
+  }
+  auto kern = attention_kernel<DT, NW, F16, ONE, KV16, QT>;
+  ensure_dyn_lds((const void*)kern, lds);
   hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, stream, at);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

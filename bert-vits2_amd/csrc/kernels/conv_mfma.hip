@@ -381,57 +381,41 @@ constexpr int SK_PD = 8;          // prefetch ring depth (units of 4 MFMAs)
 // of it the 5-fold re-read of X), their main loop at 3.7x the MFMA time.  Weights still stream global -> registers.
 constexpr int SK_XP = 64;         // staged tile width (floats): 32 + (k-1)*dil must fit
 constexpr int SK_RPW = 32;        // rows of the staged tile per wave at most
+// What a workgroup needs in front of its first global loads: its tile (column tile nt, K slice z of ksplit, row tile mt, batch item
+// b), the bases of the X rows / mask row (already at batch item b) / packed weights, and the shape of the K loop.  The generic kernel
+// fills it from the problem it picked out of ConvLaunch::p, the head form from its leading scalar arguments (bv2_kernels.h SkHead).
+struct SkTile {
+  int nt, z, mt, b, ksplit;
+  const float* xp; const float* mp; const float* wp;
+  int x_rstride, Lin, k, dil, pad_left, cin, cin_pad;
+};
+
+// One 32 x 32 output tile of the split-K kernel.  P: the problem (a by-value copy, or the one problem of a ConvLaunch1 in the kernarg
+// segment at static offsets); only fields the first loads do NOT need are read from it, and only after those loads have been issued.
 template <bool MASK, int NWV, bool LDSX>    // NWV waves per workgroup split K inside the workgroup
-__global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunch L, const int mtiles, const int ntiles,
-                                                                 const int per_xcd, const int total) {
-  extern __shared__ __attribute__((aligned(16))) float red_raw[];
+__device__ __forceinline__ void splitk_tile(float* const red_raw, const SkTile S, const ConvProb& P, const int L_L, const int64_t slab_stride,
+                                            unsigned long long* const dbg, const unsigned long long ts0) {
   float (*red)[32][33] = reinterpret_cast<float (*)[32][33]>(red_raw);   // [NWV][32][33]; LDSX: aliases the X tile (barrier between)
-  // XCD-aware placement: consecutive virtual ids (which share a weight slice) land on the same XCD
-  const int bid = blockIdx.x;
-  if (bid >= per_xcd * 8) {                                         // spare workgroups: the next launch's weights into this XCD's L2
-    prefetch_tail(L.pf, (unsigned)bid, (unsigned)(bid - per_xcd * 8), threadIdx.x, 64 * NWV);
-    return;
-  }
-  unsigned long long ts0 = 0, ts1 = 0, ts2 = 0;                    // timeline stamps (tools/timeline.py; L.dbg is null in the product)
-  if (L.dbg) ts0 = __builtin_amdgcn_s_memtime();
-  const int v = (bid & 7) * per_xcd + (bid >> 3);
-  if (v >= total) return;
-  int rem = v;
-  const int nt = rem % ntiles; rem /= ntiles;
-  const int z = rem % L.ksplit; rem /= L.ksplit;
-  const int mt = rem % mtiles; rem /= mtiles;
-  const int b = rem % L.B; rem /= L.B;
-  // The problem descriptor BY VALUE: every field's scalar load is issued here, together (one kernarg round trip).  Through a
-  // reference the loads sat at their first uses — ~15 dependent s_load / s_waitcnt pairs spread over the prologue (ISA of round 2)
-  // in front of the first global load of a kernel whose whole life is ~14k cycles.
-  const ConvProb P = L.p[rem];
+  unsigned long long ts1 = 0, ts2 = 0;                              // timeline stamps (tools/timeline.py; dbg is null in the product)
+  const int nt = S.nt, z = S.z, mt = S.mt, b = S.b;
   const int m0 = mt * 32, t0 = nt * 32;
-  if (m0 >= P.cout_pad) return;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: keeps everything derived from it in SGPRs
   const int l31 = lane & 31, lh = lane >> 5;
-  // problem fields hoisted into registers (P lives in the kernarg segment)
-  const int k = P.k, dil = P.dil, cin = P.cin;
-  int Lin = P.Lin;
-  if (L.lens) {
-    const int64_t lv = L.lens[b] * L.len_mul;
-    Lin = lv < Lin ? (int)lv : Lin;
-  }
-  const int groups = P.cin_pad / 8;
-  const float in_scale = P.in_scale, slope = P.slope;
-  const bool pre_lrelu = P.pre_act == PRE_LRELU;
-  const float* const xp = P.x[0] + (int64_t)b * P.x_bstride;       // wave-uniform bases, 32-bit byte offsets per lane
-  const float* const mp = MASK ? P.in_mask + (int64_t)b * P.in_mask_bstride : nullptr;
-  const float* const wp = P.w;
-  const unsigned x_rs4 = 4u * (unsigned)P.x_rstride;
+  const int k = S.k, dil = S.dil, cin = S.cin, Lin = S.Lin;
+  const int groups = S.cin_pad / 8;
+  const float* const xp = S.xp;                                     // wave-uniform bases, 32-bit byte offsets per lane
+  const float* const mp = MASK ? S.mp : nullptr;
+  const float* const wp = S.wp;
+  const unsigned x_rs4 = 4u * (unsigned)S.x_rstride;
   const unsigned w_tap = 1024u;                                      // bytes between consecutive taps of one group
   const unsigned w_unit = w_tap * (unsigned)k;                      // bytes between consecutive channel groups
   const unsigned w_lane = 16u * (unsigned)(lh * 32 + l31) + (unsigned)mt * (unsigned)groups * w_unit;   // this m-tile's stream
   // channel groups of this (slice z, wave wid): contiguous range, balanced
   // (32-bit: groups * slices < 2^31; the 64-bit form was three ~130-instruction software divisions in the prologue)
-  const unsigned nsl = (unsigned)(L.ksplit * NWV), sl = (unsigned)(z * NWV + wid);
+  const unsigned nsl = (unsigned)(S.ksplit * NWV), sl = (unsigned)(z * NWV + wid);
   const int g0 = (int)(((unsigned)groups * sl) / nsl), g1 = (int)(((unsigned)groups * (sl + 1u)) / nsl);
   const int U = (g1 - g0) * k;                   // units of (group, tap) = 4 MFMAs each
 
@@ -439,10 +423,11 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
 #pragma unroll
   for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc2[r] = 0.f; }
 
-  const int tcol = t0 + l31 - P.pad_left;
+  const int tcol = t0 + l31 - S.pad_left;
   f32x4 ar[SK_PD];
   float br[SK_PD][4];
-  float mr[SK_PD], vmr[SK_PD];                    // raw mask value / validity*in_scale of the unit's column
+  float mr[SK_PD];                                // raw mask value of the unit's column
+  bool vmr[SK_PD];                                // its validity (in_scale, a field of P, meets it at the use: nothing here waits for P)
 
   // Loads are UNCONDITIONAL (also past the last unit: clamped to a valid address, result unused) and nothing here reads a
   // loaded value, so the compiler's vmcnt bookkeeping is exact and the ring really keeps SK_PD units in flight; padding
@@ -469,7 +454,7 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
     const int t = tcol + lj * dil;
     const bool tok = t >= 0 && t < Lin;
     const unsigned tcl = 4u * (unsigned)(t < 0 ? 0 : (t >= Lin ? Lin - 1 : t));
-    vmr[slot] = tok ? in_scale : 0.f;
+    vmr[slot] = tok;
     mr[slot] = MASK ? ld_off(mp, tcl) : 1.f;
     unsigned ro = goff;
 #pragma unroll
@@ -482,15 +467,50 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
     if (++lj == k) { lj = 0; joff = 0; ++lg; goff = group_off(lg); woff = weight_off(lg); }
   };
 
-  // ---- epilogue operands first: every ConvProb field into a register (reading P.* after the first global store re-loads it
+  // ---- the first global loads, from S alone: the LDSX form's X tile (row rr = wid + NWV*i of the tile is channel 8*G0 + rr; lane =
+  // column) and mask value, then the ring's first SK_PD units.  Nothing up to the sched_barrier below reads a field of P, so in the
+  // head form these loads leave before the wave first waits for the kernarg segment.
+  const int G0 = (int)(((unsigned)groups * (unsigned)(z * NWV)) / nsl);
+  float* const Xs = red_raw;
+  float xv[LDSX ? SK_RPW : 1];
+  float mval = 1.f;
+  bool xtok = false;
+  if (LDSX) {
+    const int XW = 32 + (k - 1) * dil;
+    const int t = t0 - S.pad_left + lane;
+    xtok = lane < XW && t >= 0 && t < Lin;
+    const unsigned tcl = 4u * (unsigned)(t < 0 ? 0 : (t >= Lin ? Lin - 1 : t));
+    // the mask value is loaded UNCONDITIONALLY (clamped address) and only used after the X loads are in flight: inside the
+    // `tok ? ... : 0` select it was a load + s_waitcnt vmcnt(0) of its own — one exposed memory round trip per masked launch
+    if (MASK) mval = ld_off(mp, tcl);
+#pragma unroll
+    for (int i = 0; i < SK_RPW; ++i) {
+      int row = 8 * G0 + wid + NWV * i;
+      row = row < cin ? row : cin - 1;
+      xv[i] = ld_off(xp, (unsigned)row * x_rs4 + tcl);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < SK_PD; ++i) { load_unit(i); __builtin_amdgcn_sched_barrier(0); }
+
+  // ---- epilogue operands next: every ConvProb field into a register (reading P.* after the first global store re-loads it
   // from the kernarg segment per row, see conv1d_mfma_kernel's epilogue), 32-bit element offsets from wave-uniform bases, and
   // the bias / residual values of this thread's output elements in flight BEFORE the main loop — loaded after the LDS reduction
   // they were one more exposed memory round trip in every one of the ~130 split-K launches of a batch-1 step
+  // (all of them requested HERE, together — one operand list, so nothing can be scheduled between them: one trip to the kernarg segment
+  // under the loads above.  Left to the compiler, the loads of a struct at static offsets sink to their first uses, behind the branches
+  // of the optional operands: four to five dependent s_load / s_waitcnt pairs in the ISA.)
+  asm volatile("" ::"s"(P.in_scale), "s"(P.slope), "s"(P.pre_act), "s"(P.cout), "s"(P.act), "s"(P.mask_pre), "s"(P.mask_post), "s"(P.res_mode),
+               "s"(P.out_rstride), "s"(P.out_tstride), "s"(P.out_toff), "s"(P.out), "s"(P.out_bstride), "s"(P.res), "s"(P.res_bstride),
+               "s"(P.bias), "s"(P.bias2), "s"(P.bias2_bstride), "s"(P.out_mask), "s"(P.out_mask_bstride), "s"(P.omax), "s"(L_L),
+               "s"(slab_stride), "s"(dbg));
+  const float in_scale = P.in_scale, slope = P.slope;
+  const bool pre_lrelu = P.pre_act == PRE_LRELU;
   const int col = t0 + (tid & 31);
-  const bool colok = col < L.L;
+  const bool colok = col < L_L;
   const int cout = P.cout, act = P.act, mask_pre = P.mask_pre, mask_post = P.mask_post, res_mode = P.res_mode;
   const unsigned o_rs = (unsigned)P.out_rstride, o_ts = (unsigned)P.out_tstride, o_to = (unsigned)P.out_toff;
-  float* const outb = P.out + (int64_t)z * L.slab_stride + (int64_t)b * P.out_bstride;
+  float* const outb = P.out + (int64_t)z * slab_stride + (int64_t)b * P.out_bstride;
   const float* const resb = (res_mode != RES_NONE && z == 0) ? P.res + (int64_t)b * P.res_bstride : nullptr;
   const float* const biasp = z == 0 ? P.bias : nullptr;
   const float* const bias2p = (z == 0 && P.bias2) ? P.bias2 + (int64_t)b * P.bias2_bstride : nullptr;
@@ -508,27 +528,11 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
     b2v[i] = bias2p ? bias2p[row] : 0.f;          // summed in the epilogue: an add here makes the load wait for itself
     rvv[i] = resb ? ld_off(resb, 4u * ((unsigned)row * o_rs + coff)) : 0.f;
   }
-  // ---- LDSX: stage the workgroup's X tile.  Row rr = wid + NWV*i of the tile is channel 8*G0 + rr; lane = column.
-  const int G0 = (int)(((unsigned)groups * (unsigned)(z * NWV)) / nsl);
-  float* const Xs = red_raw;
+  // ---- LDSX: stage the workgroup's X tile (loaded above) with mask / pre-activation / in_scale applied
   if (LDSX) {
     const int G1 = (int)(((unsigned)groups * (unsigned)((z + 1) * NWV)) / nsl);
     const int nrows = 8 * (G1 - G0);
-    const int XW = 32 + (k - 1) * dil;
-    const int t = t0 - P.pad_left + lane;
-    const bool tok = lane < XW && t >= 0 && t < Lin;
-    const unsigned tcl = 4u * (unsigned)(t < 0 ? 0 : (t >= Lin ? Lin - 1 : t));
-    // the mask value is loaded UNCONDITIONALLY (clamped address) and only used after the X loads are in flight: inside the
-    // `tok ? ... : 0` select it was a load + s_waitcnt vmcnt(0) of its own — one exposed memory round trip per masked launch
-    const float mval = MASK ? ld_off(mp, tcl) : 1.f;
-    float xv[SK_RPW];
-#pragma unroll
-    for (int i = 0; i < SK_RPW; ++i) {
-      int row = 8 * G0 + wid + NWV * i;
-      row = row < cin ? row : cin - 1;
-      xv[i] = ld_off(xp, (unsigned)row * x_rs4 + tcl);
-    }
-    const float cs = tok ? in_scale * mval : 0.f;
+    const float cs = xtok ? in_scale * mval : 0.f;
 #pragma unroll
     for (int i = 0; i < SK_RPW; ++i) {
       const int rr = wid + NWV * i;
@@ -540,10 +544,8 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
       Xs[rr * SK_XP + lane] = (rr < nrows && 8 * G0 + rr < cin) ? x * cs : 0.f;
     }
   }
-#pragma unroll
-  for (int i = 0; i < SK_PD; ++i) { load_unit(i); __builtin_amdgcn_sched_barrier(0); }
   if (LDSX) __syncthreads();
-  if (L.dbg) ts1 = __builtin_amdgcn_s_memtime();
+  if (dbg) ts1 = __builtin_amdgcn_s_memtime();
   if (LDSX) {
     // units run (group, tap) in the order the ring was loaded; the next unit's B operands are read while this unit's MFMAs run
     int ug = g0, uj = 0;
@@ -580,7 +582,8 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
     for (int i = 0; i < SK_PD; ++i) {
       if (u0 + i < U) {
         float bq[4];
-        const float cs = MASK ? vmr[i] * mr[i] : vmr[i];
+        const float vs = vmr[i] ? in_scale : 0.f;
+        const float cs = MASK ? vs * mr[i] : vs;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float x = br[i][q];
@@ -598,7 +601,7 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
     }
   }
 
-  if (L.dbg) ts2 = __builtin_amdgcn_s_memtime();
+  if (dbg) ts2 = __builtin_amdgcn_s_memtime();
   // reduce the waves' partial tiles through LDS
 #pragma unroll
   for (int r = 0; r < 16; ++r) red[wid][(r & 3) + 8 * (r >> 2) + 4 * lh][l31] = acc[r] + acc2[r];
@@ -652,11 +655,75 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
     }
     if (omaxp) x3_publish(omaxp, 0u, vmx, lane);    // ksplit == 1 only (host): max |v| of the stored tensor, see conv1d_mfma_kernel
   }
-  if (L.dbg && tid == 0) {
+  if (dbg && tid == 0) {
     __builtin_amdgcn_s_waitcnt(0);
-    unsigned long long* d = L.dbg + 8ull * blockIdx.x;
+    unsigned long long* d = dbg + 8ull * blockIdx.x;
     timeline_record(d, ts0, ts1, ts2, U);
   }
+}
+
+// the generic form: any number of problems, any batch, `lens`
+template <bool MASK, int NWV, bool LDSX>
+__global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunch L, const int mtiles, const int ntiles,
+                                                                 const int per_xcd, const int total) {
+  extern __shared__ __attribute__((aligned(16))) float red_raw[];
+  // XCD-aware placement: consecutive virtual ids (which share a weight slice) land on the same XCD
+  const int bid = blockIdx.x;
+  if (bid >= per_xcd * 8) {                                         // spare workgroups: the next launch's weights into this XCD's L2
+    prefetch_tail(L.pf, (unsigned)bid, (unsigned)(bid - per_xcd * 8), threadIdx.x, 64 * NWV);
+    return;
+  }
+  unsigned long long ts0 = 0;
+  if (L.dbg) ts0 = __builtin_amdgcn_s_memtime();
+  const int v = (bid & 7) * per_xcd + (bid >> 3);
+  if (v >= total) return;
+  int rem = v;
+  SkTile S;
+  S.nt = rem % ntiles; rem /= ntiles;
+  S.z = rem % L.ksplit; rem /= L.ksplit;
+  S.mt = rem % mtiles; rem /= mtiles;
+  S.b = rem % L.B; rem /= L.B;
+  S.ksplit = L.ksplit;
+  // The problem descriptor BY VALUE: every field's scalar load is issued here, together (one kernarg round trip behind the one that
+  // brought `rem`'s operands).  Through a reference the loads sat at their first uses — ~15 dependent s_load / s_waitcnt pairs spread
+  // over the prologue (ISA of round 2) in front of the first global load of a kernel whose whole life is ~14k cycles.
+  const ConvProb P = L.p[rem];
+  if (S.mt * 32 >= P.cout_pad) return;
+  S.Lin = P.Lin;
+  if (L.lens) {
+    const int64_t lv = L.lens[S.b] * L.len_mul;
+    S.Lin = lv < S.Lin ? (int)lv : S.Lin;
+  }
+  S.xp = P.x[0] + (int64_t)S.b * P.x_bstride;
+  S.mp = MASK ? P.in_mask + (int64_t)S.b * P.in_mask_bstride : nullptr;
+  S.wp = P.w;
+  S.x_rstride = P.x_rstride; S.k = P.k; S.dil = P.dil; S.pad_left = P.pad_left; S.cin = P.cin; S.cin_pad = P.cin_pad;
+  splitk_tile<MASK, NWV, LDSX>(red_raw, S, P, L.L, L.slab_stride, L.dbg, ts0);
+}
+
+// The head form (bv2_kernels.h SkHead / ConvLaunch1): one problem, B = 1, no `lens`, no prefetch tail.  The 13 leading scalar dwords are
+// preloaded into SGPRs, so the tile is decoded and the first loads are addressed without a trip to the kernarg segment; the struct's
+// fields are at static offsets.  mtiles = cout_pad / 32 here (one problem), so every row tile is inside the problem.
+template <bool MASK, int NWV, bool LDSX>
+__global__ void __launch_bounds__(64 * NWV) conv1d_splitk1_kernel(const float* const x, const float* const w, const float* const in_mask,
+                                                                  const int x_rstride, const int Lin, const int ntiles, const int per_xcd,
+                                                                  const int total, const unsigned pk0, const unsigned pk1,
+                                                                  const ConvLaunch1 L) {
+  extern __shared__ __attribute__((aligned(16))) float red_raw[];
+  const int bid = blockIdx.x;
+  const unsigned long long ts0 = __builtin_amdgcn_s_memtime();     // unconditional: `if (L.dbg)` would wait for the struct first
+  const int v = (bid & 7) * per_xcd + (bid >> 3);
+  if (v >= total) return;
+  const SkSmall q = sk_head_unpack(pk0, pk1);
+  int rem = v;
+  SkTile S;
+  S.nt = rem % ntiles; rem /= ntiles;
+  S.z = rem % q.ksplit; rem /= q.ksplit;
+  S.mt = rem;
+  S.b = 0; S.ksplit = q.ksplit;
+  S.xp = x; S.mp = in_mask; S.wp = w;
+  S.x_rstride = x_rstride; S.Lin = Lin; S.k = q.k; S.dil = q.dil; S.pad_left = q.pad_left; S.cin = q.cin; S.cin_pad = q.cin_pad;
+  splitk_tile<MASK, NWV, LDSX>(red_raw, S, L.p, L.L, L.slab_stride, L.dbg, ts0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -799,6 +866,22 @@ static void launch_splitk_nw(hipStream_t stream, const ConvLaunch& L, int nw, di
   size_t lds = sizeof(float) * (size_t)nw * 32 * 33;
   if (LDSX) lds = sizeof(float) * (size_t)nw * SK_RPW * SK_XP;     // every wave stores its SK_RPW rows unconditionally (>= the reduce buffer)
   (void)stage_rows;
+  SkHead h;
+  if (nw <= 8 && sk_head_pack(L, ntiles, per_xcd, total, &h)) {     // the head form where the launch fits it (16 waves: a tuning value only)
+    const ConvLaunch1 L1{L.p[0], L.L, L.slab_stride, L.dbg};
+    if (nw == 8) {
+      auto kern = conv1d_splitk1_kernel<MASK, 8, LDSX>;
+      ensure_dyn_lds((const void*)kern, lds);
+      hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, h.x, h.w, h.in_mask, h.x_rstride, h.Lin, h.ntiles, h.per_xcd, h.total,
+                         h.pk0, h.pk1, L1);
+    } else {
+      auto kern = conv1d_splitk1_kernel<MASK, 4, LDSX>;
+      ensure_dyn_lds((const void*)kern, lds);
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, h.x, h.w, h.in_mask, h.x_rstride, h.Lin, h.ntiles, h.per_xcd, h.total,
+                         h.pk0, h.pk1, L1);
+    }
+    return;
+  }
   if (nw == 16) {
     auto kern = conv1d_splitk_kernel<MASK, 16, LDSX>;
     ensure_dyn_lds((const void*)kern, lds);

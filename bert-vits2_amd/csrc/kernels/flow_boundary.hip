@@ -26,8 +26,12 @@ constexpr int FB_G = 32;          // row groups (threads along channels)
 }  // namespace
 
 // CPT = C / 32 channels per thread in the LayerNorm part; C1 = post's output channels = pre's input channels (C / 2)
+// What a workgroup needs in front of its first global loads (its share of W_post, the LayerNorm's slabs): the generic kernel fills it
+// from FbArgs, the head form from its leading scalar arguments.
+struct FbHead { const float* post_w; const float* a; int64_t slab_stride; int T; };
+
 template <int CPT, int NSLAB>
-__global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
+__device__ __forceinline__ void flow_boundary_tile(const FbHead Hd, const FbArgs& A) {
   constexpr int C = CPT * FB_G, C1 = C / 2, R1 = C1 / FB_G;     // R1 = post rows per thread (3), CPT = pre rows per thread (6)
   static_assert(C % 64 == 0 && C1 % 32 == 0 && C1 % 8 == 0, "whole 32-row tiles, whole 8-channel groups");
   constexpr int WV4 = C * C1 / 4;                  // float4 of one weight matrix (both are C x C1 elements)
@@ -39,18 +43,18 @@ __global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
   __shared__ float x1s[C1][FB_TT];                 // updated x1 (masked): pre's input
   f32x4 wreg[WPT];
   {
-    const f32x4* wg = reinterpret_cast<const f32x4*>(A.post_w) + threadIdx.x;
+    const f32x4* wg = reinterpret_cast<const f32x4*>(Hd.post_w) + threadIdx.x;
 #pragma unroll
     for (int i = 0; i < WPT; ++i) wreg[i] = wg[i * 256];
   }
   const int tx = threadIdx.x & (FB_TT - 1), ty = threadIdx.x >> 3;
   const int b = blockIdx.y;
   const int t = blockIdx.x * FB_TT + tx;
-  const bool tok = t < A.T;
-  const int tcl = tok ? t : A.T - 1;
-  const int T = A.T;
+  const int T = Hd.T;
+  const bool tok = t < T;
+  const int tcl = tok ? t : T - 1;
   const int64_t base = (int64_t)b * C * T;
-  const float* ap = A.a + base;
+  const float* ap = Hd.a + base;
 
   // ---- LayerNorm-2 (layernorm_kernel MODE 0, no residual / speaker vector): slab sum, two-pass statistics
   float v[CPT];
@@ -60,8 +64,9 @@ __global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
     for (int i = 0; i < CPT; ++i) {
       const int off = (ty + i * FB_G) * T + tcl;
 #pragma unroll
-      for (int sl = 0; sl < NSLAB; ++sl) xs[i][sl] = ap[(int64_t)sl * A.slab_stride + off];
+      for (int sl = 0; sl < NSLAB; ++sl) xs[i][sl] = ap[(int64_t)sl * Hd.slab_stride + off];
     }
+    __builtin_amdgcn_sched_barrier(0);             // the head form: everything above is addressed from preloaded SGPRs, and leaves first
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
       float x = xs[i][0];
@@ -172,6 +177,19 @@ __global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
   }
 }
 
+template <int CPT, int NSLAB>
+__global__ void __launch_bounds__(256) flow_boundary_kernel(const FbArgs A) {
+  flow_boundary_tile<CPT, NSLAB>(FbHead{A.post_w, A.a, A.slab_stride, A.T}, A);
+}
+
+// The head form (batch 1 only, as the other head forms: layernorm.hip launch_ln_form): the 7 leading scalar dwords are preloaded into SGPRs at wave launch, so the W_post share and the slabs are requested
+// without a trip to the kernarg segment; A's other fields follow at static offsets.
+template <int CPT, int NSLAB>
+__global__ void __launch_bounds__(256) flow_boundary_head_kernel(const float* const post_w, const float* const a, const int64_t slab_stride,
+                                                                 const int T, const FbArgs A) {
+  flow_boundary_tile<CPT, NSLAB>(FbHead{post_w, a, slab_stride, T}, A);
+}
+
 bool flow_boundary_supported(const FbArgs& a) {
   if (a.C != 192 || a.C1 * 2 != a.C || a.T < 1 || a.B < 1 || !a.a || !a.mask || !a.gamma || !a.beta || !a.x1 || !a.x1_out || !a.post_w || !a.post_b) return false;
   if (a.nslab != 1 && a.nslab != 2 && a.nslab != 4 && a.nslab != 8) return false;
@@ -186,9 +204,15 @@ int launch_flow_boundary(hipStream_t stream, const FbArgs& a) {
   constexpr size_t lds = (size_t)2 * 192 * 96 * 4;   // both weight matrices
 #define FB_LAUNCH(NS)                                                                                              \
   {                                                                                                                \
-    auto kern = flow_boundary_kernel<6, NS>;                                                                       \
-    ensure_dyn_lds((const void*)kern, lds);                                                                        \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);                                                     \
+    if (!a.no_head && a.B == 1) {                                                                                  \
+      auto kern = flow_boundary_head_kernel<6, NS>;                                                                \
+      ensure_dyn_lds((const void*)kern, lds);                                                                      \
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a.post_w, a.a, a.slab_stride, a.T, a);                \
+    } else {                                                                                                       \
+      auto kern = flow_boundary_kernel<6, NS>;                                                                     \
+      ensure_dyn_lds((const void*)kern, lds);                                                                      \
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);                                                   \
+    }                                                                                                              \
   }
   switch (a.nslab) {
     case 1: FB_LAUNCH(1) break;

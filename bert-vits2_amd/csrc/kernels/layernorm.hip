@@ -20,29 +20,34 @@ namespace bv2 {
 constexpr int LN_TT = 8;       // time steps per workgroup
 constexpr int LN_G = 32;       // channel groups (threads along C)
 
-template <int CPT, int NSLAB, int MODE, bool GUARD, int KS = 0>   // CPT channels per thread; GUARD: C < CPT*LN_G allowed; KS > 0: weighted slabs, KS key ranges per head
-__global__ void __launch_bounds__(256) layernorm_kernel(const LnArgs A) {
+// What a workgroup needs in front of its first global loads (the slabs, the residual, the key ranges' (max, sum) pairs): the generic
+// kernel fills it from LnArgs, the head form from its leading scalar arguments.
+struct LnHead { const float* a; const float* add; const float* ml; int64_t slab_stride; int C, T; };
+
+// Every field of A the tile reads behind its first loads, requested together (one operand list: nothing can be scheduled between them) — one
+// trip to the kernarg segment under those loads.  Left to the compiler the loads of a struct at static offsets sink to their first uses,
+// behind the branches of the optional operands: four dependent s_load / s_waitcnt pairs in the ISA.
+#define LN_FETCH_ARGS()                                                                                                                   \
+  asm volatile("" ::"s"(A.bias), "s"(A.gamma), "s"(A.beta), "s"(A.eps), "s"(A.post_gelu), "s"(A.res), "s"(A.vec), "s"(A.vec_bstride),      \
+               "s"(A.mask), "s"(A.out), "s"(A.out2), "s"(A.vec2), "s"(A.vec2_bstride))
+
+// One tile of LN_TT time steps of batch item b.  Of A only fields the first loads do NOT need are read, after those loads have been issued.
+template <int CPT, int NSLAB, int MODE, bool GUARD, int KS>   // CPT channels per thread; GUARD: C < CPT*LN_G allowed; KS > 0: weighted slabs, KS key ranges per head
+__device__ __forceinline__ void layernorm_tile(const LnHead Hd, const LnArgs& A, const int b, const int tile) {
   __shared__ float red[2][4][LN_TT];               // [pass][wave][time step]
   const int tx = threadIdx.x & (LN_TT - 1), ty = threadIdx.x >> 3;
-  int b = blockIdx.y, tile = blockIdx.x;
-  if (A.xcd_b && !xcd_decode(blockIdx.x, A.xcd_per, A.B, b, tile)) return;   // batch item -> XCD affinity (bv2_kernels.h)
-  if (!A.xcd_b && A.pf.ptr) {                                                // B == 1: tiles padded to a multiple of 8, then PF_BLOCKS spare workgroups
-    const unsigned nt8 = ((unsigned)(A.T + LN_TT - 1) / LN_TT + 7u) & ~7u;
-    if (blockIdx.x >= nt8) { prefetch_tail(A.pf, blockIdx.x, blockIdx.x - nt8, threadIdx.x, 256); return; }
-    if (tile * LN_TT >= A.T) return;
-  }
+  const int C = Hd.C, T = Hd.T;
   const int t = tile * LN_TT + tx;
-  const bool tok = t < A.T;
-  const int tcl = tok ? t : A.T - 1;
-  const int C = A.C, T = A.T;
+  const bool tok = t < T;
+  const int tcl = tok ? t : T - 1;
   const int64_t base = (int64_t)b * C * T;
-  const float* ap = A.a + base;
+  const float* ap = Hd.a + base;
 
   float v[CPT];
   if constexpr (MODE == 0 && KS > 0) {
     // key-split attention (kernels/attention.hip): slab h*ks + r carries head h's output over key range r, normalised over that range
     // only, already behind conv_o; the flash-decoding merge weights come from the ranges' (max, sum) pairs of this column
-    const float* mlp = A.ml + (int64_t)b * NSLAB * 2 * T + tcl;
+    const float* mlp = Hd.ml + (int64_t)b * NSLAB * 2 * T + tcl;
     float mm[NSLAB], ll[NSLAB], w[NSLAB];
 #pragma unroll
     for (int sl = 0; sl < NSLAB; ++sl) { mm[sl] = mlp[(int64_t)sl * 2 * T]; ll[sl] = mlp[(int64_t)sl * 2 * T + T]; }
@@ -53,8 +58,10 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const LnArgs A) {
       if (GUARD) c = c < C ? c : C - 1;
       const int off = c * T + tcl;
 #pragma unroll
-      for (int sl = 0; sl < NSLAB; ++sl) xs[i][sl] = ap[(int64_t)sl * A.slab_stride + off];
+      for (int sl = 0; sl < NSLAB; ++sl) xs[i][sl] = ap[(int64_t)sl * Hd.slab_stride + off];
     }
+    __builtin_amdgcn_sched_barrier(0);             // the loads above are addressed from the head alone, and leave first
+    LN_FETCH_ARGS();
 #pragma unroll
     for (int h0 = 0; h0 < NSLAB; h0 += KS) {        // h0 = first slab of a head
       float M = mm[h0];
@@ -76,8 +83,8 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const LnArgs A) {
       for (int sl = 0; sl < NSLAB; ++sl) x += w[sl] * xs[i][sl];
       v[i] = x;
     }
-    if (A.add) {
-      const float* dp = A.add + base;
+    if (Hd.add) {
+      const float* dp = Hd.add + base;
 #pragma unroll
       for (int i = 0; i < CPT; ++i) {
         int c = ty + i * LN_G;
@@ -90,17 +97,19 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const LnArgs A) {
     // issued the loads in batches of 16 with a full s_waitcnt between them (ISA of round 2: 3 serial round trips for 8 slabs, a 4th
     // for the residual) — most of this kernel's life, which is one memory latency otherwise
     float xs[CPT][NSLAB], ad[CPT];
-    const float* dp = (A.add ? A.add : A.a) + base;         // no residual: any valid address, result unused
+    const float* dp = (Hd.add ? Hd.add : Hd.a) + base;      // no residual: any valid address, result unused
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
       int c = ty + i * LN_G;
       if (GUARD) c = c < C ? c : C - 1;
       const int off = c * T + tcl;
 #pragma unroll
-      for (int sl = 0; sl < NSLAB; ++sl) xs[i][sl] = ap[(int64_t)sl * A.slab_stride + off];
+      for (int sl = 0; sl < NSLAB; ++sl) xs[i][sl] = ap[(int64_t)sl * Hd.slab_stride + off];
       ad[i] = dp[off];
     }
-    const bool has_add = A.add != nullptr;
+    __builtin_amdgcn_sched_barrier(0);             // the loads above are addressed from the head alone, and leave first
+    LN_FETCH_ARGS();
+    const bool has_add = Hd.add != nullptr;
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
       float x = xs[i][0];
@@ -186,25 +195,59 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const LnArgs A) {
   }
 }
 
+// the generic form: every mode, batch item -> XCD affinity, prefetch tail
+template <int CPT, int NSLAB, int MODE, bool GUARD, int KS = 0>
+__global__ void __launch_bounds__(256) layernorm_kernel(const LnArgs A) {
+  int b = blockIdx.y, tile = blockIdx.x;
+  if (A.xcd_b && !xcd_decode(blockIdx.x, A.xcd_per, A.B, b, tile)) return;   // batch item -> XCD affinity (bv2_kernels.h)
+  if (!A.xcd_b && A.pf.ptr) {                                                // B == 1: tiles padded to a multiple of 8, then PF_BLOCKS spare workgroups
+    const unsigned nt8 = ((unsigned)(A.T + LN_TT - 1) / LN_TT + 7u) & ~7u;
+    if (blockIdx.x >= nt8) { prefetch_tail(A.pf, blockIdx.x, blockIdx.x - nt8, threadIdx.x, 256); return; }
+    if (tile * LN_TT >= A.T) return;
+  }
+  layernorm_tile<CPT, NSLAB, MODE, GUARD, KS>(LnHead{A.a, A.add, A.ml, A.slab_stride, A.C, A.T}, A, b, tile);
+}
+
+// The head form (batch 1, mode 0, no prefetch tail): the 10 leading scalar dwords are preloaded into SGPRs at wave launch, so
+// the slab / residual / (max, sum) loads are addressed without a trip to the kernarg segment; A's other fields follow at static offsets.
+template <int CPT, int NSLAB, bool GUARD, int KS = 0>
+__global__ void __launch_bounds__(256) layernorm_head_kernel(const float* const a, const float* const add, const float* const ml,
+                                                             const int64_t slab_stride, const int C, const int T, const LnArgs A) {
+  layernorm_tile<CPT, NSLAB, 0, GUARD, KS>(LnHead{a, add, ml, slab_stride, C, T}, A, (int)blockIdx.y, (int)blockIdx.x);
+}
+
+template <int CPT, int NSLAB, int MODE, bool GUARD, int KS = 0>
+static void launch_ln_form(hipStream_t stream, const LnArgs& a, dim3 grid) {
+  if constexpr (MODE == 0) {
+    // batch 1 only: there the launch is one wave of workgroups and its life is the latency chain the head shortens; a batch fills the chip and
+    // keeps the generic kernel.  (The launcher, below, has cleared pf where there is no tail.)
+    if (!a.no_head && a.B == 1 && !a.xcd_b && !a.pf.ptr) {
+      hipLaunchKernelGGL((layernorm_head_kernel<CPT, NSLAB, GUARD, KS>), grid, dim3(256), 0, stream, a.a, a.add, a.ml, a.slab_stride, a.C, a.T, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((layernorm_kernel<CPT, NSLAB, MODE, GUARD, KS>), grid, dim3(256), 0, stream, a);
+}
+
 template <int CPT, bool GUARD>
 static void launch_ln_cfg(hipStream_t stream, const LnArgs& a, dim3 grid) {
-  if (a.mode != 0) { hipLaunchKernelGGL((layernorm_kernel<CPT, 1, 1, GUARD>), grid, dim3(256), 0, stream, a); return; }
+  if (a.mode != 0) { launch_ln_form<CPT, 1, 1, GUARD>(stream, a, grid); return; }
   if (a.ml) {                                      // nslab = heads x key ranges
-    if (a.nslab == 8 && a.ml_ks == 4) hipLaunchKernelGGL((layernorm_kernel<CPT, 8, 0, GUARD, 4>), grid, dim3(256), 0, stream, a);
-    else if (a.nslab == 8) hipLaunchKernelGGL((layernorm_kernel<CPT, 8, 0, GUARD, 2>), grid, dim3(256), 0, stream, a);
-    else if (a.ml_ks == 4) hipLaunchKernelGGL((layernorm_kernel<CPT, 4, 0, GUARD, 4>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((layernorm_kernel<CPT, 4, 0, GUARD, 2>), grid, dim3(256), 0, stream, a);
+    if (a.nslab == 8 && a.ml_ks == 4) launch_ln_form<CPT, 8, 0, GUARD, 4>(stream, a, grid);
+    else if (a.nslab == 8) launch_ln_form<CPT, 8, 0, GUARD, 2>(stream, a, grid);
+    else if (a.ml_ks == 4) launch_ln_form<CPT, 4, 0, GUARD, 4>(stream, a, grid);
+    else launch_ln_form<CPT, 4, 0, GUARD, 2>(stream, a, grid);
     return;
   }
   switch (a.nslab) {
-    case 2: hipLaunchKernelGGL((layernorm_kernel<CPT, 2, 0, GUARD>), grid, dim3(256), 0, stream, a); break;
-    case 3: hipLaunchKernelGGL((layernorm_kernel<CPT, 3, 0, GUARD>), grid, dim3(256), 0, stream, a); break;   // 3 / 5 / 6 / 7: one slab per head of the
-    case 4: hipLaunchKernelGGL((layernorm_kernel<CPT, 4, 0, GUARD>), grid, dim3(256), 0, stream, a); break;   // fused attention + conv_o with n_heads off the powers of two
-    case 5: hipLaunchKernelGGL((layernorm_kernel<CPT, 5, 0, GUARD>), grid, dim3(256), 0, stream, a); break;
-    case 6: hipLaunchKernelGGL((layernorm_kernel<CPT, 6, 0, GUARD>), grid, dim3(256), 0, stream, a); break;
-    case 7: hipLaunchKernelGGL((layernorm_kernel<CPT, 7, 0, GUARD>), grid, dim3(256), 0, stream, a); break;
-    case 8: hipLaunchKernelGGL((layernorm_kernel<CPT, 8, 0, GUARD>), grid, dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL((layernorm_kernel<CPT, 1, 0, GUARD>), grid, dim3(256), 0, stream, a); break;
+    case 2: launch_ln_form<CPT, 2, 0, GUARD>(stream, a, grid); break;
+    case 3: launch_ln_form<CPT, 3, 0, GUARD>(stream, a, grid); break;   // 3 / 5 / 6 / 7: one slab per head of the
+    case 4: launch_ln_form<CPT, 4, 0, GUARD>(stream, a, grid); break;   // fused attention + conv_o with n_heads off the powers of two
+    case 5: launch_ln_form<CPT, 5, 0, GUARD>(stream, a, grid); break;
+    case 6: launch_ln_form<CPT, 6, 0, GUARD>(stream, a, grid); break;
+    case 7: launch_ln_form<CPT, 7, 0, GUARD>(stream, a, grid); break;
+    case 8: launch_ln_form<CPT, 8, 0, GUARD>(stream, a, grid); break;
+    default: launch_ln_form<CPT, 1, 0, GUARD>(stream, a, grid); break;
   }
 }
 
@@ -230,5 +273,7 @@ int launch_layernorm(hipStream_t stream, const LnArgs& a) {
   else launch_ln_cfg<8, true>(stream, ax, grid);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+#undef LN_FETCH_ARGS
 
 }  // namespace bv2

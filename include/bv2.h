@@ -749,6 +749,10 @@ void bv2_graph_destroy(bv2_graph* graph);
  *   "lean_durations"  default 1: phase A runs only the duration predictor the mix can see (bv2_encode_out); 0: both, always
  *   "phase_b_front"   default 1: the head of phase B (length regulation, prior sampling, attn path, speaker GEMVs, the fp32 Generator's
  *                     x3 slot words) is one launch; 0: five launches.  Bit-identical either way
+ *   "kernarg_head"    default 1: the launches of the batch-1 chain — one-problem split-K convs, mode-0 LayerNorms, the fp32 attention with the
+ *                     fused conv_o, the flow boundary — pass what a workgroup needs for its first global loads as leading scalar kernel
+ *                     arguments (preloaded into SGPRs at wave launch) in front of the argument struct; 0: the generic kernels (struct
+ *                     first).  Bit-identical either way
  * Captured graphs keep whatever was selected when they were recorded. */
 int bv2_set_option(bv2_handle* h, const char* key, int value);
 

@@ -249,6 +249,13 @@ int bv2_test_conv_post_cl(void* stream, const void* x0, const void* x1, const vo
 
 /* tuning experiments (tools/kbench.py): force the split-K wave count / C_in chunk / tile-count target of the fp32 conv; 0 = default */
 void bv2_test_set_tuning(int splitk_waves, int force_ck, long tile_target);
+/* bv2_set_option("kernarg_head") for the launch entries of this header, which have no handle (bv2_test_conv1d, bv2_test_conv_multi,
+ * bv2_test_layernorm*, bv2_test_attention*, bv2_test_flow_boundary): 1 (default) = the head form where a launch fits it, 0 = the generic kernels */
+void bv2_test_set_kernarg_head(int on);
+/* Host only: would a one-problem (nprob = 1) split-K launch with these values take the head form?  1: yes, and out6 = {k, dil, pad_left,
+ * ksplit, cin, cin_pad} as the kernel unpacks them from the head's two packed dwords; 0: it falls back to the generic kernel (a value does not
+ * fit its packed field — 8 bits for k / dil / pad_left / ksplit, 16 for cin / cin_pad — or B != 1, `lens` set, nprob != 1) */
+int bv2_test_splitk_head(int k, int dil, int pad_left, int ksplit, int cin, int cin_pad, int B, int has_lens, int nprob, int32_t* out6);
 /* conv_x6.hip: forced tile id (9 / 11, see bv2_kernels.h TILE_X6_*) per C_out class (multiple of 256 / of 128 / other); the last argument is unused */
 void bv2_test_set_x6_tuning(int t256, int t128, int t64, int ck);
 /* workgroups per CU hipOccupancyMaxActiveBlocksPerMultiprocessor grants the conv_x6 variants {128x64, 128x64 + loader waves, 64x128, 32x256} */

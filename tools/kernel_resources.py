@@ -11,10 +11,14 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KDIR = os.path.join(ROOT, "bert-vits2_amd", "csrc", "kernels")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage"]
+# the build's own code generation flags (bert-vits2_amd/build.py FLAGS), to assembly: the kernel descriptors in it carry what the remarks do
+# not say — how many leading scalar argument dwords the wave finds preloaded in SGPRs (`pre`; 0 = the first argument is a by-value struct)
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-kernarg-preload-count=16", "-x", "hip", "--cuda-device-only",
+         "-S", "-Rpass-analysis=kernel-resource-usage"]
 # variants that are only reachable through tuning hooks / shapes no accepted model has (16-wave split-K, the NI = 2 bf16 tile): their
 # spills cannot reach the hot path.  (Round 6: head dim 128 left this list — its long-sequence form runs on four waves and does not spill.)
 ALLOWED_SCRATCH = ("conv1d_splitk_kernelILb1ELi16E", "conv1d_splitk_kernelILb0ELi16E",
@@ -22,7 +26,14 @@ ALLOWED_SCRATCH = ("conv1d_splitk_kernelILb1ELi16E", "conv1d_splitk_kernelILb0EL
 
 
 def table(path):
-    r = subprocess.run(["hipcc"] + FLAGS + [path, "-o", os.devnull], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    with tempfile.NamedTemporaryFile(suffix=".s") as asm:
+        r = subprocess.run(["hipcc"] + FLAGS + [path, "-o", asm.name], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        preload, kern = {}, None
+        for line in open(asm.name):
+            if line.lstrip().startswith(".amdhsa_kernel "):
+                kern = line.split()[1]
+            elif kern and ".amdhsa_user_sgpr_kernarg_preload_length" in line:
+                preload[kern] = int(line.split()[-1])
     rows, cur = [], None
     for line in r.stdout.splitlines():
         m = re.search(r"remark:\s+Function Name: (\S+)", line)
@@ -33,6 +44,8 @@ def table(path):
         m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
+    for k in rows:
+        k["preload"] = preload.get(k["name"], 0)
     return rows, r.returncode
 
 
@@ -60,7 +73,7 @@ def main():
                     bad.append(k["name"])
             if not check or scratch:
                 print(f"{os.path.basename(f):22s} {short[:70]:70s} vgpr {k.get('VGPRs', 0):3d} agpr {k.get('AGPRs', 0):3d} sgpr {k.get('TotalSGPRs', 0):3d} "
-                      f"scratch {scratch:4d} occ {k.get('Occupancy', 0)} lds {k.get('LDS Size', 0)}{flag}")
+                      f"scratch {scratch:4d} occ {k.get('Occupancy', 0)} lds {k.get('LDS Size', 0)} pre {k['preload']:2d}{flag}")
     if check and bad:
         print("kernels with a scratch segment on the default path:", *bad, sep="\n  ")
         sys.exit(1)
