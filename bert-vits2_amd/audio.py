@@ -7,7 +7,8 @@ below is that step: samples at the model's sampling rate go in (fp32 in [-1, 1],
 out.  A recording at another rate goes through ``resample`` first (the reference resamples offline with librosa, resample.py): a polyphase
 Kaiser-windowed sinc on the device (``bv2_resample``, kernels/resample.hip), the same call that brings synthesised audio to the rate a
 consumer wants.  ``loudness`` / ``normalize_loudness`` measure integrated loudness (ITU-R BS.1770-4, mono) and bring audio to a target level
-on the device (``bv2_loudness_*``, kernels/loudness.hip).  Not done here: decoding of audio files.
+on the device (``bv2_loudness_*``, kernels/loudness.hip).  ``assemble`` joins pieces that lie in several tensors, each under its level
+rule, and the pauses between them into one buffer per document (``bv2_assemble``, kernels/assemble.hip).  Not done here: decoding of audio files.
 
 Nothing in here computes: the filterbank comes from ``bv2_mel_basis`` and the resampler's table from ``bv2_resample_taps`` (fp64 on the
 host, rounded to fp32), everything else runs in the two launches of ``bv2_spectrogram`` / the one of ``bv2_resample`` / the four of
@@ -17,7 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -541,6 +542,152 @@ def normalize_loudness(wav, wav_lengths=None, rate: Optional[int] = None, target
 def loudness_info(m: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return {"lufs": m["lufs"], "gain_db": 20.0 * torch.log10(m["gain"].to(torch.float64)), "gain": m["gain"], "peak": m["peak"],
             "limited": (m["flags"] & L.LOUDNESS_LIMITED) != 0, "silent": (m["flags"] & L.LOUDNESS_SILENT) != 0}
+
+
+# ---- documents (include/bv2.h bv2_assemble) ------------------------------------------------------------------------------------------------
+LEVELS = {"none": L.LEVEL_NONE, "piece": L.LEVEL_PIECE_PEAK, "group": L.LEVEL_GROUP_PEAK, "gain": L.LEVEL_GAIN}
+
+
+@dataclass(frozen=True)
+class Piece:
+    """Row ``row`` of ``sources[source]``: its first ``lengths[source][row] * hop`` samples (at most the row's S)."""
+    source: int
+    row: int
+    group: int = 0
+    doc: int = 0
+
+
+@dataclass(frozen=True)
+class Silence:
+    samples: int
+    doc: int = 0
+
+
+def pause_samples(rate: int, seconds: float) -> int:
+    """``int(rate * seconds)``: the reference's pause (webui.py:171, 191), at ``rate`` instead of its hardcoded 44100."""
+    return int(int(rate) * float(seconds))
+
+
+def paragraph_pause_samples(rate: int, interval_between_para: float, interval_between_sent: float) -> int:
+    """What follows a paragraph's last sentence IN ADDITION to the sentence pause (webui.py:193-197): ``int(rate * (para - sent))`` where
+    that difference is positive, else nothing."""
+    extra = float(interval_between_para) - float(interval_between_sent)
+    return int(int(rate) * extra) if extra > 0 else 0
+
+
+def assemble_config(level: str, as_pcm16: bool, max_capacity: int = 0) -> L.AssembleConfig:
+    if level not in LEVELS:
+        raise ValueError(f"level must be one of {sorted(LEVELS)}, got {level!r}")
+    c = L.AssembleConfig()
+    c.struct_bytes = C.sizeof(L.AssembleConfig)
+    c.output_format, c.level, c.max_capacity = (L.WAV_I16 if as_pcm16 else L.WAV_F32), LEVELS[level], int(max_capacity)
+    return c
+
+
+def assemble_plan(table, n_groups: int, n_docs: int, level: str = "piece", as_pcm16: bool = True) -> Tuple[List[int], int]:
+    """``bv2_assemble_plan`` over a host table (a ctypes array of ``lib.AssembleSegment``): ``(capacity per document, tile)``.
+    ``ValueError`` with the library's message for a table it refuses."""
+    lib = L.load()
+    cap = (C.c_int64 * max(int(n_docs), 1))()
+    tile = C.c_int32()
+    if lib.bv2_assemble_plan(C.byref(assemble_config(level, as_pcm16)), table, len(table), int(n_groups), int(n_docs), cap, C.byref(tile)) != 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return [int(v) for v in cap[:int(n_docs)]], int(tile.value)
+
+
+def _segment_table(sources, lengths, segments):
+    """The host table of ``assemble`` and its ``(n_groups, n_docs)``; every check that needs no device is made here."""
+    if len(segments) < 1:
+        raise ValueError("assemble needs at least one segment")
+    if len(lengths) != len(sources):
+        raise ValueError("lengths takes one entry per source: a device int64 tensor [B], (tensor, hop), or None")
+    rows = []
+    for k, (w, ln) in enumerate(zip(sources, lengths)):
+        if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dim() != 2 or w.dtype != torch.float32 or w.shape[1] < 1 or \
+                (w.shape[1] > 1 and w.stride(1) != 1):
+            raise ValueError(f"sources[{k}] must be a device float32 tensor [B, S] with unit sample stride")
+        t, hop = ln if isinstance(ln, tuple) else (ln, 1)
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1
+                              or t.shape[0] != w.shape[0] or (t.shape[0] > 1 and t.stride(0) != 1)):
+            raise ValueError(f"lengths[{k}] must be a dense device int64 tensor [{w.shape[0]}]")
+        if int(hop) < 1:
+            raise ValueError(f"lengths[{k}]: hop must be >= 1, got {hop}")
+        rows.append((w, t, int(hop)))
+    table = (L.AssembleSegment * len(segments))()
+    n_groups = n_docs = 1
+    for i, (sg, e) in enumerate(zip(segments, table)):
+        if isinstance(sg, Piece):
+            if not 0 <= sg.source < len(rows):
+                raise ValueError(f"segment {i}: source {sg.source} is outside [0, {len(rows)})")
+            w, t, hop = rows[sg.source]
+            if not 0 <= sg.row < w.shape[0]:
+                raise ValueError(f"segment {i}: row {sg.row} is outside [0, {w.shape[0]})")
+            e.src = w.data_ptr() + 4 * sg.row * w.stride(0)
+            e.length = None if t is None else t.data_ptr() + 8 * sg.row
+            e.samples, e.hop, e.group = int(w.shape[1]), hop, int(sg.group)
+        elif isinstance(sg, Silence):
+            e.src, e.length, e.samples, e.hop, e.group = None, None, int(sg.samples), 1, 0
+        else:
+            raise ValueError(f"segment {i} must be an audio.Piece or an audio.Silence")
+        e.doc = int(sg.doc)
+        n_groups, n_docs = max(n_groups, e.group + 1), max(n_docs, e.doc + 1)
+    return table, n_groups, n_docs
+
+
+@torch.no_grad()
+def assemble(sources: Sequence[torch.Tensor], lengths: Sequence, segments: Sequence, *, level: str = "piece", gain: Optional[torch.Tensor] = None,
+             as_pcm16: bool = True, out: Optional[Sequence[torch.Tensor]] = None
+             ) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """``bv2_assemble`` on the current stream.  ``sources[k]`` [B_k, S_k] device fp32; ``lengths[k]`` a device int64 tensor [B_k] (samples),
+    ``(tensor, hop)`` (the tensor counts frames of ``hop`` samples) or ``None`` (every row whole).  ``segments``: ``Piece(source, row,
+    group, doc)`` / ``Silence(samples, doc)`` in timeline order, documents non-decreasing.  ``level``: ``"piece"`` (each piece under its own
+    peak, the reference), ``"group"`` (under its group's peak), ``"gain"`` (``x * gain[group]``, ``gain`` fp32 [n_groups] on the device or
+    ``None`` = 1) or ``"none"``; 16-bit PCM or fp32.  Returns ``(buffers, offsets, totals)`` on the device: one 1-D buffer per document of
+    its CAPACITY (the lengths live on the device: only the first ``totals[d]`` samples are written), ``offsets`` int64 [n_segments] (each
+    segment's start inside its document) and ``totals`` int64 [n_docs].  ``out``: the caller's buffers, one per document, at least its
+    capacity long.  Bad input raises ``ValueError`` before any device call."""
+    table, n_groups, n_docs = _segment_table(sources, lengths, segments)
+    capacity, _ = assemble_plan(table, n_groups, n_docs, level, as_pcm16)
+    if gain is not None:
+        if level != "gain":
+            raise ValueError("gain goes with level='gain'")
+        if not isinstance(gain, torch.Tensor) or not gain.is_cuda or gain.dtype != torch.float32 or gain.dim() != 1 or gain.shape[0] < n_groups \
+                or (gain.shape[0] > 1 and gain.stride(0) != 1):
+            raise ValueError(f"gain must be a dense device float32 tensor of at least n_groups = {n_groups} entries")
+    dev = sources[0].device if len(sources) else torch.device("cuda", torch.cuda.current_device())     # a timeline of pauses only
+    dtype = torch.int16 if as_pcm16 else torch.float32
+    if out is not None:
+        if len(out) != n_docs:
+            raise ValueError(f"out takes one buffer per document ({n_docs})")
+        for d, (b, cap) in enumerate(zip(out, capacity)):
+            if not isinstance(b, torch.Tensor) or not b.is_cuda or b.dtype != dtype or b.dim() != 1 or b.shape[0] < cap or \
+                    (b.shape[0] > 1 and b.stride(0) != 1):
+                raise ValueError(f"out[{d}] must be a dense 1-D device {dtype} tensor of at least {cap} samples")
+        buffers = list(out)
+    else:
+        buffers = [torch.empty(cap, dtype=dtype, device=dev) for cap in capacity]
+    lib = L.load()
+    cfg = assemble_config(level, as_pcm16, max(capacity))
+    n = len(table)
+    nws = lib.bv2_assemble_workspace_bytes(C.byref(cfg), n, n_groups, n_docs)
+    if nws < 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    # one upload: the table, then the documents' base pointers and capacities
+    tb = C.sizeof(L.AssembleSegment) * n
+    host = np.empty(tb + 16 * n_docs, np.uint8)
+    host[:tb] = np.frombuffer(table, np.uint8)
+    host[tb:].view(np.int64)[:] = [b.data_ptr() for b in buffers] + capacity
+    blob = torch.from_numpy(host).to(dev)
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n, dtype=torch.int64, device=dev)
+    totals = torch.empty(n_docs, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.bv2_assemble(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), C.c_void_p(blob.data_ptr()), n, n_groups,
+                              n_docs, _ptr(gain), C.c_void_p(blob.data_ptr() + tb), C.c_void_p(blob.data_ptr() + tb + 8 * n_docs),
+                              _ptr(offsets), _ptr(totals), _ptr(ws), ws.numel())
+    if rc != 0:
+        raise RuntimeError(f"bv2_assemble failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return buffers, offsets, totals
 
 
 def to_rate(wav, wav_lengths, sampling_rate: Optional[int], model_rate: int, params: StftParams, device):

@@ -1103,6 +1103,104 @@ int bv2_loudness_apply(bv2_stream stream, const bv2_loudness_config* cfg, const 
   } catch (...) { return fail("exception", -100); }
 }
 
+// ---- documents (kernels/assemble.hip) --------------------------------------------------------------------------
+static_assert(sizeof(bv2_assemble_segment) == sizeof(AssembleSegment) && offsetof(bv2_assemble_segment, samples) == offsetof(AssembleSegment, samples) &&
+              offsetof(bv2_assemble_segment, hop) == offsetof(AssembleSegment, hop) && offsetof(bv2_assemble_segment, doc) == offsetof(AssembleSegment, doc),
+              "bv2_assemble_segment and AssembleSegment are one layout");
+static_assert(BV2_LEVEL_NONE == AS_LEVEL_NONE && BV2_LEVEL_PIECE_PEAK == AS_LEVEL_PIECE_PEAK && BV2_LEVEL_GROUP_PEAK == AS_LEVEL_GROUP_PEAK &&
+              BV2_LEVEL_GAIN == AS_LEVEL_GAIN, "BV2_LEVEL_* and AS_LEVEL_* are one numbering");
+
+// the checks every bv2_assemble_* call shares: the config and the three counts
+static int assemble_check(const char* what, const bv2_assemble_config* c, int32_t n_segments, int32_t n_groups, int32_t n_docs) {
+  auto fail = [&](const std::string& m) { g_create_err = std::string(what) + ": " + m; return -1; };
+  if (!c) return fail("cfg is null");
+  if (c->struct_bytes != (int32_t)sizeof(bv2_assemble_config)) return fail("bv2_assemble_config.struct_bytes mismatch (ABI drift)");
+  if (c->output_format != BV2_WAV_F32 && c->output_format != BV2_WAV_I16) return fail("output_format must be BV2_WAV_F32 or BV2_WAV_I16");
+  if (c->level < BV2_LEVEL_NONE || c->level > BV2_LEVEL_GAIN) return fail("level must be one of BV2_LEVEL_*");
+  if (c->reserved != 0) return fail("bv2_assemble_config.reserved must be 0");
+  if (n_segments < 1 || n_segments > AS_MAX_SEGMENTS)
+    return fail("n_segments must be in [1, " + std::to_string(AS_MAX_SEGMENTS) + "], got " + std::to_string(n_segments));
+  if (n_groups < 1 || n_groups > n_segments) return fail("n_groups must be in [1, n_segments], got " + std::to_string(n_groups));
+  if (n_docs < 1 || n_docs > AS_MAX_DOCS) return fail("n_docs must be in [1, " + std::to_string(AS_MAX_DOCS) + "], got " + std::to_string(n_docs));
+  return 0;
+}
+
+struct AssembleWs { int64_t run, doc_base, doc_seg, peaks, total; };
+static AssembleWs assemble_ws(int32_t n_segments, int32_t n_docs) {
+  AssembleWs w;
+  w.run = 0;
+  w.doc_base = w.run + 8 * ((int64_t)n_segments + 1);
+  w.doc_seg = w.doc_base + 8 * (int64_t)n_docs;
+  w.peaks = w.doc_seg + 4 * (((int64_t)n_docs + 2) & ~(int64_t)1);
+  w.total = w.peaks + 4 * (int64_t)n_segments;
+  return w;
+}
+
+int bv2_assemble_plan(const bv2_assemble_config* cfg, const bv2_assemble_segment* seg, int32_t n_segments, int32_t n_groups, int32_t n_docs,
+                      int64_t* capacity, int32_t* tile) {
+  const char* what = "bv2_assemble_plan";
+  if (int rc = assemble_check(what, cfg, n_segments, n_groups, n_docs)) return rc;
+  auto fail = [&](int i, const std::string& m) { g_create_err = std::string(what) + ": segment " + std::to_string(i) + ": " + m; return -1; };
+  if (!seg || !capacity) { g_create_err = std::string(what) + ": host_segments and capacity must not be null"; return -1; }
+  try {
+    std::vector<int64_t> cap((size_t)n_docs, 0);
+    for (int i = 0; i < n_segments; ++i) {
+      const bv2_assemble_segment& s = seg[i];
+      if (s.group < 0 || s.group >= n_groups) return fail(i, "group " + std::to_string(s.group) + " is outside [0, n_groups = " + std::to_string(n_groups) + ")");
+      if (s.doc < 0 || s.doc >= n_docs) return fail(i, "doc " + std::to_string(s.doc) + " is outside [0, n_docs = " + std::to_string(n_docs) + ")");
+      if (i && s.doc < seg[i - 1].doc) return fail(i, "document ids must be non-decreasing along the table (" + std::to_string(s.doc) + " follows " + std::to_string(seg[i - 1].doc) + ")");
+      if (s.hop < 1) return fail(i, "hop must be >= 1, got " + std::to_string(s.hop));
+      if (s.samples < 0) return fail(i, "samples must not be negative, got " + std::to_string(s.samples));
+      if (s.samples > AS_MAX_SAMPLES) return fail(i, "samples must be at most 2^40");
+      if (s.reserved != 0) return fail(i, "reserved must be 0");
+      if (s.src && s.samples < 1) return fail(i, "a piece needs a cap: samples >= 1 (the row's S)");
+      if (!s.src && s.length) return fail(i, "a length counter without src: a piece needs src, silence takes no counter");
+      cap[(size_t)s.doc] += s.samples;
+    }
+    for (int d = 0; d < n_docs; ++d)
+      if (cap[(size_t)d] > AS_MAX_CAPACITY) { g_create_err = std::string(what) + ": document " + std::to_string(d) + " exceeds the capacity of 2^42 samples"; return -1; }
+    for (int d = 0; d < n_docs; ++d) capacity[d] = cap[(size_t)d];
+    if (tile) *tile = AS_TILE;
+    return 0;
+  } catch (...) { g_create_err = std::string(what) + ": exception"; return -100; }
+}
+
+int64_t bv2_assemble_workspace_bytes(const bv2_assemble_config* cfg, int32_t n_segments, int32_t n_groups, int32_t n_docs) {
+  if (assemble_check("bv2_assemble_workspace_bytes", cfg, n_segments, n_groups, n_docs)) return -1;
+  return assemble_ws(n_segments, n_docs).total + 8;              // + 8: the call aligns the pointer it is given
+}
+
+int bv2_assemble(bv2_stream stream, const bv2_assemble_config* cfg, const bv2_assemble_segment* dev_segments, int32_t n_segments,
+                 int32_t n_groups, int32_t n_docs, const float* gain, void* const* dst_bases, const int64_t* capacity, int64_t* offsets,
+                 int64_t* totals, void* workspace, int64_t workspace_bytes) {
+  const char* what = "bv2_assemble";
+  if (int rc = assemble_check(what, cfg, n_segments, n_groups, n_docs)) return rc;
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (!dev_segments || !dst_bases || !capacity || !offsets || !totals)
+    return fail("dev_segments, dst_bases, capacity, offsets and totals must not be null", -1);
+  if (gain && cfg->level != BV2_LEVEL_GAIN) return fail("a gain table goes with BV2_LEVEL_GAIN only", -1);
+  if (cfg->max_capacity < 0 || cfg->max_capacity > AS_MAX_CAPACITY)
+    return fail("cfg->max_capacity must be the largest capacity of bv2_assemble_plan, in [0, 2^42]", -1);
+  const AssembleWs lay = assemble_ws(n_segments, n_docs);
+  if (!workspace || workspace_bytes < lay.total) return fail("workspace too small (bv2_assemble_workspace_bytes)", -5);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  if (const uintptr_t mis = reinterpret_cast<uintptr_t>(ws) & 7u) {
+    if (workspace_bytes < lay.total + 8) return fail("workspace too small (bv2_assemble_workspace_bytes)", -5);
+    ws += 8 - mis;
+  }
+  try {
+    AssembleArgs a;
+    a.seg = reinterpret_cast<const AssembleSegment*>(dev_segments);
+    a.n_segments = n_segments; a.n_groups = n_groups; a.n_docs = n_docs;
+    a.pcm16 = cfg->output_format == BV2_WAV_I16 ? 1 : 0; a.level = cfg->level; a.max_capacity = cfg->max_capacity;
+    a.gain = gain; a.dst_bases = dst_bases; a.capacity = capacity; a.offsets = offsets; a.totals = totals;
+    a.run = reinterpret_cast<int64_t*>(ws + lay.run); a.doc_base = reinterpret_cast<int64_t*>(ws + lay.doc_base);
+    a.doc_seg = reinterpret_cast<int*>(ws + lay.doc_seg); a.peaks = reinterpret_cast<unsigned*>(ws + lay.peaks);
+    if (launch_assemble(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
 // ---- forced alignment (kernels/align.hip) ----------------------------------------------------------------------
 int bv2_neg_cent(bv2_stream stream, int32_t B, int32_t inter, int32_t T, int32_t Ty, const float* z_p, const float* m_p,
                  const float* logs_p, const int64_t* x_lengths, const int64_t* y_lengths, float* neg_cent) {

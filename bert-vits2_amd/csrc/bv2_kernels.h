@@ -910,4 +910,26 @@ int launch_loudness_measure(hipStream_t stream, const LoudnessArgs& a);   // fou
 int launch_loudness_gate(hipStream_t stream, const LoudnessGateArgs& a);
 int launch_loudness_apply(hipStream_t stream, const LoudnessApplyArgs& a);
 
+// --- documents (kernels/assemble.hip): pieces and pauses joined into one buffer per document; layout, peaks, write ---
+constexpr int AS_THREADS = 256, AS_LAYOUT_THREADS = 1024;
+constexpr int AS_TILE = 4096;                        // destination samples per workgroup, both output formats (bv2_assemble_plan's tile)
+constexpr int AS_PEAK_TILES = 4;                     // tiles a workgroup of the peak launch walks
+constexpr int AS_MAX_SEGMENTS = 1 << 20, AS_MAX_DOCS = 65535;
+constexpr int64_t AS_MAX_SAMPLES = (int64_t)1 << 40; // per segment: 2^20 of them still sum inside int64
+constexpr int64_t AS_MAX_CAPACITY = (int64_t)1 << 42;   // per document: the write grid's x extent stays below 2^31
+constexpr int AS_LEVEL_NONE = 0, AS_LEVEL_PIECE_PEAK = 1, AS_LEVEL_GROUP_PEAK = 2, AS_LEVEL_GAIN = 3;   // include/bv2.h BV2_LEVEL_*
+struct AssembleSegment {                             // include/bv2.h bv2_assemble_segment, field for field
+  const float* src; const int64_t* length; int64_t samples; int32_t hop, group, doc, reserved;
+};
+struct AssembleArgs {
+  const AssembleSegment* seg; int n_segments, n_groups, n_docs;   // DEVICE table
+  int pcm16, level;
+  int64_t max_capacity;                              // HOST: the largest capacity, sizes the grid
+  const float* gain;                                 // [n_groups] or null = 1 (AS_LEVEL_GAIN)
+  void* const* dst_bases; const int64_t* capacity;   // [n_docs] each, DEVICE
+  int64_t *offsets, *totals;                         // [n_segments], [n_docs]
+  int64_t* run; int64_t* doc_base; int* doc_seg; unsigned* peaks;   // workspace: [n_segments + 1], [n_docs], [n_docs + 1], [n_segments]
+};
+int launch_assemble(hipStream_t stream, const AssembleArgs& a);   // three launches (two without a peak mode)
+
 }  // namespace bv2

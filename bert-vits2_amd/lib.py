@@ -113,6 +113,21 @@ class LoudnessConfig(C.Structure):
 LOUDNESS_SILENT, LOUDNESS_LIMITED = 1, 2
 
 
+class AssembleSegment(C.Structure):
+    """include/bv2.h bv2_assemble_segment"""
+    _fields_ = [("src", C.c_void_p), ("length", C.c_void_p), ("samples", C.c_int64), ("hop", C.c_int32), ("group", C.c_int32),
+                ("doc", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AssembleConfig(C.Structure):
+    """include/bv2.h bv2_assemble_config"""
+    _fields_ = [("struct_bytes", C.c_int32), ("output_format", C.c_int32), ("level", C.c_int32), ("reserved", C.c_int32),
+                ("max_capacity", C.c_int64)]
+
+
+LEVEL_NONE, LEVEL_PIECE_PEAK, LEVEL_GROUP_PEAK, LEVEL_GAIN = 0, 1, 2, 3
+
+
 class ProfileRow(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -188,6 +203,10 @@ SYMBOLS = [
                                     C.c_double, _P, _P, _P, _P, C.c_int64]),
     ("bv2_loudness_apply", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P, _P,
                                      C.c_int64]),
+    ("bv2_assemble_plan", C.c_int, [C.POINTER(AssembleConfig), C.POINTER(AssembleSegment), C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("bv2_assemble_workspace_bytes", C.c_int64, [C.POINTER(AssembleConfig), C.c_int32, C.c_int32, C.c_int32]),
+    ("bv2_assemble", C.c_int, [_P, C.POINTER(AssembleConfig), _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64]),
     ("bv2_neg_cent", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("bv2_maximum_path_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     ("bv2_maximum_path", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int64]),

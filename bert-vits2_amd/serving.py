@@ -304,6 +304,159 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     return (results, levels) if return_levels else results
 
 
+DOCUMENT_LEVELS = ("piece", "paragraph", "document")
+
+
+def document_timeline(documents, rate: int, *, interval_between_sent=0.2, interval_between_para=1.0, cut_by_sent=True):
+    """The timeline of reference webui.py ``tts_split`` for ``documents`` (a document: a list of paragraphs; a paragraph: a list of
+    sentences; a sentence: an ``Utterance`` or a list of them, joined with no pause between).  Returns ``(utts, timeline)``: the pieces in
+    reading order and, per document, a list of ``("piece", index into utts, paragraph number over the whole call)`` / ``("silence",
+    samples)``.  With ``cut_by_sent`` ``int(rate * interval_between_sent)`` samples follow every sentence and ``int(rate *
+    (interval_between_para - interval_between_sent))`` more a paragraph's last, where that difference is positive; without it a paragraph's
+    pieces follow each other directly and ``int(rate * interval_between_para)`` samples follow the paragraph.  The pause behind the last
+    paragraph is kept, as the reference keeps it."""
+    from . import audio
+    for v in (interval_between_sent, interval_between_para):
+        if not (math.isfinite(float(v)) and float(v) >= 0):
+            raise ValueError("interval_between_sent and interval_between_para must be finite and not negative")
+    sent = audio.pause_samples(rate, interval_between_sent)
+    extra = audio.paragraph_pause_samples(rate, interval_between_para, interval_between_sent)
+    para_only = audio.pause_samples(rate, interval_between_para)
+    utts, timeline, n_para = [], [], 0
+    if isinstance(documents, Utterance) or len(documents) < 1:
+        raise ValueError("documents must be a non-empty list of documents (lists of paragraphs)")
+    for d, doc in enumerate(documents):
+        if isinstance(doc, Utterance) or len(doc) < 1:
+            raise ValueError(f"document {d} must be a non-empty list of paragraphs")
+        line = []
+        for p, para in enumerate(doc):
+            if isinstance(para, Utterance) or len(para) < 1:
+                raise ValueError(f"document {d}, paragraph {p} must be a non-empty list of sentences")
+            for s, sentence in enumerate(para):
+                pieces = [sentence] if isinstance(sentence, Utterance) else list(sentence)
+                if not pieces or not all(isinstance(u, Utterance) for u in pieces):
+                    raise ValueError(f"document {d}, paragraph {p}, sentence {s} must be an Utterance or a non-empty list of them")
+                for u in pieces:
+                    line.append(("piece", len(utts), n_para))
+                    utts.append(u)
+                if cut_by_sent:
+                    line.append(("silence", sent))
+            if not cut_by_sent:
+                line.append(("silence", para_only))
+            elif extra > 0:
+                line.append(("silence", extra))
+            n_para += 1
+        timeline.append(line)
+    return utts, timeline
+
+
+@torch.no_grad()
+def synthesize_documents(model, documents, *, interval_between_sent: float = 0.2, interval_between_para: float = 1.0,
+                         cut_by_sent: bool = True, level: str = "piece", target_lufs: Optional[float] = None,
+                         peak_ceiling_db: float = -1.0, as_pcm16: bool = True, output_rate: Optional[int] = None,
+                         return_offsets: bool = False, sdp_ratio=0.5, noise_scale=0.6, noise_scale_w=0.9, length_scale=1.0,
+                         max_batch: int = 32, max_pad_ratio: float = 1.25, noise: Optional[Sequence] = None,
+                         requests_in_flight: int = 1):
+    """Whole documents: what the reference's web UI does behind synthesis (webui.py ``tts_split`` / ``generate_audio``) on the device —
+    every piece levelled, a pause behind every sentence, a longer one behind every paragraph, everything joined — and ONE copy out per
+    document.  ``documents``: see ``document_timeline``; the defaults are the reference web UI's sliders (webui.py:477-490), pauses are
+    ``int(rate * seconds)`` at the output rate.  All pieces of all documents share the length buckets of ``synthesize`` (same kwargs:
+    controls, voices, seeds, ``output_rate``, ``requests_in_flight``); the waves and their lengths stay on the device, one
+    ``audio.assemble`` lays the documents out there (the lengths never reach the host before it), then the host reads the totals and the
+    offsets in one small copy and exactly ``totals[d]`` samples per document into pinned memory.
+    ``level``: ``"piece"`` — each piece under its own peak, ``(x / max|x|) * 32767`` truncated, the reference's document bit for bit
+    (``synthesize(as_pcm16=True)`` joined with zero pauses); ``"paragraph"`` / ``"document"`` — under the peak of its paragraph / document,
+    which keeps the level differences inside it.  ``target_lufs``: every document is measured as one programme (``synthesize``'s
+    ``loudness_groups``) and leaves at that loudness under ``peak_ceiling_db``: one gain per document, the fixed-gain 16-bit form; it
+    overrides ``level``.  ``as_pcm16=False``: fp32 (``x / peak``, or ``x * gain``).
+    Returns one 1-D array per document; with ``return_offsets`` ``(audio, offsets)``, ``offsets[d]`` a list of ``(start sample, length)``
+    per piece of document d in reading order — for subtitles and highlighting."""
+    from . import audio
+    if model.device.type != "cuda":
+        raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
+    if level not in DOCUMENT_LEVELS:
+        raise ValueError(f"level must be one of {DOCUMENT_LEVELS}, got {level!r}")
+    dev = model.device
+    output_rate = _output_rate(model, output_rate)
+    rate = int(output_rate if output_rate is not None else model.hp.sampling_rate)
+    utts, timeline = document_timeline(documents, rate, interval_between_sent=interval_between_sent,
+                                       interval_between_para=interval_between_para, cut_by_sent=cut_by_sent)
+    if noise is not None and any(u.seed is not None for u in utts):
+        raise ValueError("noise= (injected tensors) and Utterance(seed=...) exclude each other")
+    doc_of = [d for d, line in enumerate(timeline) for e in line if e[0] == "piece"]
+    loud = _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, doc_of if target_lufs is not None else None, False)
+    hop = model.hp.total_upsample if output_rate is None else 1
+    lanes = replicas(model, requests_in_flight) if requests_in_flight > 1 else [(model, None)]
+    call = dict(sdp_ratio=sdp_ratio, noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale)
+    per_item = any(getattr(u, k) is not None for u in utts for k in call)
+    gvec = speaker_vectors(model, utts)
+    if requests_in_flight > 1:
+        torch.cuda.current_stream(dev).synchronize()       # inputs prepared on the caller's stream are visible to the lanes
+    weights = None
+    if per_item and any(u.length_scale is not None for u in utts):
+        weights = [float(length_scale if u.length_scale is None else u.length_scale) for u in utts]
+    sources, lengths, where, events = [], [], {}, []
+    for bi, idx in enumerate(plan_batches([u.length for u in utts], max_batch, max_pad_ratio, weights)):
+        lane, lane_stream = lanes[bi % len(lanes)]
+        if per_item:
+            ctl = {k: torch.tensor([float(v if getattr(utts[i], k) is None else getattr(utts[i], k)) for i in idx],
+                                   dtype=torch.float32) for k, v in call.items()}
+        else:
+            ctl = call
+        with torch.cuda.stream(lane_stream) if lane_stream is not None else contextlib.nullcontext():
+            wave, y_len, lens = _bucket_wave(lane, utts, idx, dev, noise, gvec, output_rate, **ctl)
+            if loud is not None:
+                _hold_levels(loud, idx, wave, y_len * hop if lens is None else lens, y_len, dev)    # with the event _gate_held waits for
+            elif lane_stream is not None:
+                ev = torch.cuda.Event()
+                ev.record()
+                events.append(ev)
+        for r, i in enumerate(idx):
+            where[i] = (len(sources), r)
+        sources.append(wave)
+        lengths.append((y_len.contiguous(), hop))
+    main = torch.cuda.current_stream(dev)
+    gain = None
+    if loud is not None:
+        gain = _gate_held(loud, dev)[0]["gain"]             # one gain per document, on the caller's stream behind every bucket
+        mode = "gain"
+    else:
+        for ev in events:
+            main.wait_event(ev)
+        mode = "piece" if level == "piece" else "group"
+    segments, pieces = [], []
+    for d, line in enumerate(timeline):
+        rows = []
+        for e in line:
+            if e[0] == "piece":
+                k, r = where[e[1]]
+                group = d if (mode == "gain" or level == "document") else (e[2] if level == "paragraph" else 0)
+                rows.append(len(segments))
+                segments.append(audio.Piece(k, r, group, d))
+            else:
+                segments.append(audio.Silence(e[1], d))
+        pieces.append(rows)
+    buffers, offsets, totals = audio.assemble(sources, lengths, segments, level=mode, gain=gain, as_pcm16=as_pcm16)
+    n_docs = len(timeline)
+    small = torch.cat([totals, offsets])
+    host_small = torch.empty(small.shape, dtype=torch.int64, pin_memory=True)
+    host_small.copy_(small, non_blocking=True)
+    main.synchronize()                                     # the layout is known (and the audio written): now the host can size its copies
+    tot = [int(v) for v in host_small[:n_docs]]
+    off = [int(v) for v in host_small[n_docs:]]
+    hosts = []
+    for d in range(n_docs):
+        host = torch.empty(tot[d], dtype=buffers[d].dtype, pin_memory=True)
+        host.copy_(buffers[d][:tot[d]], non_blocking=True)
+        hosts.append(host)
+    main.synchronize()
+    results = [h.numpy().copy() for h in hosts]
+    if not return_offsets:
+        return results
+    ends = [[(off[s + 1] if s + 1 < len(off) and segments[s + 1].doc == d else tot[d]) for s in rows] for d, rows in enumerate(pieces)]
+    return results, [[(off[s], e - off[s]) for s, e in zip(rows, ends[d])] for d, rows in enumerate(pieces)]
+
+
 def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels) -> Optional[dict]:
     """The loudness arguments of ``synthesize``, checked before any work: ``None`` without a target."""
     if target_lufs is None:
@@ -325,10 +478,10 @@ def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness
     return dict(rate=rate, target=float(target_lufs), ceiling=float(peak_ceiling_db), ids=ids, held=[])
 
 
-def _level_groups(level, pending, as_pcm16, dev):
+def _gate_held(level, dev):
     """Groups that span buckets: every bucket has left its audio, block mean squares and peaks on the device (``level["held"]``).  One
-    gating launch over all of them on the caller's stream, ordered behind every bucket by its event; then, on each bucket's own stream
-    and behind the gate's event, one multiply and the bucket's copy."""
+    gating launch over all of them on the caller's stream, ordered behind every bucket by its event.  Returns the gate's outputs and the
+    group id of every held row, bucket after bucket."""
     from . import audio
     held = level["held"]
     main = torch.cuda.current_stream(dev)
@@ -342,6 +495,15 @@ def _level_groups(level, pending, as_pcm16, dev):
     n_groups = max(level["ids"]) + 1
     m = audio.loudness_gate(ms, torch.cat([h["lens"] for h in held]), S, torch.cat([h["peak"] for h in held]), level["rate"], groups,
                             n_groups, level["target"], level["ceiling"])
+    return m, groups
+
+
+def _level_groups(level, pending, as_pcm16, dev):
+    """``_gate_held``; then, on each bucket's own stream and behind the gate's event, one multiply and the bucket's copy."""
+    from . import audio
+    held = level["held"]
+    main = torch.cuda.current_stream(dev)
+    m, groups = _gate_held(level, dev)
     gated = torch.cuda.Event()
     gated.record(main)
     o = 0
@@ -383,22 +545,31 @@ def _output_rate(model, output_rate) -> Optional[int]:
     return int(output_rate)
 
 
-def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio, noise_scale, noise_scale_w, length_scale,
-                output_rate=None, level=None):
-    """One bucket on the CURRENT stream: collate, infer (exact lengths), optional resampling, optional levelling or PCM16, async D2H into
-    pinned memory.  The lengths that travel with it count frames, or samples after a resampling."""
+def _bucket_wave(model, utts, idx, dev, noise, gvec, output_rate, sdp_ratio, noise_scale, noise_scale_w, length_scale):
+    """One bucket's audio on the CURRENT stream, left on the device: collate, infer (exact lengths), optional resampling.  Returns ``(wave
+    [B, S], y_len, lens)``: ``y_len`` counts frames, or samples after a resampling; ``lens`` counts samples (``None`` at the model's rate:
+    ``y_len * hop``)."""
     batch, kw = _bucket_inputs(model, utts, idx, dev, noise, gvec)
     o, _attn, y_mask, _ = model.infer(batch["x"], batch["x_lengths"], batch["sid"], batch["tone"], batch["language"],
                                       batch["bert"], batch["ja_bert"], batch["en_bert"], sdp_ratio=sdp_ratio,
                                       noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale,
                                       want_attn=False, exact_lengths=True, **kw)
     y_len = model.last_encode["y_lengths"]             # int64 [B], already on the device (phase A output)
-    from . import audio as _audio
     if output_rate is None:
-        wave, lens = o[:, 0], None if level is None else y_len * model.hp.total_upsample
-    else:
-        wave, y_len = _audio.resample(o[:, 0], y_len * model.hp.total_upsample, model.hp.sampling_rate, output_rate)
-        lens = y_len
+        return o[:, 0], y_len, None
+    from . import audio as _audio
+    wave, y_len = _audio.resample(o[:, 0], y_len * model.hp.total_upsample, model.hp.sampling_rate, output_rate)
+    return wave, y_len, y_len
+
+
+def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio, noise_scale, noise_scale_w, length_scale,
+                output_rate=None, level=None):
+    """One bucket on the CURRENT stream: ``_bucket_wave``, optional levelling or PCM16, async D2H into pinned memory.  The lengths that
+    travel with it count frames, or samples after a resampling."""
+    wave, y_len, lens = _bucket_wave(model, utts, idx, dev, noise, gvec, output_rate, sdp_ratio, noise_scale, noise_scale_w, length_scale)
+    from . import audio as _audio
+    if lens is None and level is not None:
+        lens = y_len * model.hp.total_upsample
     if level is None:
         audio = pcm16(model, wave[:, None], y_len, hop=None if output_rate is None else 1) if as_pcm16 else wave
         _enqueue_copy(pending, idx, audio, y_len)
@@ -407,11 +578,17 @@ def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio
         audio = _audio.loudness_apply(wave, lens, level["rate"], m["gain"], None, as_pcm16)
         _enqueue_copy(pending, idx, audio, y_len, torch.stack([m["lufs"], m["gain"].double(), m["peak"].double(), m["flags"].double()]))
     else:                                              # groups may span buckets: energies and peaks wait on the device (_level_groups)
-        m = _audio.loudness_measure(wave, lens, level["rate"], gate=False)
-        ev = torch.cuda.Event()
-        ev.record()
-        level["held"].append(dict(idx=idx, wave=wave, lens=lens, y_len=y_len, block_ms=m["block_ms"], peak=m["peak"], ev=ev,
-                                  stream=torch.cuda.current_stream(dev)))
+        _hold_levels(level, idx, wave, lens, y_len, dev)
+
+
+def _hold_levels(level, idx, wave, lens, y_len, dev):
+    """A bucket of a grouped measurement: its block energies and peaks, and an event behind them, in ``level["held"]``."""
+    from . import audio as _audio
+    m = _audio.loudness_measure(wave, lens, level["rate"], gate=False)
+    ev = torch.cuda.Event()
+    ev.record()
+    level["held"].append(dict(idx=idx, wave=wave, lens=lens, y_len=y_len, block_ms=m["block_ms"], peak=m["peak"], ev=ev,
+                              stream=torch.cuda.current_stream(dev)))
 
 
 def _bucket_inputs(model, utts, idx, dev, noise, gvec):

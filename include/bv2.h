@@ -521,6 +521,71 @@ int bv2_loudness_apply(bv2_stream stream, const bv2_loudness_config* cfg, const 
                        int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, const float* gain, float* dst_f32, int16_t* dst_i16,
                        int64_t dst_bstride);
 
+/* ---- documents: sentences joined on the device with pauses, one buffer per document (handle-free; kernels/assemble.hip) --------
+ * What the reference's callers do on the host after synthesis (webui.py tts_split / generate_audio, hiyoriUI.py:319-349): every piece
+ * peak-normalised to 16 bit, a pause behind every sentence, a longer one behind every paragraph, everything concatenated.  tts_split
+ * normalises each paragraph a second time, in fp64; a non-silent piece already peaks at +-32767, and trunc(k / 32767.0 * 32767.0) == k for
+ * every integer k in [-32767, 32767], so that pass is the identity: the reference's document is each piece under its own peak by
+ * bv2_pcm16's rule, with zero-filled pauses between (a paragraph of silent pieces only, 0 / 0 there, is zeros here).
+ * The timeline is a caller-built table of SEGMENTS, a DEVICE array filled on the host and uploaded.  A segment is a PIECE (src != NULL:
+ * the device address of its first fp32 sample; `length` the device address of an int64 counter, `hop` what multiplies it, `samples` the
+ * cap — the row's S) or SILENCE (src == NULL: `samples` zeros; length must be NULL).  A piece has min(max(*length, 0) * hop, samples)
+ * samples (length == NULL: `samples` of them): the counters are read on the device when the call runs, so a timeline is laid out without
+ * the host ever knowing a length.  Every segment carries a level group and a document; document ids are non-decreasing along the table.
+ * Three launches on `stream`, no allocation, no host sync:
+ *   layout  offsets[i] = the start of segment i inside its document, totals[d] = the document's samples: an exclusive int64 scan per
+ *           document, integer arithmetic (the same bits in any order); a document without segments has total 0;
+ *   peaks   (the two peak modes only) max|x| per piece, or per level group over that group's pieces wherever they lie, as the bit
+ *           pattern of a non-negative float under an integer max: the order of arrival does not matter;
+ *   write   the grid runs over tiles of every document's CAPACITY (the host's upper bound: the sum of its caps and silences,
+ *           bv2_assemble_plan); a tile at or behind totals[d] returns without storing.  A workgroup finds the first segment that
+ *           reaches into its tile by binary search over the ends and walks from there; stores are 16 bytes per thread on the aligned body
+ *           of the destination, the source is loaded as 16 bytes where it shares that phase and as dwords otherwise.  Samples at or
+ *           behind totals[d] (and anything in front of dst_bases[d]) are NOT written; nor is anything at or behind capacity[d].
+ * Value rules, x a piece's sample; each is reproducible in numpy bit for bit (IEEE fp32 division and multiplication, no contraction):
+ *   BV2_LEVEL_PIECE_PEAK  pk = the piece's own max|x|:  fp32 x / pk,  16 bit (int16)(int)((x / pk) * 32767.f)       (bv2_pcm16's rule)
+ *   BV2_LEVEL_GROUP_PEAK  the same with pk the peak of the piece's group (a paragraph or a document keeps its inner level differences)
+ *   BV2_LEVEL_GAIN        v = x * gain[group], ONE fp32 multiply:  fp32 v,  16 bit trunc(clamp(v * 32767.0f, -32768, 32767))
+ *                         (bv2_loudness_apply's rule); gain == NULL: gain 1
+ *   BV2_LEVEL_NONE        BV2_LEVEL_GAIN with gain 1 (gain must be NULL)
+ * A piece or group whose peak is 0 comes out as zeros.  NaN samples: not specified, as in bv2_pcm16.  The value of a sample depends on
+ * the sample, its level and nothing else: not on the row, tensor, S or phase it is read from, nor on how groups are numbered.
+ * Envelope: 1 <= n_segments <= 1 048 576, 1 <= n_groups <= n_segments, 1 <= n_docs <= 65 535, hop >= 1, 0 <= samples <= 2^40 per
+ * segment (a piece: >= 1), a document's capacity <= 2^42; offsets and totals are int64.  Every argument is checked before anything
+ * touches the device: -1 with a message in bv2_last_error(NULL), -5 for a null or short workspace.  What lives on the device cannot be
+ * checked: the CALLER guarantees that dev_segments holds what bv2_assemble_plan saw and that dst_bases[d] has room for capacity[d] samples
+ * of the output format (ids are clamped into range on the device, so a table that differs can misplace samples but not leave the arrays). */
+enum { BV2_LEVEL_NONE = 0, BV2_LEVEL_PIECE_PEAK = 1, BV2_LEVEL_GROUP_PEAK = 2, BV2_LEVEL_GAIN = 3 };
+typedef struct bv2_assemble_segment {
+  const float* src;                /* a piece: DEVICE address of its first sample; NULL: silence */
+  const int64_t* length;           /* a piece: DEVICE address of its int64 counter, or NULL (= samples); silence: NULL */
+  int64_t samples;                 /* a piece: the cap (>= 1); silence: its length (>= 0) */
+  int32_t hop;                     /* >= 1; multiplies the counter */
+  int32_t group;                   /* level group, in [0, n_groups) */
+  int32_t doc;                     /* document, in [0, n_docs), non-decreasing along the table */
+  int32_t reserved;                /* 0 */
+} bv2_assemble_segment;
+typedef struct bv2_assemble_config {
+  int32_t struct_bytes;            /* = sizeof(bv2_assemble_config) */
+  int32_t output_format;           /* BV2_WAV_F32 / BV2_WAV_I16 */
+  int32_t level;                   /* BV2_LEVEL_* */
+  int32_t reserved;                /* 0 */
+  int64_t max_capacity;            /* bv2_assemble only: the largest capacity[d] bv2_assemble_plan returned — the HOST's size of the grid */
+} bv2_assemble_config;
+/* HOST: validates the host copy of the table (ids in range, documents non-decreasing, hop >= 1, samples >= 0, a piece has src and a cap,
+ * silence has no counter, reserved 0) and returns capacity[d] = the sum of document d's caps and silences (capacity [n_docs], HOST) and
+ * the tile: the destination samples one workgroup owns, counted from the 16-byte boundary at or in front of dst_bases[d].  tile may be NULL. */
+int bv2_assemble_plan(const bv2_assemble_config* cfg, const bv2_assemble_segment* host_segments, int32_t n_segments, int32_t n_groups,
+                      int32_t n_docs, int64_t* capacity, int32_t* tile);
+/* Bytes of DEVICE workspace of bv2_assemble. */
+int64_t bv2_assemble_workspace_bytes(const bv2_assemble_config* cfg, int32_t n_segments, int32_t n_groups, int32_t n_docs);
+/* dev_segments [n_segments], gain fp32 [n_groups] or NULL, dst_bases [n_docs] (one device pointer per document, fp32 or int16 by
+ * cfg->output_format, any alignment of the element size), capacity int64 [n_docs] (the plan's), offsets int64 [n_segments] and totals
+ * int64 [n_docs] (outputs): all DEVICE. */
+int bv2_assemble(bv2_stream stream, const bv2_assemble_config* cfg, const bv2_assemble_segment* dev_segments, int32_t n_segments,
+                 int32_t n_groups, int32_t n_docs, const float* gain, void* const* dst_bases, const int64_t* capacity, int64_t* offsets,
+                 int64_t* totals, void* workspace, int64_t workspace_bytes);
+
 /* ---- forced alignment: the reference's own aligner (handle-free; kernels/align.hip) --------------------------------------
  * SynthesizerTrn.forward() aligns a recording to its text with two steps that need no weights (models.py:960-991): the negative
  * cross-entropy between every latent frame z_p[:, y] of the recording and every symbol's prior N(m_p[:, x], exp(logs_p[:, x])), and
