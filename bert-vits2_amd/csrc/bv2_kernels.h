@@ -142,11 +142,11 @@ struct ConvLaunch {
 };
 
 // The split-K kernel's HEAD form (one problem, B = 1, no `lens`).  Everything a workgroup needs to decode its tile and to form the
-// addresses of its first global loads (X tile, mask row, weight ring) travels as LEADING SCALAR kernel arguments — 13 dwords, which
+// addresses of its first global loads (X tile, mask row, weight ring) travels as LEADING SCALAR kernel arguments — 14 dwords, which
 // gfx950 preloads into SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count=16; only leading scalars are eligible, a by-value
 // struct is a `byref` argument) — and the rest of the one problem follows in a ConvLaunch1 at static offsets: no computed index into
 // p[], and a kernarg segment of one ConvProb instead of BV2_MAX_PROBS.  The small fields are packed: pk0 = k | dil << 8 |
-// pad_left << 16 | ksplit << 24 (8 bits each), pk1 = cin | cin_pad << 16.
+// pad_left << 16 | ksplit << 24 (8 bits each), pk1 = cin | cin_pad << 16, pk2 = the block staging's 65536 / XW + 1 | rows per pass << 16.
 struct ConvLaunch1 {
   ConvProb p;
   int L; int64_t slab_stride; unsigned long long* dbg;
@@ -155,6 +155,7 @@ struct SkHead {
   const float* x; const float* w; const float* in_mask;
   int x_rstride, Lin, ntiles, per_xcd, total;          // the row tile is what remains of the virtual id: one problem, mtiles = cout_pad / 32
   unsigned pk0, pk1;
+  unsigned pk2 = 0;                                    // LDSX block staging (conv_mfma.hip SK_DUMP): 65536 / XW + 1 | rows per pass << 16; the launcher fills it
 };
 struct SkSmall { int k, dil, pad_left, ksplit, cin, cin_pad; };
 #if defined(__HIPCC__)
@@ -197,6 +198,9 @@ int launch_conv1d(hipStream_t stream, const ConvLaunch& L, int tile, const char*
 enum { PLACE_PLAIN = 0, PLACE_PER_XCD = 1, PLACE_SNAKE = 2 };
 void conv_note_placement(int place);
 int conv_last_placement();
+// how the last split-K launch staged its X tile: -1 = not at all (the register form), 0 = row per wave, 16 / 24 = block staging with that
+// many loads per thread (conv_mfma.hip SK_DUMP)
+int conv_last_splitk_stage();
 // fp32 conv on the bf16 matrix core (kernels/conv_x6.hip): every fp32 operand is the exact sum of three bf16 values
 // (v = h1 + h2 + h3, 8 + 8 + 8 significand bits), and the product is accumulated from the six largest of the nine cross terms
 // (w1x1, w1x2, w2x1, w1x3, w2x2, w3x1 — the three dropped ones are below 2^-23 of the product, the rounding of an fp32 multiply).

@@ -786,7 +786,12 @@ int launch_attention(hipStream_t stream, const AttnArgs& a) {
 // fused conv_o form only).
 int attention_pick_ksplit(int B, int H, int T, int max_slabs) {
   const int ntiles = (T + AK - 1) / AK;
-  if (ntiles <= 8 || H < 1 || (H & (H - 1))) return 1;
+  if (H < 1 || (H & (H - 1))) return 1;
+  // The exception: four key tiles at batch 1 (the text encoder at T = 97..128) — two heads x 8 query tiles are 16 workgroups on a 256-CU chip and
+  // the launch is one workgroup's life; on two key ranges it is 32 workgroups with two key tiles each and LayerNorm-1 merges four slabs.
+  // Kernel trace at T = 128: 12.13 -> 10.81 us per launch, LayerNorm-1 5.15 -> 5.20 (profiles/ab_splitk_stage.txt).
+  if (ntiles == 4 && B == 1 && H * 2 <= max_slabs && H * 2 <= 8) return 2;
+  if (ntiles <= 8) return 1;
   int ks = 1;
   auto wgs = [&](int k) {
     const int qt = attention_pick_qtile(B, H, T, 32, k, false);

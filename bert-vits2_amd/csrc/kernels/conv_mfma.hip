@@ -381,6 +381,13 @@ constexpr int SK_PD = 8;          // prefetch ring depth (units of 4 MFMAs)
 // of it the 5-fold re-read of X), their main loop at 3.7x the MFMA time.  Weights still stream global -> registers.
 constexpr int SK_XP = 64;         // staged tile width (floats): 32 + (k-1)*dil must fit
 constexpr int SK_RPW = 32;        // rows of the staged tile per wave at most
+// Block staging (EPT > 0, the head form): the row-per-wave staging below (lane = column, SK_RPW rows per wave, always) spends a
+// 64-lane load and a 64-lane ds_write on a row of XW = 34..44 columns, and 32 of each per lane on a tile of 96 x 34 / 256 = 13 elements
+// per thread.  Here the workgroup's 64*NWV threads cover RPP = 64*NWV / XW whole rows per pass — thread tid owns column tid % XW of
+// rows tid / XW + RPP*i — so a thread's column, its mask value, its clamped column offset and its validity are computed ONCE, as
+// before, and it issues ceil(rows / RPP) <= EPT loads and stores (the < XW threads past the last whole row carry nothing).  The one
+// division is a multiply by st_mul = 65536 / XW + 1 (exact for tid < 1024, XW <= 64); both come from the host in the head.
+constexpr int SK_DUMP = 1;        // one more tile row: where a block-staging store that carries nothing goes (never read)
 // What a workgroup needs in front of its first global loads: its tile (column tile nt, K slice z of ksplit, row tile mt, batch item
 // b), the bases of the X rows / mask row (already at batch item b) / packed weights, and the shape of the K loop.  The generic kernel
 // fills it from the problem it picked out of ConvLaunch::p, the head form from its leading scalar arguments (bv2_kernels.h SkHead).
@@ -388,11 +395,12 @@ struct SkTile {
   int nt, z, mt, b, ksplit;
   const float* xp; const float* mp; const float* wp;
   int x_rstride, Lin, k, dil, pad_left, cin, cin_pad;
+  unsigned st_mul; int st_rpp;      // block staging only (EPT > 0): 65536 / XW + 1 and 64*NWV / XW
 };
 
 // One 32 x 32 output tile of the split-K kernel.  P: the problem (a by-value copy, or the one problem of a ConvLaunch1 in the kernarg
 // segment at static offsets); only fields the first loads do NOT need are read from it, and only after those loads have been issued.
-template <bool MASK, int NWV, bool LDSX>    // NWV waves per workgroup split K inside the workgroup
+template <bool MASK, int NWV, bool LDSX, int EPT = 0>    // NWV waves per workgroup split K inside the workgroup; EPT: block staging
 __device__ __forceinline__ void splitk_tile(float* const red_raw, const SkTile S, const ConvProb& P, const int L_L, const int64_t slab_stride,
                                             unsigned long long* const dbg, const unsigned long long ts0) {
   float (*red)[32][33] = reinterpret_cast<float (*)[32][33]>(red_raw);   // [NWV][32][33]; LDSX: aliases the X tile (barrier between)
@@ -472,22 +480,35 @@ __device__ __forceinline__ void splitk_tile(float* const red_raw, const SkTile S
   // head form these loads leave before the wave first waits for the kernarg segment.
   const int G0 = (int)(((unsigned)groups * (unsigned)(z * NWV)) / nsl);
   float* const Xs = red_raw;
-  float xv[LDSX ? SK_RPW : 1];
+  constexpr int XN = LDSX ? (EPT ? EPT : SK_RPW) : 1;              // X loads (and tile stores) per thread
+  float xv[XN];
   float mval = 1.f;
   bool xtok = false;
+  const int sr0 = EPT ? (int)(((unsigned)tid * S.st_mul) >> 16) : 0;                 // block staging: this thread's first tile row ...
+  const int sc = EPT ? tid - sr0 * (32 + (k - 1) * dil) : lane;                      // ... and its column of the tile
   if (LDSX) {
     const int XW = 32 + (k - 1) * dil;
-    const int t = t0 - S.pad_left + lane;
-    xtok = lane < XW && t >= 0 && t < Lin;
+    const int t = t0 - S.pad_left + sc;
+    xtok = sc < XW && t >= 0 && t < Lin;
     const unsigned tcl = 4u * (unsigned)(t < 0 ? 0 : (t >= Lin ? Lin - 1 : t));
     // the mask value is loaded UNCONDITIONALLY (clamped address) and only used after the X loads are in flight: inside the
     // `tok ? ... : 0` select it was a load + s_waitcnt vmcnt(0) of its own — one exposed memory round trip per masked launch
     if (MASK) mval = ld_off(mp, tcl);
+    if constexpr (EPT > 0) {
+      int row = 8 * G0 + sr0;
 #pragma unroll
-    for (int i = 0; i < SK_RPW; ++i) {
-      int row = 8 * G0 + wid + NWV * i;
-      row = row < cin ? row : cin - 1;
-      xv[i] = ld_off(xp, (unsigned)row * x_rs4 + tcl);
+      for (int i = 0; i < EPT; ++i) {
+        const int rc = row < cin ? row : cin - 1;
+        xv[i] = ld_off(xp, (unsigned)rc * x_rs4 + tcl);
+        row += S.st_rpp;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < SK_RPW; ++i) {
+        int row = 8 * G0 + wid + NWV * i;
+        row = row < cin ? row : cin - 1;
+        xv[i] = ld_off(xp, (unsigned)row * x_rs4 + tcl);
+      }
     }
   }
 #pragma unroll
@@ -533,6 +554,21 @@ __device__ __forceinline__ void splitk_tile(float* const red_raw, const SkTile S
     const int G1 = (int)(((unsigned)groups * (unsigned)((z + 1) * NWV)) / nsl);
     const int nrows = 8 * (G1 - G0);
     const float cs = xtok ? in_scale * mval : 0.f;
+    if constexpr (EPT > 0) {
+      // as unconditional as below: a store that carries nothing (a row past this slice's, or a thread past the last whole row of a
+      // pass) goes to the dump row, by a select on the ADDRESS — no branch for the compiler to sink the row's load into
+      const bool mine = sr0 < S.st_rpp;
+      int rr = sr0;
+#pragma unroll
+      for (int i = 0; i < EPT; ++i) {
+        float x = xv[i];
+        const float xn = x * slope;
+        x = (pre_lrelu && x < 0.f) ? xn : x;
+        const bool ok = mine && rr < nrows;
+        Xs[(ok ? rr : 32 * NWV) * SK_XP + sc] = (ok && 8 * G0 + rr < cin) ? x * cs : 0.f;
+        rr += S.st_rpp;
+      }
+    } else
 #pragma unroll
     for (int i = 0; i < SK_RPW; ++i) {
       const int rr = wid + NWV * i;
@@ -698,16 +734,17 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk_kernel(const ConvLaunc
   S.mp = MASK ? P.in_mask + (int64_t)S.b * P.in_mask_bstride : nullptr;
   S.wp = P.w;
   S.x_rstride = P.x_rstride; S.k = P.k; S.dil = P.dil; S.pad_left = P.pad_left; S.cin = P.cin; S.cin_pad = P.cin_pad;
+  S.st_mul = 0; S.st_rpp = 0;
   splitk_tile<MASK, NWV, LDSX>(red_raw, S, P, L.L, L.slab_stride, L.dbg, ts0);
 }
 
-// The head form (bv2_kernels.h SkHead / ConvLaunch1): one problem, B = 1, no `lens`, no prefetch tail.  The 13 leading scalar dwords are
+// The head form (bv2_kernels.h SkHead / ConvLaunch1): one problem, B = 1, no `lens`, no prefetch tail.  The 14 leading scalar dwords are
 // preloaded into SGPRs, so the tile is decoded and the first loads are addressed without a trip to the kernarg segment; the struct's
 // fields are at static offsets.  mtiles = cout_pad / 32 here (one problem), so every row tile is inside the problem.
-template <bool MASK, int NWV, bool LDSX>
+template <bool MASK, int NWV, bool LDSX, int EPT>
 __global__ void __launch_bounds__(64 * NWV) conv1d_splitk1_kernel(const float* const x, const float* const w, const float* const in_mask,
                                                                   const int x_rstride, const int Lin, const int ntiles, const int per_xcd,
-                                                                  const int total, const unsigned pk0, const unsigned pk1,
+                                                                  const int total, const unsigned pk0, const unsigned pk1, const unsigned pk2,
                                                                   const ConvLaunch1 L) {
   extern __shared__ __attribute__((aligned(16))) float red_raw[];
   const int bid = blockIdx.x;
@@ -723,7 +760,8 @@ __global__ void __launch_bounds__(64 * NWV) conv1d_splitk1_kernel(const float* c
   S.b = 0; S.ksplit = q.ksplit;
   S.xp = x; S.mp = in_mask; S.wp = w;
   S.x_rstride = x_rstride; S.Lin = Lin; S.k = q.k; S.dil = q.dil; S.pad_left = q.pad_left; S.cin = q.cin; S.cin_pad = q.cin_pad;
-  splitk_tile<MASK, NWV, LDSX>(red_raw, S, L.p, L.L, L.slab_stride, L.dbg, ts0);
+  S.st_mul = pk2 & 65535u; S.st_rpp = (int)(pk2 >> 16);
+  splitk_tile<MASK, NWV, LDSX, EPT>(red_raw, S, L.p, L.L, L.slab_stride, L.dbg, ts0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -738,10 +776,11 @@ static const TileCfg kTiles[] = {
 static const TileCfg kTile128x64 = {TILE_128x64, 128, 64, 2, "conv1d_mfma<128x64>"};
 
 // tuning experiments (tools/kbench.py drive these through bv2_test_set_tuning; 0 = the shipped heuristics)
-static int g_tune_splitk_waves = 0, g_tune_force_ck = 0, g_tune_no_ldsx = 0, g_tune_no_snake = 0;
+static int g_tune_splitk_waves = 0, g_tune_force_ck = 0, g_tune_no_ldsx = 0, g_tune_no_snake = 0, g_tune_row_stage = 0;
 static long g_tune_tile_target = 0;
 void conv_set_tuning(int splitk_waves, int force_ck, long tile_target) {
-  g_tune_no_ldsx = splitk_waves >= 100 ? 1 : 0;                     // +100: the non-staged split-K form (A/B comparisons)
+  g_tune_no_ldsx = splitk_waves >= 100 && splitk_waves < 200 ? 1 : 0;   // +100: the non-staged split-K form (A/B comparisons)
+  g_tune_row_stage = splitk_waves >= 200 ? 1 : 0;                   // +200: the staged form with its row-per-wave staging everywhere
   g_tune_splitk_waves = splitk_waves % 100; g_tune_force_ck = force_ck % 100; g_tune_tile_target = tile_target;
   g_tune_no_snake = force_ck >= 100 ? 1 : 0;                        // force_ck + 100: plain z-major placement (A/B comparisons)
 }
@@ -749,6 +788,8 @@ void conv_set_tuning(int splitk_waves, int force_ck, long tile_target) {
 static int g_last_placement = PLACE_PLAIN;
 void conv_note_placement(int place) { g_last_placement = place; }
 int conv_last_placement() { return g_last_placement; }
+static int g_last_splitk_stage = -1;
+int conv_last_splitk_stage() { return g_last_splitk_stage; }
 
 static unsigned long long* g_tl_buf = nullptr;
 static long long g_tl_cap = 0, g_tl_off = 0;
@@ -860,28 +901,46 @@ static int splitk_stage_rows(const ConvLaunch& L, int nw) {
   return rows;
 }
 
+template <bool MASK, int NWV, bool LDSX, int EPT>
+static void launch_splitk_head(hipStream_t stream, dim3 grid, size_t lds, const SkHead& h, const ConvLaunch1& L1) {
+  auto kern = conv1d_splitk1_kernel<MASK, NWV, LDSX, EPT>;
+  ensure_dyn_lds((const void*)kern, lds);
+  hipLaunchKernelGGL(kern, grid, dim3(64 * NWV), lds, stream, h.x, h.w, h.in_mask, h.x_rstride, h.Lin, h.ntiles, h.per_xcd, h.total,
+                     h.pk0, h.pk1, h.pk2, L1);
+}
+template <bool MASK, int NWV, bool LDSX>
+static void launch_splitk_head_ept(hipStream_t stream, dim3 grid, size_t lds, const SkHead& h, const ConvLaunch1& L1, int ept) {
+  if constexpr (LDSX) {
+    if (ept == 16) return launch_splitk_head<MASK, NWV, true, 16>(stream, grid, lds, h, L1);
+    if (ept == 24) return launch_splitk_head<MASK, NWV, true, 24>(stream, grid, lds, h, L1);
+  }
+  launch_splitk_head<MASK, NWV, LDSX, 0>(stream, grid, lds, h, L1);
+}
+
 template <bool MASK, bool LDSX>
 static void launch_splitk_nw(hipStream_t stream, const ConvLaunch& L, int nw, dim3 grid, int mtiles, int ntiles, int per_xcd,
                              int total, int stage_rows) {
   size_t lds = sizeof(float) * (size_t)nw * 32 * 33;
-  if (LDSX) lds = sizeof(float) * (size_t)nw * SK_RPW * SK_XP;     // every wave stores its SK_RPW rows unconditionally (>= the reduce buffer)
-  (void)stage_rows;
+  // every wave stores its SK_RPW rows unconditionally (>= the reduce buffer); block staging adds the dump row
+  if (LDSX) lds = sizeof(float) * (size_t)(nw * SK_RPW + SK_DUMP) * SK_XP;
   SkHead h;
   if (nw <= 8 && sk_head_pack(L, ntiles, per_xcd, total, &h)) {     // the head form where the launch fits it (16 waves: a tuning value only)
     const ConvLaunch1 L1{L.p[0], L.L, L.slab_stride, L.dbg};
-    if (nw == 8) {
-      auto kern = conv1d_splitk1_kernel<MASK, 8, LDSX>;
-      ensure_dyn_lds((const void*)kern, lds);
-      hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, h.x, h.w, h.in_mask, h.x_rstride, h.Lin, h.ntiles, h.per_xcd, h.total,
-                         h.pk0, h.pk1, L1);
-    } else {
-      auto kern = conv1d_splitk1_kernel<MASK, 4, LDSX>;
-      ensure_dyn_lds((const void*)kern, lds);
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, h.x, h.w, h.in_mask, h.x_rstride, h.Lin, h.ntiles, h.per_xcd, h.total,
-                         h.pk0, h.pk1, L1);
+    // block staging (see SK_DUMP): rows per pass, and the loads per thread its largest slice needs -> the instantiation that covers them;
+    // more than the largest one keeps the row-per-wave staging (EPT = 0)
+    int ept = 0;
+    if (LDSX && !g_tune_row_stage) {
+      const int xw = 32 + (L.p[0].k - 1) * L.p[0].dil, rpp = 64 * nw / xw;
+      const int need = (stage_rows + rpp - 1) / rpp;
+      ept = need <= 16 ? 16 : (need <= 24 ? 24 : 0);
+      h.pk2 = (unsigned)(65536 / xw + 1) | (unsigned)rpp << 16;
     }
+    g_last_splitk_stage = LDSX ? ept : -1;
+    if (nw == 8) launch_splitk_head_ept<MASK, 8, LDSX>(stream, grid, lds, h, L1, ept);
+    else launch_splitk_head_ept<MASK, 4, LDSX>(stream, grid, lds, h, L1, ept);
     return;
   }
+  g_last_splitk_stage = LDSX ? 0 : -1;
   if (nw == 16) {
     auto kern = conv1d_splitk_kernel<MASK, 16, LDSX>;
     ensure_dyn_lds((const void*)kern, lds);

@@ -249,6 +249,10 @@ int bv2_test_conv_post_cl(void* stream, const void* x0, const void* x1, const vo
 
 /* tuning experiments (tools/kbench.py): force the split-K wave count / C_in chunk / tile-count target of the fp32 conv; 0 = default */
 void bv2_test_set_tuning(int splitk_waves, int force_ck, long tile_target);
+/* splitk_waves + 100: the split-K kernel's register form (no staged X tile); + 200: the staged form with its row-per-wave staging in the
+ * head form too.  bv2_test_splitk_stage: how the last split-K launch staged X: -1 = register form, 0 = row per wave, 16 / 24 = block
+ * staging with that many loads per thread */
+int bv2_test_splitk_stage(void);
 /* bv2_set_option("kernarg_head") for the launch entries of this header, which have no handle (bv2_test_conv1d, bv2_test_conv_multi,
  * bv2_test_layernorm*, bv2_test_attention*, bv2_test_flow_boundary): 1 (default) = the head form where a launch fits it, 0 = the generic kernels */
 void bv2_test_set_kernarg_head(int on);
