@@ -946,26 +946,35 @@ int run_stage_dp(bv2_handle* h, hipStream_t s, int B, int T, const float* x, con
 // WN.forward (modules.py:185-210) in fp32, 2 launches per layer: in_layer + g_l + gate (ACT_GATE epilogue), then res_skip as two
 // problems of one launch — x = (x + rs[:H]) * mask in place, output += rs[H:] (first layer: =; last layer: all H rows, * mask).
 // The residual flow's couplings and the posterior encoder (16 layers) run on it; gl: the layers' conditioning rows [nl][2H] per item.
+// The two launches are said once, below, for this executor and for the tests' entry points (bv2_testing.cpp).
+ConvProb wn_in_prob(const ConvW& in, const float* blob, const float* x, float* acts, const float* gl, int gl_bstride, int Ty) {
+  ConvProb p = conv_prob(in, blob, x, acts, Ty);
+  p.bias2 = gl; p.bias2_bstride = gl_bstride;
+  p.act = ACT_GATE; p.out_bstride = (int64_t)(in.cout / 2) * Ty;
+  return p;
+}
+ConvLaunch wn_res_skip_launch(const ConvW* res, const ConvW& skip, bool first, const float* blob, const float* acts, float* x, float* outacc,
+                              const float* mask, int B, int Ty) {
+  ConvLaunch cl{};
+  cl.B = B; cl.L = Ty; cl.nprob = 0;
+  if (res) {
+    ConvProb r = conv_prob(*res, blob, acts, x, Ty);
+    r.res = x; r.res_mode = RES_ADD; r.out_mask = mask; r.mask_post = 1;
+    cl.p[cl.nprob++] = r;
+  }
+  ConvProb sk = conv_prob(skip, blob, acts, outacc, Ty);
+  if (!first) { sk.res = outacc; sk.res_mode = RES_ADD; }
+  if (!res) { sk.out_mask = mask; sk.mask_post = 1; }
+  cl.p[cl.nprob++] = sk;
+  return cl;
+}
 static void run_wn(Ctx& c, const WnW& W, const float* gl, int gl_bstride, float* x, float* acts, float* outacc, const float* mask, int B,
                    int H, int Ty) {
   const int nl = W.layers;
   for (int i = 0; i < nl; ++i) {
     const bool last = i == nl - 1;
-    ConvProb p = c.prob(W.in[i], x, acts, Ty);
-    p.bias2 = gl + (int64_t)i * 2 * H; p.bias2_bstride = gl_bstride;
-    p.act = ACT_GATE; p.out_bstride = (int64_t)H * Ty;
-    c.conv1(p, B, Ty, "wn.in+gate");
-    ConvLaunch cl;
-    cl.B = B; cl.L = Ty; cl.nprob = 0;
-    if (!last) {
-      ConvProb r = c.prob(W.res[i], acts, x, Ty);
-      r.res = x; r.res_mode = RES_ADD; r.out_mask = mask; r.mask_post = 1;
-      cl.p[cl.nprob++] = r;
-    }
-    ConvProb sk = c.prob(W.skip[i], acts, outacc, Ty);
-    if (i > 0) { sk.res = outacc; sk.res_mode = RES_ADD; }
-    if (last) { sk.out_mask = mask; sk.mask_post = 1; }
-    cl.p[cl.nprob++] = sk;
+    c.conv1(wn_in_prob(W.in[i], c.blob, x, acts, gl + (int64_t)i * 2 * H, gl_bstride, Ty), B, Ty, "wn.in+gate");
+    ConvLaunch cl = wn_res_skip_launch(last ? nullptr : &W.res[i], W.skip[i], i == 0, c.blob, acts, x, outacc, mask, B, Ty);
     c.conv(cl, "wn.res_skip");
   }
 }

@@ -388,6 +388,13 @@ ConvPostArgs conv_post_args(const float* const src[3], int nsrc, const float* w,
                             const int64_t* lens, int len_mul);
 ConvPostClArgs conv_post_cl_args(const uint16_t* const src[3], int nsrc, const float* w, float* out, int C, int k, int B, int L,
                                  const int64_t* lens, int len_mul, bool generic);
+// The two launches of an fp32 WN layer (run_wn), built in one place for the executor and for the tests' entry points.  in_layer + g_l + gate:
+// `in` has its 2H rows in gate order, gl is the layer's conditioning slice [B][gl_bstride] in the same order, acts gets H rows.
+ConvProb wn_in_prob(const ConvW& in, const float* blob, const float* x, float* acts, const float* gl, int gl_bstride, int Ty);
+// res_skip: x = (x + res(acts)) * mask in place and outacc (+)= skip(acts) as two problems; res == nullptr is the last layer, whose one
+// problem is skip(acts) into outacc, masked.  first: outacc is written, not added to.  ksplit / slab_stride / no_head are the caller's.
+ConvLaunch wn_res_skip_launch(const ConvW* res, const ConvW& skip, bool first, const float* blob, const float* acts, float* x, float* outacc,
+                              const float* mask, int B, int Ty);
 // streamed decode: the flow once (run_stream_begin), the Generator window by window (run_stream_chunk)
 int generator_halo(const Model& m);
 int64_t stream_plan_bytes(const Model& m, int B, int Ty, int window_frames);            // what a stream itself needs (without phase A)

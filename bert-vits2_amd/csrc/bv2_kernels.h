@@ -82,8 +82,9 @@ inline void ensure_dyn_lds(const void* kern, size_t lds) {
 enum { PRE_NONE = 0, PRE_LRELU = 1 };
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GATE = 2, ACT_GELU = 3 };   // ACT_GELU: exact erf GELU (BERT intermediate, bv2_bert.cpp)
 // ACT_GATE (WN, reference commons.py:98-105): the GEMM rows come packed so that rows [0,16) of every 32-row tile are the tanh half and
-// rows [16,32) the sigmoid half of the same 16 channels (bv2_model.cpp wn_gate_row); the epilogue writes
-// out[16*mt + j] = tanh(v[j]) * sigmoid(v[j+16]) — `out` has cout/2 rows.  No residual / masks with it.
+// rows [16,32) the sigmoid half of the same 16 channels (bv2_pack.h wn_gate_row); the epilogue writes
+// out[16*mt + j] = tanh(v[j]) * sigmoid(v[j+16]) — `out` has cout/2 rows.  No residual / masks / K split with it, whole 32-row tiles
+// only, never on the x6 / x3 tiles: launch_conv1d refuses anything else (conv_gate_ok below).
 enum { RES_NONE = 0, RES_ADD = 1, RES_RSUB = 2 };   // v += res  |  v = res - v
 
 struct ConvProb {
@@ -193,6 +194,12 @@ enum { TILE_AUTO = 0, TILE_128x128 = 1, TILE_64x128 = 2, TILE_64x64 = 3, TILE_32
 // (13 was TILE_SPLITK_X6, the split-K kernel's split-bf16 form: measured at +0.4 % on config 2 for +195 MB of blob and deleted in round 6 —
 //  DESIGN.md "measured and not kept", profiles/r05_ab_splitk_x6_not_kept.txt)
 int launch_conv1d(hipStream_t stream, const ConvLaunch& L, int tile, const char** variant_name);
+// what an ACT_GATE problem may ask for (host only; launch_conv1d returns -1 and launches nothing otherwise): its epilogues skip the residual,
+// both masks and the max |out| publication, gate every partial slab of a K split (tanh of a partial sum is no partial tanh), pair rows r and
+// r + 16 of whole 32-row tiles, and conv_x6.hip has no gate at all
+inline bool conv_gate_ok(const ConvProb& p, int ksplit, int tile) {
+  return ksplit <= 1 && p.res_mode == RES_NONE && !p.out_mask && !p.mask_pre && !p.mask_post && p.cout % 32 == 0 && tile < TILE_X6;
+}
 // tests only: how the last launch_conv1d of this process mapped workgroups to (column tile, problem) — the plain grid, contiguous per-XCD
 // column ranges (always for the split-K kernel), or the cost-sorted snake (conv_mfma.hip launch_variant / conv_x6.hip launch_x6_variant)
 enum { PLACE_PLAIN = 0, PLACE_PER_XCD = 1, PLACE_SNAKE = 2 };
@@ -201,6 +208,7 @@ int conv_last_placement();
 // how the last split-K launch staged its X tile: -1 = not at all (the register form), 0 = row per wave, 16 / 24 = block staging with that
 // many loads per thread (conv_mfma.hip SK_DUMP)
 int conv_last_splitk_stage();
+int conv_last_splitk_waves();                                   // ... and with how many waves per workgroup (4 / 8 / 16: the kernel's NWV)
 // fp32 conv on the bf16 matrix core (kernels/conv_x6.hip): every fp32 operand is the exact sum of three bf16 values
 // (v = h1 + h2 + h3, 8 + 8 + 8 significand bits), and the product is accumulated from the six largest of the nine cross terms
 // (w1x1, w1x2, w2x1, w1x3, w2x2, w3x1 — the three dropped ones are below 2^-23 of the product, the rounding of an fp32 multiply).
@@ -478,7 +486,7 @@ struct HcProb {
   uint16_t* k16; uint16_t* v16; int kv_row0, kv_rows, k16_ld;
 };
 bool conv_f16_ln_supported(int cout);
-// act == ACT_GATE (out_ct = 0 only; WN, reference commons.py:98-105): the weight rows come in gate order (bv2_model.cpp wn_gate_row:
+// act == ACT_GATE (out_ct = 0 only; WN, reference commons.py:98-105): the weight rows come in gate order (bv2_pack.h wn_gate_row:
 // rows [0,16) of every 32-row tile = tanh half, rows [16,32) = sigmoid half of the same 16 channels); the epilogue writes
 // out[b][t][16*mt + j] = fp16( tanh(v[j]) * sigmoid(v[j+16]) ), `out` has cout/2 channels (out_bstride = cout/2 * L).
 // A launch carries 1 or 2 problems (blockIdx.z) with the same cin / k / dil / cout_pad and input form: the two row halves of

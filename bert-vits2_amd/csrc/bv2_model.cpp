@@ -268,7 +268,7 @@ ConvFlowW pack_convflow(Packer& P, const std::string& p, int hid) {
 WnW pack_wn(Packer& P, const std::string& p, int hid, int nl, int gin, bool f16) {
   WnW W;
   W.layers = nl;
-  const std::function<int(int)> gate_row = [hid](int n) { const int mt = n / 32, j = n % 32; return j < 16 ? 16 * mt + j : hid + 16 * mt + (j - 16); };
+  const std::function<int(int)> gate_row = [hid](int n) { return wn_gate_row(hid, n); };
   const std::function<int(int)> cond_row = [hid, &gate_row](int n) { return (n / (2 * hid)) * 2 * hid + gate_row(n % (2 * hid)); };
   W.cond = P.gemv(p + ".cond_layer", 2 * hid * nl, gin, true, /*wn=*/true, &cond_row);
   P.emit_f16 = f16;

@@ -45,6 +45,13 @@ inline ConvW conv_cl_desc(int cin, int cout, int k) {            // channels-las
   return c;
 }
 
+// ---- the WN gate order (ACT_GATE, bv2_kernels.h): packed row n of an in_layer (2 * hid rows; also of a layer's cond_layer slice) is source
+// row wn_gate_row(hid, n) — every 32-row tile holds the tanh rows of 16 channels, then the sigmoid rows (source row hid + c) of the same 16
+inline int wn_gate_row(int hid, int n) {
+  const int mt = n / 32, j = n % 32;
+  return j < 16 ? 16 * mt + j : hid + 16 * mt + (j - 16);
+}
+
 // ---- sizes, in floats unless the name says otherwise
 inline int64_t conv_w_floats(const ConvW& c) { return (int64_t)c.k * c.cin_pad * c.w_ld; }
 inline int64_t cl_w_floats(const ConvW& c) { return (cl_w_elems(c.cin, c.cout_pad, c.k) + 1) / 2; }

@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "bv2_internal.h"
@@ -82,10 +83,13 @@ int64_t bv2_test_x3_omax_off(int cin, int cout, int k) { return t_x3_off(cin, co
 // one conv w_host [cout][cin][k] + bias_host [cout] (or null) into a zeroed region of bv2_test_conv_pack_floats(cin, cout, k) floats: the
 // packed fp32 stream, the bias behind it, with x6 the three bf16 planes at t_x6_off, and with x3 the region at t_x3_off:
 // [max |x| slot] [max |out| slot] (X3_SLOT_WORDS each, left zero) [1 / S_w] (X3_HDR_FLOATS) [the two scaled fp16 planes]
-static void t_pack_conv(float* pk, const float* w_host, const float* bias_host, int cin, int cout, int k, bool x6, bool x3 = false) {
-  const auto src = t_dense(w_host, cin, k);
+// (rowmap: packed row co is row rowmap(co) of w_host / bias_host, as Packer::conv1d's; null: co itself)
+static void t_pack_conv(float* pk, const float* w_host, const float* bias_host, int cin, int cout, int k, bool x6, bool x3 = false,
+                        const std::function<int(int)>* rowmap = nullptr) {
+  const auto dense = t_dense(w_host, cin, k);
+  const auto src = [&](int co, int ci, int j) { return dense(rowmap ? (*rowmap)(co) : co, ci, j); };
   pack_f32(pk, cin, cout, k, src);
-  if (bias_host) pack_bias(pk + conv_w_floats(conv_desc(cin, cout, k)), cout, t_bias(bias_host));
+  if (bias_host) pack_bias(pk + conv_w_floats(conv_desc(cin, cout, k)), cout, [&](int co) { return bias_host[rowmap ? (*rowmap)(co) : co]; });
   if (!x6) return;
   pack_x6(reinterpret_cast<uint16_t*>(pk + t_x6_off(cin, cout, k)), cin, cout, k, src);
   if (!x3) return;
@@ -125,7 +129,7 @@ int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const flo
                     int mask_post, const float* bias2, int nsrc, const float* x1, const float* x2, float in_scale, int ksplit,
                     int64_t slab_stride) {
   try {
-    if (relu != ACT_NONE && relu != ACT_RELU && relu != ACT_GELU) return -1;
+    if (relu != ACT_NONE && relu != ACT_RELU && relu != ACT_GATE && relu != ACT_GELU) return -1;
     const ConvW c = conv_desc(cin, cout, k);
     std::vector<float> pk;
     const size_t boff = (size_t)conv_w_floats(c);
@@ -157,7 +161,7 @@ int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const flo
     p.w = wpack_dev; p.bias = bias_host ? wpack_dev + boff : nullptr;
     if (x6) p.w6 = reinterpret_cast<const uint16_t*>(wpack_dev + t_x6_off(cin, cout, k));
     p.bias2 = bias2; p.bias2_bstride = cout;
-    p.out = out; p.out_bstride = (int64_t)cout * L; p.out_rstride = L; p.out_tstride = 1; p.out_toff = 0;
+    p.out = out; p.out_bstride = (int64_t)(relu == ACT_GATE ? cout / 2 : cout) * L; p.out_rstride = L; p.out_tstride = 1; p.out_toff = 0;
     p.res = res; p.res_bstride = p.out_bstride; p.res_mode = res_mode;
     p.cin = cin; p.cin_pad = c.cin_pad; p.cout = cout; p.cout_pad = c.cout_pad; p.w_ld = c.w_ld; p.k = k; p.dil = dil;
     p.pad_left = pad_left < 0 ? ((k - 1) / 2) * dil : pad_left;
@@ -595,6 +599,7 @@ int bv2_test_conv_timeline_report(long long* meta, int max_launches) { return co
 
 void bv2_test_set_tuning(int splitk_waves, int force_ck, long tile_target) { conv_set_tuning(splitk_waves, force_ck, tile_target); }
 int bv2_test_splitk_stage(void) { return conv_last_splitk_stage(); }
+int bv2_test_splitk_waves(void) { return conv_last_splitk_waves(); }
 void bv2_test_set_x6_tuning(int t256, int t128, int t64, int ck) { conv_x6_set_tuning(t256, t128, t64, ck); }
 void bv2_test_x6_occupancy(int* out4) { conv_x6_occupancy(out4); }
 void bv2_test_set_variants(const char* cl_spec, int cl_generic, int hc_generic) {
@@ -805,6 +810,47 @@ int bv2_test_conv_post_cl(void* stream, const void* x0, const void* x1, const vo
                             nsrc > 2 ? static_cast<const uint16_t*>(x2) : nullptr};
   return launch_conv_post_cl(static_cast<hipStream_t>(stream),
                              conv_post_cl_args(src, nsrc, w_dev, out, C, k, B, L, lens, len_mul < 1 ? 1 : len_mul, generic != 0));
+}
+
+// ---- the fp32 WN layer's two launches as run_wn builds them (tests/test_wn_forms_*.py)
+int bv2_test_wn_gate_row(int hid, int n) { return wn_gate_row(hid, n); }
+int64_t bv2_test_wn_in_pack_floats(int B, int H) { return t_region(H, 2 * H, kFlowKernel) + (int64_t)B * 2 * H; }
+int bv2_test_wn_in_layer(void* stream, const float* x, const float* w_host, const float* bias_host, const float* gl_host, float* acts,
+                         float* wpack_dev, int B, int H, int L, int tile) {
+  try {
+    if (!x || !w_host || !bias_host || !gl_host || !acts || !wpack_dev || B < 1 || H < 16 || H % 16 || L < 1 || tile >= TILE_X6) return -2;
+    const int k = kFlowKernel;
+    const int64_t one = t_region(H, 2 * H, k);
+    const std::function<int(int)> gate_row = [H](int n) { return wn_gate_row(H, n); };
+    std::vector<float> pk((size_t)bv2_test_wn_in_pack_floats(B, H), 0.f);
+    t_pack_conv(pk.data(), w_host, bias_host, H, 2 * H, k, false, false, &gate_row);
+    for (int b = 0; b < B; ++b)                    // the layer's cond_layer slice: the same rows (Packer::gemv with pack_wn's cond_row)
+      for (int n = 0; n < 2 * H; ++n) pk[(size_t)one + (size_t)b * 2 * H + n] = gl_host[(size_t)b * 2 * H + gate_row(n)];
+    if (hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
+    ConvLaunch cl{};
+    cl.p[0] = wn_in_prob(t_conv_w(0, H, 2 * H, k, true, false), wpack_dev, x, acts, wpack_dev + one, 2 * H, L);
+    cl.nprob = 1; cl.B = B; cl.L = L; cl.ksplit = 1; cl.no_head = g_test_no_head;
+    const char* vn = nullptr;
+    return launch_conv1d(static_cast<hipStream_t>(stream), cl, tile, &vn);
+  } catch (...) { return -100; }
+}
+int64_t bv2_test_wn_res_skip_pack_floats(int H) { return 2 * t_region(H, H, 1); }
+int bv2_test_wn_res_skip(void* stream, const float* acts, const float* w_host, const float* bias_host, float* x, float* outacc,
+                         const float* mask, float* wpack_dev, int B, int H, int L, int tile, int first, int last) {
+  try {
+    if (!acts || !w_host || !bias_host || !x || !outacc || !mask || !wpack_dev || B < 1 || H < 1 || L < 1 || tile >= TILE_X6) return -2;
+    // as pack_wn: rows [0,H) the x update, rows [H,2H) the skip rows, two convs of H rows; the last layer's H rows are all skip rows
+    const int64_t one = t_region(H, H, 1);
+    std::vector<float> pk((size_t)(2 * one), 0.f);
+    if (!last) t_pack_conv(pk.data(), w_host, bias_host, H, H, 1, false);
+    t_pack_conv(pk.data() + one, w_host + (last ? 0 : (size_t)H * H), bias_host + (last ? 0 : H), H, H, 1, false);
+    if (hipMemcpy(wpack_dev, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice) != hipSuccess) return -6;
+    const ConvW res = t_conv_w(0, H, H, 1, true, false), skip = t_conv_w(one, H, H, 1, true, false);
+    ConvLaunch cl = wn_res_skip_launch(last ? nullptr : &res, skip, first != 0, wpack_dev, acts, x, outacc, mask, B, L);
+    cl.ksplit = 1; cl.slab_stride = 0; cl.no_head = g_test_no_head;
+    const char* vn = nullptr;
+    return launch_conv1d(static_cast<hipStream_t>(stream), cl, tile, &vn);
+  } catch (...) { return -100; }
 }
 
 int bv2_test_spline(void* stream, float* z, int src, int dst, const float* params, int prow, const float* mask,

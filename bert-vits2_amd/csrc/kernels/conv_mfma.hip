@@ -336,10 +336,13 @@ __global__ void __launch_bounds__(256) conv1d_mfma_kernel(const ConvLaunch L, co
         const unsigned off0 = (unsigned)row0 * o_rs + (unsigned)colc * o_ts + o_to;
         float rv[16];
         if (resb) {
+          // a row past cout reads the item's row 0 instead (the value is dropped): row0 itself is past the tensor when its whole 8-row
+          // group is, as in the last m-tile of a tile height that does not divide cout_pad
+          const unsigned offc = (unsigned)colc * o_ts + o_to;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int dr = (r & 3) + 8 * (r >> 2);
-            const unsigned off = row0 + dr < cout ? off0 + (unsigned)dr * o_rs : off0;
+            const unsigned off = row0 + dr < cout ? off0 + (unsigned)dr * o_rs : offc;
             rv[r] = ld_off(resb, 4u * off);
           }
         }
@@ -788,8 +791,9 @@ void conv_set_tuning(int splitk_waves, int force_ck, long tile_target) {
 static int g_last_placement = PLACE_PLAIN;
 void conv_note_placement(int place) { g_last_placement = place; }
 int conv_last_placement() { return g_last_placement; }
-static int g_last_splitk_stage = -1;
+static int g_last_splitk_stage = -1, g_last_splitk_waves = 0;
 int conv_last_splitk_stage() { return g_last_splitk_stage; }
+int conv_last_splitk_waves() { return g_last_splitk_waves; }
 
 static unsigned long long* g_tl_buf = nullptr;
 static long long g_tl_cap = 0, g_tl_off = 0;
@@ -970,6 +974,7 @@ static int launch_splitk(hipStream_t stream, const ConvLaunch& L0, int max_cout_
   int nw = splitk_waves(L);
   for (int i = 0; i < L.nprob; ++i)
     if (L.p[i].act == ACT_GATE && nw == 16) nw = 8;   // the gate pairs rows inside one thread: at most 16 rows per pass
+  g_last_splitk_waves = nw;
   if (variant_name) *variant_name = nw == 16 ? "conv1d_splitk<32x32,16w>" : (nw == 8 ? "conv1d_splitk<32x32,8w>" : "conv1d_splitk<32x32,4w>");
   const dim3 grid(per_xcd * 8 + (L.pf.ptr && L.pf.bytes ? PF_BLOCKS : 0));
   conv_note_placement(PLACE_PER_XCD);
@@ -1029,6 +1034,7 @@ int launch_conv1d(hipStream_t stream, const ConvLaunch& L, int tile, const char*
   for (int i = 0; i < L.nprob; ++i) {
     const ConvProb& p = L.p[i];
     if (p.cout_pad % 32 || p.cin_pad % 16 || p.k < 1 || p.dil < 1 || p.w_ld % 128 || p.w_ld < p.cout_pad) return -1;
+    if (p.act == ACT_GATE && !conv_gate_ok(p, L.ksplit, tile)) return -1;
     if (p.cout_pad > max_cout_pad) max_cout_pad = p.cout_pad;
     if ((p.k - 1) * p.dil > max_extra) max_extra = (p.k - 1) * p.dil;
     if (p.cin_pad % 32) ck = 16;

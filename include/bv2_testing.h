@@ -19,8 +19,13 @@ int64_t bv2_test_conv_pack_floats(int cin, int cout, int k);
  * shapes, 6 = split-K kernel; see bv2_kernels.h TILE_*).  With tile 6 and ksplit > 1 the output is `ksplit` partial
  * slabs, `slab_stride` floats apart, whose SUM is the result (bias / residual ride on slab 0).  w_host [cout][cin][k] / bias_host [cout] are HOST pointers (packed + uploaded
  * synchronously into wpack_dev); every other pointer is DEVICE.  x [B][cin][L], out/res [B][cout][L*out_tstride],
- * masks [B][L].  pad_left < 0 means "same" padding ((k-1)/2*dil).  `relu` is the activation code: 0 = none, 1 = ReLU, 3 = exact erf
- * GELU (ACT_GELU); any other value is refused with -1 before anything is packed or launched. */
+ * masks [B][L].  pad_left < 0 means "same" padding ((k-1)/2*dil).  `relu` is the activation code: 0 = none, 1 = ReLU, 2 = the WN gate
+ * (ACT_GATE), 3 = exact erf GELU (ACT_GELU); any other value is refused with -1 before anything is packed or launched.  With the gate,
+ * weight, bias and bias2 rows are taken as given, in gate order (rows [0,16) of every 32 the tanh rows, [16,32) the sigmoid rows of the
+ * same 16 channels), and out has cout / 2 rows per item ([B][cout/2][L]).  The entry itself checks nothing about a gate launch: a K split,
+ * a residual, a mask, cout % 32 != 0 or an x6 / x3 tile (>= 8) goes to launch_conv1d as asked, and the -1 that comes back is the
+ * launcher's (bv2_kernels.h conv_gate_ok; the weights have been packed and uploaded by then, no conv kernel has run).  With w_host NULL
+ * and cin % 32 != 0 the entry makes no device call of its own in front of the launcher's checks. */
 int bv2_test_conv1d(void* stream, const float* x, const float* w_host, const float* bias_host, float* out, float* wpack_dev,
                     int B, int cin, int cout, int k, int dil, int pad_left, int L, int tile, float lrelu_slope, int relu,
                     const float* res, int res_mode, const float* in_mask, const float* out_mask, int mask_pre,
@@ -247,12 +252,30 @@ int bv2_test_conv_post(void* stream, const float* x0, const float* x1, const flo
 int bv2_test_conv_post_cl(void* stream, const void* x0, const void* x1, const void* x2, int nsrc, const float* w_host, float* w_dev,
                           float* out, const int64_t* lens, int len_mul, int B, int C, int k, int L, int generic);
 
+/* The fp32 WN layer's two launches, built by the executor's own functions (wn_in_prob / wn_res_skip_launch), from weights in the
+ * REFERENCE's row order (tests/test_wn_forms_*.py).  H = hidden channels (a multiple of 16), k = 5, tile 0 = the product's pick, 1..7 forced.
+ * bv2_test_wn_gate_row (host only): the source row of packed row n of an in_layer / a layer's cond_layer slice (bv2_pack.h wn_gate_row). */
+int bv2_test_wn_gate_row(int hid, int n);
+/* acts [B][H][L] = tanh(v[:H]) * sigmoid(v[H:]), v = conv1d(x [B][H][L], w_host [2H][H][5]) + bias_host [2H] + gl_host [B][2H] (all three
+ * HOST, permuted into gate order by the packer's code); no masks.  wpack_dev needs bv2_test_wn_in_pack_floats(B, H) floats. */
+int64_t bv2_test_wn_in_pack_floats(int B, int H);
+int bv2_test_wn_in_layer(void* stream, const float* x, const float* w_host, const float* bias_host, const float* gl_host, float* acts,
+                         float* wpack_dev, int B, int H, int L, int tile);
+/* rs = conv1d(acts [B][H][L], w_host [2H][H][1]) + bias_host [2H] (HOST; [H][H][1] / [H] when last).  Not last: x = (x + rs[:H]) * mask in
+ * place and outacc (+)= rs[H:] unmasked, two problems of one launch; last: outacc = (outacc + rs) * mask.  first: outacc is written, not
+ * added to.  x / outacc [B][H][L], mask [B][L] DEVICE.  wpack_dev needs bv2_test_wn_res_skip_pack_floats(H) floats. */
+int64_t bv2_test_wn_res_skip_pack_floats(int H);
+int bv2_test_wn_res_skip(void* stream, const float* acts, const float* w_host, const float* bias_host, float* x, float* outacc,
+                         const float* mask, float* wpack_dev, int B, int H, int L, int tile, int first, int last);
+
 /* tuning experiments (tools/kbench.py): force the split-K wave count / C_in chunk / tile-count target of the fp32 conv; 0 = default */
 void bv2_test_set_tuning(int splitk_waves, int force_ck, long tile_target);
 /* splitk_waves + 100: the split-K kernel's register form (no staged X tile); + 200: the staged form with its row-per-wave staging in the
  * head form too.  bv2_test_splitk_stage: how the last split-K launch staged X: -1 = register form, 0 = row per wave, 16 / 24 = block
  * staging with that many loads per thread */
 int bv2_test_splitk_stage(void);
+/* ... and the waves per workgroup of the last split-K launch (4 / 8 / 16: which instantiation of the kernel ran) */
+int bv2_test_splitk_waves(void);
 /* bv2_set_option("kernarg_head") for the launch entries of this header, which have no handle (bv2_test_conv1d, bv2_test_conv_multi,
  * bv2_test_layernorm*, bv2_test_attention*, bv2_test_flow_boundary): 1 (default) = the head form where a launch fits it, 0 = the generic kernels */
 void bv2_test_set_kernarg_head(int on);

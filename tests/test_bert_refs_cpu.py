@@ -216,5 +216,6 @@ def test_launchers_refuse_before_any_device_call():
     for Cc in (64, 200, 1152):
         assert ln(Cc) == -1, Cc
     assert lib.bv2_test_bert_embed_ln(None, p, None, p, None, None, None, p, p, 1e-7, p, 1, 4, 2049, 8, 8, 1, None, 0) == -1
-    assert lib.bv2_test_conv1d(None, p, p, None, p, p, 1, 32, 32, 1, 1, -1, 8, 0, 0.0, 2, None, 0, None, None, 0, 0, None, 1, None, None,
+    # an activation code the conv kernels do not have (2, the WN gate, is one they have: tests/test_wn_forms_cpu.py holds its refusals)
+    assert lib.bv2_test_conv1d(None, p, p, None, p, p, 1, 32, 32, 1, 1, -1, 8, 0, 0.0, 4, None, 0, None, None, 0, 0, None, 1, None, None,
                                1.0, 1, 0) == -1
