@@ -7,7 +7,9 @@ below is that step: samples at the model's sampling rate go in (fp32 in [-1, 1],
 out.  A recording at another rate goes through ``resample`` first (the reference resamples offline with librosa, resample.py): a polyphase
 Kaiser-windowed sinc on the device (``bv2_resample``, kernels/resample.hip), the same call that brings synthesised audio to the rate a
 consumer wants.  ``loudness`` / ``normalize_loudness`` measure integrated loudness (ITU-R BS.1770-4, mono) and bring audio to a target level
-on the device (``bv2_loudness_*``, kernels/loudness.hip).  ``assemble`` joins pieces that lie in several tensors, each under its level
+on the device (``bv2_loudness_*``, kernels/loudness.hip); ``true_peak`` (``bv2_true_peak``, kernels/truepeak.hip), ``loudness(true_peak=,
+want_range=)`` and ``normalize_loudness(peak="true")`` add the rest of an EBU R128 delivery sheet: true peak, loudness range, the maximum
+momentary and short-term loudness, and a ceiling in dBTP.  ``assemble`` joins pieces that lie in several tensors, each under its level
 rule, and the pauses between them into one buffer per document (``bv2_assemble``, kernels/assemble.hip).  Not done here: decoding of audio files.
 
 Nothing in here computes: the filterbank comes from ``bv2_mel_basis`` and the resampler's table from ``bv2_resample_taps`` (fp64 on the
@@ -320,6 +322,7 @@ def resample(wav: torch.Tensor, wav_lengths=None, rate_in: Optional[int] = None,
 
 # ---- loudness (include/bv2.h bv2_loudness_*) ----------------------------------------------------------------------------------------------
 LOUDNESS_RATES = (8000, 192000)
+PEAKS = ("sample", "true")            # what a peak ceiling limits: dBFS of the samples, or dBTP
 
 
 def loudness_config(rate: int, input_format: int = L.WAV_F32) -> L.LoudnessConfig:
@@ -484,6 +487,111 @@ def loudness_apply(wav: torch.Tensor, wl: Optional[torch.Tensor], rate: int, gai
     return out
 
 
+def true_peak_plan(rate: int) -> Tuple[int, int]:
+    """``(F, K)`` at a sampling rate (``bv2_true_peak_plan``): the oversampling factor — 4 below 96 kHz, 2 below 192 kHz, 1 at 192 kHz — and
+    the interpolator's reach in input samples (36; 0 when F = 1).  ``ValueError`` outside 8 000 .. 192 000 Hz."""
+    lib = L.load()
+    v = [C.c_int32() for _ in range(2)]
+    if lib.bv2_true_peak_plan(C.byref(loudness_config(rate)), *[C.byref(x) for x in v]) != 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return tuple(int(x.value) for x in v)
+
+
+def true_peak_measure(wav: torch.Tensor, wl: Optional[torch.Tensor], rate: int) -> torch.Tensor:
+    """``bv2_true_peak`` on the current stream: ``wav`` [B, S] (device, fp32 or int16, unit sample stride), ``wl`` [B] device int64 or
+    ``None`` -> fp32 [B] on the device: the larger of the sample peak and the peak of the F-times oversampled signal, which is never
+    written (two launches)."""
+    if not wav.is_cuda or wav.dim() != 2 or wav.stride(1) != 1 or wav.dtype not in (torch.float32, torch.int16):
+        raise ValueError("wav must be a device tensor [B, S], float32 or int16, with unit sample stride")
+    B, S = wav.shape
+    dev = wav.device
+    F, _ = true_peak_plan(rate)
+    cfg = loudness_config(rate, L.WAV_I16 if wav.dtype == torch.int16 else L.WAV_F32)
+    lib = L.load()
+    n = lib.bv2_true_peak_workspace_bytes(C.byref(cfg), B, S)
+    if n < 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    taps = device_taps(rate, F * rate, dev) if F > 1 else None
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.bv2_true_peak(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), _ptr(taps), _ptr(wav),
+                               wav.stride(0) if B > 1 else S, _ptr(wl), B, S, _ptr(out), _ptr(ws), ws.numel())
+    if rc != 0:
+        raise RuntimeError(f"bv2_true_peak failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return out
+
+
+def loudness_steps_count(rate: int, n: int) -> int:
+    """Whole 100 ms steps of an item of ``n`` samples (``bv2_loudness_steps_count``)."""
+    lib = L.load()
+    r = lib.bv2_loudness_steps_count(C.byref(loudness_config(rate)), int(n))
+    if r < 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return int(r)
+
+
+def loudness_steps(wav: torch.Tensor, wl: Optional[torch.Tensor], rate: int, want_blocks: bool = False) -> Dict[str, torch.Tensor]:
+    """``bv2_loudness_steps`` on the current stream: ``step_ss`` fp64 [B, steps(S)], the K-weighted energy of every whole 100 ms step
+    (zeros behind an item's last one) and, with ``want_blocks``, ``peak`` and ``block_ms`` as ``loudness_measure(gate=False)`` gives
+    them (four step energies added in order and divided by the block ARE ``block_ms``, bit for bit)."""
+    if not wav.is_cuda or wav.dim() != 2 or wav.stride(1) != 1 or wav.dtype not in (torch.float32, torch.int16):
+        raise ValueError("wav must be a device tensor [B, S], float32 or int16, with unit sample stride")
+    B, S = wav.shape
+    dev = wav.device
+    cfg = loudness_config(rate, L.WAV_I16 if wav.dtype == torch.int16 else L.WAV_F32)
+    lib = L.load()
+    n = lib.bv2_loudness_workspace_bytes(C.byref(cfg), B, S)
+    if n < 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    width = loudness_steps_count(rate, S)
+    out = {"step_ss": torch.empty(B, max(width, 1), dtype=torch.float64, device=dev)[:, :width]}     # S below a step: [B, 0]
+    if want_blocks:
+        out["peak"] = torch.empty(B, dtype=torch.float32, device=dev)
+        out["block_ms"] = torch.empty(B, loudness_blocks(rate, S), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.bv2_loudness_steps(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), _ptr(wav),
+                                    wav.stride(0) if B > 1 else S, _ptr(wl), B, S, C.c_void_p(out["step_ss"].data_ptr()), max(width, 1),
+                                    _ptr(out.get("peak")), _ptr(out.get("block_ms")), _ptr(ws), ws.numel())
+    if rc != 0:
+        raise RuntimeError(f"bv2_loudness_steps failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return out
+
+
+def loudness_range(step_ss: torch.Tensor, wl: Optional[torch.Tensor], S: int, rate: int, groups: Optional[torch.Tensor] = None,
+                   n_groups: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """``bv2_loudness_range`` on the current stream (EBU Tech 3342): from step energies [B, >= steps(S)] that ``loudness_steps`` produced,
+    possibly in several calls (rows padded to one width).  Returns device tensors [G]: ``lra`` (LU), ``st_low`` / ``st_high`` (LUFS at the
+    10th and 95th percentile of the gated short-term loudness), ``max_short_term``, ``max_momentary`` (LUFS), all fp64, and ``flags``
+    int32 (``lib.RANGE_SHORT``: no whole 3 s block; ``lib.RANGE_SILENT``: nothing above -70 LUFS; then ``lra`` is 0 and the rest -inf)."""
+    B = step_ss.shape[0]
+    dev = step_ss.device
+    G = B if groups is None else int(n_groups)
+    width = loudness_steps_count(rate, S)
+    if step_ss.dtype != torch.float64 or step_ss.shape[1] < width:
+        raise ValueError(f"step_ss must be float64 [B, >= {width}]")
+    if step_ss.shape[1] == 0:
+        step_ss = torch.zeros(B, 1, dtype=torch.float64, device=dev)
+    step_ss = step_ss.contiguous()
+    cfg = loudness_config(rate)
+    lib = L.load()
+    n = lib.bv2_loudness_range_workspace_bytes(C.byref(cfg), B, int(S))
+    if n < 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    keys = ("lra", "st_low", "st_high", "max_short_term", "max_momentary")
+    out = {k: torch.empty(G, dtype=torch.float64, device=dev) for k in keys}
+    out["flags"] = torch.empty(G, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.bv2_loudness_range(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), _ptr(step_ss), step_ss.shape[1],
+                                    _ptr(wl), B, int(S), _ptr(groups), G, *[_ptr(out[k]) for k in keys], _ptr(out["flags"]), _ptr(ws),
+                                    ws.numel())
+    if rc != 0:
+        raise RuntimeError(f"bv2_loudness_range failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return out
+
+
 def _device_groups(groups, ids, dev) -> Optional[torch.Tensor]:
     if groups is None:
         return None
@@ -502,38 +610,79 @@ def _groups_arg(groups, B):
 
 
 @torch.no_grad()
-def loudness(wav, wav_lengths=None, rate: Optional[int] = None, groups=None, want_blocks: bool = False, device=None
-             ) -> Dict[str, torch.Tensor]:
+def loudness(wav, wav_lengths=None, rate: Optional[int] = None, groups=None, want_blocks: bool = False, device=None,
+             true_peak: bool = False, want_range: bool = False) -> Dict[str, torch.Tensor]:
     """Integrated loudness (ITU-R BS.1770-4, mono) of ``wav`` [B, S] or [S] at ``rate`` — fp32, or int16 PCM read as ``x / 32768``; host
     or device, any batch stride; ``wav_lengths`` as in ``resample`` (the padding is never read).  Returns device tensors: ``lufs`` fp64
     [G] (``-inf`` for a group with no block above -70 LUFS), ``peak`` fp32 [B] (sample peak), ``silent`` bool [G] and, with
     ``want_blocks``, ``block_ms`` fp64 [B, blocks(S)] (the block mean squares, ``-0.691 + 10 log10`` of which is the momentary curve).
     ``groups`` [B]: items with one id are the pieces of one programme and are measured together; ``None``: every item on its own, G = B.
-    An item shorter than 400 ms is one block of its own length."""
+    An item shorter than 400 ms is one block of its own length.
+    ``true_peak``: adds ``true_peak`` fp32 [B] (``audio.true_peak``).  ``want_range`` (EBU Tech 3342): adds ``lra`` (LU), ``st_low``,
+    ``st_high``, ``max_short_term``, ``max_momentary`` (LUFS), fp64 [G], and ``range_short`` bool [G] (no whole 3 s block: ``lra`` 0, the
+    rest ``-inf``; a group with nothing above -70 LUFS reads the same and is ``silent``).  The measurement then runs once, as
+    ``loudness_steps`` followed by ``loudness_gate`` and ``loudness_range``; ``lufs`` and ``block_ms`` are the same bits either way."""
     rate, B, S, _, move = _loudness_input(wav, wav_lengths, rate, device)
     ids, G = _groups_arg(groups, B)
     dev, w, wl = move()
-    m = loudness_measure(w, wl, rate, _device_groups(groups, ids, dev), G, want_blocks=want_blocks)
+    g = _device_groups(groups, ids, dev)
+    if want_range:
+        st = loudness_steps(w, wl, rate, want_blocks=True)
+        lens = wl if wl is not None else torch.full((B,), S, dtype=torch.int64, device=dev)
+        m = loudness_gate(st["block_ms"], lens, S, st["peak"], rate, g, G)
+        m["block_ms"] = st["block_ms"]
+    else:
+        m = loudness_measure(w, wl, rate, g, G, want_blocks=want_blocks)
     out = {"lufs": m["lufs"], "peak": m["peak"], "silent": (m["flags"] & L.LOUDNESS_SILENT) != 0}
     if want_blocks:
         out["block_ms"] = m["block_ms"]
+    if true_peak:
+        out["true_peak"] = true_peak_measure(w, wl, rate)
+    if want_range:
+        r = loudness_range(st["step_ss"], wl, S, rate, g, G)
+        out.update({k: r[k] for k in ("lra", "st_low", "st_high", "max_short_term", "max_momentary")})
+        out["range_short"] = (r["flags"] & L.RANGE_SHORT) != 0
     return out
 
 
 @torch.no_grad()
+def true_peak(wav, wav_lengths=None, rate: Optional[int] = None, device=None) -> torch.Tensor:
+    """True peak (ITU-R BS.1770-4 annex 2) of ``wav`` [B, S] or [S] at ``rate``, fp32 [B] on the device; input handling as ``loudness``.
+    It is ``max(|wav|.max(), |resample(wav, rate, F * rate)|.max())`` to the bit — F = 4 below 96 kHz, 2 below 192 kHz, 1 at 192 kHz —
+    without the oversampled signal ever being written.  Amplitude, not dB: ``20 log10`` of it is dBTP."""
+    rate, B, S, _, move = _loudness_input(wav, wav_lengths, rate, device)
+    dev, w, wl = move()
+    return true_peak_measure(w, wl, rate)
+
+
+@torch.no_grad()
 def normalize_loudness(wav, wav_lengths=None, rate: Optional[int] = None, target_lufs: float = -23.0, peak_ceiling_db: float = -1.0,
-                       groups=None, as_pcm16: bool = False, device=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+                       groups=None, as_pcm16: bool = False, device=None, peak: str = "sample"
+                       ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """``wav`` brought to ``target_lufs``: ``(out [B, S], info)`` on the device.  Every group gets ONE static gain ``10^((target - L) /
     20)``, lowered to ``ceiling / peak`` where the group's sample peak would pass ``peak_ceiling_db`` (``info["limited"]``); a silent
     group keeps gain 1.  ``out = wav * gain`` is one fp32 multiply (zeros behind each item's length); ``as_pcm16``: int16
     ``trunc(clamp(v * 32767))`` of that product, the fixed-gain rule of streamed PCM.  ``info``: ``lufs`` fp64 [G], ``gain_db`` fp64 [G],
-    ``gain`` fp32 [G] (the factor that was applied), ``peak`` fp32 [B], ``limited`` and ``silent`` bool [G]."""
+    ``gain`` fp32 [G] (the factor that was applied), ``peak`` fp32 [B], ``limited`` and ``silent`` bool [G].
+    ``peak="true"``: the ceiling is in dBTP — the gain is lowered where the group's TRUE peak (``audio.true_peak``) would pass it, which
+    is what EBU R128 asks for; ``info`` gains ``true_peak`` fp32 [B] and ``info["peak"]`` stays the sample peak."""
+    if peak not in PEAKS:
+        raise ValueError(f"peak must be one of {PEAKS}, got {peak!r}")
     rate, B, S, _, move = _loudness_input(wav, wav_lengths, rate, device)
     ids, G = _groups_arg(groups, B)
     if not (np.isfinite(target_lufs) and np.isfinite(peak_ceiling_db)):
         raise ValueError("target_lufs and peak_ceiling_db must be finite")
     dev, w, wl = move()
     g = _device_groups(groups, ids, dev)
+    if peak == "true":
+        m0 = loudness_measure(w, wl, rate, gate=False)
+        tp = true_peak_measure(w, wl, rate)
+        lens = wl if wl is not None else torch.full((B,), S, dtype=torch.int64, device=dev)
+        m = loudness_gate(m0["block_ms"], lens, S, tp, rate, g, G, target_lufs, peak_ceiling_db)
+        out = loudness_apply(w, wl, rate, m["gain"], g, as_pcm16)
+        info = loudness_info(dict(m, peak=m0["peak"]))
+        info["true_peak"] = tp
+        return out, info
     m = loudness_measure(w, wl, rate, g, G, target_lufs, peak_ceiling_db)
     out = loudness_apply(w, wl, rate, m["gain"], g, as_pcm16)
     return out, loudness_info(m)

@@ -1103,6 +1103,139 @@ int bv2_loudness_apply(bv2_stream stream, const bv2_loudness_config* cfg, const 
   } catch (...) { return fail("exception", -100); }
 }
 
+// ---- true peak (kernels/truepeak.hip) ----------------------------------------------------------------------------
+static_assert(BV2_TRUE_PEAK_TILE == TP_TILE, "BV2_TRUE_PEAK_TILE and TP_TILE are one number");
+
+static int true_peak_factor(const bv2_loudness_config* c) { return c->sample_rate < 96000 ? 4 : (c->sample_rate < 192000 ? 2 : 1); }
+
+int bv2_true_peak_plan(const bv2_loudness_config* cfg, int32_t* factor, int32_t* K) {
+  if (int rc = loudness_check(cfg, "bv2_true_peak_plan")) return rc;
+  const int F = true_peak_factor(cfg);
+  if (F > 1) {                                                                // the table's K comes from the resampler's own plan
+    bv2_resample_config r = {(int32_t)sizeof(bv2_resample_config), cfg->sample_rate, F * cfg->sample_rate, cfg->input_format};
+    ResamplePlan p;
+    if (int rc = resample_plan(&r, "bv2_true_peak_plan", &p)) return rc;
+    if (p.L != F || p.M != 1 || p.K != TP_K) { g_create_err = "bv2_true_peak_plan: the resampler's plan is not (F, 1, 36)"; return -1; }
+  }
+  if (factor) *factor = F;
+  if (K) *K = F > 1 ? TP_K : 0;
+  return 0;
+}
+
+int64_t bv2_true_peak_workspace_bytes(const bv2_loudness_config* cfg, int32_t B, int64_t S) {
+  if (loudness_check(cfg, "bv2_true_peak_workspace_bytes")) return -1;
+  if (B < 1 || B > LD_MAX_B || S < 1 || S > LD_MAX_S) {
+    g_create_err = "bv2_true_peak_workspace_bytes: B must be in [1, " + std::to_string(LD_MAX_B) + "] and S in [1, 2^31 - 4096]";
+    return -1;
+  }
+  return (int64_t)B * ((S + TP_TILE - 1) / TP_TILE) * 4 + 256;
+}
+
+int bv2_true_peak(bv2_stream stream, const bv2_loudness_config* cfg, const float* taps, const void* wav, int64_t wav_bstride,
+                  const int64_t* lengths, int32_t B, int64_t S, float* peak_out, void* workspace, int64_t workspace_bytes) {
+  const char* what = "bv2_true_peak";
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  int32_t F = 0;
+  if (int rc = bv2_true_peak_plan(cfg, &F, nullptr)) { g_create_err = std::string(what) + ": " + g_create_err; return rc; }
+  if (!wav) return fail("wav is null", -1);
+  if (!peak_out) return fail("peak_out is null", -1);
+  if (wav_bstride < 0) return fail("wav_bstride must not be negative", -1);
+  if (F > 1 && !taps) return fail("taps is null (the DEVICE copy of bv2_resample_taps(rate, F * rate))", -1);
+  const int64_t need = (B >= 1 && B <= LD_MAX_B && S >= 1 && S <= LD_MAX_S) ? (int64_t)B * ((S + TP_TILE - 1) / TP_TILE) * 4 : 1;
+  unsigned char* ws = nullptr;
+  if (int rc = loudness_common(what, cfg, B, S, nullptr, B, workspace, workspace_bytes, need, &ws)) return rc;
+  try {
+    TruePeakArgs a;
+    a.wav = wav; a.bstride = wav_bstride; a.lengths = lengths; a.B = B; a.S = S; a.input_format = cfg->input_format;
+    a.factor = F; a.taps = F > 1 ? taps : nullptr;
+    a.tile_peak = reinterpret_cast<float*>(ws); a.peak = peak_out;
+    if (launch_true_peak(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
+// ---- step energies and loudness range (kernels/loudness.hip) -----------------------------------------------------
+static_assert(BV2_RANGE_SHORT == LD_RANGE_SHORT && BV2_RANGE_SILENT == LD_RANGE_SILENT, "BV2_RANGE_* and LD_RANGE_* are one numbering");
+
+int64_t bv2_loudness_steps_count(const bv2_loudness_config* cfg, int64_t n) {
+  if (loudness_check(cfg, "bv2_loudness_steps_count")) return -1;
+  if (n < 0 || n > LD_MAX_S) { g_create_err = "bv2_loudness_steps_count: n must be in [0, 2^31 - 4096]"; return -1; }
+  return n / loudness_step(cfg);
+}
+
+int bv2_loudness_steps(bv2_stream stream, const bv2_loudness_config* cfg, const void* wav, int64_t wav_bstride, const int64_t* lengths,
+                       int32_t B, int64_t S, double* step_ss, int64_t ss_bstride, float* peak, double* block_ms, void* workspace,
+                       int64_t workspace_bytes) {
+  const char* what = "bv2_loudness_steps";
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (int rc = loudness_check(cfg, what)) return rc;
+  if (!wav) return fail("wav is null", -1);
+  if (!step_ss) return fail("step_ss is null", -1);
+  if (wav_bstride < 0) return fail("wav_bstride must not be negative", -1);
+  unsigned char* ws = nullptr;
+  const LoudnessWs lay = (B >= 1 && B <= LD_MAX_B && S >= 1 && S <= LD_MAX_S) ? loudness_ws(loudness_step(cfg), B, S) : LoudnessWs{};
+  if (int rc = loudness_common(what, cfg, B, S, nullptr, B, workspace, workspace_bytes, lay.total ? lay.total : 1, &ws)) return rc;
+  if (ss_bstride < S / loudness_step(cfg)) return fail("ss_bstride is shorter than bv2_loudness_steps_count(S)", -1);
+  try {
+    LoudnessStepsArgs s;
+    LoudnessArgs& a = s.m;
+    a.wav = wav; a.bstride = wav_bstride; a.lengths = lengths; a.B = B; a.S = S; a.step = loudness_step(cfg);
+    a.input_format = cfg->input_format;
+    loudness_filter(cfg->sample_rate, &a.filter);
+    a.tile_z = reinterpret_cast<double*>(ws + lay.tile_z);
+    a.tile_s = reinterpret_cast<double*>(ws + lay.tile_s);
+    a.part = reinterpret_cast<double*>(ws + lay.part);
+    a.tile_peak = reinterpret_cast<float*>(ws + lay.tile_peak);
+    LoudnessGateArgs& g = a.gate;
+    loudness_gate_args(cfg, &g, ws + lay.item, lengths, B, S, nullptr, B, 0.0, 0.0);
+    g.part = a.part; g.tile_peak = a.tile_peak; g.nt = (int)((S + LD_TILE - 1) / LD_TILE);
+    g.block_ms = block_ms ? block_ms : reinterpret_cast<double*>(ws + lay.block_ms);
+    g.ms_bstride = g.ms_width;
+    g.gate = 0;
+    g.lufs = nullptr; g.gain = nullptr; g.flags = nullptr;
+    g.peak = peak ? peak : reinterpret_cast<float*>(ws + lay.item);           // the gate's per-item scratch is idle without a gate
+    s.want_blocks = (peak || block_ms) ? 1 : 0;
+    s.step_ss = step_ss; s.ss_bstride = ss_bstride; s.ss_width = S / a.step;
+    if (launch_loudness_steps(static_cast<hipStream_t>(stream), s)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
+int64_t bv2_loudness_range_workspace_bytes(const bv2_loudness_config* cfg, int32_t B, int64_t S) {
+  if (loudness_check(cfg, "bv2_loudness_range_workspace_bytes")) return -1;
+  if (B < 1 || B > LD_MAX_B || S < 1 || S > LD_MAX_S) {
+    g_create_err = "bv2_loudness_range_workspace_bytes: B must be in [1, " + std::to_string(LD_MAX_B) + "] and S in [1, 2^31 - 4096]";
+    return -1;
+  }
+  return (int64_t)B * std::max<int64_t>(S / loudness_step(cfg), 1) * 8 + 256;
+}
+
+int bv2_loudness_range(bv2_stream stream, const bv2_loudness_config* cfg, const double* step_ss, int64_t ss_bstride, const int64_t* lengths,
+                       int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, double* lra, double* st_low, double* st_high,
+                       double* max_short_term, double* max_momentary, int32_t* flags, void* workspace, int64_t workspace_bytes) {
+  const char* what = "bv2_loudness_range";
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  if (int rc = loudness_check(cfg, what)) return rc;
+  if (!step_ss || !lra || !st_low || !st_high || !max_short_term || !max_momentary || !flags)
+    return fail("step_ss, lra, st_low, st_high, max_short_term, max_momentary and flags must not be null", -1);
+  const int64_t width = (S >= 1 && S <= LD_MAX_S) ? S / loudness_step(cfg) : 0;
+  const int64_t need = (int64_t)(B > 0 && B <= LD_MAX_B ? B : 1) * std::max<int64_t>(width, 1) * 8;
+  unsigned char* ws = nullptr;
+  if (int rc = loudness_common(what, cfg, B, S, groups, n_groups, workspace, workspace_bytes, need, &ws)) return rc;
+  if (ss_bstride < width) return fail("ss_bstride is shorter than bv2_loudness_steps_count(S)", -1);
+  try {
+    LoudnessRangeArgs a;
+    a.step_ss = step_ss; a.ss_bstride = ss_bstride; a.ss_width = width;
+    a.lengths = lengths; a.S = S; a.B = B; a.groups = groups; a.n_groups = n_groups;
+    a.step = loudness_step(cfg);
+    a.abs_ms = std::pow(10.0, (-70.0 + 0.691) / 10.0);
+    a.st = reinterpret_cast<double*>(ws);
+    a.lra = lra; a.st_low = st_low; a.st_high = st_high; a.max_short_term = max_short_term; a.max_momentary = max_momentary; a.flags = flags;
+    if (launch_loudness_range(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
 // ---- documents (kernels/assemble.hip) --------------------------------------------------------------------------
 static_assert(sizeof(bv2_assemble_segment) == sizeof(AssembleSegment) && offsetof(bv2_assemble_segment, samples) == offsetof(AssembleSegment, samples) &&
               offsetof(bv2_assemble_segment, hop) == offsetof(AssembleSegment, hop) && offsetof(bv2_assemble_segment, doc) == offsetof(AssembleSegment, doc),

@@ -921,6 +921,36 @@ struct LoudnessApplyArgs {
 int launch_loudness_measure(hipStream_t stream, const LoudnessArgs& a);   // four launches
 int launch_loudness_gate(hipStream_t stream, const LoudnessGateArgs& a);
 int launch_loudness_apply(hipStream_t stream, const LoudnessApplyArgs& a);
+// step energies and loudness range (EBU Tech 3342; kernels/loudness.hip)
+constexpr int LD_ST_STEPS = 30;                      // a short-term block: 3 s, every 100 ms
+constexpr int LD_RANGE_SHORT = 1, LD_RANGE_SILENT = 2;   // include/bv2.h BV2_RANGE_SHORT / BV2_RANGE_SILENT
+struct LoudnessStepsArgs {
+  LoudnessArgs m;                                    // the three tile launches; m.gate runs (blocks and peaks, gate 0) when want_blocks
+  int want_blocks;
+  double* step_ss; int64_t ss_bstride, ss_width;     // [B][ss_bstride >= ss_width]; ss_width = S / step; zeros behind an item's whole steps
+};
+struct LoudnessRangeArgs {
+  const double* step_ss; int64_t ss_bstride, ss_width;
+  const int64_t* lengths; int64_t S; int B;
+  const int* groups; int n_groups;                   // as LoudnessGateArgs
+  int step;
+  double abs_ms;
+  double* st;                                        // workspace [B][max(ss_width, 1)]: the items' short-term energies
+  double *lra, *st_low, *st_high, *max_short_term, *max_momentary; int* flags;   // [n_groups] each
+};
+int launch_loudness_steps(hipStream_t stream, const LoudnessStepsArgs& a);   // three tile launches, (blocks and peaks,) the steps
+int launch_loudness_range(hipStream_t stream, const LoudnessRangeArgs& a);   // two launches
+
+// --- true peak (kernels/truepeak.hip): the resampler's rate -> factor * rate outputs, fused with max |.|; nothing is written but peaks ---
+constexpr int TP_THREADS = 256, TP_PER = 4, TP_TILE = TP_THREADS * TP_PER, TP_K = 36;   // include/bv2.h BV2_TRUE_PEAK_TILE
+struct TruePeakArgs {
+  const void* wav; int64_t bstride; const int64_t* lengths; int B; int64_t S; int input_format;
+  int factor;                                        // 4, 2 or 1
+  const float* taps;                                 // [factor][2 TP_K + 1], DEVICE; null when factor == 1
+  float* tile_peak;                                  // [B][ceil(S / TP_TILE)]
+  float* peak;                                       // [B]
+};
+int launch_true_peak(hipStream_t stream, const TruePeakArgs& a);          // two launches
 
 // --- documents (kernels/assemble.hip): pieces and pauses joined into one buffer per document; layout, peaks, write ---
 constexpr int AS_THREADS = 256, AS_LAYOUT_THREADS = 1024;

@@ -346,7 +346,8 @@ __global__ void __launch_bounds__(LD_THREADS) loudness_apply_kernel(const T* src
   }
 }
 
-int launch_loudness_measure(hipStream_t stream, const LoudnessArgs& a) {
+// launches 1 to 3 of a measurement
+static int launch_loudness_tiles(hipStream_t stream, const LoudnessArgs& a) {
   if (a.B < 1 || a.B > 65535 || a.S < 1 || a.step <= LD_SEG) return -1;
   const int64_t nt = (a.S + LD_TILE - 1) / LD_TILE;
   const int nparts = (LD_TILE - 1) / a.step + 2;
@@ -369,7 +370,11 @@ int launch_loudness_measure(hipStream_t stream, const LoudnessArgs& a) {
     hipLaunchKernelGGL((loudness_tile_kernel<float, true>), grid, block, 0, stream, w, a.bstride, a.lengths, a.S, (int)nt, a.step, nparts,
                        a.filter, a.tile_z, a.tile_s, a.part, a.tile_peak);
   }
-  if (BV2_CHECK_LAUNCH()) return -1;
+  return BV2_CHECK_LAUNCH();
+}
+
+int launch_loudness_measure(hipStream_t stream, const LoudnessArgs& a) {
+  if (launch_loudness_tiles(stream, a)) return -1;
   return launch_loudness_gate(stream, a.gate);
 }
 
@@ -393,6 +398,202 @@ int launch_loudness_apply(hipStream_t stream, const LoudnessApplyArgs& a) {
   else
     hipLaunchKernelGGL(loudness_apply_kernel<float>, grid, block, 0, stream, static_cast<const float*>(a.src), a.src_bstride, a.lengths, a.S,
                        a.groups, a.n_gain, a.gain, a.dst, a.dst16, a.dst_bstride);
+  return BV2_CHECK_LAUNCH();
+}
+
+// ---- step energies and loudness range (EBU Tech 3342; include/bv2.h bv2_loudness_steps / bv2_loudness_range) ----
+// step_ss[b][k]: the energy of the item's whole step k — ld_step_energy, the sum the gate kernel forms for the same step, so four of
+// them added in order and divided by the block are the bits of block_ms.  The range then works on step energies alone:
+//   1. loudness_st_kernel     grid (steps, B): short-term energy s_j = (30 steps, added in ascending order) / (30 step)        -> st
+//   2. loudness_range_kernel  one workgroup per group: both gates of Tech 3342 over the group's pooled short-term blocks, the two
+//                             percentiles by a radix select over the fp64 bit patterns (a positive double orders as its uint64: 8
+//                             passes of 8-bit histograms, integer atomics in LDS only — exact, the elements a sort would return), and
+//                             the maxima of the short-term and the momentary (four steps) energies
+__global__ void __launch_bounds__(LD_THREADS) loudness_steps_kernel(const double* part, const int64_t* lengths, int64_t S, int nt, int step,
+                                                                    double* step_ss, int64_t ss_bstride, int64_t ss_width) {
+  const int b = blockIdx.y;
+  const int64_t k = (int64_t)blockIdx.x * LD_THREADS + threadIdx.x;
+  if (k >= ss_width) return;
+  const int64_t n = ld_item_len(lengths, b, S);
+  step_ss[(size_t)b * ss_bstride + k] = k < n / step ? ld_step_energy(part + (size_t)b * nt * LD_MAX_PARTS, k, n, step) : 0.0;
+}
+
+__device__ __forceinline__ int64_t ld_st_blocks(int64_t n, int step) {
+  const int64_t steps = n / step;
+  return steps >= LD_ST_STEPS ? steps - (LD_ST_STEPS - 1) : 0;
+}
+
+__global__ void __launch_bounds__(LD_THREADS) loudness_st_kernel(LoudnessRangeArgs a) {
+  const int b = blockIdx.y;
+  const int64_t j = (int64_t)blockIdx.x * LD_THREADS + threadIdx.x;
+  const int64_t stw = a.ss_width > 0 ? a.ss_width : 1;
+  if (j >= stw) return;
+  double v = 0.0;
+  if (j < ld_st_blocks(ld_item_len(a.lengths, b, a.S), a.step)) {
+    const double* e = a.step_ss + (size_t)b * a.ss_bstride + j;
+    double s = 0.0;
+    for (int q = 0; q < LD_ST_STEPS; ++q) s += e[q];
+    v = s / ((double)LD_ST_STEPS * (double)a.step);
+  }
+  a.st[(size_t)b * stw + j] = v;
+}
+
+__device__ __forceinline__ double ld_block_sum(double* red, double v) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int stride = LD_THREADS / 2; stride >= 1; stride >>= 1) {
+    if (tid < stride) red[tid] += red[tid + stride];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__device__ __forceinline__ double ld_block_max(double* red, double v) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int stride = LD_THREADS / 2; stride >= 1; stride >>= 1) {
+    if (tid < stride) red[tid] = fmax(red[tid], red[tid + stride]);
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// the element of rank `rank` (zero-based, ascending) among the group's short-term energies above both thresholds, as its bit pattern
+__device__ unsigned long long ld_select(const LoudnessRangeArgs& a, int g, int b_lo, int b_hi, double thr, int64_t rank, unsigned* hist,
+                                        unsigned* runs, unsigned long long* pick) {
+  const int tid = threadIdx.x;
+  const int64_t stw = a.ss_width > 0 ? a.ss_width : 1;
+  unsigned long long prefix = 0;
+  __syncthreads();
+  if (tid == 0) pick[1] = (unsigned long long)rank;                          // the rank inside the bin that is still open
+  for (int pass = 7; pass >= 0; --pass) {
+    const int shift = 8 * pass;
+    __syncthreads();
+    hist[tid] = 0u;
+    __syncthreads();
+    for (int b = b_lo; b < b_hi; ++b) {
+      if (a.groups && a.groups[b] != g) continue;                            // block-uniform
+      const int64_t nst = ld_st_blocks(ld_item_len(a.lengths, b, a.S), a.step);
+      const double* st = a.st + (size_t)b * stw;
+      for (int64_t j = tid; j < nst; j += LD_THREADS) {
+        const double v = st[j];
+        if (!(v > a.abs_ms && v > thr)) continue;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
+        if (pass == 7 || (bits >> (shift + 8)) == prefix) atomicAdd(&hist[(unsigned)(bits >> shift) & 255u], 1u);
+      }
+    }
+    __syncthreads();
+    if (tid < 16) {                                                          // the bin that holds the rank: 16 runs of 16 bins, then one run
+      unsigned t = 0;
+      for (int i = 0; i < 16; ++i) t += hist[tid * 16 + i];
+      runs[tid] = t;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int64_t r = (int64_t)pick[1], cum = 0;
+      int run = 0;
+      for (; run < 15; ++run) {
+        if (cum + (int64_t)runs[run] > r) break;
+        cum += runs[run];
+      }
+      int bin = run * 16;
+      for (; bin < run * 16 + 15; ++bin) {
+        if (cum + (int64_t)hist[bin] > r) break;
+        cum += hist[bin];
+      }
+      pick[0] = (prefix << 8) | (unsigned long long)bin;
+      pick[1] = (unsigned long long)(r - cum);
+    }
+    __syncthreads();
+    prefix = pick[0];
+  }
+  return prefix;
+}
+
+__global__ void __launch_bounds__(LD_THREADS) loudness_range_kernel(LoudnessRangeArgs a) {
+  __shared__ double red[LD_THREADS];
+  __shared__ unsigned hist[LD_THREADS];
+  __shared__ unsigned runs[16];
+  __shared__ unsigned long long pick[2];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int b_lo = a.groups ? 0 : g, b_hi = a.groups ? a.B : g + 1;
+  const int64_t stw = a.ss_width > 0 ? a.ss_width : 1;
+  const double block = 4.0 * (double)a.step;
+
+  double s = 0.0, c = 0.0, total = 0.0, mx_st = 0.0, mx_mo = 0.0;            // counts as doubles: exact below 2^53
+  for (int b = b_lo; b < b_hi; ++b) {
+    if (a.groups && a.groups[b] != g) continue;                              // block-uniform
+    const int64_t n = ld_item_len(a.lengths, b, a.S);
+    const int64_t nst = ld_st_blocks(n, a.step);
+    const int64_t nmo = n / a.step >= 4 ? n / a.step - 3 : 0;
+    const double* st = a.st + (size_t)b * stw;
+    const double* e = a.step_ss + (size_t)b * a.ss_bstride;
+    for (int64_t j = tid; j < nst; j += LD_THREADS) {
+      const double v = st[j];
+      total += 1.0;
+      mx_st = fmax(mx_st, v);
+      if (v > a.abs_ms) { s += v; c += 1.0; }
+    }
+    for (int64_t j = tid; j < nmo; j += LD_THREADS) mx_mo = fmax(mx_mo, (((e[j] + e[j + 1]) + e[j + 2]) + e[j + 3]) / block);
+  }
+  s = ld_block_sum(red, s);
+  c = ld_block_sum(red, c);
+  total = ld_block_sum(red, total);
+  mx_st = ld_block_max(red, mx_st);
+  mx_mo = ld_block_max(red, mx_mo);
+
+  int flags = 0;
+  if (total == 0.0) flags = LD_RANGE_SHORT;
+  else if (c == 0.0) flags = LD_RANGE_SILENT;
+  double lra = 0.0, lo_l = -INFINITY, hi_l = -INFINITY, st_l = -INFINITY, mo_l = -INFINITY;
+  if (!flags) {                                                              // block-uniform
+    const double thr = s / c * 0.01;                                         // 20 LU below the absolute-gated mean
+    double kept = 0.0;
+    for (int b = b_lo; b < b_hi; ++b) {
+      if (a.groups && a.groups[b] != g) continue;
+      const int64_t nst = ld_st_blocks(ld_item_len(a.lengths, b, a.S), a.step);
+      const double* st = a.st + (size_t)b * stw;
+      for (int64_t j = tid; j < nst; j += LD_THREADS) {
+        const double v = st[j];
+        kept += (v > a.abs_ms && v > thr) ? 1.0 : 0.0;
+      }
+    }
+    kept = ld_block_sum(red, kept);
+    const int64_t nk = (int64_t)kept;                                        // >= 1: the largest gated block is above 0.01 of their mean
+    const int64_t r_lo = ((nk - 1) * 10 + 50) / 100, r_hi = ((nk - 1) * 95 + 50) / 100;
+    const double v_lo = __longlong_as_double((long long)ld_select(a, g, b_lo, b_hi, thr, r_lo, hist, runs, pick));
+    const double v_hi = __longlong_as_double((long long)ld_select(a, g, b_lo, b_hi, thr, r_hi, hist, runs, pick));
+    lra = 10.0 * log10(v_hi / v_lo);
+    lo_l = -0.691 + 10.0 * log10(v_lo);
+    hi_l = -0.691 + 10.0 * log10(v_hi);
+    st_l = -0.691 + 10.0 * log10(mx_st);
+    mo_l = -0.691 + 10.0 * log10(mx_mo);
+  }
+  if (tid == 0) {
+    a.lra[g] = lra; a.st_low[g] = lo_l; a.st_high[g] = hi_l; a.max_short_term[g] = st_l; a.max_momentary[g] = mo_l; a.flags[g] = flags;
+  }
+}
+
+int launch_loudness_steps(hipStream_t stream, const LoudnessStepsArgs& a) {
+  if (launch_loudness_tiles(stream, a.m)) return -1;
+  if (a.want_blocks && launch_loudness_gate(stream, a.m.gate)) return -1;
+  if (a.ss_width < 1) return 0;                                              // S is shorter than a step: no item has one
+  const int64_t gx = (a.ss_width + LD_THREADS - 1) / LD_THREADS;
+  hipLaunchKernelGGL(loudness_steps_kernel, dim3((unsigned)gx, (unsigned)a.m.B), dim3(LD_THREADS), 0, stream, a.m.part, a.m.lengths, a.m.S,
+                     a.m.gate.nt, a.m.step, a.step_ss, a.ss_bstride, a.ss_width);
+  return BV2_CHECK_LAUNCH();
+}
+
+int launch_loudness_range(hipStream_t stream, const LoudnessRangeArgs& a) {
+  if (a.B < 1 || a.B > 65535 || a.n_groups < 1 || a.n_groups > 65535 || a.step < 1 || (!a.groups && a.n_groups != a.B)) return -1;
+  const int64_t stw = a.ss_width > 0 ? a.ss_width : 1;
+  const int64_t gx = (stw + LD_THREADS - 1) / LD_THREADS;
+  hipLaunchKernelGGL(loudness_st_kernel, dim3((unsigned)gx, (unsigned)a.B), dim3(LD_THREADS), 0, stream, a);
+  hipLaunchKernelGGL(loudness_range_kernel, dim3(a.n_groups), dim3(LD_THREADS), 0, stream, a);
   return BV2_CHECK_LAUNCH();
 }
 

@@ -111,6 +111,8 @@ class LoudnessConfig(C.Structure):
 
 
 LOUDNESS_SILENT, LOUDNESS_LIMITED = 1, 2
+RANGE_SHORT, RANGE_SILENT = 1, 2
+TRUE_PEAK_TILE = 1024      # include/bv2.h BV2_TRUE_PEAK_TILE
 
 
 class AssembleSegment(C.Structure):
@@ -203,6 +205,15 @@ SYMBOLS = [
                                     C.c_double, _P, _P, _P, _P, C.c_int64]),
     ("bv2_loudness_apply", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P, _P,
                                      C.c_int64]),
+    ("bv2_true_peak_plan", C.c_int, [C.POINTER(LoudnessConfig), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("bv2_true_peak_workspace_bytes", C.c_int64, [C.POINTER(LoudnessConfig), C.c_int32, C.c_int64]),
+    ("bv2_true_peak", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64]),
+    ("bv2_loudness_steps_count", C.c_int64, [C.POINTER(LoudnessConfig), C.c_int64]),
+    ("bv2_loudness_steps", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P, _P,
+                                     C.c_int64]),
+    ("bv2_loudness_range_workspace_bytes", C.c_int64, [C.POINTER(LoudnessConfig), C.c_int32, C.c_int64]),
+    ("bv2_loudness_range", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P, _P, _P,
+                                     _P, _P, _P, C.c_int64]),
     ("bv2_assemble_plan", C.c_int, [C.POINTER(AssembleConfig), C.POINTER(AssembleSegment), C.c_int32, C.c_int32, C.c_int32,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("bv2_assemble_workspace_bytes", C.c_int64, [C.POINTER(AssembleConfig), C.c_int32, C.c_int32, C.c_int32]),

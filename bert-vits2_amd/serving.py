@@ -235,7 +235,7 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
                max_batch: int = 32, max_pad_ratio: float = 1.25, as_pcm16: bool = False,
                noise: Optional[Sequence] = None, requests_in_flight: int = 1, output_rate: Optional[int] = None,
                target_lufs: Optional[float] = None, peak_ceiling_db: float = -1.0, loudness_groups: Optional[Sequence] = None,
-               return_levels: bool = False) -> List[np.ndarray]:
+               return_levels: bool = False, peak: str = "sample") -> List[np.ndarray]:
     """Synthesise every utterance; returns one 1-D array per utterance in input order (float32 like reference
     infer.py:315-319, or int16 with ``as_pcm16``).  Defaults are the reference web UI's (webui.py:443-454).
     ``noise`` (tests): per utterance a pair ``(noise_w [2,T], noise_z [inter, >= T_y])`` to inject instead of drawing.
@@ -259,7 +259,9 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     last bucket has run, then one gating launch and one multiply per bucket follow (ungrouped calls keep the overlap of a bucket's copy
     with the next bucket's kernels).  ``return_levels``: ``(audio, levels)`` with one dict per utterance — ``lufs`` (measured, of its
     group), ``gain_db`` and ``gain`` (the fp32 factor that was applied), ``peak`` (its own sample peak before the gain), ``limited``,
-    ``silent``."""
+    ``silent``.  ``peak="true"``: ``peak_ceiling_db`` is in dBTP — the gain is lowered where the TRUE peak (``audio.true_peak``, measured
+    on the device at the output rate) of the utterance, or of its group, would pass the ceiling; the levels then carry ``true_peak``
+    beside ``peak``.  ``"sample"`` is today's output to the bit; ``"true"`` without ``target_lufs`` raises."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
     if noise is not None and any(u.seed is not None for u in utts):
@@ -269,7 +271,7 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     output_rate = _output_rate(model, output_rate)
     if output_rate is not None:
         hop = 1                                            # the buckets' lengths then count output-rate samples
-    level = _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels)
+    level = _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels, peak)
     results: List[Optional[np.ndarray]] = [None] * len(utts)
     pending = []
     lanes = replicas(model, requests_in_flight) if requests_in_flight > 1 else [(model, None)]
@@ -298,9 +300,11 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
         for r, i in enumerate(idx):
             results[i] = host[r, :int(y_len[r]) * hop].numpy().copy()
             if lv:
-                lufs, gain, peak, flags = (float(v) for v in lv[0][:, r])
-                levels[i] = dict(lufs=lufs, gain_db=20.0 * math.log10(gain), gain=gain, peak=peak, limited=bool(int(flags) & 2),
+                lufs, gain, pk, flags = (float(v) for v in lv[0][:4, r])
+                levels[i] = dict(lufs=lufs, gain_db=20.0 * math.log10(gain), gain=gain, peak=pk, limited=bool(int(flags) & 2),
                                  silent=bool(int(flags) & 1))
+                if lv[0].shape[0] > 4:                         # peak="true"
+                    levels[i]["true_peak"] = float(lv[0][4, r])
     return (results, levels) if return_levels else results
 
 
@@ -354,7 +358,8 @@ def document_timeline(documents, rate: int, *, interval_between_sent=0.2, interv
 def synthesize_documents(model, documents, *, interval_between_sent: float = 0.2, interval_between_para: float = 1.0,
                          cut_by_sent: bool = True, level: str = "piece", target_lufs: Optional[float] = None,
                          peak_ceiling_db: float = -1.0, as_pcm16: bool = True, output_rate: Optional[int] = None,
-                         return_offsets: bool = False, sdp_ratio=0.5, noise_scale=0.6, noise_scale_w=0.9, length_scale=1.0,
+                         return_offsets: bool = False, peak: str = "sample", sdp_ratio=0.5, noise_scale=0.6, noise_scale_w=0.9,
+                         length_scale=1.0,
                          max_batch: int = 32, max_pad_ratio: float = 1.25, noise: Optional[Sequence] = None,
                          requests_in_flight: int = 1):
     """Whole documents: what the reference's web UI does behind synthesis (webui.py ``tts_split`` / ``generate_audio``) on the device —
@@ -368,7 +373,8 @@ def synthesize_documents(model, documents, *, interval_between_sent: float = 0.2
     (``synthesize(as_pcm16=True)`` joined with zero pauses); ``"paragraph"`` / ``"document"`` — under the peak of its paragraph / document,
     which keeps the level differences inside it.  ``target_lufs``: every document is measured as one programme (``synthesize``'s
     ``loudness_groups``) and leaves at that loudness under ``peak_ceiling_db``: one gain per document, the fixed-gain 16-bit form; it
-    overrides ``level``.  ``as_pcm16=False``: fp32 (``x / peak``, or ``x * gain``).
+    overrides ``level``; ``peak="true"`` puts the ceiling in dBTP (the document's true peak, ``synthesize``'s ``peak``).
+    ``as_pcm16=False``: fp32 (``x / peak``, or ``x * gain``).
     Returns one 1-D array per document; with ``return_offsets`` ``(audio, offsets)``, ``offsets[d]`` a list of ``(start sample, length)``
     per piece of document d in reading order — for subtitles and highlighting."""
     from . import audio
@@ -384,7 +390,7 @@ def synthesize_documents(model, documents, *, interval_between_sent: float = 0.2
     if noise is not None and any(u.seed is not None for u in utts):
         raise ValueError("noise= (injected tensors) and Utterance(seed=...) exclude each other")
     doc_of = [d for d, line in enumerate(timeline) for e in line if e[0] == "piece"]
-    loud = _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, doc_of if target_lufs is not None else None, False)
+    loud = _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, doc_of if target_lufs is not None else None, False, peak)
     hop = model.hp.total_upsample if output_rate is None else 1
     lanes = replicas(model, requests_in_flight) if requests_in_flight > 1 else [(model, None)]
     call = dict(sdp_ratio=sdp_ratio, noise_scale=noise_scale, noise_scale_w=noise_scale_w, length_scale=length_scale)
@@ -457,15 +463,19 @@ def synthesize_documents(model, documents, *, interval_between_sent: float = 0.2
     return results, [[(off[s], e - off[s]) for s, e in zip(rows, ends[d])] for d, rows in enumerate(pieces)]
 
 
-def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels) -> Optional[dict]:
+def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels, peak="sample") -> Optional[dict]:
     """The loudness arguments of ``synthesize``, checked before any work: ``None`` without a target."""
+    from . import audio
+    if peak not in audio.PEAKS:
+        raise ValueError(f"peak must be one of {audio.PEAKS}, got {peak!r}")
     if target_lufs is None:
         if loudness_groups is not None or return_levels:
             raise ValueError("loudness_groups and return_levels need target_lufs")
+        if peak != "sample":
+            raise ValueError("peak='true' needs target_lufs")
         return None
     if not (math.isfinite(float(target_lufs)) and math.isfinite(float(peak_ceiling_db))):
         raise ValueError("target_lufs and peak_ceiling_db must be finite")
-    from . import audio
     rate = int(output_rate if output_rate is not None else model.hp.sampling_rate)
     audio.loudness_plan(rate)                               # ValueError naming the envelope
     ids = None
@@ -475,7 +485,7 @@ def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness
             raise ValueError("loudness_groups takes one hashable per utterance")
         dense = {}
         ids = [dense.setdefault(k, len(dense)) for k in keys]
-    return dict(rate=rate, target=float(target_lufs), ceiling=float(peak_ceiling_db), ids=ids, held=[])
+    return dict(rate=rate, target=float(target_lufs), ceiling=float(peak_ceiling_db), ids=ids, held=[], true=peak == "true")
 
 
 def _gate_held(level, dev):
@@ -493,7 +503,8 @@ def _gate_held(level, dev):
     rows = [i for h in held for i in h["idx"]]
     groups = torch.tensor([level["ids"][i] for i in rows], dtype=torch.int32).to(dev)
     n_groups = max(level["ids"]) + 1
-    m = audio.loudness_gate(ms, torch.cat([h["lens"] for h in held]), S, torch.cat([h["peak"] for h in held]), level["rate"], groups,
+    which = "true_peak" if level["true"] else "peak"         # what the ceiling limits
+    m = audio.loudness_gate(ms, torch.cat([h["lens"] for h in held]), S, torch.cat([h[which] for h in held]), level["rate"], groups,
                             n_groups, level["target"], level["ceiling"])
     return m, groups
 
@@ -514,8 +525,10 @@ def _level_groups(level, pending, as_pcm16, dev):
             torch.cuda.current_stream(dev).wait_event(gated)
             out = audio.loudness_apply(h["wave"], h["lens"], level["rate"], m["gain"], g, as_pcm16)
             gl = g.long()
-            lv = torch.stack([m["lufs"][gl], m["gain"][gl].double(), h["peak"].double(), m["flags"][gl].double()])
-            _enqueue_copy(pending, h["idx"], out, h["y_len"], lv)
+            lv = [m["lufs"][gl], m["gain"][gl].double(), h["peak"].double(), m["flags"][gl].double()]
+            if level["true"]:
+                lv.append(h["true_peak"].double())
+            _enqueue_copy(pending, h["idx"], out, h["y_len"], torch.stack(lv))
         o += B
 
 
@@ -573,6 +586,13 @@ def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio
     if level is None:
         audio = pcm16(model, wave[:, None], y_len, hop=None if output_rate is None else 1) if as_pcm16 else wave
         _enqueue_copy(pending, idx, audio, y_len)
+    elif level["ids"] is None and level["true"]:       # the same, under a true-peak ceiling: blocks and sample peaks, true peaks, the gate
+        m0 = _audio.loudness_measure(wave, lens, level["rate"], gate=False)
+        tp = _audio.true_peak_measure(wave, lens, level["rate"])
+        m = _audio.loudness_gate(m0["block_ms"], lens, wave.shape[1], tp, level["rate"], None, wave.shape[0], level["target"], level["ceiling"])
+        audio = _audio.loudness_apply(wave, lens, level["rate"], m["gain"], None, as_pcm16)
+        _enqueue_copy(pending, idx, audio, y_len,
+                      torch.stack([m["lufs"], m["gain"].double(), m0["peak"].double(), m["flags"].double(), tp.double()]))
     elif level["ids"] is None:                         # every utterance its own programme: measure, scale, copy
         m = _audio.loudness_measure(wave, lens, level["rate"], None, None, level["target"], level["ceiling"])
         audio = _audio.loudness_apply(wave, lens, level["rate"], m["gain"], None, as_pcm16)
@@ -582,12 +602,14 @@ def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio
 
 
 def _hold_levels(level, idx, wave, lens, y_len, dev):
-    """A bucket of a grouped measurement: its block energies and peaks, and an event behind them, in ``level["held"]``."""
+    """A bucket of a grouped measurement: its block energies and peaks (the true peaks beside the sample peaks where the ceiling is in
+    dBTP), and an event behind them, in ``level["held"]``."""
     from . import audio as _audio
     m = _audio.loudness_measure(wave, lens, level["rate"], gate=False)
+    tp = _audio.true_peak_measure(wave, lens, level["rate"]) if level["true"] else None
     ev = torch.cuda.Event()
     ev.record()
-    level["held"].append(dict(idx=idx, wave=wave, lens=lens, y_len=y_len, block_ms=m["block_ms"], peak=m["peak"], ev=ev,
+    level["held"].append(dict(idx=idx, wave=wave, lens=lens, y_len=y_len, block_ms=m["block_ms"], peak=m["peak"], true_peak=tp, ev=ev,
                               stream=torch.cuda.current_stream(dev)))
 
 

@@ -521,6 +521,61 @@ int bv2_loudness_apply(bv2_stream stream, const bv2_loudness_config* cfg, const 
                        int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, const float* gain, float* dst_f32, int16_t* dst_i16,
                        int64_t dst_bstride);
 
+/* ---- true peak (ITU-R BS.1770-4 annex 2; kernels/truepeak.hip) ---------------------------------------------------------------
+ * The oversampling factor F follows the sampling rate: F = 4 below 96 000, F = 2 from 96 000 to below 192 000, F = 1 at 192 000 (true peak =
+ * sample peak).  For F > 1 the interpolator is the project's own polyphase table for rate -> F rate: L = F, M = 1, c = 0.91, K = 36, 73 taps
+ * per phase — bv2_resample_taps at that rate pair.  Item b's true peak is
+ *   max( max_k |x_b[k]| , max_n |y_b[n]| ),
+ * y_b EXACTLY the outputs bv2_resample produces for that rate pair: every output one fmaf chain over ascending jj from 0.f, fp32 table
+ * values, samples outside [0, len_b) selected to zero and never loaded, int16 read as x / 32768 — so |y| here and there are the same bits,
+ * alone and in any batch, at any row and batch stride.  The maximum with the sample peak is part of the definition (phase 0 of the table is
+ * not the identity: its centre tap is 0.91), so true peak >= sample peak always.  The result is fp32 [B]; an item of length 0 gives 0.  The
+ * oversampled signal is never written.
+ * Non-finite input, as for the sample peak of bv2_loudness_measure: the maximum skips NaN operands (fmaxf), so a NaN sample and the outputs
+ * it reaches do not count; an infinite sample gives +inf.
+ * A workgroup owns BV2_TRUE_PEAK_TILE input samples of one item, counted from the item's first sample.  Envelope, argument checks before
+ * anything touches the device and error codes are those of the loudness calls (cfg is a bv2_loudness_config); asynchronous on `stream`, no
+ * allocation, no host sync, two launches. */
+enum { BV2_TRUE_PEAK_TILE = 1024 };
+/* HOST: F and K at cfg's sampling rate (K = 0 when F = 1); each pointer may be NULL. */
+int bv2_true_peak_plan(const bv2_loudness_config* cfg, int32_t* factor, int32_t* K);
+/* Bytes of DEVICE workspace of bv2_true_peak at (B, S): one fp32 per tile. */
+int64_t bv2_true_peak_workspace_bytes(const bv2_loudness_config* cfg, int32_t B, int64_t S);
+/* wav, wav_bstride, lengths, B, S as in bv2_loudness_measure; taps is the DEVICE copy of bv2_resample_taps(rate, F rate) — NULL when
+ * F = 1; peak_out fp32 [B] DEVICE. */
+int bv2_true_peak(bv2_stream stream, const bv2_loudness_config* cfg, const float* taps, const void* wav, int64_t wav_bstride,
+                  const int64_t* lengths, int32_t B, int64_t S, float* peak_out, void* workspace, int64_t workspace_bytes);
+
+/* ---- step energies, short-term loudness and loudness range (EBU Tech 3342; kernels/loudness.hip) --------------------------------
+ * step_ss[b][k], k < steps(len_b) = len_b / step (whole steps only), is the sum of squares of the K-weighted samples [k step, (k + 1) step)
+ * of item b, formed from the tiles' partial sums in tile order — the order the gate uses for a step.  For an item of at least one block,
+ *   (((e_j + e_{j+1}) + e_{j+2}) + e_{j+3}) / block   is block_ms[j] BIT FOR BIT: it is the expression the gate evaluates.
+ * Short-term block j of an item covers its steps [j, j + 30) (3 s every 100 ms), only whole blocks count: energy s_j = (the 30 step sums
+ * added in ascending order) / (30 step), loudness -0.691 + 10 log10 s_j.  Blocks never span two items; a group pools the short-term blocks
+ * of its items, as the integrated measurement pools its 400 ms blocks.  Gating (Tech 3342): the blocks above -70 LUFS; of those, the blocks
+ * above (-0.691 + 10 log10 of their mean energy) - 20.  Of the n values left, sorted ascending r[0..n): lo = ((n - 1) 10 + 50) / 100,
+ * hi = ((n - 1) 95 + 50) / 100 (integer division), LRA = 10 log10(r[hi] / r[lo]).  The selection is exact — r[lo] and r[hi] are the elements
+ * a sort would return (a radix select over the bit patterns) — and all of it is fp64.  max_momentary is the maximum over the 400 ms
+ * blocks formed from four whole steps.  flags: BV2_RANGE_SHORT when the group has no whole 3 s block, BV2_RANGE_SILENT when no short-term
+ * block passes -70; with either, lra = 0 and the four LUFS outputs are -inf. */
+enum { BV2_RANGE_SHORT = 1, BV2_RANGE_SILENT = 2 };
+/* HOST: whole steps of an item of n samples, n / step; negative for a bad config or n outside [0, 2^31 - 4096]. */
+int64_t bv2_loudness_steps_count(const bv2_loudness_config* cfg, int64_t n);
+/* The measurement's three tile launches and one more that writes step_ss fp64 [B][ss_bstride >= bv2_loudness_steps_count(S)] (zeros behind
+ * an item's whole steps).  peak fp32 [B] and block_ms fp64 [B][bv2_loudness_blocks(S)] may be NULL; if either is given, the launch that forms
+ * them in bv2_loudness_measure runs too, and they are what that call returns.  Workspace: bv2_loudness_workspace_bytes(cfg, B, S). */
+int bv2_loudness_steps(bv2_stream stream, const bv2_loudness_config* cfg, const void* wav, int64_t wav_bstride, const int64_t* lengths,
+                       int32_t B, int64_t S, double* step_ss, int64_t ss_bstride, float* peak, double* block_ms, void* workspace,
+                       int64_t workspace_bytes);
+/* Bytes of DEVICE workspace of bv2_loudness_range at (B, S): the items' short-term energies. */
+int64_t bv2_loudness_range_workspace_bytes(const bv2_loudness_config* cfg, int32_t B, int64_t S);
+/* Two launches.  step_ss [B][ss_bstride >= bv2_loudness_steps_count(S)], lengths and groups (as in bv2_loudness_gate) are inputs, possibly
+ * gathered from several bv2_loudness_steps calls.  Outputs, all DEVICE [n_groups]: lra, st_low, st_high (LUFS at the two percentiles),
+ * max_short_term, max_momentary fp64; flags int32. */
+int bv2_loudness_range(bv2_stream stream, const bv2_loudness_config* cfg, const double* step_ss, int64_t ss_bstride, const int64_t* lengths,
+                       int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, double* lra, double* st_low, double* st_high,
+                       double* max_short_term, double* max_momentary, int32_t* flags, void* workspace, int64_t workspace_bytes);
+
 /* ---- documents: sentences joined on the device with pauses, one buffer per document (handle-free; kernels/assemble.hip) --------
  * What the reference's callers do on the host after synthesis (webui.py tts_split / generate_audio, hiyoriUI.py:319-349): every piece
  * peak-normalised to 16 bit, a pause behind every sentence, a longer one behind every paragraph, everything concatenated.  tts_split
