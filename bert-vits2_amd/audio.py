@@ -522,6 +522,79 @@ def true_peak_measure(wav: torch.Tensor, wl: Optional[torch.Tensor], rate: int) 
     return out
 
 
+def limiter_config(rate: int, lookahead_ms: float = 3.0, release_ms: float = 60.0, input_format: int = L.WAV_F32) -> L.LimiterConfig:
+    c = L.LimiterConfig()
+    c.struct_bytes = C.sizeof(L.LimiterConfig)
+    c.sample_rate, c.input_format, c.reserved = int(rate), int(input_format), 0
+    c.lookahead_ms, c.release_ms = float(lookahead_ms), float(release_ms)
+    return c
+
+
+def limiter_plan(rate: int, lookahead_ms: float = 3.0, release_ms: float = 60.0) -> Tuple[int, int, int, int]:
+    """``(H, P, F, K)`` of the limiter (``bv2_limiter_plan``): ``H = max(1, round(lookahead_ms rate / 2000))``, ``P = max(H,
+    round(release_ms rate / 2000))`` and the true-peak plan's oversampling factor and reach.  ``ValueError`` outside the envelope
+    (the rate, negative or non-finite times, ``H + P > lib.LIMITER_MAX_REACH``), with the library's message."""
+    lib = L.load()
+    v = [C.c_int32() for _ in range(4)]
+    if lib.bv2_limiter_plan(C.byref(limiter_config(rate, lookahead_ms, release_ms)), *[C.byref(x) for x in v]) != 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return tuple(int(x.value) for x in v)
+
+
+def limiter_window(rate: int, lookahead_ms: float = 3.0, release_ms: float = 60.0) -> np.ndarray:
+    """The smoothing window ``[P + H + 1]`` fp32 from ``bv2_limiter_window``: ``w[k]`` at index ``k + P``, a half-Hann on either side of
+    ``k = 0``, normalised to sum 1 in fp64 and rounded once."""
+    H, P, _, _ = limiter_plan(rate, lookahead_ms, release_ms)
+    lib = L.load()
+    out = np.empty(P + H + 1, np.float32)
+    if lib.bv2_limiter_window(C.byref(limiter_config(rate, lookahead_ms, release_ms)), C.c_void_p(out.ctypes.data)) != 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    return out
+
+
+_WINDOWS: Dict[tuple, torch.Tensor] = {}
+
+
+def device_window(rate: int, lookahead_ms: float, release_ms: float, dev) -> torch.Tensor:
+    key = (int(rate), float(lookahead_ms), float(release_ms), str(torch.device(dev)))
+    if key not in _WINDOWS:
+        _WINDOWS[key] = torch.from_numpy(limiter_window(rate, lookahead_ms, release_ms)).to(dev)
+    return _WINDOWS[key]
+
+
+def limit_apply(wav: torch.Tensor, wl: Optional[torch.Tensor], rate: int, gain: torch.Tensor, groups: Optional[torch.Tensor] = None,
+                ceiling_db: float = -1.0, lookahead_ms: float = 3.0, release_ms: float = 60.0, as_pcm16: bool = False,
+                want_curve: bool = False) -> Dict[str, torch.Tensor]:
+    """``bv2_limit`` on the current stream (two launches): ``wav`` [B, S] (device, fp32 or int16, unit sample stride) times ``gain[group]``
+    times the limiter's gain curve under a true-peak ceiling.  Returns device tensors ``out`` [B, S] (fp32, or int16 by the fixed-gain
+    rule), ``min_gain`` fp32 [B], ``limited_samples`` int64 [B] and, if asked, ``curve`` fp32 [B, S]."""
+    if not wav.is_cuda or wav.dim() != 2 or wav.stride(1) != 1 or wav.dtype not in (torch.float32, torch.int16):
+        raise ValueError("wav must be a device tensor [B, S], float32 or int16, with unit sample stride")
+    B, S = wav.shape
+    dev = wav.device
+    cfg = limiter_config(rate, lookahead_ms, release_ms, L.WAV_I16 if wav.dtype == torch.int16 else L.WAV_F32)
+    _, _, F, _ = limiter_plan(rate, lookahead_ms, release_ms)
+    lib = L.load()
+    n = lib.bv2_limiter_workspace_bytes(C.byref(cfg), B, S)
+    if n < 0:
+        raise ValueError(lib.bv2_last_error(None).decode())
+    taps = device_taps(rate, F * rate, dev) if F > 1 else None
+    window = device_window(rate, lookahead_ms, release_ms, dev)
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    r = {"out": torch.empty(B, S, dtype=torch.int16 if as_pcm16 else torch.float32, device=dev),
+         "min_gain": torch.empty(B, dtype=torch.float32, device=dev), "limited_samples": torch.empty(B, dtype=torch.int64, device=dev)}
+    if want_curve:
+        r["curve"] = torch.empty(B, S, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.bv2_limit(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(cfg), _ptr(taps), _ptr(window), _ptr(wav),
+                           wav.stride(0) if B > 1 else S, _ptr(wl), B, S, _ptr(groups), gain.numel(), _ptr(gain), float(ceiling_db),
+                           None if as_pcm16 else _ptr(r["out"]), _ptr(r["out"]) if as_pcm16 else None, S, _ptr(r.get("curve")),
+                           _ptr(r["min_gain"]), _ptr(r["limited_samples"]), _ptr(ws), ws.numel())
+    if rc != 0:
+        raise RuntimeError(f"bv2_limit failed ({rc}): {lib.bv2_last_error(None).decode()}")
+    return r
+
+
 def loudness_steps_count(rate: int, n: int) -> int:
     """Whole 100 ms steps of an item of ``n`` samples (``bv2_loudness_steps_count``)."""
     lib = L.load()
@@ -655,9 +728,81 @@ def true_peak(wav, wav_lengths=None, rate: Optional[int] = None, device=None) ->
     return true_peak_measure(w, wl, rate)
 
 
+NO_CEILING_DB = 1000.0                # a ceiling no peak times gain reaches: the gate's gain to the target alone
+MAKEUP_PASSES = (0, 3)
+
+
+def _limiter_args(rate, B, lookahead_ms, release_ms, makeup_passes=0):
+    """The limiter's host-side checks, before anything touches the device."""
+    limiter_plan(rate, lookahead_ms, release_ms)                   # ValueError naming the envelope
+    if B > 65535:
+        raise ValueError(f"the limiter takes at most 65535 items per call, got {B}")
+    if int(makeup_passes) != makeup_passes or not MAKEUP_PASSES[0] <= makeup_passes <= MAKEUP_PASSES[1]:
+        raise ValueError(f"makeup_passes must be an integer in [{MAKEUP_PASSES[0]}, {MAKEUP_PASSES[1]}], got {makeup_passes!r}")
+
+
+def min_gain_db(min_gain: torch.Tensor) -> torch.Tensor:
+    return 20.0 * torch.log10(min_gain.to(torch.float64))
+
+
+def limit_to_target(w: torch.Tensor, wl: Optional[torch.Tensor], rate: int, gain: torch.Tensor, g: Optional[torch.Tensor], G: int,
+                    target_lufs: float, ceiling_db: float, lookahead_ms: float, release_ms: float, makeup_passes: int, as_pcm16: bool,
+                    measure=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """The limiter under a loudness target, on the current stream and without a host sync: limit ``w * gain[group]``, measure the output,
+    and ``makeup_passes`` times raise the gain by what the limiter took and limit the ORIGINAL input again.  ``measure(out) -> lufs [G]``
+    measures an output (default: ``loudness_measure`` with these groups).  Returns ``(out, {gain, lufs_out, limited, min_gain_db,
+    limited_samples})``; a group whose output is silent keeps its gain."""
+    if measure is None:
+        def measure(o):
+            return loudness_measure(o, wl, rate, g, G)["lufs"]
+    for left in range(int(makeup_passes), -1, -1):
+        r = limit_apply(w, wl, rate, gain, g, ceiling_db, lookahead_ms, release_ms, as_pcm16 and left == 0)
+        lufs_out = measure(r["out"])
+        if left:
+            up = torch.pow(10.0, (float(target_lufs) - lufs_out) / 20.0)
+            gain = torch.where(torch.isfinite(up), gain.to(torch.float64) * up, gain.to(torch.float64)).to(torch.float32)
+    hit = (r["limited_samples"] > 0).to(torch.int64)
+    if g is not None:
+        hit = torch.zeros(G, dtype=torch.int64, device=w.device).index_add_(0, g.to(torch.int64).clamp(0, G - 1), hit)
+    return r["out"], {"gain": gain, "lufs_out": lufs_out, "limited": hit > 0, "min_gain_db": min_gain_db(r["min_gain"]),
+                      "limited_samples": r["limited_samples"]}
+
+
+@torch.no_grad()
+def limit(wav, wav_lengths=None, rate: Optional[int] = None, gain=None, ceiling_db: float = -1.0, lookahead_ms: float = 3.0,
+          release_ms: float = 60.0, groups=None, as_pcm16: bool = False, want_curve: bool = False, device=None
+          ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """Look-ahead true-peak limiter (include/bv2.h ``bv2_limit``): ``(out [B, S], info)`` on the device.  ``out = (wav * gain[group]) *
+    s``, with the gain curve ``s`` at most 1 and below 1 only around crests whose TRUE peak, after the static gain, would pass
+    ``ceiling_db`` (dBTP): it starts to move ``H + P + 1`` samples before a crest and is back at 1 as many behind it, ``H`` / ``P``
+    from ``lookahead_ms`` / ``release_ms`` (``limiter_plan``).  ``|out| <= c (1 + 3 * 2^-24)`` by construction; an item that never
+    reaches the ceiling leaves as ``loudness_apply`` writes it, bit for bit.  Input handling as ``loudness``; ``gain``: ``None`` (1), a
+    number, or fp32 [G] indexed by ``groups`` ([B] when ``groups`` is ``None``).  ``info``: ``min_gain_db`` fp64 [B] (0 where nothing
+    was limited), ``min_gain`` fp32 [B], ``limited_samples`` int64 [B] and, with ``want_curve``, ``curve`` fp32 [B, S]."""
+    rate, B, S, _, move = _loudness_input(wav, wav_lengths, rate, device)
+    ids, G = _groups_arg(groups, B)
+    if not np.isfinite(ceiling_db):
+        raise ValueError("ceiling_db must be finite")
+    _limiter_args(rate, B, lookahead_ms, release_ms)
+    dev, w, wl = move()
+    g = _device_groups(groups, ids, dev)
+    if gain is None or isinstance(gain, (int, float)):
+        gain = torch.full((G,), 1.0 if gain is None else float(gain), dtype=torch.float32, device=dev)
+    else:
+        gain = torch.as_tensor(gain).to(dev, torch.float32).reshape(-1).contiguous()
+        if gain.numel() < G:
+            raise ValueError(f"gain must hold one value per group ({G}), got {gain.numel()}")
+    r = limit_apply(w, wl, rate, gain, g, ceiling_db, lookahead_ms, release_ms, as_pcm16, want_curve)
+    info = {"min_gain_db": min_gain_db(r["min_gain"]), "min_gain": r["min_gain"], "limited_samples": r["limited_samples"]}
+    if want_curve:
+        info["curve"] = r["curve"]
+    return r["out"], info
+
+
 @torch.no_grad()
 def normalize_loudness(wav, wav_lengths=None, rate: Optional[int] = None, target_lufs: float = -23.0, peak_ceiling_db: float = -1.0,
-                       groups=None, as_pcm16: bool = False, device=None, peak: str = "sample"
+                       groups=None, as_pcm16: bool = False, device=None, peak: str = "sample", limiter: bool = False,
+                       lookahead_ms: float = 3.0, release_ms: float = 60.0, makeup_passes: int = 1
                        ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """``wav`` brought to ``target_lufs``: ``(out [B, S], info)`` on the device.  Every group gets ONE static gain ``10^((target - L) /
     20)``, lowered to ``ceiling / peak`` where the group's sample peak would pass ``peak_ceiling_db`` (``info["limited"]``); a silent
@@ -665,15 +810,35 @@ def normalize_loudness(wav, wav_lengths=None, rate: Optional[int] = None, target
     ``trunc(clamp(v * 32767))`` of that product, the fixed-gain rule of streamed PCM.  ``info``: ``lufs`` fp64 [G], ``gain_db`` fp64 [G],
     ``gain`` fp32 [G] (the factor that was applied), ``peak`` fp32 [B], ``limited`` and ``silent`` bool [G].
     ``peak="true"``: the ceiling is in dBTP — the gain is lowered where the group's TRUE peak (``audio.true_peak``) would pass it, which
-    is what EBU R128 asks for; ``info`` gains ``true_peak`` fp32 [B] and ``info["peak"]`` stays the sample peak."""
+    is what EBU R128 asks for; ``info`` gains ``true_peak`` fp32 [B] and ``info["peak"]`` stays the sample peak.
+    ``limiter=True``: the target holds.  The gate is asked for the gain to the target WITHOUT the ceiling and the look-ahead limiter
+    (``audio.limit``) enforces ``peak_ceiling_db`` instead, always as a true-peak ceiling; ``peak=`` then only selects what ``info``
+    reports.  Limiting removes energy, so the output is measured again and the gain becomes ``g * 10^((target - L_out) / 20)`` — on the
+    device, no host sync — and the limiter runs again from the ORIGINAL input, ``makeup_passes`` times (0 .. 3).  ``info`` gains
+    ``lufs_out`` fp64 [G] (the loudness of what is returned), ``min_gain_db`` fp64 [B] and ``limited_samples`` int64 [B];
+    ``info["limited"]`` then means "the limiter engaged on the group".  A silent group keeps gain 1 and passes through."""
     if peak not in PEAKS:
         raise ValueError(f"peak must be one of {PEAKS}, got {peak!r}")
     rate, B, S, _, move = _loudness_input(wav, wav_lengths, rate, device)
     ids, G = _groups_arg(groups, B)
     if not (np.isfinite(target_lufs) and np.isfinite(peak_ceiling_db)):
         raise ValueError("target_lufs and peak_ceiling_db must be finite")
+    if limiter:
+        _limiter_args(rate, B, lookahead_ms, release_ms, makeup_passes)
     dev, w, wl = move()
     g = _device_groups(groups, ids, dev)
+    if limiter:
+        m0 = loudness_measure(w, wl, rate, gate=False)
+        lens = wl if wl is not None else torch.full((B,), S, dtype=torch.int64, device=dev)
+        m = loudness_gate(m0["block_ms"], lens, S, m0["peak"], rate, g, G, target_lufs, NO_CEILING_DB)
+        out, lim = limit_to_target(w, wl, rate, m["gain"], g, G, target_lufs, peak_ceiling_db, lookahead_ms, release_ms, makeup_passes,
+                                   as_pcm16)
+        info = loudness_info(dict(m, gain=lim["gain"]))
+        info.update(limited=lim["limited"], lufs_out=lim["lufs_out"], min_gain_db=lim["min_gain_db"],
+                    limited_samples=lim["limited_samples"])
+        if peak == "true":
+            info["true_peak"] = true_peak_measure(w, wl, rate)
+        return out, info
     if peak == "true":
         m0 = loudness_measure(w, wl, rate, gate=False)
         tp = true_peak_measure(w, wl, rate)

@@ -22,10 +22,10 @@ STAMP = os.path.join(CSRC, ".libbv2.stamp")
 
 SOURCES = [
     "bv2_api.cpp", "bv2_testing.cpp", "bv2_model.cpp", "bv2_exec.cpp", "bv2_bert.cpp",
-    "kernels/conv_mfma.hip", "kernels/conv_x6.hip", "kernels/respair_x6.hip", "kernels/resblock_fused.hip", "kernels/gen_bf16.hip", "kernels/resblock_cl_bf16.hip", "kernels/resblock_c16_bf16.hip", "kernels/respair_cl_bf16.hip", "kernels/enc_f16.hip", "kernels/layernorm.hip", "kernels/attention.hip", "kernels/misc.hip", "kernels/dds_fused.hip", "kernels/sdp_forward.hip", "kernels/flow_boundary.hip", "kernels/bert.hip", "kernels/deberta_attn.hip", "kernels/ref_enc.hip", "kernels/stft.hip", "kernels/stream.hip", "kernels/resample.hip", "kernels/align.hip", "kernels/loudness.hip", "kernels/truepeak.hip", "kernels/assemble.hip",
+    "kernels/conv_mfma.hip", "kernels/conv_x6.hip", "kernels/respair_x6.hip", "kernels/resblock_fused.hip", "kernels/gen_bf16.hip", "kernels/resblock_cl_bf16.hip", "kernels/resblock_c16_bf16.hip", "kernels/respair_cl_bf16.hip", "kernels/enc_f16.hip", "kernels/layernorm.hip", "kernels/attention.hip", "kernels/misc.hip", "kernels/dds_fused.hip", "kernels/sdp_forward.hip", "kernels/flow_boundary.hip", "kernels/bert.hip", "kernels/deberta_attn.hip", "kernels/ref_enc.hip", "kernels/stft.hip", "kernels/stream.hip", "kernels/resample.hip", "kernels/align.hip", "kernels/loudness.hip", "kernels/truepeak.hip", "kernels/limiter.hip", "kernels/assemble.hip",
 ]
 EXPORTS = "libbv2.map"     # linker version script: export bv2_* only
-HEADERS = [EXPORTS, "bv2_internal.h", "bv2_kernels.h", "bv2_pack.h", "kernels/spline.h", "kernels/dds_tile.h", "kernels/cl_bf16.h", "kernels/device_helpers.h", "kernels/rng.h", os.path.join(ROOT, "include", "bv2.h"),
+HEADERS = [EXPORTS, "bv2_internal.h", "bv2_kernels.h", "bv2_pack.h", "kernels/spline.h", "kernels/dds_tile.h", "kernels/cl_bf16.h", "kernels/device_helpers.h", "kernels/rng.h", "kernels/truepeak_taps.h", os.path.join(ROOT, "include", "bv2.h"),
            os.path.join(ROOT, "include", "bv2_testing.h"), os.path.join(ROOT, "include", "bv2_bert.h")]
 # -amdgpu-kernarg-preload-count: up to 16 dwords of a kernel's LEADING SCALAR arguments arrive in SGPRs at wave launch (kernels whose
 # first argument is a by-value struct are unaffected: preload length 0; tools/kernel_resources.py prints the length per kernel)

@@ -1154,6 +1154,119 @@ int bv2_true_peak(bv2_stream stream, const bv2_loudness_config* cfg, const float
   } catch (...) { return fail("exception", -100); }
 }
 
+// ---- look-ahead true-peak limiter (kernels/limiter.hip) ------------------------------------------------------------
+static_assert(BV2_LIMITER_TILE == LM_TILE && BV2_LIMITER_MAX_REACH == LM_MAX_REACH, "BV2_LIMITER_* and LM_* are one pair of numbers");
+
+struct LimiterPlan { int H, P, F, K; };
+
+static int limiter_plan(const bv2_limiter_config* c, const char* what, LimiterPlan* out) {
+  auto fail = [&](const std::string& m) { g_create_err = std::string(what) + ": " + m; return -1; };
+  if (!c) return fail("cfg is null");
+  if (c->struct_bytes != (int32_t)sizeof(bv2_limiter_config)) return fail("bv2_limiter_config.struct_bytes mismatch (ABI drift)");
+  if (c->reserved != 0) return fail("bv2_limiter_config.reserved must be 0");
+  const bv2_loudness_config lc = {(int32_t)sizeof(bv2_loudness_config), c->sample_rate, c->input_format};
+  int32_t F = 0, K = 0;
+  if (int rc = bv2_true_peak_plan(&lc, &F, &K)) {                             // the rate envelope, the input format, the table's K
+    const std::string m = g_create_err;
+    const size_t at = m.find(": ");
+    fail(at == std::string::npos ? m : m.substr(at + 2));
+    return rc;
+  }
+  if (!(c->lookahead_ms >= 0.0) || !(c->release_ms >= 0.0) || std::isinf(c->lookahead_ms) || std::isinf(c->release_ms))
+    return fail("lookahead_ms and release_ms must be finite and not negative");
+  const double h = std::floor(c->lookahead_ms * c->sample_rate / 2000.0 + 0.5), p = std::floor(c->release_ms * c->sample_rate / 2000.0 + 0.5);
+  const double H = std::max(1.0, h), P = std::max(H, p);
+  if (H + P > (double)LM_MAX_REACH)
+    return fail("H + P = " + std::to_string((long long)H) + " + " + std::to_string((long long)P) + " exceeds BV2_LIMITER_MAX_REACH = " +
+                std::to_string(LM_MAX_REACH) + " samples (lookahead_ms " + std::to_string(c->lookahead_ms) + ", release_ms " +
+                std::to_string(c->release_ms) + " at " + std::to_string(c->sample_rate) + " Hz)");
+  out->H = (int)H; out->P = (int)P; out->F = F; out->K = K;
+  return 0;
+}
+
+int bv2_limiter_plan(const bv2_limiter_config* cfg, int32_t* H, int32_t* P, int32_t* factor, int32_t* K) {
+  LimiterPlan p;
+  if (int rc = limiter_plan(cfg, "bv2_limiter_plan", &p)) return rc;
+  if (H) *H = p.H;
+  if (P) *P = p.P;
+  if (factor) *factor = p.F;
+  if (K) *K = p.K;
+  return 0;
+}
+
+int bv2_limiter_window(const bv2_limiter_config* cfg, float* out) {
+  LimiterPlan p;
+  if (int rc = limiter_plan(cfg, "bv2_limiter_window", &p)) return rc;
+  if (!out) { g_create_err = "bv2_limiter_window: out is null"; return -1; }
+  try {
+    const double pi = 3.14159265358979323846;
+    std::vector<double> u((size_t)p.P + p.H + 1);
+    double sum = 0;
+    for (int k = -p.P; k <= p.H; ++k) {
+      u[(size_t)(k + p.P)] = 0.5 + 0.5 * std::cos(pi * (double)k / (double)((k >= 0 ? p.H : p.P) + 1));
+      sum += u[(size_t)(k + p.P)];
+    }
+    for (size_t i = 0; i < u.size(); ++i) out[i] = (float)(u[i] / sum);
+    return 0;
+  } catch (...) { g_create_err = "bv2_limiter_window: out of memory"; return -100; }
+}
+
+int64_t bv2_limiter_workspace_bytes(const bv2_limiter_config* cfg, int32_t B, int64_t S) {
+  LimiterPlan p;
+  if (limiter_plan(cfg, "bv2_limiter_workspace_bytes", &p)) return -1;
+  if (B < 1 || B > 65535 || S < 1 || S > LD_MAX_S) {
+    g_create_err = "bv2_limiter_workspace_bytes: B must be in [1, 65535] and S in [1, 2^31 - 4096]";
+    return -1;
+  }
+  return (int64_t)B * S * 4 + (int64_t)B * ((S + LM_TILE - 1) / LM_TILE) * 4 + 256;
+}
+
+int bv2_limit(bv2_stream stream, const bv2_limiter_config* cfg, const float* taps, const float* window, const void* src,
+              int64_t src_bstride, const int64_t* lengths, int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, const float* gain,
+              double ceiling_db, float* dst_f32, int16_t* dst_i16, int64_t dst_bstride, float* curve, float* min_gain,
+              int64_t* limited_samples, void* workspace, int64_t workspace_bytes) {
+  const char* what = "bv2_limit";
+  auto fail = [&](const std::string& m, int rc) { g_create_err = std::string(what) + ": " + m; return rc; };
+  LimiterPlan p;
+  if (int rc = limiter_plan(cfg, what, &p)) return rc;
+  if (!src) return fail("src is null", -1);
+  if (!gain) return fail("gain is null", -1);
+  if (p.F > 1 && !taps) return fail("taps is null (the DEVICE copy of bv2_resample_taps(rate, F * rate))", -1);
+  if (!window) return fail("window is null (the DEVICE copy of bv2_limiter_window)", -1);
+  if (!min_gain || !limited_samples) return fail("min_gain and limited_samples must not be null", -1);
+  if ((dst_f32 != nullptr) == (dst_i16 != nullptr)) return fail("exactly one of dst_f32 / dst_i16 must be given", -1);
+  if (src_bstride < 0) return fail("src_bstride must not be negative", -1);
+  if (B < 1 || B > 65535) return fail("B must be in [1, 65535]", -1);
+  if (S < 1 || S > LD_MAX_S) return fail("S must be in [1, 2^31 - 4096]", -1);
+  if (groups ? n_groups < 1 : n_groups != B)
+    return fail("n_groups (the length of gain) must be at least 1 with groups, and equal to B without", -1);
+  if (dst_bstride < S) return fail("dst_bstride is shorter than S", -1);
+  if (!(ceiling_db == ceiling_db) || std::isinf(ceiling_db)) return fail("ceiling_db must be finite", -1);
+  const float c = (float)std::pow(10.0, ceiling_db / 20.0);
+  if (!(c > 0.f) || std::isinf(c)) return fail("10^(ceiling_db / 20) is not a positive finite float", -1);
+  const int64_t need = (int64_t)B * S * 4 + (int64_t)B * ((S + LM_TILE - 1) / LM_TILE) * 4;
+  if (!workspace || workspace_bytes < need) return fail("workspace too small (bv2_limiter_workspace_bytes)", -5);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const uintptr_t mis = reinterpret_cast<uintptr_t>(ws) & 7u;
+  if (mis) {
+    if (workspace_bytes < need + 8) return fail("workspace too small (bv2_limiter_workspace_bytes)", -5);
+    ws += 8 - mis;
+  }
+  try {
+    LimitArgs a;
+    a.src = src; a.src_bstride = src_bstride; a.lengths = lengths; a.B = B; a.S = S; a.input_format = cfg->input_format;
+    a.factor = p.F; a.taps = p.F > 1 ? taps : nullptr;
+    a.H = p.H; a.P = p.P; a.window = window;
+    a.groups = groups; a.n_gain = n_groups; a.gain = gain; a.ceiling = c;
+    a.dst = dst_f32; a.dst16 = dst_i16; a.dst_bstride = dst_bstride; a.curve = curve;
+    a.min_gain = min_gain; a.limited_samples = limited_samples;
+    a.req = reinterpret_cast<float*>(ws);
+    a.tile_min = reinterpret_cast<int*>(ws + (size_t)B * S * 4);
+    if (launch_limit(static_cast<hipStream_t>(stream), a)) return fail("kernel launch failed", -6);
+    return 0;
+  } catch (...) { return fail("exception", -100); }
+}
+
 // ---- step energies and loudness range (kernels/loudness.hip) -----------------------------------------------------
 static_assert(BV2_RANGE_SHORT == LD_RANGE_SHORT && BV2_RANGE_SILENT == LD_RANGE_SILENT, "BV2_RANGE_* and LD_RANGE_* are one numbering");
 

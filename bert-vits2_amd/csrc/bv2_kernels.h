@@ -952,6 +952,23 @@ struct TruePeakArgs {
 };
 int launch_true_peak(hipStream_t stream, const TruePeakArgs& a);          // two launches
 
+// --- true-peak limiter (kernels/limiter.hip): the per-sample true-peak envelope as a required gain, then hold, smoothing and the product ---
+constexpr int LM_THREADS = 256, LM_PER = 4, LM_TILE = LM_THREADS * LM_PER;   // include/bv2.h BV2_LIMITER_TILE
+constexpr int LM_MAX_REACH = 6144;                   // H + P; include/bv2.h BV2_LIMITER_MAX_REACH
+struct LimitArgs {
+  const void* src; int64_t src_bstride; const int64_t* lengths; int B; int64_t S; int input_format;
+  int factor; const float* taps;                     // as TruePeakArgs
+  int H, P; const float* window;                     // [P + H + 1], DEVICE: w[k] at window[k + P]
+  const int* groups; int n_gain; const float* gain;  // as LoudnessApplyArgs
+  float ceiling;                                     // c, an amplitude
+  float* dst; int16_t* dst16; int64_t dst_bstride;   // exactly one of the two
+  float* curve;                                      // [B][S] or null
+  float* min_gain; int64_t* limited_samples;         // [B] each
+  float* req;                                        // workspace [B][S]: r[i] for i < len_b
+  int* tile_min;                                     // workspace [B][ceil(S / LM_TILE)]: the smallest r of a tile, as its bit pattern
+};
+int launch_limit(hipStream_t stream, const LimitArgs& a);                  // two launches
+
 // --- documents (kernels/assemble.hip): pieces and pauses joined into one buffer per document; layout, peaks, write ---
 constexpr int AS_THREADS = 256, AS_LAYOUT_THREADS = 1024;
 constexpr int AS_TILE = 4096;                        // destination samples per workgroup, both output formats (bv2_assemble_plan's tile)

@@ -16,27 +16,11 @@
 #include <stdint.h>
 
 #include "../bv2_kernels.h"
+#include "truepeak_taps.h"
 
 namespace bv2 {
 
 #define BV2_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -1)
-
-constexpr int TP_NT = 2 * TP_K + 1;                         // 73 taps per phase
-constexpr int TP_XS = TP_TILE + 2 * TP_K;                   // the tile and its two halos
-static_assert(TP_TILE == TP_THREADS * TP_PER, "a thread owns TP_PER positions, TP_THREADS apart");
-
-template <typename T>
-__device__ __forceinline__ float tp_load(const T* p);
-template <>
-__device__ __forceinline__ float tp_load<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float tp_load<int16_t>(const int16_t* p) { return (float)*p * (1.f / 32768.f); }
-
-__device__ __forceinline__ int64_t tp_item_len(const int64_t* lengths, int b, int64_t S) {
-  int64_t n = lengths ? lengths[b] : S;
-  n = n < 0 ? 0 : n;
-  return n > S ? S : n;
-}
 
 template <typename T, int F>
 __global__ void __launch_bounds__(TP_THREADS) true_peak_tile_kernel(const T* wav, int64_t bstride, const int64_t* lengths, int64_t S,
@@ -50,37 +34,13 @@ __global__ void __launch_bounds__(TP_THREADS) true_peak_tile_kernel(const T* wav
   if (base >= len) return;                                                   // block-uniform: the tile lies behind the item
   const T* src = wav + (int64_t)b * bstride;
   if (tid == 0) pk_bits = 0u;
-  for (int e = tid; e < TP_XS; e += TP_THREADS) {
-    const int64_t i = base - TP_K + e;
-    xs[e] = (i >= 0 && i < len) ? tp_load<T>(src + i) : 0.f;                 // selected, never loaded outside the item
-  }
-  if (F > 1) {
-    for (int e = tid; e < TP_NT * F; e += TP_THREADS) {
-      const int p = e / TP_NT, jj = e - p * TP_NT;
-      tl[jj * F + p] = taps[e];
-    }
-  }
+  tp_stage<T, F>(xs, tl, src, base, len, taps, tid);
   __syncthreads();
 
   float pk = 0.f;
   if (F > 1) {
     float acc[TP_PER][F];
-#pragma unroll
-    for (int r = 0; r < TP_PER; ++r)
-#pragma unroll
-      for (int p = 0; p < F; ++p) acc[r][p] = 0.f;
-#pragma unroll 1
-    for (int jj = 0; jj < TP_NT; ++jj) {
-      float t[F];
-#pragma unroll
-      for (int p = 0; p < F; ++p) t[p] = tl[jj * F + p];
-#pragma unroll
-      for (int r = 0; r < TP_PER; ++r) {
-        const float x = xs[tid + TP_THREADS * r + jj];
-#pragma unroll
-        for (int p = 0; p < F; ++p) acc[r][p] = fmaf(x, t[p], acc[r][p]);
-      }
-    }
+    tp_phases<F>(xs, tl, tid, acc);                                          // truepeak_taps.h: shared with limiter.hip
 #pragma unroll
     for (int r = 0; r < TP_PER; ++r) {
       if (base + tid + TP_THREADS * r < len) {                               // the F outputs of a position inside the item

@@ -110,9 +110,16 @@ class LoudnessConfig(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("sample_rate", C.c_int32), ("input_format", C.c_int32)]
 
 
+class LimiterConfig(C.Structure):
+    """include/bv2.h bv2_limiter_config"""
+    _fields_ = [("struct_bytes", C.c_int32), ("sample_rate", C.c_int32), ("input_format", C.c_int32), ("reserved", C.c_int32),
+                ("lookahead_ms", C.c_double), ("release_ms", C.c_double)]
+
+
 LOUDNESS_SILENT, LOUDNESS_LIMITED = 1, 2
 RANGE_SHORT, RANGE_SILENT = 1, 2
 TRUE_PEAK_TILE = 1024      # include/bv2.h BV2_TRUE_PEAK_TILE
+LIMITER_TILE, LIMITER_MAX_REACH = 1024, 6144      # include/bv2.h BV2_LIMITER_TILE / BV2_LIMITER_MAX_REACH
 
 
 class AssembleSegment(C.Structure):
@@ -208,6 +215,11 @@ SYMBOLS = [
     ("bv2_true_peak_plan", C.c_int, [C.POINTER(LoudnessConfig), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("bv2_true_peak_workspace_bytes", C.c_int64, [C.POINTER(LoudnessConfig), C.c_int32, C.c_int64]),
     ("bv2_true_peak", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64]),
+    ("bv2_limiter_plan", C.c_int, [C.POINTER(LimiterConfig)] + [C.POINTER(C.c_int32)] * 4),
+    ("bv2_limiter_window", C.c_int, [C.POINTER(LimiterConfig), _P]),
+    ("bv2_limiter_workspace_bytes", C.c_int64, [C.POINTER(LimiterConfig), C.c_int32, C.c_int64]),
+    ("bv2_limit", C.c_int, [_P, C.POINTER(LimiterConfig), _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, C.c_double,
+                            _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64]),
     ("bv2_loudness_steps_count", C.c_int64, [C.POINTER(LoudnessConfig), C.c_int64]),
     ("bv2_loudness_steps", C.c_int, [_P, C.POINTER(LoudnessConfig), _P, C.c_int64, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P, _P,
                                      C.c_int64]),

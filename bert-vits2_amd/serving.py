@@ -235,7 +235,8 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
                max_batch: int = 32, max_pad_ratio: float = 1.25, as_pcm16: bool = False,
                noise: Optional[Sequence] = None, requests_in_flight: int = 1, output_rate: Optional[int] = None,
                target_lufs: Optional[float] = None, peak_ceiling_db: float = -1.0, loudness_groups: Optional[Sequence] = None,
-               return_levels: bool = False, peak: str = "sample") -> List[np.ndarray]:
+               return_levels: bool = False, peak: str = "sample", limiter: bool = False, lookahead_ms: float = 3.0,
+               release_ms: float = 60.0, makeup_passes: int = 1) -> List[np.ndarray]:
     """Synthesise every utterance; returns one 1-D array per utterance in input order (float32 like reference
     infer.py:315-319, or int16 with ``as_pcm16``).  Defaults are the reference web UI's (webui.py:443-454).
     ``noise`` (tests): per utterance a pair ``(noise_w [2,T], noise_z [inter, >= T_y])`` to inject instead of drawing.
@@ -261,7 +262,13 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     group), ``gain_db`` and ``gain`` (the fp32 factor that was applied), ``peak`` (its own sample peak before the gain), ``limited``,
     ``silent``.  ``peak="true"``: ``peak_ceiling_db`` is in dBTP — the gain is lowered where the TRUE peak (``audio.true_peak``, measured
     on the device at the output rate) of the utterance, or of its group, would pass the ceiling; the levels then carry ``true_peak``
-    beside ``peak``.  ``"sample"`` is today's output to the bit; ``"true"`` without ``target_lufs`` raises."""
+    beside ``peak``.  ``"sample"`` is today's output to the bit; ``"true"`` without ``target_lufs`` raises.
+    ``limiter=True``: the target holds (``audio.normalize_loudness(limiter=True)``, on both paths): the gain goes to the target without
+    the ceiling and the look-ahead limiter keeps ``peak_ceiling_db`` as a TRUE-peak ceiling, ``lookahead_ms`` / ``release_ms`` /
+    ``makeup_passes`` as there; it runs after the resampling, before the one copy.  ``peak=`` then only selects what the levels report;
+    they gain ``lufs_out`` (the loudness of what is returned, of the utterance's group) and ``min_gain_db`` (its own deepest gain
+    reduction), and ``limited`` means "the limiter engaged on its group".  A grouped call limits behind the last bucket, on the caller's
+    stream.  ``False`` is today's output to the bit; ``True`` without ``target_lufs`` raises."""
     if model.device.type != "cuda":
         raise RuntimeError("bert_vits2_amd.serving needs the model on a GPU: there is no CPU fallback")
     if noise is not None and any(u.seed is not None for u in utts):
@@ -271,7 +278,8 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
     output_rate = _output_rate(model, output_rate)
     if output_rate is not None:
         hop = 1                                            # the buckets' lengths then count output-rate samples
-    level = _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels, peak)
+    level = _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels, peak,
+                        dict(lookahead_ms=lookahead_ms, release_ms=release_ms, makeup_passes=makeup_passes) if limiter else None)
     results: List[Optional[np.ndarray]] = [None] * len(utts)
     pending = []
     lanes = replicas(model, requests_in_flight) if requests_in_flight > 1 else [(model, None)]
@@ -303,7 +311,9 @@ def synthesize(model, utts: Sequence[Utterance], *, sdp_ratio=0.5, noise_scale=0
                 lufs, gain, pk, flags = (float(v) for v in lv[0][:4, r])
                 levels[i] = dict(lufs=lufs, gain_db=20.0 * math.log10(gain), gain=gain, peak=pk, limited=bool(int(flags) & 2),
                                  silent=bool(int(flags) & 1))
-                if lv[0].shape[0] > 4:                         # peak="true"
+                if level["limiter"] is not None:               # the last two rows
+                    levels[i].update(lufs_out=float(lv[0][-2, r]), min_gain_db=float(lv[0][-1, r]))
+                if level["true"]:
                     levels[i]["true_peak"] = float(lv[0][4, r])
     return (results, levels) if return_levels else results
 
@@ -463,7 +473,8 @@ def synthesize_documents(model, documents, *, interval_between_sent: float = 0.2
     return results, [[(off[s], e - off[s]) for s, e in zip(rows, ends[d])] for d, rows in enumerate(pieces)]
 
 
-def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels, peak="sample") -> Optional[dict]:
+def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness_groups, return_levels, peak="sample",
+                limiter: Optional[dict] = None) -> Optional[dict]:
     """The loudness arguments of ``synthesize``, checked before any work: ``None`` without a target."""
     from . import audio
     if peak not in audio.PEAKS:
@@ -473,11 +484,15 @@ def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness
             raise ValueError("loudness_groups and return_levels need target_lufs")
         if peak != "sample":
             raise ValueError("peak='true' needs target_lufs")
+        if limiter is not None:
+            raise ValueError("limiter=True needs target_lufs")
         return None
     if not (math.isfinite(float(target_lufs)) and math.isfinite(float(peak_ceiling_db))):
         raise ValueError("target_lufs and peak_ceiling_db must be finite")
     rate = int(output_rate if output_rate is not None else model.hp.sampling_rate)
     audio.loudness_plan(rate)                               # ValueError naming the envelope
+    if limiter is not None:
+        audio._limiter_args(rate, 1, **limiter)
     ids = None
     if loudness_groups is not None:
         keys = list(loudness_groups)
@@ -485,7 +500,8 @@ def _level_plan(model, utts, output_rate, target_lufs, peak_ceiling_db, loudness
             raise ValueError("loudness_groups takes one hashable per utterance")
         dense = {}
         ids = [dense.setdefault(k, len(dense)) for k in keys]
-    return dict(rate=rate, target=float(target_lufs), ceiling=float(peak_ceiling_db), ids=ids, held=[], true=peak == "true")
+    return dict(rate=rate, target=float(target_lufs), ceiling=float(peak_ceiling_db), ids=ids, held=[], true=peak == "true",
+                limiter=limiter)
 
 
 def _gate_held(level, dev):
@@ -504,8 +520,9 @@ def _gate_held(level, dev):
     groups = torch.tensor([level["ids"][i] for i in rows], dtype=torch.int32).to(dev)
     n_groups = max(level["ids"]) + 1
     which = "true_peak" if level["true"] else "peak"         # what the ceiling limits
+    ceiling = level["ceiling"] if level["limiter"] is None else audio.NO_CEILING_DB      # the limiter keeps the ceiling instead
     m = audio.loudness_gate(ms, torch.cat([h["lens"] for h in held]), S, torch.cat([h[which] for h in held]), level["rate"], groups,
-                            n_groups, level["target"], level["ceiling"])
+                            n_groups, level["target"], ceiling)
     return m, groups
 
 
@@ -515,6 +532,8 @@ def _level_groups(level, pending, as_pcm16, dev):
     held = level["held"]
     main = torch.cuda.current_stream(dev)
     m, groups = _gate_held(level, dev)
+    if level["limiter"] is not None:
+        return _limit_groups(level, pending, as_pcm16, dev, m, groups)
     gated = torch.cuda.Event()
     gated.record(main)
     o = 0
@@ -530,6 +549,42 @@ def _level_groups(level, pending, as_pcm16, dev):
                 lv.append(h["true_peak"].double())
             _enqueue_copy(pending, h["idx"], out, h["y_len"], torch.stack(lv))
         o += B
+
+
+def _limit_groups(level, pending, as_pcm16, dev, m, groups):
+    """The limiter under a grouped target (``audio.limit_to_target`` over buckets), on the caller's stream behind ``_gate_held``: every
+    bucket is limited under its groups' gains; the outputs' block energies go through one gate, which gives every group its loudness;
+    ``makeup_passes`` times the gains are raised by what is missing and the buckets are limited again from their unlevelled audio."""
+    from . import audio
+    held, lim, rate = level["held"], level["limiter"], level["rate"]
+    n_groups = m["gain"].numel()
+    spans, o = [], 0
+    for h in held:
+        spans.append(groups[o:o + len(h["idx"])])
+        o += len(h["idx"])
+    S = max(h["wave"].shape[1] for h in held)
+    lens = torch.cat([h["lens"] for h in held])
+    gain = m["gain"]
+    for left in range(int(lim["makeup_passes"]), -1, -1):
+        outs = [audio.limit_apply(h["wave"], h["lens"], rate, gain, g, level["ceiling"], lim["lookahead_ms"], lim["release_ms"],
+                                  as_pcm16 and left == 0) for h, g in zip(held, spans)]
+        ms = [audio.loudness_measure(r["out"], h["lens"], rate, gate=False) for r, h in zip(outs, held)]
+        width = max(v["block_ms"].shape[1] for v in ms)
+        lufs_out = audio.loudness_gate(torch.cat([torch.nn.functional.pad(v["block_ms"], (0, width - v["block_ms"].shape[1])) for v in ms]),
+                                       lens, S, torch.cat([v["peak"] for v in ms]), rate, groups, n_groups)["lufs"]
+        if left:
+            up = torch.pow(10.0, (level["target"] - lufs_out) / 20.0)
+            gain = torch.where(torch.isfinite(up), gain.to(torch.float64) * up, gain.to(torch.float64)).to(torch.float32)
+    hit = torch.zeros(n_groups, dtype=torch.int64, device=dev).index_add_(
+        0, groups.long(), (torch.cat([r["limited_samples"] for r in outs]) > 0).to(torch.int64)) > 0
+    flags = (m["flags"] & 1) + 2 * hit.to(torch.int32)
+    for h, g, r in zip(held, spans, outs):
+        gl = g.long()
+        lv = [m["lufs"][gl], gain[gl].double(), h["peak"].double(), flags[gl].double()]
+        if level["true"]:
+            lv.append(h["true_peak"].double())
+        lv += [lufs_out[gl], audio.min_gain_db(r["min_gain"])]
+        _enqueue_copy(pending, h["idx"], r["out"], h["y_len"], torch.stack(lv))
 
 
 def _enqueue_copy(pending, idx, audio, y_len, levels=None):
@@ -586,6 +641,17 @@ def _run_bucket(model, utts, idx, dev, noise, pending, as_pcm16, gvec, sdp_ratio
     if level is None:
         audio = pcm16(model, wave[:, None], y_len, hop=None if output_rate is None else 1) if as_pcm16 else wave
         _enqueue_copy(pending, idx, audio, y_len)
+    elif level["ids"] is None and level["limiter"] is not None:   # the gain to the target alone; the limiter keeps the ceiling
+        B = wave.shape[0]
+        lim = level["limiter"]
+        m0 = _audio.loudness_measure(wave, lens, level["rate"], gate=False)
+        m = _audio.loudness_gate(m0["block_ms"], lens, wave.shape[1], m0["peak"], level["rate"], None, B, level["target"], _audio.NO_CEILING_DB)
+        audio, r = _audio.limit_to_target(wave, lens, level["rate"], m["gain"], None, B, level["target"], level["ceiling"],
+                                          lim["lookahead_ms"], lim["release_ms"], lim["makeup_passes"], as_pcm16)
+        lv = [m["lufs"], r["gain"].double(), m0["peak"].double(), ((m["flags"] & 1) + 2 * r["limited"].to(torch.int32)).double()]
+        if level["true"]:
+            lv.append(_audio.true_peak_measure(wave, lens, level["rate"]).double())
+        _enqueue_copy(pending, idx, audio, y_len, torch.stack(lv + [r["lufs_out"], r["min_gain_db"]]))
     elif level["ids"] is None and level["true"]:       # the same, under a true-peak ceiling: blocks and sample peaks, true peaks, the gate
         m0 = _audio.loudness_measure(wave, lens, level["rate"], gate=False)
         tp = _audio.true_peak_measure(wave, lens, level["rate"])

@@ -546,6 +546,67 @@ int64_t bv2_true_peak_workspace_bytes(const bv2_loudness_config* cfg, int32_t B,
 int bv2_true_peak(bv2_stream stream, const bv2_loudness_config* cfg, const float* taps, const void* wav, int64_t wav_bstride,
                   const int64_t* lengths, int32_t B, int64_t S, float* peak_out, void* workspace, int64_t workspace_bytes);
 
+/* ---- look-ahead true-peak limiter (kernels/limiter.hip) ------------------------------------------------------------------------
+ * A static gain under a ceiling (bv2_loudness_gate, BV2_LOUDNESS_LIMITED) leaves a programme with one loud crest under its target.  The
+ * limiter holds the ceiling with a gain CURVE instead: the item keeps its static gain g and only the crests are turned down.  The
+ * definition is such that numpy restates it bit for bit.  All indices count from the item's first sample; nothing at or behind lengths[b]
+ * is loaded.  F, K and the interpolation table are those of bv2_true_peak_plan.  Every fp32 operation below is ONE separately rounded
+ * operation (multiply, add, subtract, IEEE division; nothing is contracted into an FMA), as in bv2_loudness_apply.
+ *   g      the item's static gain, gain[groups ? groups[b] : b] as in bv2_loudness_apply (1 for an id outside the table)
+ *   c      (float) 10^(ceiling_db / 20), formed in fp64 on the host and rounded once
+ *   H      max(1, floor(lookahead_ms * rate / 2000 + 0.5));   P = max(H, floor(release_ms * rate / 2000 + 0.5))
+ *   e[i]   max(|x[i]|, max_p |y[i F + p]|), y EXACTLY bv2_resample's outputs for rate -> F rate (bv2_true_peak's fmaf chains, the same
+ *          bits); F = 1: e[i] = |x[i]|.  max_i e[i] is bv2_true_peak to the bit.
+ *   r[i]   fminf(1, c / (e[i] * g)); r = 1 outside [0, len); e * g = 0 gives c / 0 = inf, hence 1
+ *   m[j]   min r[t] over t in [j - H - 1, j + P + 1]                                       (the hold)
+ *   d[j]   1 - m[j], and 0 outside [0, len)
+ *   A[i]   sum_{k = -P..H} w[k] * d[i + k], accumulated from 0.f over ascending k, product and sum rounded separately
+ *   s[i]   fminf(1 - A[i], fminf(r[i - 1], fminf(r[i], r[i + 1])))                         (the gain curve)
+ *   out[i] (x[i] * g) * s[i] — bv2_loudness_apply's product times s — for i < len, zeros behind the length up to S; the 16-bit form is
+ *          bv2_loudness_apply's rule applied to out
+ * The window (bv2_limiter_window) is a half-Hann on either side of k = 0: u[k] = 0.5 + 0.5 cos(pi k / (H + 1)) for k >= 0,
+ * 0.5 + 0.5 cos(pi k / (P + 1)) for k < 0, w = u / sum(u) in fp64, rounded once to fp32.  s[i] depends on r[i - H - P - 1 .. i + H + P + 1]:
+ * that is the limiter's reach on either side, and H + P + 1 + K samples is the delay a streaming form would need.
+ * What the definition gives:
+ *   sample peak   every m[i + k], k in [-P, H], covers r[i - 1], r[i] and r[i + 1], so every d in the window of A[i] is at least
+ *                 1 - min(r[i - 1], r[i], r[i + 1]) and, the weights summing to 1, s[i] <= r[i] in exact arithmetic; the last fminf makes it
+ *                 hold after rounding too.  |out[i]| = |x g| s <= (e g)(c / (e g)) with three roundings: |out[i]| <= c (1 + 3 * 2^-24),
+ *                 derived, not measured.
+ *   pass-through  where no r within reach is below 1, d is exactly 0, A is exactly 0 and s is exactly 1.0f: an item that never reaches
+ *                 the ceiling leaves as bv2_loudness_apply writes it, bit for bit.
+ *   true peak     the output's TRUE peak is not bounded by construction — the gain moves between samples — it is measured
+ *                 (docs/MEASUREMENTS.md, "Limiter"): the ceiling times 1.0000043 (0.00004 dB) at most on the inputs tried.
+ *   invariance    an item's s and out depend on its own samples, g, c, H and P only: the same bits alone and in any batch, at any row,
+ *                 batch stride or S.
+ *   non-finite    as bv2_true_peak: the envelope's fmaxf skips a NaN operand; a NaN sample leaves as NaN.
+ * Per item the call returns min_gain (fp32, the minimum of s over the item, 1 when nothing was limited) and limited_samples (int64, the
+ * count of s < 1), both through integer atomics on slots the call itself initialises; optionally the curve s (fp32 [B][S], 1 behind the
+ * length).  A workgroup owns BV2_LIMITER_TILE samples of an item and stages r over tile and reach in LDS: H + P <= BV2_LIMITER_MAX_REACH
+ * (the defaults 3 ms / 60 ms at 192 kHz are 288 + 5760).  Envelope: 8000 <= sample_rate <= 192000, lookahead_ms and release_ms finite and
+ * not negative, B <= 65535, S as in the loudness calls.  Anything outside is refused before the device is touched: -1 with a message in
+ * bv2_last_error(NULL) (the size query a negative value), -5 for a null or short workspace. */
+enum { BV2_LIMITER_TILE = 1024, BV2_LIMITER_MAX_REACH = 6144 };
+typedef struct bv2_limiter_config {
+  int32_t struct_bytes;            /* = sizeof(bv2_limiter_config) */
+  int32_t sample_rate;
+  int32_t input_format;            /* BV2_WAV_F32 / BV2_WAV_I16 */
+  int32_t reserved;                /* 0 */
+  double lookahead_ms, release_ms;
+} bv2_limiter_config;
+/* HOST: H, P, F and K (K = 0 when F = 1); each pointer may be NULL. */
+int bv2_limiter_plan(const bv2_limiter_config* cfg, int32_t* H, int32_t* P, int32_t* factor, int32_t* K);
+/* HOST: the window, out[k + P] = w[k] for k in [-P, H]: P + H + 1 floats. */
+int bv2_limiter_window(const bv2_limiter_config* cfg, float* out);
+/* Bytes of DEVICE workspace of bv2_limit at (B, S): r, one fp32 per sample, and one word per tile. */
+int64_t bv2_limiter_workspace_bytes(const bv2_limiter_config* cfg, int32_t B, int64_t S);
+/* Two launches on `stream`, no allocation, no host sync.  src, src_bstride, lengths, B, S, groups, n_groups, gain, dst_f32 / dst_i16 and
+ * dst_bstride as in bv2_loudness_apply; taps is the DEVICE copy of bv2_resample_taps(rate, F rate) (NULL when F = 1) and window the DEVICE
+ * copy of bv2_limiter_window.  curve fp32 [B][S] or NULL; min_gain fp32 [B] and limited_samples int64 [B], DEVICE, are required. */
+int bv2_limit(bv2_stream stream, const bv2_limiter_config* cfg, const float* taps, const float* window, const void* src,
+              int64_t src_bstride, const int64_t* lengths, int32_t B, int64_t S, const int32_t* groups, int32_t n_groups, const float* gain,
+              double ceiling_db, float* dst_f32, int16_t* dst_i16, int64_t dst_bstride, float* curve, float* min_gain,
+              int64_t* limited_samples, void* workspace, int64_t workspace_bytes);
+
 /* ---- step energies, short-term loudness and loudness range (EBU Tech 3342; kernels/loudness.hip) --------------------------------
  * step_ss[b][k], k < steps(len_b) = len_b / step (whole steps only), is the sum of squares of the K-weighted samples [k step, (k + 1) step)
  * of item b, formed from the tiles' partial sums in tile order — the order the gate uses for a step.  For an item of at least one block,
